@@ -21,9 +21,11 @@ communication is the barrier and the max-over-ranks of the elapsed time.  `--sca
 phases its own N DNMs; `--scaling strong` (config 4): the SAME N DNMs cut into contiguous shards.
 `python bench.py --gpus N` without a launcher starts the N ranks itself.
 
-Extra objects on the JSON line: `roofline` for the K1 site-scan kernel (HBM-bound; algorithmic bytes = 20 B/site),
-`issue_model` for the read stage, `link` (achieved host-link GB/s of the staged pass), and `cpu_baseline`: the CPU
-oracle (a C port of the reference's algorithm, oracle/) timed on this box's host cores on a bounded sample of the
+A plain run sets up, warms up, times --steps steps of the headline pass, writes --dump-outputs if asked and prints the line
+(`link`: achieved host-link GB/s of the staged pass).  `--full` adds everything else: the resident pass and the staged pass's
+parity with it, the streamed form, per-kernel times, `roofline` for the K1 site-scan kernel (HBM-bound; algorithmic bytes =
+20 B/site), `issue_model` for the read stage, the files -> results passes (`feed`, `feed_filler`), config 5, and `cpu_baseline`:
+the CPU oracle (a C port of the reference's algorithm, oracle/) timed on this box's host cores on a bounded sample of the
 same DNMs, whose results are also compared with the GPU's (parity at bench scale).
 """
 import argparse
@@ -83,6 +85,13 @@ def parse():
                     help="feed pass: who inflates the BGZF blocks of the BAM -- the device (uz_bgzf_inflate_to_host) or the host's cores")
     ap.add_argument("--feed-level", type=int, default=6, help="deflate level of the files written for the feed pass (samtools / bgzip default: 6)")
     ap.add_argument("--feed-dir", default=None, help="where the files of the feed pass go (default: a temporary directory in /dev/shm, else /tmp)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: the resident pass (value_resident) and the staged pass's parity with it, the streamed form, "
+                         "per-kernel times, roofline and issue model, the files -> results passes (feed, feed_filler), the CPU baseline and config 5.  Without it "
+                         "a run sets up, warms up, times --steps steps of the headline pass, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed pass returned in its last step (status, counts, origin, evidence; config 5: etype, cnv_counts too) as "
+                         "DIR/<name>.npy in float64, at most 64 MB in all (beyond that a fixed, seeded sample of rows, listed in sample_rows.npy)")
     return ap.parse_args()
 
 
@@ -150,6 +159,27 @@ def bind_near_gpu(torch, local_rank):
         return node
     except Exception:
         return None
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(d, res, rank, world):
+    """--dump-outputs: the per-DNM arrays the timed pass returned in its last step, one DIR/<name>.npy each in float64 (every value is an
+    int32: exact), so that two builds can be compared output for output.  Rows beyond 64 MB in all: a fixed, seeded sample of them, the same
+    rows in every array, their indices in sample_rows.npy.  More than one rank: <name>.rank<r>.npy, each rank its own shard."""
+    arrs = {k: np.asarray(v) for k, v in sorted(res.items()) if isinstance(v, np.ndarray)}
+    n = min(a.shape[0] for a in arrs.values())
+    row_bytes = 8 * sum(int(np.prod(a.shape[1:])) for a in arrs.values())
+    if n * row_bytes > DUMP_BYTES:
+        keep = DUMP_BYTES // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(20260).choice(n, size=keep, replace=False))
+        arrs = {k: a[rows] for k, a in arrs.items()}
+        arrs["sample_rows"] = rows
+    os.makedirs(d, exist_ok=True)
+    sfx = ".rank%d" % rank if world > 1 else ""
+    for k, a in arrs.items():
+        np.save(os.path.join(d, k + sfx + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def main():
@@ -242,11 +272,12 @@ def main():
     def timed(step):
         for _ in range(args.warmup):
             res = step()
-        # Inside the timed region only the roofline kernel (K1) carries HIP events; the per-kernel table of the line comes from a
+        # --full: inside the timed region only the roofline kernel (K1) carries HIP events; the per-kernel table of the line comes from a
         # few more steps behind it with every id timed (two event records per launch are host work in front of ~40 launches per
-        # chunk -- on the small chunks of config 5 the host's queueing IS on the critical path)
-        eng.prof_enable([K_SITE_SCAN])
-        eng.prof_reset()
+        # chunk -- on the small chunks of config 5 the host's queueing IS on the critical path).  Without --full nothing is timed per kernel.
+        if args.full:
+            eng.prof_enable([K_SITE_SCAN])
+            eng.prof_reset()
         # (the cyclic collector stays out of the timed region, as it stays out of the product's phasing calls -- session.no_gc_pauses: a full
         # collection walks every container this process holds, the generator's tables' wrappers included, and lands in whichever step crosses
         # the allocation threshold)
@@ -271,6 +302,8 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.SUM)
             timed.per_rank = [float(x) for x in t.tolist()]
             elapsed = max(timed.per_rank)
+        if not args.full:
+            return res, elapsed, None
         k1 = eng.prof_get(K_SITE_SCAN)
         eng.prof_enable(True)
         eng.prof_reset()
@@ -301,11 +334,14 @@ def main():
         rtrace.append([round((b - a) * 1e3, 2) for a, b in ((t0, t1), (t1, t2), (t2, time.perf_counter()))])
         return r
 
-    res_r, el_r, prof_r = timed(step_resident)
-    host_cpu_resident = timed.host_cpu_s
-    if rtrace:
-        print("[resident step, ms] drop_derived | read stage | allele balance:", rtrace, file=sys.stderr)
-    per_rank_r = list(timed.per_rank)
+    # (the headline with --no-staged; beside the staged headline, and as its parity check, under --full only)
+    res_r = prof_r = host_cpu_resident = per_rank_r = None
+    if args.full or args.no_staged:
+        res_r, el_r, prof_r = timed(step_resident)
+        host_cpu_resident = timed.host_cpu_s
+        if rtrace:
+            print("[resident step, ms] drop_derived | read stage | allele balance:", rtrace, file=sys.stderr)
+        per_rank_r = list(timed.per_rank)
 
     # ---------------------------------------------------------------- staged pass
     # (the pass itself is the product's: unfazed_amd/pipeline.py; what the decoders would leave in pinned memory -- the site windows and the
@@ -336,12 +372,12 @@ def main():
         host_cpu_staged = timed.host_cpu_s
         if trace:
             print("[staged step, ms] site stage 0, then per chunk: find (behind the read stage of chunk k - 2) | its results | enqueue records, the site windows of chunk k + 2 | queue the read stage of chunk k - 1 (config 5: + allele balance of chunk k - 2); last read stages:", trace[-2:], file=sys.stderr)
-        mism = sum(int((np.asarray(res_s[k]) != np.asarray(res_r[k])).sum()) for k in res_r)
+        mism = sum(int((np.asarray(res_s[k]) != np.asarray(res_r[k])).sum()) for k in res_r) if res_r is not None else None
         # The same steps as ONE stream of chunks (what a cohort run hands the pipeline: batch after batch): the first uploads of a step travel beside
         # the last read stages of the step before, so the head and the tail of the pipeline are paid once, not per step.  Reported beside `value`
         # (which stays the step-by-step pass: every step collected before the next one starts), never instead of it.
         streamed = None
-        if not args.one_site_table and not args.no_streamed and world == 1:
+        if args.full and not args.one_site_table and not args.no_streamed and world == 1:
             S = max(2, args.steps)
             rep = [dict(c, a=c["a"] + s_ * n, b=c["b"] + s_ * n) for s_ in range(S) for c in chunks]
             pipeline.run_pipelined(eng, P, mode, 2 * n, rep[: 2 * len(chunks)], cnv=cnv)  # (warm-up: two steps' worth)
@@ -366,10 +402,14 @@ def main():
         res = res_s
     else:
         res = res_r
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, rank, world)
 
     n_total = n * world if args.scaling == "weak" else sum(np.diff(shard.shard_bounds(args.dnms, world)))
-    value_resident = n_total * args.steps / el_r
-    ms_resident = el_r / args.steps * 1e3
+    value_resident = ms_resident = None
+    if res_r is not None:
+        value_resident = n_total * args.steps / el_r
+        ms_resident = el_r / args.steps * 1e3
     if staged:
         value = n_total * args.steps / staged["elapsed"]
         ms_per_step = staged["elapsed"] / args.steps * 1e3
@@ -390,64 +430,66 @@ def main():
                 "phase": round(prof[K_PHASE][0] / args.steps, 3),
                 "cnv_count": round(prof[K_CNV][0] / args.steps, 3)}
 
-    k1_ms, k1_n = prof_r[K_SITE_SCAN]
-    k1_us = k1_ms / max(1, k1_n) * 1e3
-    bytes_per_site = 20.0  # 19 B read (packed trio GT + 9 x u16) + 1 B class written; DESIGN.md "K1"
-    achieved = bytes_per_site * sc.n / (k1_us * 1e-6) / 1e9 if k1_n else 0.0
-    # counters come from a committed profile (separate --pmc passes, scripts/profile_round.sh) and are quoted only while that profile
-    # measured THIS build's kernels (it records the hash of the device sources); otherwise null + where to look
-    ksha = build.kernel_source_hash()
-    traffic, traffic_note = None, None
-    tpath = os.path.join(ROOT, "profiles", "k1_traffic.json")
-    if os.path.exists(tpath):
-        try:
-            tj = json.load(open(tpath))
-            if int(tj.get("n_sites", -1)) == sc.n and tj.get("kernel_source_sha") == ksha:
-                traffic = tj.get("hbm_bytes_per_launch")
-            else:
-                traffic_note = "profiles/k1_traffic.json was collected on other kernel sources (%s) or another table size: not quoted" % tj.get("kernel_source_sha")
-        except Exception:
-            traffic = None
-    # two byte counts: `achieved` / `frac` on the bytes the kernel moves (20 B per site: it does not read `pos`), and the same launch priced at
-    # SURVEY.md 8(d)'s fixed 24 B per site (pos + packed GT + 9 x u16 + class)
-    survey_bytes = 24.0 * sc.n
-    roofline = {"bound": "hbm", "kernel": "k_site_scan", "achieved": round(achieved, 1), "peak": 8000.0, "unit": "GB/s",
-                "frac": round(achieved / 8000.0, 4), "traffic": traffic, "avg_launch_us": round(k1_us, 2),
-                "algorithmic_bytes_per_launch": int(bytes_per_site * sc.n), "bytes_moved": int(bytes_per_site * sc.n),
-                "algorithmic_bytes_survey": int(survey_bytes),
-                "achieved_on_survey_bytes": round(survey_bytes / (k1_us * 1e-6) / 1e9, 1) if k1_n else 0.0,
-                "frac_on_survey_bytes": round(survey_bytes / (k1_us * 1e-6) / 1e9 / 8000.0, 4) if k1_n else 0.0,
-                "kernel_source_sha": ksha}
-    if traffic_note:
-        roofline["traffic_note"] = traffic_note
+    # (--full: the resident pass's kernel profile against the committed counters)
+    roofline = issue_model = None
+    if args.full:
+        k1_ms, k1_n = prof_r[K_SITE_SCAN]
+        k1_us = k1_ms / max(1, k1_n) * 1e3
+        bytes_per_site = 20.0  # 19 B read (packed trio GT + 9 x u16) + 1 B class written; DESIGN.md "K1"
+        achieved = bytes_per_site * sc.n / (k1_us * 1e-6) / 1e9 if k1_n else 0.0
+        # counters come from a committed profile (separate --pmc passes, scripts/profile_round.sh) and are quoted only while that profile
+        # measured THIS build's kernels (it records the hash of the device sources); otherwise null + where to look
+        ksha = build.kernel_source_hash()
+        traffic, traffic_note = None, None
+        tpath = os.path.join(ROOT, "profiles", "k1_traffic.json")
+        if os.path.exists(tpath):
+            try:
+                tj = json.load(open(tpath))
+                if int(tj.get("n_sites", -1)) == sc.n and tj.get("kernel_source_sha") == ksha:
+                    traffic = tj.get("hbm_bytes_per_launch")
+                else:
+                    traffic_note = "profiles/k1_traffic.json was collected on other kernel sources (%s) or another table size: not quoted" % tj.get("kernel_source_sha")
+            except Exception:
+                traffic = None
+        # two byte counts: `achieved` / `frac` on the bytes the kernel moves (20 B per site: it does not read `pos`), and the same launch priced at
+        # SURVEY.md 8(d)'s fixed 24 B per site (pos + packed GT + 9 x u16 + class)
+        survey_bytes = 24.0 * sc.n
+        roofline = {"bound": "hbm", "kernel": "k_site_scan", "achieved": round(achieved, 1), "peak": 8000.0, "unit": "GB/s",
+                    "frac": round(achieved / 8000.0, 4), "traffic": traffic, "avg_launch_us": round(k1_us, 2),
+                    "algorithmic_bytes_per_launch": int(bytes_per_site * sc.n), "bytes_moved": int(bytes_per_site * sc.n),
+                    "algorithmic_bytes_survey": int(survey_bytes),
+                    "achieved_on_survey_bytes": round(survey_bytes / (k1_us * 1e-6) / 1e9, 1) if k1_n else 0.0,
+                    "frac_on_survey_bytes": round(survey_bytes / (k1_us * 1e-6) / 1e9 / 8000.0, 4) if k1_n else 0.0,
+                    "kernel_source_sha": ksha}
+        if traffic_note:
+            roofline["traffic_note"] = traffic_note
 
-    # k_phase has no GB/s figure: it is bound by instruction issue (integer VALU work) with memory latency on top.  The
-    # counters of the same workload (profiles/phase_issue.json, scripts/profile_round.sh) give the floor: VALU
-    # wave-instructions x 4 cycles / 1024 SIMDs at the measured shader clock; frac = floor / this run's kernel time.
-    issue_model = None
-    tpath = os.path.join(ROOT, "profiles", "phase_issue.json")
-    ph_ms, ph_n = prof_r[K_PHASE]
-    if os.path.exists(tpath) and ph_n:
-        try:
-            tj = json.load(open(tpath))
-            if int(tj.get("dnms", -1)) == n and tj.get("kernel_source_sha") != ksha:
-                issue_model = {"kernel": "k_phase", "stale": True, "source": "profiles/phase_issue.json",
-                               "note": "collected on other kernel sources (%s): not quoted for this build (%s)" % (tj.get("kernel_source_sha"), ksha)}
-            elif int(tj.get("dnms", -1)) == n:
-                measured = ph_ms / ph_n
-                issue_model = {"kernel": "k_phase", "bound": "instruction issue (one wavefront per DNM, as many DNMs per SIMD as the LDS arenas leave room for: waves_per_simd); measured_ms covers the three launches of a batch (arena build, its larger-arena rerun, HBM build)",
-                               "valu_wave_instructions_per_dnm": round(tj["valu_wave_instructions_per_dnm_with_candidates"], 0),
-                               "valu_pipe_busy_frac_profiled": round(tj["valu_pipe_busy_frac"], 4),
-                               "valu_lane_utilisation": round(tj["valu_lane_utilisation"], 4),
-                               "wave_cycles_parked_frac": round(tj["wave_cycles_parked_frac"], 4),
-                               "waves_per_simd": round(tj["waves_per_simd"], 2), "shader_clock_GHz": round(tj["shader_clock_GHz"], 3),
-                               "valu_floor_ms": round(tj["valu_floor_ms"], 3), "measured_ms": round(measured, 3),
-                               "frac": round(tj["valu_floor_ms"] / measured, 4), "source": "profiles/phase_issue.json"}
-        except Exception:
-            issue_model = None
+        # k_phase has no GB/s figure: it is bound by instruction issue (integer VALU work) with memory latency on top.  The
+        # counters of the same workload (profiles/phase_issue.json, scripts/profile_round.sh) give the floor: VALU
+        # wave-instructions x 4 cycles / 1024 SIMDs at the measured shader clock; frac = floor / this run's kernel time.
+        tpath = os.path.join(ROOT, "profiles", "phase_issue.json")
+        ph_ms, ph_n = prof_r[K_PHASE]
+        if os.path.exists(tpath) and ph_n:
+            try:
+                tj = json.load(open(tpath))
+                if int(tj.get("dnms", -1)) == n and tj.get("kernel_source_sha") != ksha:
+                    issue_model = {"kernel": "k_phase", "stale": True, "source": "profiles/phase_issue.json",
+                                   "note": "collected on other kernel sources (%s): not quoted for this build (%s)" % (tj.get("kernel_source_sha"), ksha)}
+                elif int(tj.get("dnms", -1)) == n:
+                    measured = ph_ms / ph_n
+                    issue_model = {"kernel": "k_phase", "bound": "instruction issue (one wavefront per DNM, as many DNMs per SIMD as the LDS arenas leave room for: waves_per_simd); measured_ms covers the three launches of a batch (arena build, its larger-arena rerun, HBM build)",
+                                   "valu_wave_instructions_per_dnm": round(tj["valu_wave_instructions_per_dnm_with_candidates"], 0),
+                                   "valu_pipe_busy_frac_profiled": round(tj["valu_pipe_busy_frac"], 4),
+                                   "valu_lane_utilisation": round(tj["valu_lane_utilisation"], 4),
+                                   "wave_cycles_parked_frac": round(tj["wave_cycles_parked_frac"], 4),
+                                   "waves_per_simd": round(tj["waves_per_simd"], 2), "shader_clock_GHz": round(tj["shader_clock_GHz"], 3),
+                                   "valu_floor_ms": round(tj["valu_floor_ms"], 3), "measured_ms": round(measured, 3),
+                                   "frac": round(tj["valu_floor_ms"] / measured, 4), "source": "profiles/phase_issue.json"}
+            except Exception:
+                issue_model = None
 
     feed = feed_filler = None
-    if rank == 0 and world == 1 and not cnv and args.feed_dnms > 0:
+    if args.full and rank == 0 and world == 1 and not cnv and args.feed_dnms > 0:
         if getattr(bind_near_gpu, "compact", None):  # the files -> results pass is host work: 2 q CPUs next to each other, next to the GPU
             os.sched_setaffinity(0, bind_near_gpu.compact)
         elif getattr(bind_near_gpu, "before", None):  # ... or every core of the box
@@ -470,7 +512,7 @@ def main():
             feed_filler = ff
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu and args.cpu_dnms > 0:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and args.cpu_dnms > 0:
         if getattr(bind_near_gpu, "before", None):  # the CPU baseline gets every core of the box back
             os.sched_setaffinity(0, bind_near_gpu.before)
         cpu = cpu_baseline(args, wl, sc, ev, dn, per_ev, cl, cfg, P, cutoff, res, ev_vt, ev_refs, ev_alts, cnv)
@@ -484,11 +526,11 @@ def main():
                           "the same windows, all host threads) + %.2f s oracle at its best thread count" % (m_f, feed["cpu_decode_s"], feed["cpu_decode_records"], m_f / cpu["value"]))
 
     config5 = None
-    if rank == 0 and world == 1 and not cnv and not args.no_config5 and args.dnms == 100000:
+    if args.full and rank == 0 and world == 1 and not cnv and not args.no_config5 and args.dnms == 100000:
         # BASELINE configs[4] in the same driver-run line: the 10 k DEL/DUP workload as a child process (its own generator state and
         # contexts; this process has let go of nothing it needs and waits)
         try:
-            cmd = [sys.executable, os.path.abspath(__file__), "--workload", "cnv", "--steps", str(args.steps), "--warmup", str(args.warmup), "--no-config5",
+            cmd = [sys.executable, os.path.abspath(__file__), "--workload", "cnv", "--full", "--steps", str(args.steps), "--warmup", str(args.warmup), "--no-config5",
                    "--cpu-dnms", "10000" if not args.no_cpu else "0"] + (["--no-cpu"] if args.no_cpu else [])
             cp = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=900)
             line5 = [x for x in cp.stdout.decode().splitlines() if x.startswith("{")]
@@ -515,11 +557,11 @@ def main():
                        "dnms_per_gpu": n, "sites": sc.n, "coverage": "30x", "search_dist": 5000, "dnm_placement": "uniform",
                        "read_clusters": cl.n, "dnms_sharing_a_cluster": int(cl.nd[cl.nd > 1].sum()),
                        "alignment_records": wl.n_segs, "parallelism": "dnm-shard x%d, no collective" % world},
-            "value_resident": round(value_resident, 1), "ms_per_step_resident": round(ms_resident, 3),
+            "value_resident": round(value_resident, 1) if res_r is not None else None, "ms_per_step_resident": round(ms_resident, 3) if res_r is not None else None,
             # CPU seconds of rank 0's process per step (every thread of it): what eight ranks on one node would ask of the host's cores between them
-            "host_cpu_seconds_per_step": {"staged": round(staged["host_cpu_s"], 5) if staged else None, "resident": round(host_cpu_resident, 5)},
+            "host_cpu_seconds_per_step": {"staged": round(staged["host_cpu_s"], 5) if staged else None, "resident": round(host_cpu_resident, 5) if res_r is not None else None},
             "ms_per_step_by_rank": [round(x / args.steps * 1e3, 3) for x in (per_rank_s if staged else per_rank_r)],
-            "ms_per_step_resident_by_rank": [round(x / args.steps * 1e3, 3) for x in per_rank_r],
+            "ms_per_step_resident_by_rank": [round(x / args.steps * 1e3, 3) for x in per_rank_r] if res_r is not None else None,
             "roofline": roofline,
             "issue_model": issue_model,
             "cpu_baseline": cpu,
@@ -527,7 +569,7 @@ def main():
             "feed": feed,
             "feed_filler": feed_filler,
             "config5": config5,
-            "kernels_ms_per_step": kern_ms(prof_r),
+            "kernels_ms_per_step": kern_ms(prof_r) if prof_r is not None else None,
             "calls": {"phased": phased, "correct_vs_truth": correct, "status_counts": np.bincount(status, minlength=6).tolist(),
                       "dnms_redone_by_hbm_build_of_k_phase": getattr(timed, "hbm_build_dnms", None)},
             "generate_s": round(t_gen, 1), "numa_node": numa,
@@ -536,13 +578,21 @@ def main():
             out["link"] = {"bytes_per_step": int(staged["bytes"]), "read_records_staged": int(staged["records"]), "sites_staged": staged["sites"], "site_stage": staged["site_stage"],
                            "bytes_per_dnm": round(staged["bytes"] / n, 1),
                            "achieved_GBps": round(staged["bytes"] * args.steps / staged["elapsed"] / 1e9, 2), "peak_GBps": 64.0,
-                           "chunks": staged["chunks"], "decode_s": round(staged["decode_s"], 1),
-                           "result_mismatches_vs_resident": staged["mismatches_vs_resident"]}
-            out["kernels_ms_per_step_staged"] = kern_ms(staged["prof"])
+                           "chunks": staged["chunks"], "decode_s": round(staged["decode_s"], 1)}
+            if staged["mismatches_vs_resident"] is not None:
+                out["link"]["result_mismatches_vs_resident"] = staged["mismatches_vs_resident"]
+            if staged["prof"] is not None:
+                out["kernels_ms_per_step_staged"] = kern_ms(staged["prof"])
             if staged.get("streamed"):
                 st_ = dict(staged["streamed"])
                 st_["link_achieved_GBps"] = round(staged["bytes"] / (st_["ms_per_step"] * 1e-3) / 1e9, 2)
                 out["streamed"] = st_
+        if not args.full:  # (a plain run measured none of these)
+            for k in ("roofline", "issue_model", "cpu_baseline", "value_e2e", "feed", "feed_filler", "config5", "kernels_ms_per_step"):
+                del out[k]
+            if res_r is None:
+                for k in ("value_resident", "ms_per_step_resident", "ms_per_step_resident_by_rank"):
+                    del out[k]
         print(json.dumps(out))
     wl.free()
     if dist is not None:

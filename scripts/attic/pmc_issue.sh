@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="$ROOT/bench.py --no-staged --no-cpu --steps 2 --warmup 1 $*"
+ARGS="$ROOT/bench.py --full --no-staged --no-cpu --steps 2 --warmup 1 $*"
 rocprofv3 --output-format csv --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_INSTS_BRANCH SQ_INSTS_FLAT SQ_INSTS_VMEM SQ_WAVES -d $OUT/i1 -o run -- python3 $ARGS > $OUT/i1.log 2>&1
 rocprofv3 --output-format csv --kernel-trace --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_FLAT SQ_ACTIVE_INST_MISC SQ_BUSY_CYCLES SQ_THREAD_CYCLES_VALU -d $OUT/i2 -o run -- python3 $ARGS > $OUT/i2.log 2>&1
 rocprofv3 --output-format csv --kernel-trace --pmc SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_FLAT_NO_LDS SQ_INST_CYCLES_SALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY -d $OUT/i3 -o run -- python3 $ARGS > $OUT/i3.log 2>&1

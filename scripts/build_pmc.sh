@@ -7,7 +7,7 @@ for e in "$@"; do export "$e"; done
 cd /tmp && export TMPDIR=/tmp
 OUT="$ROOT/gpurun_out/$TAG"; mkdir -p "$OUT"; rm -rf "$OUT/bp_"*
 ONLY='--kernel-include-regex k_pack_link|k_pack_rec'
-ARGS="$ROOT/bench.py --no-cpu --feed-dnms 0 --no-config5 --steps 1 --warmup 1"
+ARGS="$ROOT/bench.py --full --no-cpu --feed-dnms 0 --no-config5 --steps 1 --warmup 1"
 run() { n=$1; shift; rocprofv3 $ONLY --output-format csv --kernel-trace --pmc "$@" -d "$OUT/bp_$n" -o run -- python3 $ARGS > "$OUT/bp_$n.log" 2>&1; }
 run a SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA
 run b SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_BRANCH SQ_THREAD_CYCLES_VALU

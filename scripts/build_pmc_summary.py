@@ -20,7 +20,7 @@ except Exception:
 out = {
     "kernel": "k_pack_link (header build of the link form, csrc/k_reads.hip)",
     "kernel_source_sha": j.get("bench", {}).get("kernel_source_sha"),
-    "how": "scripts/build_pmc.sh: rocprofv3 --kernel-trace --pmc in six passes over `bench.py --no-cpu --feed-dnms 0 --no-config5 --steps 1 --warmup 1` (the staged pass of "
+    "how": "scripts/build_pmc.sh: rocprofv3 --kernel-trace --pmc in six passes over `bench.py --full --no-cpu --feed-dnms 0 --no-config5 --steps 1 --warmup 1` (the staged pass of "
            "100 k DNMs: %s chunks; under --pmc kernels run one at a time: solo durations); per launch, mean over the launches; scripts/build_pmc_summary.py" % j.get("bench", {}).get("chunks"),
     "records_per_launch_mean": recs,
     "launches": k["counters_per_launch"]["SQ_WAVES"]["launches"],

@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 for e in "$@"; do export "$e"; done
 cd /tmp && export TMPDIR=/tmp
 OUT="$ROOT/gpurun_out/bsolo"; rm -rf "$OUT"; mkdir -p "$OUT"
-rocprofv3 --kernel-include-regex 'k_pack|k_pair_link|k_expand_seq2|k_widen8|k_fold_complex|k_phase' --output-format csv --kernel-trace --pmc SQ_WAVES GRBM_GUI_ACTIVE -d "$OUT/a" -o run -- python3 "$ROOT/bench.py" --no-cpu --feed-dnms 0 --no-config5 --steps 2 --warmup 1 > "$OUT/a.log" 2>&1
+rocprofv3 --kernel-include-regex 'k_pack|k_pair_link|k_expand_seq2|k_widen8|k_fold_complex|k_phase' --output-format csv --kernel-trace --pmc SQ_WAVES GRBM_GUI_ACTIVE -d "$OUT/a" -o run -- python3 "$ROOT/bench.py" --full --no-cpu --feed-dnms 0 --no-config5 --steps 2 --warmup 1 > "$OUT/a.log" 2>&1
 cd "$ROOT"
 python3 - <<'P'
 import pandas as pd, glob

@@ -3,17 +3,18 @@
 # when, where the device idles, and what the host is doing meanwhile
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
-rm -rf "$ROOT/gpurun_out/cnvtl"
-rocprofv3 --output-format csv --kernel-trace --hip-runtime-trace -d $ROOT/gpurun_out/cnvtl -o run -- python3 $ROOT/bench.py --workload cnv --no-cpu --steps 3 --warmup 2 ${CNV_ARGS} > /dev/null 2>&1
+export TL=$(mktemp -d)  # the trace, removed at the end
+rocprofv3 --output-format csv --kernel-trace --hip-runtime-trace -d $TL -o run -- python3 $ROOT/bench.py --full --workload cnv --no-cpu --steps 3 --warmup 2 ${CNV_ARGS} > /dev/null 2>&1
 cd $ROOT
-ls gpurun_out/cnvtl
+ls $TL
 python3 - <<'P'
+import os
 import pandas as pd, numpy as np
-k = pd.read_csv('gpurun_out/cnvtl/run_kernel_trace.csv').sort_values('Start_Timestamp').reset_index(drop=True)
+k = pd.read_csv(os.environ['TL'] + '/run_kernel_trace.csv').sort_values('Start_Timestamp').reset_index(drop=True)
 k['nm'] = k.Kernel_Name.str.replace('void ', '').str.replace('(anonymous namespace)::', '', regex=False).str.split('(').str[0].str[:30]
 ph = np.nonzero(k.nm.str.startswith('k_phase<true>').values)[0]
 # the staged steps come before the resident ones: the staged step's read stages are the chunked ones -- take the LAST step that has 3 read stages close together
-a = pd.read_csv('gpurun_out/cnvtl/run_hip_api_trace.csv').sort_values('Start_Timestamp').reset_index(drop=True)
+a = pd.read_csv(os.environ['TL'] + '/run_hip_api_trace.csv').sort_values('Start_Timestamp').reset_index(drop=True)
 cn = np.nonzero(k.nm.str.contains('k_cnv_count').values)[0]
 # staged steps: k_cnv_count appears 3x per step; resident 1x per step.  find the last triple whose span < 8 ms
 t = k.Start_Timestamp.values
@@ -30,4 +31,4 @@ hs['s'] = (hs.Start_Timestamp - lo) / 1e6; hs['e'] = (hs.End_Timestamp - lo) / 1
 ks[['nm', 's', 'e']].to_csv('gpurun_out/cnv_step_kernels.csv', index=False, float_format='%.4f')
 hs[['Function', 's', 'e']].to_csv('gpurun_out/cnv_step_hip.csv', index=False, float_format='%.4f')
 P
-rm -rf gpurun_out/cnvtl
+rm -rf "$TL"

@@ -7,7 +7,7 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd $ROOT
 for J in device host; do
-  timeout 900 python bench.py --no-cpu --no-config5 --no-staged --steps 3 --warmup 1 --feed-joins $J "$@" > $OUT/bench_$J.log 2> $OUT/bench_$J.err; echo "bench $J rc $?"
+  timeout 900 python bench.py --full --no-cpu --no-config5 --no-staged --steps 3 --warmup 1 --feed-joins $J "$@" > $OUT/bench_$J.log 2> $OUT/bench_$J.err; echo "bench $J rc $?"
   grep "^{" $OUT/bench_$J.log | tail -1 | python -c "
 import json,sys
 j=json.loads(sys.stdin.read())

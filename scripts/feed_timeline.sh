@@ -4,7 +4,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
 OUT=$ROOT/gpurun_out/ftl
 rm -rf $OUT
-UZ_BENCH_NO_PRODUCT=1 rocprofv3 --output-format csv --kernel-trace --memory-copy-trace -d $OUT -o run -- python3 $ROOT/bench.py --no-cpu --no-config5 --no-staged --steps 1 --warmup 0 --feed-reps 2 "$@" > $OUT.log 2>&1
+UZ_BENCH_NO_PRODUCT=1 rocprofv3 --output-format csv --kernel-trace --memory-copy-trace -d $OUT -o run -- python3 $ROOT/bench.py --full --no-cpu --no-config5 --no-staged --steps 1 --warmup 0 --feed-reps 2 "$@" > $OUT.log 2>&1
 cd $ROOT
 python3 - <<'P'
 import pandas as pd, numpy as np

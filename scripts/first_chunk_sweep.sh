@@ -1,5 +1,5 @@
 run() {
-  python3 bench.py --no-cpu --feed-dnms 0 --no-config5 --steps 12 --warmup 3 "$@" 2>/dev/null | tail -1 | python3 -c "
+  python3 bench.py --full --no-cpu --feed-dnms 0 --no-config5 --steps 12 --warmup 3 "$@" 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('  $*: ms', d['ms_per_step'], 'mismatches', d['link']['result_mismatches_vs_resident'])"
 }

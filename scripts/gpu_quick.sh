@@ -8,7 +8,7 @@ mkdir -p $OUT
 cd $ROOT
 timeout 1500 python -m pytest tests -m gpu -x -q "$@" > $OUT/pytest.log 2>&1; echo "pytest rc $?" >> $OUT/pytest.log
 tail -5 $OUT/pytest.log
-timeout 600 python bench.py --no-cpu --no-config5 --feed-dnms 0 --steps 10 > $OUT/bench.log 2> $OUT/bench.err; echo "bench rc $?"
+timeout 600 python bench.py --full --no-cpu --no-config5 --feed-dnms 0 --steps 10 > $OUT/bench.log 2> $OUT/bench.err; echo "bench rc $?"
 grep "^{" $OUT/bench.log | tail -1 | python -c "
 import json,sys
 j=json.loads(sys.stdin.read())

@@ -51,7 +51,7 @@ def c(kernel, name):
     return pmc[kernel]["counters_per_launch"][name]["mean"]
 
 
-how = ("rocprofv3 --kernel-trace --pmc <counters> in separate passes (scripts/profile_round.sh) over `bench.py --no-staged --no-cpu "
+how = ("rocprofv3 --kernel-trace --pmc <counters> in separate passes (scripts/profile_round.sh) over `bench.py --full --no-staged --no-cpu "
        "--steps 3 --warmup 1` (100 k DNMs, 20 M sites); per launch, mean over the launches of the run")
 # K1: pure 16-byte streams -> the guide's x2 correction of FETCH_SIZE applies (MI355X_MICROARCH.md, HBM)
 f, w = c("k_site_scan", "FETCH_SIZE") * 1024, c("k_site_scan", "WRITE_SIZE") * 1024

@@ -12,7 +12,7 @@ for spec in "$@"; do
   [ "$v" != base ] && export UZ_HIP_LIB="$ROOT/build_variants/libunfazed_hip_$v.so"
   [ -n "$kb" ] && [ "$kb" != 0 ] && export UZ_PHASE_LDS_KB=$kb
   [ -n "$wgs" ] && export UZ_PHASE_WGS_PER_CU=$wgs
-  timeout 300 python bench.py --no-staged --no-cpu --no-config5 --feed-dnms 0 --steps 10 > "$OUT/$v.$kb.$wgs.$rep.log" 2> "$OUT/$v.$kb.$wgs.$rep.err"
+  timeout 300 python bench.py --full --no-staged --no-cpu --no-config5 --feed-dnms 0 --steps 10 > "$OUT/$v.$kb.$wgs.$rep.log" 2> "$OUT/$v.$kb.$wgs.$rep.err"
   grep "^{" "$OUT/$v.$kb.$wgs.$rep.log" | tail -1 | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print('$spec', $rep, j['ms_per_step_resident'], j['kernels_ms_per_step'], j['calls']['dnms_redone_by_hbm_build_of_k_phase'])"

@@ -7,7 +7,7 @@ i=0
 for rep in 1 2; do
 for e in "$@"; do
   i=$((i+1))
-  env $e timeout 300 python bench.py --no-staged --no-cpu --no-config5 --feed-dnms 0 --steps 10 > "$OUT/run$i.log" 2> "$OUT/run$i.err"
+  env $e timeout 300 python bench.py --full --no-staged --no-cpu --no-config5 --feed-dnms 0 --steps 10 > "$OUT/run$i.log" 2> "$OUT/run$i.err"
   grep "^{" "$OUT/run$i.log" | tail -1 | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print('[$e]', $rep, j['ms_per_step_resident'], j['kernels_ms_per_step'], j['calls']['dnms_redone_by_hbm_build_of_k_phase'])"

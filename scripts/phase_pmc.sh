@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT="$ROOT/gpurun_out/$TAG"; mkdir -p "$OUT"
 for e in "$@"; do export "$e"; done
 cd /tmp && export TMPDIR=/tmp
-ARGS="$ROOT/bench.py --no-staged --no-cpu --steps 3 --warmup 1 --feed-dnms 0 --no-config5"
+ARGS="$ROOT/bench.py --full --no-staged --no-cpu --steps 3 --warmup 1 --feed-dnms 0 --no-config5"
 ONLY='--kernel-include-regex k_phase<'
 run() { n=$1; shift; rocprofv3 $ONLY --output-format csv --kernel-trace --pmc "$@" -d "$OUT/$n" -o run -- python3 $ARGS > "$OUT/$n.log" 2>&1; }
 run sq SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA

@@ -12,4 +12,4 @@ out = os.path.join(ROOT, "build_variants", "libunfazed_hip_timing.so")
 os.makedirs(os.path.dirname(out), exist_ok=True)
 build.build(extra_flags=["-DUZ_PHASE_TIMING"] + sys.argv[1:], out=out)  # cross-compiles in the authoring container; fresh builds travel
 env = dict(os.environ, UZ_HIP_LIB=out)
-sys.exit(subprocess.call([sys.executable, os.path.join(ROOT, "bench.py"), "--no-staged", "--no-cpu", "--steps", "2", "--warmup", "1"], env=env))
+sys.exit(subprocess.call([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-staged", "--no-cpu", "--steps", "2", "--warmup", "1"], env=env))

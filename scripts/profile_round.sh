@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="$ROOT/bench.py --no-staged --no-cpu --steps 3 --warmup 1 --feed-dnms 0 --no-config5"
+ARGS="$ROOT/bench.py --full --no-staged --no-cpu --steps 3 --warmup 1 --feed-dnms 0 --no-config5"
 # counters only for the product's kernels (the synthetic generator's launches would be serialised and counted too)
 ONLY='--kernel-include-regex k_phase|k_site_scan|k_window|k_pack_rec|k_pack_link|k_expand_seq2|k_cnv|k_bounds_reduce'
 rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/stats -o run -- python3 $ARGS > $OUT/stats.log 2>&1
@@ -44,22 +44,22 @@ find $OUT -name "*kernel_trace.csv" -delete; find $OUT -name "*agent_info.csv" -
 du -sh $OUT
 # the staged pass (the headline `value`): kernel statistics of the command the driver runs, without the CPU legs
 cd /tmp
-rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/staged -o run -- python3 $ROOT/bench.py --no-cpu --feed-dnms 0 --no-config5 --steps 5 --warmup 1 > $OUT/staged.log 2>&1
+rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/staged -o run -- python3 $ROOT/bench.py --full --no-cpu --feed-dnms 0 --no-config5 --steps 5 --warmup 1 > $OUT/staged.log 2>&1
 cd $ROOT
 find $OUT/staged -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/staged_kernel_stats.csv
 grep "^{" $OUT/staged.log | tail -1 > $OUT/bench_staged_under_rocprof.json
 find $OUT -name "*kernel_trace.csv" -delete; find $OUT -name "*agent_info.csv" -delete
 # the feed pass (files -> results: BGZF inflate, CRC-32, record walk, descriptor filter, extract on the device): kernel statistics, then counters of its kernels
 cd /tmp
-UZ_BENCH_NO_PRODUCT=1 rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/feed -o run -- python3 $ROOT/bench.py --no-cpu --no-config5 --no-staged --steps 1 --warmup 0 > $OUT/feed.log 2>&1
+UZ_BENCH_NO_PRODUCT=1 rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/feed -o run -- python3 $ROOT/bench.py --full --no-cpu --no-config5 --no-staged --steps 1 --warmup 0 > $OUT/feed.log 2>&1
 cd $ROOT
 find $OUT/feed -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/feed_kernel_stats.csv
 grep "^{" $OUT/feed.log | tail -1 > $OUT/bench_feed_under_rocprof.json
 cd /tmp
 FONLY='--kernel-include-regex k_bam_walk|k_bam_extract|k_desc_filter|k_tab_insert|k_bgzf_crc32|k_bgzf_inflate|k_join_|k_final_'
-UZ_BENCH_NO_PRODUCT=1 rocprofv3 $FONLY --output-format csv --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d $OUT/feedpmc -o run -- python3 $ROOT/bench.py --no-cpu --no-config5 --no-staged --steps 1 --warmup 0 > $OUT/feedpmc.log 2>&1
-UZ_BENCH_NO_PRODUCT=1 rocprofv3 $FONLY --output-format csv --kernel-trace --pmc FETCH_SIZE -d $OUT/feedfetch -o run -- python3 $ROOT/bench.py --no-cpu --no-config5 --no-staged --steps 1 --warmup 0 > $OUT/feedfetch.log 2>&1
-UZ_BENCH_NO_PRODUCT=1 rocprofv3 $FONLY --output-format csv --kernel-trace --pmc WRITE_SIZE -d $OUT/feedwrite -o run -- python3 $ROOT/bench.py --no-cpu --no-config5 --no-staged --steps 1 --warmup 0 > $OUT/feedwrite.log 2>&1
+UZ_BENCH_NO_PRODUCT=1 rocprofv3 $FONLY --output-format csv --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d $OUT/feedpmc -o run -- python3 $ROOT/bench.py --full --no-cpu --no-config5 --no-staged --steps 1 --warmup 0 > $OUT/feedpmc.log 2>&1
+UZ_BENCH_NO_PRODUCT=1 rocprofv3 $FONLY --output-format csv --kernel-trace --pmc FETCH_SIZE -d $OUT/feedfetch -o run -- python3 $ROOT/bench.py --full --no-cpu --no-config5 --no-staged --steps 1 --warmup 0 > $OUT/feedfetch.log 2>&1
+UZ_BENCH_NO_PRODUCT=1 rocprofv3 $FONLY --output-format csv --kernel-trace --pmc WRITE_SIZE -d $OUT/feedwrite -o run -- python3 $ROOT/bench.py --full --no-cpu --no-config5 --no-staged --steps 1 --warmup 0 > $OUT/feedwrite.log 2>&1
 cd $ROOT
 (python3 scripts/pmc_rows.py $OUT/feedpmc; python3 scripts/pmc_rows.py $OUT/feedfetch; python3 scripts/pmc_rows.py $OUT/feedwrite) > $OUT/feed_pmc.txt 2>&1
 find $OUT -name "*kernel_trace.csv" -delete; find $OUT -name "*agent_info.csv" -delete; find $OUT -name "*counter_collection.csv" -size +4M -delete
@@ -103,7 +103,7 @@ bash scripts/resident_timeline.sh > $OUT/resident_timeline.txt 2>&1
 cp gpurun_out/resident_timeline.json $OUT/resident_timeline.json 2>/dev/null
 # the driver's command, last: the bench line of the round
 cd $ROOT
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_line.log 2> $OUT/bench_line.err
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_line.log 2> $OUT/bench_line.err
 grep "^{" $OUT/bench_line.log | tail -1 > $OUT/bench_line.json
-python3 bench.py --no-cpu --no-config5 --feed-dnms 0 --dnms 12500 --steps 20 --warmup 5 2>/dev/null | grep "^{" | tail -1 > $OUT/bench_line_shard12500.json
+python3 bench.py --full --no-cpu --no-config5 --feed-dnms 0 --dnms 12500 --steps 20 --warmup 5 2>/dev/null | grep "^{" | tail -1 > $OUT/bench_line_shard12500.json
 du -sh $OUT

@@ -1,6 +1,6 @@
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 run() {
-  python3 bench.py --no-cpu --feed-dnms 0 --no-config5 --steps 20 --warmup 5 "$@" 2>/dev/null | tail -1 | python3 -c "
+  python3 bench.py --full --no-cpu --feed-dnms 0 --no-config5 --steps 20 --warmup 5 "$@" 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('  $*: ms', d['ms_per_step'], 'resident', d['ms_per_step_resident'], 'cpu', d['host_cpu_seconds_per_step'], 'mism', d['link']['result_mismatches_vs_resident'])"
 }

@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
 OUT=$ROOT/gpurun_out/stl
 rm -rf $OUT
-rocprofv3 --output-format csv --kernel-trace --memory-copy-trace -d $OUT -o run -- python3 $ROOT/bench.py --no-cpu --feed-dnms 0 --no-config5 --steps 4 --warmup 2 "$@" > $OUT.log 2>&1
+rocprofv3 --output-format csv --kernel-trace --memory-copy-trace -d $OUT -o run -- python3 $ROOT/bench.py --full --no-cpu --feed-dnms 0 --no-config5 --steps 4 --warmup 2 "$@" > $OUT.log 2>&1
 cd $ROOT
 python3 - <<'P'
 import pandas as pd, numpy as np, json

@@ -18,7 +18,7 @@ def test_n_ranks_on_one_device(ranks, hip_lib):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--dnms", "6000", "--sites", "1500000", "--steps", "2", "--warmup", "1",
-                          "--no-cpu", "--feed-dnms", "0", "--no-config5"], env=env, capture_output=True, text=True, timeout=600)
+                          "--no-cpu", "--feed-dnms", "0", "--no-config5", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [x for x in out.stdout.splitlines() if x.startswith("{")]
     assert len(lines) == 1  # rank 0 alone prints

@@ -1,7 +1,7 @@
 """Native decoders (libunfazed_io.so, include/unfazed_io.h) against the Python decoders that state
 the formats (unfazed_amd/io_bam.py, io_vcf.py): every column of the two tables must be equal, on
 the synthetic trio files, on hand-made edge cases, and on the VCFs the reference ships under
-test/data when this container has them.  CPU only."""
+test/data (held as fixtures under tests/golden/refdata).  CPU only."""
 import ctypes as C
 import gzip
 import os
@@ -179,15 +179,12 @@ def test_vcf_errors(tmp_path):
     assert e.value.code == -3
 
 
-REF_DATA = "/root/reference/test/data"
+REF_DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "refdata")  # the reference's test/data, as fixtures
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="the reference's test data is only present in the authoring container")
 @pytest.mark.parametrize("name", ["trio_hets_snvs_chr22.vcf.gz", "trio_hets_svs_chr22.vcf.gz", "trio_svs_chr22.vcf.gz"])
 def test_reference_vcfs(name):
     path = os.path.join(REF_DATA, name)
-    if not os.path.exists(path):
-        pytest.skip("absent")
     t = _same_sites(path, 4)
     assert t.n_sites > 0
 
