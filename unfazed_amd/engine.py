@@ -109,26 +109,6 @@ def load_library(path: Optional[str] = None):
     return L
 
 
-class _CappedWalk:
-    """the engine's walk / join primitives for io_native.BamSource.select_kept(join=...), with the cap on a walked batch's inflated bytes applied
-    where the plan is first seen"""
-
-    def __init__(self, eng, cap: int):
-        self._eng, self._cap = eng, int(cap)
-
-    def walk(self, plan):
-        if int(plan["out_bytes"]) > self._cap:
-            raise _WalkTooLarge()
-        return self._eng.walk(plan)
-
-    def __getattr__(self, name):
-        return getattr(self._eng, name)
-
-
-class _WalkTooLarge(Exception):
-    """the blocks of a batch inflate to more than the device walk keeps in HBM (HipEngine.stage_reads falls back to the host route)"""
-
-
 class HipEngine:
     """One context on one GPU.  Backend interface used by hostpath.PhasingHost."""
 
@@ -153,23 +133,13 @@ class HipEngine:
         # one; with the joins on the device the device's chain is the bound and a batch's walk -- a latency-bound kernel of ~1 900 wavefronts -- leaves
         # the chip to the next batch's inflate: 1 / 2 / 3 at once = 117 / 130 / 128 k DNMs/s in bench.py's feed pass
         self._walk_sem = threading.BoundedSemaphore(int(os.environ.get("UZ_WALKS_AT_ONCE", "2")))
-        self._inflate_bufs = None  # PinnedPair of upload_reads_staged
-        self._stage_pool = None    # PinnedPool of upload_reads_staged: the staged columns' page-locked block, kept from batch to batch
-        self._chunk_pools = [None, None]  # stage_reads: two alternating sets of page-locked buffers (columns; gathered / inflated blocks)
-        self._chunk_pairs = [None, None]
+        self._slots = {}  # stage_reads: slot -> (PinnedPool of the staged columns, PinnedPair of the gathered / inflated blocks)
 
     def close(self):
-        if getattr(self, "_inflate_bufs", None) is not None:
-            self._inflate_bufs.free_all()
-            self._inflate_bufs = None
-        if getattr(self, "_stage_pool", None) is not None:
-            self._stage_pool.free_all()
-            self._stage_pool = None
-        for k in range(len(getattr(self, "_chunk_pools", []))):
-            if self._chunk_pools[k] is not None:
-                self._chunk_pools[k].free_all()
-                self._chunk_pairs[k].free_all()
-                self._chunk_pools[k] = self._chunk_pairs[k] = None
+        for pool, pair in getattr(self, "_slots", {}).values():
+            pool.free_all()
+            pair.free_all()
+        self._slots = {}
         if getattr(self, "h", None):
             self.L.uz_destroy(self.h)
             self.h = None
@@ -272,111 +242,63 @@ class HipEngine:
         return rid.value
 
     def upload_reads_staged(self, src, fc, flo, fhi, fex, min_base_qual: int, all_bases: bool = False, wide_no_units: bool = False):
-        """One batch straight from an indexed BAM (io_native.BamSource): the records its fetches return + their mates, built in the
-        link form in pinned memory by one pass over the file's blocks (uz_bam_stage_*), uploaded as one table.
-        -> (reads id, the staged view: `.qnames` maps the name ids of the result lists back to strings)"""
-        # the page-locked block of the staged columns is kept from batch to batch (pinning a gigabyte takes about a second: round 3's
-        # product route spent 1.2 s of its 2.4 s per 20 k DNMs there): rewound when it is large enough, replaced when not
-        if self._stage_pool is None:
-            self._stage_pool = PinnedPool()
-        pool = self._stage_pool
-        pool.keep = True
+        """One batch straight from an indexed BAM (io_native.BamSource) uploaded as one table: stage_reads on a slot of its own, then
+        upload_reads_packed.  -> (reads id, the staged view: `.qnames` maps the name ids of the result lists back to strings -- names of the
+        caller's own, valid after the table is freed and after later batches are staged on any route)"""
+        staged = self.stage_reads(src, fc, flo, fhi, fex, min_base_qual, all_bases=all_bases, wide_no_units=wide_no_units, slot="single")
         rid = None
-        if os.environ.get("UZ_INFLATE", "device") == "device" and os.environ.get("UZ_WALK", "device") == "device":
-            # the record walk on the device (include/uz_bamwalk.h; stage_reads has the chunked form): blocks inflated, checked and walked in HBM, the
-            # joins here on descriptors, the table unpacked where the records lie.  UZ_WALK=host: the link form below
-            if self._inflate_bufs is None:
-                self._inflate_bufs = PinnedPair()
-            pair = self._inflate_bufs
-            pair.start()
-            cap = int(os.environ.get("UZ_WALK_MAX_BYTES", 16 << 30))  # (stage_reads: a batch beyond it takes the host route below)
-
-            def walk(plan):
-                if int(plan["out_bytes"]) > cap:
-                    raise _WalkTooLarge()
-                return self.bam_walk(plan, alloc=pair.alloc)
-            try:
-                # (UZ_JOINS=host: the descriptors come down and the host joins them, round 5's route; default: the joins on the device too, k_bamjoin.hip)
-                dev_joins = os.environ.get("UZ_JOINS", "device") == "device"
-                kb = src.select_kept(fc, flo, fhi, int(min_base_qual), walk=None if dev_joins else walk, join=_CappedWalk(self, cap) if dev_joins else None,
-                                     all_bases=bool(all_bases), alloc=pair.alloc, extra=fex, release=self.bam_walk_release)
-            except _WalkTooLarge:
-                kb = None
-            if kb is not None:
-                rid = self.reads_from_bam(kb, names=True)
-                if getattr(kb, "joined", False):  # (this caller may free the table before it asks for names: they come down now, all of them)
-                    kb.qnames = kb.qnames.frozen()
-                names = type("StagedNames", (), {})()
-                names.qnames, names.io_stats, names.timing = kb.qnames, kb.io_stats, kb.timing
-                return rid, names
         try:
-            inflate = inflate_alloc = None
-            if os.environ.get("UZ_INFLATE", "device") == "device":  # the batch's BGZF blocks inflated on the device (UZ_INFLATE=host: by the host's cores)
-                if self._inflate_bufs is None:
-                    self._inflate_bufs = PinnedPair()
-                self._inflate_bufs.start()
-                inflate, inflate_alloc = self.inflate_blocks, self._inflate_bufs.alloc
-            packed = src.select(fc, flo, fhi, int(min_base_qual), pool=pool, all_bases=bool(all_bases), extra=fex, wide_no_units=bool(wide_no_units),
-                                inflate=inflate, inflate_alloc=inflate_alloc)
-            pool.end_slab()
-            rid = self.upload_reads_packed(packed)
-            self.wait_reads(rid)  # the pinned buffers go back right away
-            self._staged.pop(rid, None)
+            rid = self.upload_reads_packed(staged)
+            if self._staged.get(rid) is staged:  # the link form: the pinned columns go back right away (a walked batch's table was built from HBM)
+                self.wait_reads(rid)
+                self._staged.pop(rid)
         except BaseException:
-            if rid is not None:  # the copy may still be reading the pinned block: let it finish before the block goes back
+            if self._staged.get(rid) is staged:  # the copy may still be reading the pinned block: let it finish before the block goes back
                 try:
                     self.wait_reads(rid)
                 except UnfazedHipError:
                     pass
                 self._staged.pop(rid, None)
             raise
-        names = type("StagedNames", (), {})()
-        names.qnames, names.io_stats, names.timing = packed.qnames, packed.io_stats, packed.timing
-        return rid, names
+        if hasattr(staged.qnames, "frozen"):  # names in the table or in the slot's buffers (a walked batch): copied out, all of them
+            staged.qnames = staged.qnames.frozen()
+        return rid, staged
 
-    def stage_reads(self, src, fc, flo, fhi, fex, min_base_qual: int, all_bases: bool = False, wide_no_units: bool = False, slot: int = 0):
-        """The first half of upload_reads_staged alone -- the batch's records built in the link form in page-locked memory -- for a caller that
-        overlaps it with the device work of the batch before (hostpath: chunks of a large batch; may be called from a worker thread, the
-        device inflates the BGZF blocks on streams of its own).  slot: which set of page-locked buffers to use (sets are made as they are asked
-        for); the block of a slot is re-used by the next stage_reads on it, so the table staged there must have landed on the device by then.
-        -> the packed view for upload_reads_packed (`.qnames`, `.io_stats`, `.timing` ride on it)"""
-        slot = int(slot)
-        while len(self._chunk_pools) <= slot:
-            self._chunk_pools.append(None)
-            self._chunk_pairs.append(None)
-        if self._chunk_pools[slot] is None:
-            self._chunk_pools[slot] = PinnedPool()
-            self._chunk_pools[slot].keep = True
-            self._chunk_pairs[slot] = PinnedPair()
-        pool, pair = self._chunk_pools[slot], self._chunk_pairs[slot]
-        inflate = inflate_alloc = None
-        if os.environ.get("UZ_INFLATE", "device") == "device" and os.environ.get("UZ_WALK", "device") == "device":
-            # the record walk on the device too (include/uz_bamwalk.h): the batch's blocks are inflated AND walked in HBM, the host runs the joins on
-            # 64-byte descriptors, and upload_reads_packed builds the table from the bytes the walk left on the device (UZ_WALK=host: the link form)
-            from . import io_native
+    def stage_reads(self, src, fc, flo, fhi, fex, min_base_qual: int, all_bases: bool = False, wide_no_units: bool = False, slot=0):
+        """One batch of an indexed BAM (io_native.BamSource) -- the records its fetches return + their mates -- made ready for
+        upload_reads_packed, by the route the switches choose (read here, on every call):
+          default          the blocks go up and are inflated, checked and walked in HBM (include/uz_bamwalk.h), the joins run there too
+                           (csrc/k_bamjoin.hip) -> io_native.KeptBatch, whose table is built where the records lie;
+          UZ_JOINS=host    ... the walk's descriptors come down and the host joins them (round 5's route);
+          UZ_WALK=host     the link form, built in page-locked memory by one pass over the blocks (uz_bam_stage_*), the blocks inflated by the
+                           device (inflate_blocks) -> the packed view;
+          UZ_INFLATE=host  ... the blocks inflated by the host's cores.
+        A walked batch keeps its compressed blocks, the inflated bytes and worst-case descriptor slices (64 B per 36 B of inflated data) in HBM
+        until its table is built, in one of four slots: a batch whose blocks inflate to more than UZ_WALK_MAX_BYTES takes the link form instead
+        of failing in hipMalloc.
+        slot: the set of page-locked buffers to use, made when first asked for and kept from batch to batch (pinning a gigabyte takes about a
+        second: round 3's product route spent 1.2 s of its 2.4 s per 20 k DNMs there).  The next stage_reads on a slot re-uses them: the table
+        staged there must have landed on the device by then, and names that lie there (host joins) answer for the later batch.  May be called
+        from a worker thread (hostpath._chunked_batch stages chunk k + 1 beside the device work of chunk k).
+        `.qnames`, `.io_stats`, `.timing` ride on the result."""
+        if slot not in self._slots:
+            pool = PinnedPool()
+            pool.keep = True
+            self._slots[slot] = (pool, PinnedPair())
+        pool, pair = self._slots[slot]
+        inflate = os.environ.get("UZ_INFLATE", "device") == "device"
+        if inflate and os.environ.get("UZ_WALK", "device") == "device":
             pair.start()
-            # a walked batch keeps its compressed blocks, the inflated bytes and worst-case descriptor slices (64 B per 36 B of inflated data) in
-            # HBM until its table is built, in one of four slots: a batch whose blocks inflate to more than the cap takes the host route below
-            # (the link form: nothing but the packed table reaches the device) instead of failing in hipMalloc
-            cap = int(os.environ.get("UZ_WALK_MAX_BYTES", 16 << 30))
-
-            def walk(plan):
-                if int(plan["out_bytes"]) > cap:
-                    raise _WalkTooLarge()
-                return self.bam_walk(plan, alloc=pair.alloc)
-            try:
-                dev_joins = os.environ.get("UZ_JOINS", "device") == "device"  # (as upload_reads_staged)
-                kb = src.select_kept(fc, flo, fhi, int(min_base_qual), walk=None if dev_joins else walk, join=_CappedWalk(self, cap) if dev_joins else None,
-                                     all_bases=bool(all_bases), alloc=pair.alloc, extra=fex, release=self.bam_walk_release)
-                kb._alloc = pair.alloc  # (host joins: the names of its records come back into page-locked memory of the same set: reads_from_bam)
+            host_joins = os.environ.get("UZ_JOINS", "device") != "device"
+            kb = src.select_kept(fc, flo, fhi, int(min_base_qual), walk=(lambda plan: self.bam_walk(plan, alloc=pair.alloc)) if host_joins else None,
+                                 join=None if host_joins else self, all_bases=bool(all_bases), alloc=pair.alloc, extra=fex, release=self.bam_walk_release,
+                                 walk_max_bytes=int(os.environ.get("UZ_WALK_MAX_BYTES", 16 << 30)))
+            if kb is not None:
+                kb._alloc = pair.alloc  # (host joins: the names of its records come back into the slot's page-locked memory: reads_from_bam)
                 return kb
-            except _WalkTooLarge:
-                pass
-        if os.environ.get("UZ_INFLATE", "device") == "device":
-            pair.start()
-            inflate, inflate_alloc = self.inflate_blocks, pair.alloc
+        pair.start()
         packed = src.select(fc, flo, fhi, int(min_base_qual), pool=pool, all_bases=bool(all_bases), extra=fex, wide_no_units=bool(wide_no_units),
-                            inflate=inflate, inflate_alloc=inflate_alloc)
+                            inflate=self.inflate_blocks if inflate else None, inflate_alloc=pair.alloc if inflate else None)
         pool.end_slab()
         return packed
 
@@ -439,44 +361,40 @@ class HipEngine:
                 raise UnfazedHipError("uz_bgzf_inflate_to_host: %s" % (self.L.uz_last_error(self.h) or b"").decode(errors="replace"))
 
     # ---- the record walk on the device (include/uz_bamwalk.h)
+    def _walk_start(self, plan: dict):
+        """uz_bam_walk (the caller holds _walk_sem: UZ_WALKS_AT_ONCE batches at a time): the plan's blocks up, inflated, checked against their
+        CRC-32 and walked in HBM -> (walk id, descriptors)"""
+        wid, nd = C.c_int(-1), C.c_int64(0)
+        rc = self.L.uz_bam_walk(self.h, plan["comp"].ctypes.data, int(plan["comp_bytes"]), int(plan["n_blocks"]), plan["in_off"].ctypes.data,
+                                plan["out_off"].ctypes.data, plan["blk_coff"].ctypes.data, plan["blk_crc"].ctypes.data if plan.get("blk_crc") is not None else None,
+                                int(plan["task"].shape[0]), plan["task"].ctypes.data, int(plan["span"].shape[0]), plan["span"].ctypes.data,
+                                int(plan["reach"].shape[0]), plan["reach"].ctypes.data, int(plan["fetch"].shape[0]), plan["fetch"].ctypes.data,
+                                C.byref(wid), C.byref(nd))
+        if rc != 0:
+            raise UnfazedHipError("uz_bam_walk: %s" % (self.L.uz_last_error(self.h) or b"").decode(errors="replace"))
+        return wid.value, int(nd.value)
+
     def bam_walk(self, plan: dict, alloc=None):
         """io_native.BamSource.select_kept(walk=engine.bam_walk): the batch's gathered BGZF blocks inflated in HBM and walked there
         (uz_bam_walk + uz_bam_walk_fetch).  -> (descriptors, d_first, d_flags, d_walked, walk id); the inflated bytes wait on the device for
         reads_from_bam (or bam_walk_release).  May be called from a decoder's worker thread."""
         from . import io_native
-        wid, nd = C.c_int(-1), C.c_int64(0)
         nt = int(plan["task"].shape[0])
-        with self._walk_sem:  # (UZ_WALKS_AT_ONCE batches at a time)
-            rc = self.L.uz_bam_walk(self.h, plan["comp"].ctypes.data, int(plan["comp_bytes"]), int(plan["n_blocks"]), plan["in_off"].ctypes.data,
-                                    plan["out_off"].ctypes.data, plan["blk_coff"].ctypes.data,
-                                    plan["blk_crc"].ctypes.data if plan.get("blk_crc") is not None and os.environ.get("UZ_WALK_CRC", "1") != "0" else None, nt, plan["task"].ctypes.data, int(plan["span"].shape[0]),
-                                    plan["span"].ctypes.data, int(plan["reach"].shape[0]), plan["reach"].ctypes.data, int(plan["fetch"].shape[0]),
-                                    plan["fetch"].ctypes.data, C.byref(wid), C.byref(nd))
-            if rc != 0:
-                raise UnfazedHipError("uz_bam_walk: %s" % (self.L.uz_last_error(self.h) or b"").decode(errors="replace"))
-            n = int(nd.value)
+        with self._walk_sem:  # (held across the descriptors' fetch)
+            wid, n = self._walk_start(plan)
             desc = (alloc(max(1, n) * 64).view(io_native.WALK_DESC) if alloc else np.zeros(max(1, n), io_native.WALK_DESC))[: max(1, n)]
             d_first, d_flags, d_walked = np.zeros(nt + 1, np.int64), np.zeros(max(1, nt), np.int32), np.zeros(max(1, nt), np.int64)
-            rc = self.L.uz_bam_walk_fetch(self.h, wid.value, desc.ctypes.data, d_first.ctypes.data, d_flags.ctypes.data, d_walked.ctypes.data)
+            rc = self.L.uz_bam_walk_fetch(self.h, wid, desc.ctypes.data, d_first.ctypes.data, d_flags.ctypes.data, d_walked.ctypes.data)
             if rc != 0:
-                self.L.uz_bam_walk_release(self.h, wid.value)
+                self.L.uz_bam_walk_release(self.h, wid)
                 raise UnfazedHipError("uz_bam_walk_fetch: %s" % (self.L.uz_last_error(self.h) or b"").decode(errors="replace"))
-        return desc[:n], d_first, d_flags[:nt], d_walked[:nt], wid.value
+        return desc[:n], d_first, d_flags[:nt], d_walked[:nt], wid
 
     # ---- the joins of a walked batch on the device (csrc/k_bamjoin.hip): the primitives io_native.BamSource.select_kept(join=engine) drives
     def walk(self, plan: dict):
         """uz_bam_walk alone: blocks up, inflated, checked and walked in HBM -> (walk id, descriptors the joins can need).  Nothing comes down."""
-        wid, nd = C.c_int(-1), C.c_int64(0)
-        nt = int(plan["task"].shape[0])
         with self._walk_sem:
-            rc = self.L.uz_bam_walk(self.h, plan["comp"].ctypes.data, int(plan["comp_bytes"]), int(plan["n_blocks"]), plan["in_off"].ctypes.data,
-                                    plan["out_off"].ctypes.data, plan["blk_coff"].ctypes.data,
-                                    plan["blk_crc"].ctypes.data if plan.get("blk_crc") is not None and os.environ.get("UZ_WALK_CRC", "1") != "0" else None, nt, plan["task"].ctypes.data, int(plan["span"].shape[0]),
-                                    plan["span"].ctypes.data, int(plan["reach"].shape[0]), plan["reach"].ctypes.data, int(plan["fetch"].shape[0]),
-                                    plan["fetch"].ctypes.data, C.byref(wid), C.byref(nd))
-            if rc != 0:
-                raise UnfazedHipError("uz_bam_walk: %s" % (self.L.uz_last_error(self.h) or b"").decode(errors="replace"))
-        return wid.value, int(nd.value)
+            return self._walk_start(plan)
 
     def walk_flags(self, token: int, nt: int):
         d_flags, d_walked = np.zeros(max(1, nt), np.int32), np.zeros(max(1, nt), np.int64)
@@ -551,9 +469,9 @@ class HipEngine:
             self._ck(self.L.uz_reads_from_walk(self.h, int(kb.token), int(kb.min_base_qual), 1 if names else 0, C.byref(rid), tot.ctypes.data), "uz_reads_from_walk")
             kb.token = None
             # a batch is through and its sizes are known: the other slots a pipeline will use grow to them now, not inside a later batch's walk
-            # (a no-op once they have; UZ_WALK_RESERVE=0 leaves the slots to grow at first use)
+            # (a no-op once they have)
             self._walked = getattr(self, "_walked", 0) + 1
-            if self._walked in (1, 2, 4) and os.environ.get("UZ_WALK_RESERVE", "1") != "0":
+            if self._walked in (1, 2, 4):
                 self._ck(self.L.uz_walk_reserve(self.h, 4), "uz_walk_reserve")
             if names:
                 kb.qnames = io_native.DeviceNames(self, rid.value, int(kb.n_qnames))

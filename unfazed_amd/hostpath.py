@@ -13,6 +13,7 @@ Mirrors, by name and argument meaning:
 from __future__ import annotations
 
 import sys
+import types
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -631,8 +632,7 @@ class PhasingHost:
                         vo, vv = self.backend.votes(len(part))
                     lists = _VoteLists(vo, vv)
                 res = dict(status=rr["status"], counts=rr["counts"], origin=rr["origin"], evidence=rr["evidence"], lists=lists)
-                table = type("StagedNames", (), {})()
-                table.qnames = names.pop(k).qnames
+                table = types.SimpleNamespace(qnames=names.pop(k).qnames)
                 if lists is not None:
                     # the name and position lists of the chunk's records, built HERE -- beside the native decode of the chunks that follow -- and
                     # not in a pass over the whole batch behind the pipeline

@@ -450,6 +450,27 @@ def pack_reads(reads: "abi.Held", min_base_qual: int, threads: int = 0, alloc=No
     return out
 
 
+def _fetch_lists(contig, lo, hi, extra=None):
+    """a batch's fetches (contig[k], lo[k], hi[k]; extra[k]: bases read past the fetched position) as the C ABI takes them"""
+    contig, lo, hi = (np.ascontiguousarray(a, np.int32) for a in (contig, lo, hi))
+    if extra is not None:
+        extra = np.ascontiguousarray(extra, np.uint16)
+        assert extra.size == contig.size
+    return contig, lo, hi, extra
+
+
+def _link_defaults(tup8, base_lists, wide_no_units: bool):
+    """the link form's defaults -> (tup8, base_lists).  tup8: the dictionary index in one byte, but not for an SV batch (wide_no_units): its step
+    is a chain of dependent launches over three heavy chunks, not bytes -- the kernel that rebuilds the 16-bit column stands in that chain: config 5
+    4.56 ms with the 16-bit index, 4.64 with the byte.  base_lists: the fetched bases as lists (UZ_BASE_LISTS=0: every record's staged units as
+    rows, the form of round 3)."""
+    if tup8 is None:
+        tup8 = not wide_no_units
+    if base_lists is None:
+        base_lists = os.environ.get("UZ_BASE_LISTS", "1") != "0"
+    return bool(tup8), bool(base_lists)
+
+
 class ReadsSource:
     """A packed table in host memory opened for fetch-reach selections (uz_reads_source_open)."""
 
@@ -464,7 +485,7 @@ class ReadsSource:
     def select(self, contig, lo, hi, alloc=None, want_index=False, all_bases=False, lists=True, with_end=None, extra=None, cigar_compact=True,
                tuples=True, d16=True, start8=True, wide_no_units=False, narrow8=True, pair8=True, base_lists=None, tup8=None):
         """The records the fetches (contig[k], lo[k], hi[k]) return plus their mates, as a packed table.
-        tup8 (default: on, UZ_TUP8=0 turns it off): the dictionary index in one byte (uz_types.h tup8; abi.compact_tup) -- what crosses the link.  Records that
+        tup8 (default: on, not for SV batches: _link_defaults): the dictionary index in one byte (uz_types.h tup8; abi.compact_tup) -- what crosses the link.  Records that
         are reachable only as mates are staged without their bases unless all_bases (--no-extended batches need them).
         lists: the qualities as counts + listed positions (what the host link carries); False keeps the plane (plane sources only).
         extra (uint16 per fetch, staging.fetch_points(..., allele_len=)): stage only the 32-base units of a record's rows that
@@ -479,21 +500,13 @@ class ReadsSource:
         pair8 (with start8): tlen, mate and name id in the pair form's ONE byte (uz_types.h, pair_d8) when the source's name ids ascend
         by first appearance (any decoder's table; else the narrow8 form).  The output then numbers the names of the selection by first
         appearance: `.qname_map[output id]` = the source's id."""
-        contig = np.ascontiguousarray(contig, np.int32)
-        lo = np.ascontiguousarray(lo, np.int32)
-        hi = np.ascontiguousarray(hi, np.int32)
-        if tup8 is None:
-            # (not for an SV batch: its step is a chain of dependent launches over three heavy chunks, not bytes -- the kernel that rebuilds the
-            # 16-bit column stands in that chain: config 5 4.56 ms with the 16-bit index, 4.64 with the byte)
-            tup8 = os.environ.get("UZ_TUP8", "1") != "0" and not wide_no_units
+        contig, lo, hi, extra = _fetch_lists(contig, lo, hi, extra)
+        tup8, base_lists = _link_defaults(tup8, base_lists, wide_no_units)
         sel = C.c_void_p()
         masks = extra is not None and lists and not all_bases
-        if masks:
-            extra = np.ascontiguousarray(extra, np.uint16)
-            assert extra.size == contig.size
         _check(self.lib, self.lib.uz_reads_select_plan(self._h.ptr, int(contig.size), contig.ctypes.data, lo.ctypes.data,
                                                        hi.ctypes.data, 1 if all_bases else 0,
-                                                       ((3 if wide_no_units else 1) | (4 if (os.environ.get("UZ_BASE_LISTS", "1") != "0" if base_lists is None else base_lists) else 0)) if masks else 0,
+                                                       ((3 if wide_no_units else 1) | (4 if base_lists else 0)) if masks else 0,
                                                        extra.ctypes.data if masks else None,
                                                        (1 | (2 if cigar_compact else 0) | (4 if lists else 0)) if tuples else 0,
                                                        int(self.threads), C.byref(sel)))
@@ -516,7 +529,7 @@ class ReadsSource:
                                                      else self.lib.uz_select_n_esc16_start8 if start8 else self.lib.uz_select_n_esc16)(sel)) if d16 else None,
                                         start8=bool(d16 and start8), narrow8=bool(d16 and start8 and narrow8), pair8=pair8,
                                         n_bl=n_bl if n_bl >= 0 else None, n_bl_units=int(self.lib.uz_select_n_bl_units(sel)), bl_wide=bool(self.lib.uz_select_bl_wide(sel)),
-                                        pk_sums=_PK_SUMS, tup_off_link=bool(tup8 and n_tup >= 0))
+                                        pk_sums=True, tup_off_link=bool(tup8 and n_tup >= 0))
             idx = np.zeros(max(1, n), np.int32) if want_index else None
             _check(self.lib, self.lib.uz_reads_select_fill(sel, int(self.threads), out.ref(),
                                                            idx.ctypes.data if want_index else None))
@@ -614,9 +627,6 @@ KEPT_NO_SEQ = 0xFFFFFFFF
 WALK_SRC_AUX = 1 << 63
 
 
-_PK_SUMS = os.environ.get("UZ_PK_SUMS", "1") != "0"  # the packers hand the device the span sums of what they packed (UZ_PK_SUMS=0: the device computes them)
-
-
 def block_sums(held: "abi.Held", threads: int = 0) -> "abi.Held":
     """The span sums of a filled packed view (uz_packed_block_sums) into its pk_sums array (abi.packed_view_alloc(pk_sums=True)): the device's header
     build then packs from them instead of computing them in a pass of its own.  A view without the array is returned as it is."""
@@ -671,6 +681,10 @@ class _KeptNames(Sequence):
         a, b = self._bounds(self._records(np.asarray(ids)))
         mv = memoryview(self._buf)  # (not tobytes(): the buffer holds the names of every kept record of the batch, tens of megabytes)
         return [str(mv[x:y], "utf-8") for x, y in zip(a.tolist(), b.tolist())]
+
+    def frozen(self) -> "_KeptNames":
+        """the same names out of memory of their own: for a caller whose batch's page-locked buffers are staged into again"""
+        return _KeptNames(self._buf.copy(), self._off.copy(), self._total, self._n, self._stage)
 
 
 def names_of_buffer(buf: np.ndarray, off: np.ndarray) -> list:
@@ -749,6 +763,29 @@ class KeptBatch:
         self.qnames = _KeptNames(buf, self.kept["name_off"], int(self.n_name_bytes), int(self.n_qnames), self._stage)
 
 
+def _io_stats(lib, sh) -> dict:
+    """what a stage read, inflated, walked and kept (uz_stage_io_stats)"""
+    io = (C.c_int64 * 8)()
+    lib.uz_stage_io_stats(sh.ptr, io)
+    return dict(zip(("file_bytes_read", "blocks_inflated", "records_walked", "records_kept", "reach_intervals", "index_mate_lookups",
+                     "blocks_from_the_device", "gathered_bytes"), (int(x) for x in io)))
+
+
+def _gather_blocks(lib, sh, alloc, max_bytes=None):
+    """the BGZF blocks a stage's walk will read, gathered back to back into alloc(nbytes) (uz_stage_gather_blocks)
+    -> dict(comp, comp_bytes, in_off, out_off, out_bytes, n_blocks), or None when they inflate to more than max_bytes"""
+    nb, cb, ob = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    _check(lib, lib.uz_stage_gather_blocks(sh.ptr, None, 0, None, None, C.byref(nb), C.byref(cb), C.byref(ob)))
+    nb, cb, ob = int(nb.value), int(cb.value), int(ob.value)
+    if max_bytes is not None and ob > int(max_bytes):
+        return None
+    comp = alloc(cb + 64)
+    in_off, out_off = np.zeros(max(1, nb), np.int64), np.zeros(nb + 1, np.int64)
+    if nb:
+        _check(lib, lib.uz_stage_gather_blocks(sh.ptr, comp.ctypes.data, cb, in_off.ctypes.data, out_off.ctypes.data, None, None, None))
+    return dict(comp=comp, comp_bytes=cb, in_off=in_off[:nb], out_off=out_off, out_bytes=ob, n_blocks=nb)
+
+
 def _stage_extra(lib, sh, tot, d0, a0):
     """what the stage holds for the device from descriptor d0 / aux byte a0 on (uz_stage_extra) -> (descriptors, aux bytes, reference of every look-up task)"""
     nd, na = int(tot[0]) - d0, int(tot[1]) - a0
@@ -787,17 +824,9 @@ class BamSource:
         plan, and the walk copies records out of what comes back (each block still held against its CRC-32) instead of inflating;
         inflate_alloc(nbytes) -> uint8 array: where the gathered and the inflated bytes go (pinned memory for full link speed); a batch whose
         blocks inflate to more than inflate_max_bytes stays with the host's inflate (that much memory would have to be page-locked)."""
-        if tup8 is None:
-            tup8 = os.environ.get("UZ_TUP8", "1") != "0" and not wide_no_units  # (as ReadsSource.select)
-        contig = np.ascontiguousarray(contig, np.int32)
-        lo = np.ascontiguousarray(lo, np.int32)
-        hi = np.ascontiguousarray(hi, np.int32)
+        contig, lo, hi, extra = _fetch_lists(contig, lo, hi, extra)
+        tup8, base_lists = _link_defaults(tup8, base_lists, wide_no_units)
         masks = extra is not None and lists and not all_bases
-        if extra is not None:
-            extra = np.ascontiguousarray(extra, np.uint16)
-            assert extra.size == contig.size
-        if base_lists is None:  # (UZ_BASE_LISTS=0: every record's staged units as rows, the form of round 3)
-            base_lists = os.environ.get("UZ_BASE_LISTS", "1") != "0"
         flags = (STAGE_ALL_BASES if all_bases else 0) | (STAGE_UNIT_MASKS if masks else 0) | (0 if lists else STAGE_PLANE) | (STAGE_WIDE_NO_UNITS if wide_no_units and masks else 0) \
             | (STAGE_BASE_LISTS if base_lists and masks else 0)
         st = C.c_void_p()
@@ -812,20 +841,17 @@ class BamSource:
                                                          extra.ctypes.data if extra is not None else None, flags, int(min_base_qual), int(self.threads),
                                                          C.byref(st)))
             sh = _Handle(st.value, self.lib.uz_stage_free)
-            nb, cb, ob = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-            _check(self.lib, self.lib.uz_stage_gather_blocks(sh.ptr, None, 0, None, None, C.byref(nb), C.byref(cb), C.byref(ob)))
-            if nb.value and ob.value <= int(inflate_max_bytes):
-                ia = inflate_alloc or (lambda nbytes: np.empty(max(16, nbytes), np.uint8))
-                comp = ia(int(cb.value) + 64)
-                inflated = ia(int(ob.value) + 64)
-                in_off, out_off = np.zeros(nb.value, np.int64), np.zeros(nb.value + 1, np.int64)
-                t_g = time.perf_counter()
-                _check(self.lib, self.lib.uz_stage_gather_blocks(sh.ptr, comp.ctypes.data, int(cb.value), in_off.ctypes.data, out_off.ctypes.data, None, None, None))
+            ia = inflate_alloc or (lambda nbytes: np.empty(max(16, nbytes), np.uint8))
+            t_g = time.perf_counter()
+            g = _gather_blocks(self.lib, sh, ia, inflate_max_bytes)
+            if g is not None and g["n_blocks"]:
+                inflated = ia(g["out_bytes"] + 64)
                 t_i = time.perf_counter()
-                inflate(comp, int(cb.value), in_off, out_off, inflated)
+                inflate(g["comp"], g["comp_bytes"], g["in_off"], g["out_off"], inflated)
                 t_e = time.perf_counter()
                 _check(self.lib, self.lib.uz_stage_set_inflated(sh.ptr, inflated.ctypes.data))
-                pre = dict(blocks=int(nb.value), comp_bytes=int(cb.value), out_bytes=int(ob.value), gather_s=t_i - t_g, inflate_s=t_e - t_i, keep=(comp, inflated))
+                pre = dict(blocks=g["n_blocks"], comp_bytes=g["comp_bytes"], out_bytes=g["out_bytes"], gather_s=t_i - t_g, inflate_s=t_e - t_i,
+                           keep=(g["comp"], inflated))
             _check(self.lib, self.lib.uz_bam_stage_finish(sh.ptr))
         z = (C.c_int64 * 16)()
         self.lib.uz_stage_sizes(sh.ptr, z)
@@ -842,18 +868,15 @@ class BamSource:
         out = abi.packed_view_alloc(n, len(self.contigs), n_cig + n_om, n_units, alloc, n_seq_units=n_seq, n_exc=n_exc,
                                     n_qlow_pos=n_qpos if lists else None, qlow_pos_wide=bool(wide) and lists, with_end=False, with_umask=bool(has_um),
                                     cigar_omitted=n_om, n_tup=n_tup, n_esc16=n_esc, start8=True, pair8=True,
-                                    n_bl=n_bl if has_bl else None, n_bl_units=n_blu, bl_wide=bool(wide) and bool(has_bl), pk_sums=_PK_SUMS,
-                                    tup_off_link=bool(tup8))
+                                    n_bl=n_bl if has_bl else None, n_bl_units=n_blu, bl_wide=bool(wide) and bool(has_bl), pk_sums=True,
+                                    tup_off_link=tup8)
         _check(self.lib, self.lib.uz_stage_fill(sh.ptr, int(self.threads), out.ref()))
         block_sums(out, self.threads)  # (the span sums the device's header build packs from: uz_types.h pk_sums)
         if tup8:
             abi.compact_tup(out, alloc)  # (the dictionary index in one byte: uz_types.h tup8)
-        io = (C.c_int64 * 8)()
-        self.lib.uz_stage_io_stats(sh.ptr, io)
         tm = (C.c_double * 6)()
         self.lib.uz_stage_timing(sh.ptr, tm)
-        out.io_stats = dict(zip(("file_bytes_read", "blocks_inflated", "records_walked", "records_kept", "reach_intervals", "index_mate_lookups",
-                                 "blocks_from_the_device", "gathered_bytes"), (int(x) for x in io)))
+        out.io_stats = _io_stats(self.lib, sh)
         out.pre_inflate = None if pre is None else {k: v for k, v in pre.items() if k != "keep"}
         out.timing = dict(zip(("spans", "walk", "mates", "numbering", "fill"), (float(x) for x in tm)))
         out.qnames = _StageNames(self.lib, sh, n_names)
@@ -902,10 +925,7 @@ class BamSource:
         out.n, out.n_qnames, out.n_cigar_total, out.n_row_units, out.n_seq_units, out.n_name_bytes = (int(v) for v in totals[:6])
         out.n_aux, out.host_tasks, out.kept = a0, int(np.count_nonzero(h_flags[:n_host])), None
         out.n_desc, out.n_extra_desc, out.join_calls = int(n_desc), d0, rounds
-        io = (C.c_int64 * 8)()
-        lib.uz_stage_io_stats(sh.ptr, io)
-        out.io_stats = dict(zip(("file_bytes_read", "blocks_inflated", "records_walked", "records_kept", "reach_intervals", "index_mate_lookups",
-                                 "blocks_from_the_device", "gathered_bytes"), (int(v) for v in io)))
+        out.io_stats = _io_stats(lib, sh)
         out.io_stats["records_walked"] += int(d_walked.sum())
         out.io_stats["records_kept"] = out.n
         out.timing = dict(plan=t1 - t0, walk=t2 - t1, joins=t3 - t2, kept=0.0, mates=0.0, numbering=0.0)
@@ -915,7 +935,7 @@ class BamSource:
         return out
 
     def select_kept(self, contig, lo, hi, min_base_qual: int, walk=None, all_bases=False, alloc=None, extra=None, release=None, small_tasks=None, merge=False,
-                    join=None) -> "KeptBatch":
+                    join=None, walk_max_bytes=None) -> "KeptBatch":
         """The same batch through the device's walk (include/uz_bamwalk.h): the blocks are gathered, `walk(plan)` inflates them in HBM and walks
         them there (HipEngine.bam_walk -> descriptors, d_first, d_flags, d_walked; None: the host's twin uz_stage_walk_host -- tests), the
         batch-wide joins run here on the descriptors, and the answer is the list of kept records for uz_reads_from_bam.
@@ -923,27 +943,21 @@ class BamSource:
         merge: the descriptors of the plan's sub-tasks are joined per task of the stage first (uz_stage_merge_subtasks: `.desc` / `.d_first` are then per
         task, for the parity tests); default: the joins read them as they came (uz_bam_stage_finish_sub).
         release(token): gives the walked batch on the device up (HipEngine.bam_walk_release) -- called when the joins fail here, or when the returned
-        batch is dropped without its table having been built."""
-        contig = np.ascontiguousarray(contig, np.int32)
-        lo = np.ascontiguousarray(lo, np.int32)
-        hi = np.ascontiguousarray(hi, np.int32)
-        if extra is not None:
-            extra = np.ascontiguousarray(extra, np.uint16)
+        batch is dropped without its table having been built.
+        walk_max_bytes: a batch whose blocks inflate to more than this is not walked -> None (HipEngine.stage_reads: the link form instead)."""
+        contig, lo, hi, extra = _fetch_lists(contig, lo, hi, extra)
         ia = alloc or (lambda nbytes: np.empty(max(16, nbytes), np.uint8))
         if small_tasks is None:  # (a plan for the device's walk takes smaller tasks: one wavefront walks a task)
-            small_tasks = (walk is not None or join is not None) and os.environ.get("UZ_STAGE_SUBTASKS", "1") != "0"  # (0: the stage's own tasks as walk tasks -- a development aid)
+            small_tasks = walk is not None or join is not None
         flags = (STAGE_ALL_BASES if all_bases else 0) | (STAGE_SMALL_TASKS if small_tasks else 0)
         st = C.c_void_p()
         t0 = time.perf_counter()
         _check(self.lib, self.lib.uz_bam_stage_begin(self._h.ptr, int(contig.size), contig.ctypes.data, lo.ctypes.data, hi.ctypes.data,
                                                      extra.ctypes.data if extra is not None else None, flags, int(min_base_qual), int(self.threads), C.byref(st)))
         sh = _Handle(st.value, self.lib.uz_stage_free)
-        nb, cb, ob = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        _check(self.lib, self.lib.uz_stage_gather_blocks(sh.ptr, None, 0, None, None, C.byref(nb), C.byref(cb), C.byref(ob)))
-        comp = ia(int(cb.value) + 64)
-        in_off, out_off = np.zeros(max(1, nb.value), np.int64), np.zeros(nb.value + 1, np.int64)
-        if nb.value:
-            _check(self.lib, self.lib.uz_stage_gather_blocks(sh.ptr, comp.ctypes.data, int(cb.value), in_off.ctypes.data, out_off.ctypes.data, None, None, None))
+        plan = _gather_blocks(self.lib, sh, ia, walk_max_bytes)
+        if plan is None:
+            return None
         z = (C.c_int64 * 8)()
         self.lib.uz_stage_walk_plan_sizes(sh.ptr, z)
         nt, nsp, nr, nf, nblk, n_host = (int(x) for x in z[:6])  # (nt: the device's walk tasks -- sub-tasks of the stage's n_host tasks under small_tasks)
@@ -954,8 +968,7 @@ class BamSource:
         blk_coff, blk_crc = np.zeros(max(1, nblk), np.int64), np.zeros(max(1, nblk), np.uint32)
         _check(self.lib, self.lib.uz_stage_walk_plan(sh.ptr, task.ctypes.data, span.ctypes.data, reach.ctypes.data, fetch.ctypes.data, blk_coff.ctypes.data,
                                                      blk_crc.ctypes.data))
-        plan = dict(comp=comp, comp_bytes=int(cb.value), in_off=in_off[: nb.value], out_off=out_off, out_bytes=int(ob.value), n_blocks=int(nb.value),
-                    task=task[:nt], span=span[:nsp], reach=reach[:nr], fetch=fetch[:nf], blk_coff=blk_coff[:nblk], blk_crc=blk_crc[:nblk], n_ref=len(self.contigs))
+        plan.update(task=task[:nt], span=span[:nsp], reach=reach[:nr], fetch=fetch[:nf], blk_coff=blk_coff[:nblk], blk_crc=blk_crc[:nblk], n_ref=len(self.contigs))
         t1 = time.perf_counter()
         if join is not None:
             return self._joined_on_the_device(join, sh, plan, n_host, nt, int(min_base_qual), bool(all_bases), release, t0, t1)
@@ -1005,10 +1018,7 @@ class BamSource:
                                                 out.aux.ctypes.data, int(n_aux)))
         out.n_aux = n_aux
         t4 = time.perf_counter()
-        io = (C.c_int64 * 8)()
-        self.lib.uz_stage_io_stats(sh.ptr, io)
-        out.io_stats = dict(zip(("file_bytes_read", "blocks_inflated", "records_walked", "records_kept", "reach_intervals", "index_mate_lookups",
-                                 "blocks_from_the_device", "gathered_bytes"), (int(x) for x in io)))
+        out.io_stats = _io_stats(self.lib, sh)
         tm = (C.c_double * 6)()
         self.lib.uz_stage_timing(sh.ptr, tm)
         out.timing = dict(plan=t1 - t0, walk=t2 - t1, joins=t3 - t2, kept=t4 - t3, mates=float(tm[2]), numbering=float(tm[3]))
