@@ -1,0 +1,95 @@
+"""The header build from LDS (k_pack_link) against the build that reads every part from memory (k_pack_rec, UZ_BUILD_FROM_MEMORY=1): the
+same table, uploaded in a fresh process each way, must come back with the same record headers -- start, end, template length, mate and name
+id -- and a pair form that contradicts itself must be refused by both.  The tables are the pair form of test_upload_forms_gpu.py: FIRST /
+SECOND pairs that straddle the 256-record rounds and the 1024-record spans of the build, SECONDs that bring their own template length, and
+records spelled out in the escape list."""
+import json
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TESTS = os.path.join(ROOT, "tests")
+
+_CHILD = r"""
+import json, sys
+import numpy as np
+sys.path[:0] = [sys.argv[1], sys.argv[2]]
+from test_upload_forms_gpu import _odd_table
+from unfazed_amd import io_native
+from unfazed_amd.engine import HipEngine, UnfazedHipError
+n_dnms, breakage, out = int(sys.argv[3]), sys.argv[4], sys.argv[5]
+rh, arrs, N = _odd_table(n_dnms)
+src = io_native.ReadsSource(io_native.pack_reads(rh, 20))
+contig_of = np.searchsorted(arrs["contig_off"], np.arange(N), side="right") - 1
+fc = np.unique(contig_of).astype(np.int32)
+# the form the staged pass sends: `end` derived, two-bit rows, quality lists and unit masks (the fetches' units: the whole contig here)
+part = src.select(fc, np.zeros(fc.size, np.int32), np.full(fc.size, 2 ** 31 - 1, np.int32), extra=np.ones(fc.size, np.uint16))
+p = part.arrays["pair_d8"]
+f = np.nonzero((p[:N] >= 1) & (p[:N] <= 252))[0]
+if breakage == "second_named_twice":
+    i, j = int(f[5]), int(f[5]) + int(p[f[5]])
+    k = next(int(x) for x in f if x != i and 0 < j - int(x) <= 252)
+    p[k] = j - k
+elif breakage == "orphan_second":
+    p[int(f[7])] = 0
+elif breakage == "first_names_a_first":
+    i = int(f[9])
+    k = next(int(x) for x in f if 0 < int(x) - i <= 252 and int(x) != i + int(p[i]))
+    p[i] = k - i
+codes = np.unique(p[:N]).tolist()
+eng = HipEngine(0)
+res = {"n": int(N), "codes": codes, "error": None}
+try:
+    rid = eng.upload_reads_packed(part)
+    eng.wait_reads(rid)
+    got = eng.reads_headers(rid, N)
+    eng.free_reads(rid)
+    np.savez(out, **got)
+except UnfazedHipError as e:
+    res["error"] = str(e)
+eng.close()
+print("RESULT " + json.dumps(res))
+"""
+
+
+def _build(tmp_path, from_memory, n_dnms, breakage="none"):
+    out = str(tmp_path / ("%s_%d_%s.npz" % ("rec" if from_memory else "link", n_dnms, breakage)))
+    env = dict(os.environ, UZ_BUILD_LOG="1")
+    env.pop("UZ_BUILD_FROM_MEMORY", None)
+    if from_memory:
+        env["UZ_BUILD_FROM_MEMORY"] = "1"
+    r = subprocess.run([sys.executable, "-c", _CHILD, ROOT, TESTS, str(n_dnms), breakage, out], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    res = json.loads([x for x in r.stdout.splitlines() if x.startswith("RESULT ")][-1][len("RESULT "):])
+    builds = [x for x in r.stderr.splitlines() if x.startswith("[uz_build_records]")]
+    assert builds and all(x.endswith("from_lds %d" % (0 if from_memory else 1)) for x in builds), builds
+    return res, (dict(np.load(out)) if res["error"] is None else None)
+
+
+@pytest.mark.parametrize("n_dnms", [40, 260])
+def test_link_headers_equal_the_memory_build(tmp_path, n_dnms):
+    link, got = _build(tmp_path, False, n_dnms)
+    rec, want = _build(tmp_path, True, n_dnms)
+    assert link["error"] is None and rec["error"] is None
+    assert link["n"] > 2048  # several spans of 1024 records, every one of its four rounds
+    # SECONDs, FIRSTs, SECONDs with their own template length and spelled-out records all occur
+    codes = set(link["codes"])
+    assert 0 in codes and any(1 <= c <= 252 for c in codes) and {253, 254} <= codes, sorted(codes)
+    for k in ("start", "end", "tlen", "mate", "qname"):
+        assert np.array_equal(got[k], want[k]), k
+
+
+@pytest.mark.parametrize("breakage", ["second_named_twice", "orphan_second", "first_names_a_first"])
+def test_a_contradicting_pair_form_is_refused_by_both_builds(tmp_path, breakage):
+    link, _ = _build(tmp_path, False, 20, breakage)
+    rec, _ = _build(tmp_path, True, 20, breakage)
+    assert link["error"] is not None and rec["error"] is not None
+    rc = [re.search(r"failed \((-?\d+)\)", e["error"]).group(1) for e in (link, rec)]
+    assert rc[0] == rc[1], (link["error"], rec["error"])

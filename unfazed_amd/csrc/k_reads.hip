@@ -859,7 +859,8 @@ __global__ __launch_bounds__(256) void k_pack_dict(RecColumns c, int32_t n_tup, 
     e.w = 0u;
     dict[k] = e;
 }
-__global__ __launch_bounds__(256, 3) void k_pack_link(int64_t n, RecColumns c_in, const unsigned long long *__restrict__ sums, int32_t n_tup, const uint4 *__restrict__ dict, RecA *ra, RecB *rb,
+// (30 KB of LDS and <= 96 VGPRs: five workgroups per CU)
+__global__ __launch_bounds__(256, 5) void k_pack_link(int64_t n, RecColumns c_in, const unsigned long long *__restrict__ sums, int32_t n_tup, const uint4 *__restrict__ dict, RecA *ra, RecB *rb,
                                                      uint32_t *fm, uint32_t *qoff, uint8_t *nlow, uint16_t *umask_out, uint32_t *plane_out,
                                                      uint16_t *qs, int32_t *coarse, int32_t *mid_idx, int32_t *mid8, int32_t *hflags) {
     RecColumns c = uz_columns_of<true>(c_in);
@@ -869,8 +870,11 @@ __global__ __launch_bounds__(256, 3) void k_pack_link(int64_t n, RecColumns c_in
     __shared__ uint32_t s_cig[UZ_PL_CIG];
     __shared__ unsigned long long s_esck[UZ_PL_ESC];
     __shared__ int32_t s_escv[UZ_PL_ESC];
-    __shared__ RecA s_ra[UZ_PL_SPAN]; // the span's headers: finished here (a SECOND record writes its FIRST's template length), stored once at the end
-    __shared__ RecB s_rb[UZ_PL_SPAN];
+    // A SECOND stands at most UZ_P8_MAX_DIST < 256 records behind its FIRST: in the same round of 256 records or in the round before.  So only
+    // the last two rounds' headers are held here, in a ring of 512: a record's RecA is stored at once (nothing changes it), its RecB once the
+    // round after its own has been joined (a SECOND writes its FIRST's template length) -- 12 KB of LDS where the whole span's headers took 32
+    __shared__ int2 s_se[2 * 256];  // start, end: what a SECOND reads of its FIRST's RecA
+    __shared__ RecB s_rb[2 * 256];
     __shared__ uint8_t s_back[UZ_PL_SPAN];        // how far back a SECOND's FIRST stands (0: not named inside the span)
     __shared__ uint32_t s_named[UZ_PL_SPAN / 4];  // how often a record was named (a byte each)
     __shared__ uint32_t wsum[UZ_PK_SCANNED][4];
@@ -931,13 +935,13 @@ __global__ __launch_bounds__(256, 3) void k_pack_link(int64_t n, RecColumns c_in
         __syncthreads();
     }
     PK_TICK(0); // columns + sums rows
-    // the dictionary entry of a round's record is requested a round ahead (the first one here, beside the lists)
+    // the dictionary entry of a round's record (requested at the top of its round: five workgroups per CU hide the trip, where holding it a
+    // round ahead cost the registers that keep the kernel at 96 VGPRs)
     auto dict_of = [&](int k) -> uint4 {
         uint32_t tp = k < cnt ? (uint32_t)s_tup[k] : 0u;
         if ((int)tp >= n_tup) { hflags[0] = 1; tp = 0u; } // (an index beyond the dictionary)
         return dict[tp];
     };
-    uint4 de_next = dict_of(t);
     // Everything below counts in 32 bits from the span's own base: the running offsets inside the span (rel), the span's share of every
     // quantity (len: next row - this row; the host has checked that the rows ascend and that the totals fit 32 bits), the bases of the five
     // quantities that become absolute offsets.  All of it uniform: read back through readfirstlane so that it lives in scalar registers.
@@ -997,8 +1001,7 @@ __global__ __launch_bounds__(256, 3) void k_pack_link(int64_t n, RecColumns c_in
         const bool in = k < cnt;
         uint4 de = make_uint4(0u, 0u, 0u, 0u);
         uint32_t p = UZ_P8_NEW, sd = 0;
-        if (in) { de = de_next; p = s_pd[k]; sd = s_sd[k]; }
-        if (it + 1 < UZ_PL_SPAN / 256) de_next = dict_of(k + 256);
+        if (in) { de = dict_of(k); p = s_pd[k]; sd = s_sd[k]; }
         const uint32_t flag = de.x & 0xFFFFu, ls = de.x >> 16, nc = de.y & 0xFFFFu, um = in ? (de.y >> 16) : UZ_UMASK_ALL;
         const uint32_t mapq = de.z & 0xFFu, ax = (de.z >> 8) & 0xFFu, nb = de.z >> 24;
         const int nl = (int)((de.z >> 16) & 0xFFu);
@@ -1020,6 +1023,8 @@ __global__ __launch_bounds__(256, 3) void k_pack_link(int64_t n, RecColumns c_in
             for (int q = 0; q < UZ_PK_SCANNED; q++) wsum[q][wv] = inc[q];
         }
         PL_BARRIER();
+        // (every round before this one has been joined: the RecBs of the round before the last are final, and this round reuses their slots)
+        if (it >= 2 && k - 512 < cnt) rb[s0 + k - 512] = s_rb[k & 511];
         // where the record's parts end, counted from the span's base: the rounds before, the waves before, the lanes before and the record
         // itself; the running offsets move on at once, so that only the eight offsets below live through the rest of the round.  Nothing
         // of a record may end beyond the span's share: nothing is read or written outside it.
@@ -1032,7 +1037,7 @@ __global__ __launch_bounds__(256, 3) void k_pack_link(int64_t n, RecColumns c_in
             for (int w = 0; w < 4; w++) { if (w < wv) pre += wsum[q][w]; tot += wsum[q][w]; }
             e32[q] = rel[q] + pre + inc[q];
             if (q != 5 && q != 6) fits &= e32[q] <= len[q] && e32[q] >= inc[q]; // (no wrap)
-            rel[q] += tot;
+            rel[q] += (uint32_t)__builtin_amdgcn_readfirstlane((int)tot);
         }
         if (in && !fits) hflags[0] = 1;
         const uint32_t o_cg = base_cg + e32[0] - v[0], o_sq = base_sq + e32[2] - v[2], o_sql = base_sql + e32[7] - v[7];
@@ -1078,7 +1083,9 @@ __global__ __launch_bounds__(256, 3) void k_pack_link(int64_t n, RecColumns c_in
                 RecA A;
                 RecB B;
                 uz_pack_rec(A, B, st0, en0, cg, sq, mt0, qn0, (uint16_t)ls, (uint16_t)nc, tl0);
-                s_ra[k] = A; s_rb[k] = B;
+                ra[i] = A;
+                s_se[k & 511] = make_int2(st0, en0);
+                s_rb[k & 511] = B;
             }
             if (p >= 1u && p <= UZ_P8_MAX_DIST && mt0 >= 0 && k + (int)p < UZ_PL_SPAN) { // a FIRST whose SECOND lies in this span: tell it
                 const int j = k + (int)p;
@@ -1096,15 +1103,15 @@ __global__ __launch_bounds__(256, 3) void k_pack_link(int64_t n, RecColumns c_in
             if (p == UZ_P8_SECOND || p == UZ_P8_SECOND_TLEN) {
                 const int d = (int)s_back[k];
                 if (d) { // its FIRST stands d records back, in this span
-                    const int f = k - d;
-                    const RecA FA = s_ra[f];
+                    const int f = k - d, sf = f & 511, sk = k & 511;
+                    const int2 FA = s_se[sf];
                     int32_t tlf; // the FIRST's template length
                     if (p == UZ_P8_SECOND_TLEN) tlf = -tl0;
-                    else { tlf = (FA.end > en0 ? FA.end : en0) - FA.start; tl0 = -tlf; }
-                    s_rb[f].tlen = tlf;
-                    s_rb[k].mate = (int32_t)(s0 + f);
-                    s_rb[k].qname = s_rb[f].qname;
-                    s_rb[k].tlen = tl0;
+                    else { tlf = (FA.y > en0 ? FA.y : en0) - FA.x; tl0 = -tlf; }
+                    s_rb[sf].tlen = tlf;
+                    s_rb[sk].mate = (int32_t)(s0 + f);
+                    s_rb[sk].qname = s_rb[sf].qname;
+                    s_rb[sk].tlen = tl0;
                 }
                 // (else: its FIRST lies in the span before this one -- k_pair_link -- or nowhere: the totals of the packer's sums tell)
             } else if (named) hflags[0] = 8; // named as a mate, but not a SECOND record
@@ -1185,7 +1192,7 @@ __global__ __launch_bounds__(256, 3) void k_pack_link(int64_t n, RecColumns c_in
     if (threadIdx.x == 0) for (int q = 0; q < 10; q++) atomicAdd(&uz_pack_ticks[q], ptk__[q]);
 #endif
     PL_BARRIER();
-    for (int q = t; q < cnt; q += 256) { ra[s0 + q] = s_ra[q]; rb[s0 + q] = s_rb[q]; }
+    for (int q = 512 + t; q < cnt; q += 256) rb[s0 + q] = s_rb[q & 511]; // (the last two rounds)
     if (t == 0) { // the span's own sums must add up to exactly the packer's next row (the two difference columns modulo 2^32)
         bool same = true;
 #pragma unroll
