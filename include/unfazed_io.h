@@ -129,6 +129,15 @@ const char *uz_vcf_info(const uz_vcf *h, int64_t i, const char *key, int32_t *le
 /* 1 when the file was BCF (no text lines: uz_vcf_line is empty) */
 int uz_vcf_is_bcf(const uz_vcf *h);
 
+/* The compact link form of a site table (uz_types.h: uz_sites_view.pos_d16 ...): the plain columns of `in` -> one block at `out` (256-byte
+ * aligned; every column at a 256-byte aligned offset, so that the block crosses the link as one copy) and `view` pointing into it
+ * (n_sites, n_contigs and contig_off are taken over from `in`).  *bytes: the block's size -- call with out NULL first.  UZ_IO_E_RANGE: a
+ * base outside UZ_BASE3_CODES or a site flag other than UZ_SF_COMPLEX (the caller keeps the plain form); UZ_IO_E_ARG: contig_off does
+ * not describe the table, or cap is too small. */
+int uz_sites_pack(const uz_sites_view *in, uint8_t *out, int64_t cap, uz_sites_view *view, int64_t *bytes);
+/* its inverse on the host (what the device's expansion computes): the plain columns of a compact view */
+int uz_sites_unpack(const uz_sites_view *v, int32_t *pos, uint8_t *sflags, uint8_t *ref_base, uint8_t *alt_base);
+
 /* ------------------------------------------------------------------ staged (packed) records
  * uz_reads_packed_view (uz_types.h) is what crosses the host link.  The caller owns the output buffers (pinned
  * memory from uz_pinned_alloc for the upload): the `out` view arrives with every pointer set to a WRITABLE

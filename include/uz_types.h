@@ -108,7 +108,29 @@ typedef struct uz_sites_view {
     const uint8_t *sflags;     /* [S] UZ_SF_* */
     const uint8_t *ref_base;   /* [S] ASCII, 0 for complex records */
     const uint8_t *alt_base;   /* [S] */
+    /* The compact link form (uz_sites_pack writes it; pos / sflags / ref_base / alt_base are then NULL): 4 bytes per site cross the link
+     * instead of 7.  Sites are taken in spans of UZ_SITE_SPAN; span s starts at site s * UZ_SITE_SPAN.
+     *   pos_d16[i]      pos[i] - pos[i - 1] where that lies in [0, UZ_POS_D16_LIMIT) (anything where site i starts a span or escapes)
+     *   bases8[i]       UZ_BASE3 code of ref_base | code of alt_base << 3 | complex (UZ_SF_COMPLEX) << 6
+     *   span_pos[s]     pos of the span's first site
+     *   pos_esc_*       the escapes, ascending by site index: every other site whose difference does not fit, and the first site of every
+     *                   contig -- index and absolute pos; pos_esc_off[s] = first escape of span s (n_spans + 1 entries, the last n_pos_esc)
+     * pos[i] is then the value of the last anchor at or before i within its span (the span's first site, or an escape) plus the pos_d16 of
+     * the sites after that anchor up to i.  Only uz_sites_family_upload_async takes this form; the device expands it into the plain
+     * columns at first use. */
+    const uint16_t *pos_d16;
+    const uint8_t *bases8;
+    const int32_t *span_pos;    /* [n_spans] */
+    int64_t n_pos_esc;
+    const int32_t *pos_esc_idx; /* [n_pos_esc] */
+    const int32_t *pos_esc_val; /* [n_pos_esc] */
+    const int32_t *pos_esc_off; /* [n_spans + 1] */
 } uz_sites_view;
+#define UZ_SITE_SPAN 1024
+#define UZ_POS_D16_LIMIT 32768
+/* the bases of a plain site in three bits (bases8): 0 = none (complex records), 1 .. 5 = A C G T N */
+#define UZ_BASE3_CODES "\0ACGTN"
+
 
 /* genotype columns of one trio, member order kid, dad, mom */
 typedef struct uz_family_view {

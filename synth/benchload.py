@@ -108,28 +108,44 @@ class BenchLoad:
             np.add.at(kk, hi_i, -1)
         return np.nonzero(np.cumsum(kk[:-1]) > 0)[0]
 
-    def pinned_sites(self, pool, sel, eight_bit=True):
-        """the site + genotype columns of `sel` in pinned memory, as one slab -> (held view, site columns, genotype columns, wide list, n)"""
-        from unfazed_amd import abi
+    def pinned_sites(self, pool, sel, eight_bit=True, compact=False):
+        """the site + genotype columns of `sel` in pinned memory, as one slab -> (held view, site columns, genotype columns, wide list, n);
+        compact: the site columns in the compact link form (io_native.pack_sites; hs_k["link_bytes"]: the packer's count)"""
+        from unfazed_amd import abi, io_native
         sc = self.sc
         co_s = np.asarray(sc.contig_off, np.int64)
         pool.new_slab(int(sel.size) * 28 + (1 << 20))
-        hs_k = {k: pinned_copy(pool, getattr(sc, k)[sel]) for k in ("pos", "sflags", "ref_base", "alt_base", "gt")}
+        plain = ("pos", "sflags", "ref_base", "alt_base")
+        hs_k = {k: (getattr(sc, k)[sel] if compact and k in plain else pinned_copy(pool, getattr(sc, k)[sel])) for k in plain + ("gt",)}
         hs_k["contig_off"] = pinned_copy(pool, np.searchsorted(sel, co_s).astype(np.int64))
+        svc = None
+        if compact:
+            sv0 = abi.SitesView()
+            sv0.n_sites, sv0.n_contigs = int(sel.size), len(sc.contig_off) - 1
+            for k in ("contig_off",) + plain:
+                setattr(sv0, k, hs_k[k].ctypes.data)
+            svc, hs_k["compact"], nb = io_native.pack_sites(sv0, alloc=pool.alloc)
+            hs_k["link_bytes"] = nb
         hg_k = {k: [getattr(sc, k)[m][sel] for m in range(3)] for k in ("rd", "ad", "gq")}
         wide_k = None
         if eight_bit:  # the nine genotype columns in eight bits (uz_types.h: depths of 255 and more, or missing, through the wide list)
             r8, a8, g8, wide_k = abi.family_columns8(hg_k["rd"], hg_k["ad"], hg_k["gq"])
             hg_k = dict(rd=list(r8), ad=list(a8), gq=list(g8))
         hg_k = {k: [pinned_copy(pool, x) for x in v] for k, v in hg_k.items()}
-        svk = abi.SitesView()
-        svk.n_sites, svk.n_contigs = int(sel.size), len(sc.contig_off) - 1
-        for k in ("contig_off", "pos", "sflags", "ref_base", "alt_base"):
-            setattr(svk, k, hs_k[k].ctypes.data)
+        if svc is not None:
+            svk = svc
+            for k in plain:
+                del hs_k[k]
+        else:
+            svk = abi.SitesView()
+            svk.n_sites, svk.n_contigs = int(sel.size), len(sc.contig_off) - 1
+            for k in ("contig_off",) + plain:
+                setattr(svk, k, hs_k[k].ctypes.data)
         pool.end_slab()
         return abi.Held(svk, hs_k), hs_k, hg_k, wide_k, int(sel.size)
 
-    def stage(self, eng, P, mode, fid, pool, chunks=None, last_chunk=0.7, first_chunk=None, sites16=False, per_chunk_sites=True, log_first=False):
+    def stage(self, eng, P, mode, fid, pool, chunks=None, last_chunk=0.7, first_chunk=None, sites16=False, per_chunk_sites=True, log_first=False,
+              compact_sites=True):
         """What the decoders would leave in pinned memory for a staged pass: per chunk of DNMs (whole clusters) the records the chunk's fetches
         return + their mates, in the link form (selected on the host out of the generator's table), and the site windows.
         -> (chunks for pipeline.run_pipelined, stats)"""
@@ -174,10 +190,11 @@ class BenchLoad:
             # the site columns cut per chunk (the windows of the chunk's DNMs): the site stage of chunk k + 1 then runs while the records of
             # chunk k are still on the link (config 5 the same way: the allele-balance stage of a chunk runs on the chunk's own windows)
             for c in out:
-                held, hs_k, hg_k, wide_k, ns = self.pinned_sites(pool, self.window_sites(c["a"], c["b"], P), eight_bit=not sites16)
+                held, hs_k, hg_k, wide_k, ns = self.pinned_sites(pool, self.window_sites(c["a"], c["b"], P), eight_bit=not sites16, compact=compact_sites)
                 c["sites"] = (held, hs_k, hg_k, wide_k)
                 n_sites_staged += ns
-                site_bytes += ns * (4 + 1 + 1 + 1 + 1 + (18 if sites16 else 9)) + (0 if wide_k is None else len(wide_k[0]) * 32)
+                # (the site columns: the packer's count, or 4 + 1 + 1 + 1 B per site; gt; the nine genotype columns; the wide list)
+                site_bytes += (hs_k["link_bytes"] if compact_sites else ns * 7) + ns * (1 + (18 if sites16 else 9)) + (0 if wide_k is None else len(wide_k[0]) * 32)
         return out, dict(read_bytes=staged_bytes, records=staged_records, sites=n_sites_staged, site_bytes=site_bytes)
 
     def free(self):

@@ -86,6 +86,14 @@ class SitesView(C.Structure):
         ("sflags", _p),
         ("ref_base", _p),
         ("alt_base", _p),
+        # the compact link form (uz_types.h; io_native.pack_sites): then pos / sflags / ref_base / alt_base are NULL
+        ("pos_d16", _p),
+        ("bases8", _p),
+        ("span_pos", _p),
+        ("n_pos_esc", C.c_int64),
+        ("pos_esc_idx", _p),
+        ("pos_esc_val", _p),
+        ("pos_esc_off", _p),
     ]
 
 

@@ -140,6 +140,7 @@ SitesDev &sites_of(uz_ctx *c, int id) {
         s.pending = false;
         UZ_HIP(hipStreamWaitEvent(c->stream, s.ready, 0));
     }
+    uz_sites_expand(c, s, nullptr); // (compact form used before its family: the sites alone)
     return s;
 }
 FamilyDev &fam_of(uz_ctx *c, int id) {
@@ -148,9 +149,15 @@ FamilyDev &fam_of(uz_ctx *c, int id) {
     if (f.pending) { // queued by uz_sites_family_upload_async: the compute stream waits for the copies, then folds the complex flag
         f.pending = false;
         UZ_HIP(hipStreamWaitEvent(c->stream, f.ready, 0));
-        SitesDev &s = sites_of(c, f.sites_id);
-        uz_family_widen(c, f, s.n);
-        uz_fold_complex(c, f.gt, s.sflags, s.n);
+        SitesDev &s0 = c->sites[f.sites_id];
+        if (s0.expand_pending) { // compact site form: ONE launch expands the sites and readies the family
+            if (s0.pending) { s0.pending = false; UZ_HIP(hipStreamWaitEvent(c->stream, s0.ready, 0)); }
+            uz_sites_expand(c, s0, &f);
+        } else {
+            SitesDev &s = sites_of(c, f.sites_id);
+            uz_family_widen(c, f, s.n);
+            uz_fold_complex(c, f.gt, s.sflags, s.n);
+        }
     }
     return f;
 }
@@ -478,6 +485,7 @@ int uz_set_params(uz_ctx *c, const uz_params *p) {
 int uz_sites_upload(uz_ctx *c, const uz_sites_view *v, int *id) {
     return guarded(c, [&] {
         UZ_REQUIRE(v && id && v->n_sites >= 0 && v->n_contigs >= 0, UZ_E_ARG, "bad sites view");
+        UZ_REQUIRE(!v->pos_d16 && !v->bases8, UZ_E_ARG, "the compact site form is taken by uz_sites_family_upload_async only");
         UZ_REQUIRE(v->n_sites < (int64_t)0x7FFFFFF0, UZ_E_RANGE, "more than 2^31 sites");
         const int k = new_slot(c->sites);
         SitesDev s;
@@ -505,6 +513,7 @@ int uz_sites_upload(uz_ctx *c, const uz_sites_view *v, int *id) {
 int uz_sites_adopt_device(uz_ctx *c, const uz_sites_view *v, int *id) {
     return guarded(c, [&] {
         UZ_REQUIRE(v && id && v->n_sites >= 0 && v->n_contigs >= 0, UZ_E_ARG, "bad sites view");
+        UZ_REQUIRE(!v->pos_d16 && !v->bases8, UZ_E_ARG, "the compact site form is taken by uz_sites_family_upload_async only");
         const int k = new_slot(c->sites);
         SitesDev s;
         s.live = true; s.owned = false;
@@ -525,6 +534,26 @@ int uz_sites_adopt_device(uz_ctx *c, const uz_sites_view *v, int *id) {
         c->sites[k] = s;
         *id = k;
     });
+}
+
+// which form the site columns of a view come in: true = compact (uz_sites_view.pos_d16 ...), its escape list checked here, on the host,
+// since the expansion kernel places every escape in its span by it
+static bool sites_view_compact(const uz_sites_view *v) {
+    if (!v->pos_d16 && !v->bases8) return false;
+    const int64_t n = v->n_sites, n_spans = (n + UZ_SITE_SPAN - 1) / UZ_SITE_SPAN;
+    UZ_REQUIRE(v->pos_d16 && v->bases8 && !v->pos && !v->sflags && !v->ref_base && !v->alt_base, UZ_E_ARG,
+               "a compact sites view sets pos_d16 and bases8 and leaves pos / sflags / ref_base / alt_base null");
+    UZ_REQUIRE(v->span_pos && v->pos_esc_off && v->n_pos_esc >= 0 && (v->n_pos_esc == 0 || (v->pos_esc_idx && v->pos_esc_val)), UZ_E_ARG,
+               "a compact sites view needs span_pos, pos_esc_off and its escape list");
+    UZ_REQUIRE(v->pos_esc_off[0] == 0 && v->pos_esc_off[n_spans] == v->n_pos_esc, UZ_E_ARG, "pos_esc_off does not cover the escape list");
+    for (int64_t sp = 0; sp < n_spans; sp++) {
+        const int64_t a = v->pos_esc_off[sp], b = v->pos_esc_off[sp + 1];
+        UZ_REQUIRE(a <= b, UZ_E_ARG, "pos_esc_off must ascend");
+        for (int64_t e = a; e < b; e++)
+            UZ_REQUIRE(v->pos_esc_idx[e] >= sp * UZ_SITE_SPAN && v->pos_esc_idx[e] < std::min(n, (sp + 1) * UZ_SITE_SPAN) &&
+                           (e == a || v->pos_esc_idx[e] > v->pos_esc_idx[e - 1]), UZ_E_ARG, "an escape outside its span, or out of order");
+    }
+    return true;
 }
 
 // which form the nine columns of a family view come in: true = eight bits (all nine of ref_depth8 / alt_depth8 / gq8 set, the 16-bit ones null)
@@ -630,11 +659,20 @@ int uz_sites_family_upload_async(uz_ctx *c, const uz_sites_view *v, const uz_fam
         FamilyDev f;
         f.owned = true;
         const bool eight = family_view_eight(fv);
+        const bool compact = sites_view_compact(v);
+        const size_t n_spans = (n + UZ_SITE_SPAN - 1) / UZ_SITE_SPAN, n_esc = compact ? (size_t)v->n_pos_esc : 0;
         uint8_t *st8[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        uint16_t *c_d16 = nullptr;
+        uint8_t *c_b8 = nullptr;
+        int32_t *c_span = nullptr, *c_eidx = nullptr, *c_eval = nullptr, *c_eoff = nullptr;
         for (int pass = 0; pass < 2; pass++) {
             Carver cv(pass ? s.block.p : nullptr);
             s.contig_off = cv.take<int64_t>((size_t)v->n_contigs + 1);
             s.pos = cv.take<int32_t>(n); s.sflags = cv.take<uint8_t>(n); s.ref_base = cv.take<uint8_t>(n); s.alt_base = cv.take<uint8_t>(n);
+            if (compact) {
+                c_d16 = cv.take<uint16_t>(n); c_b8 = cv.take<uint8_t>(n); c_span = cv.take<int32_t>(n_spans);
+                c_eidx = cv.take<int32_t>(n_esc); c_eval = cv.take<int32_t>(n_esc); c_eoff = cv.take<int32_t>(n_spans + 1);
+            }
             if (!pass) s.block = uz_block_get(c, cv.off + 256);
         }
         for (int pass = 0; pass < 2; pass++) {
@@ -652,8 +690,14 @@ int uz_sites_family_upload_async(uz_ctx *c, const uz_sites_view *v, const uz_fam
             for (int stage_pass = 0; stage_pass < 2; stage_pass++) {
                 if (stage_pass) slab_commit(c, st, plan, s.mirror);
                 s.contig_off = const_cast<int64_t *>(h2d(st, s.contig_off, v->contig_off, (size_t)v->n_contigs + 1));
-                s.pos = const_cast<int32_t *>(h2d(st, s.pos, v->pos, n)); s.sflags = const_cast<uint8_t *>(h2d(st, s.sflags, v->sflags, n));
-                s.ref_base = const_cast<uint8_t *>(h2d(st, s.ref_base, v->ref_base, n)); s.alt_base = const_cast<uint8_t *>(h2d(st, s.alt_base, v->alt_base, n));
+                if (compact) { // (the staged bytes may end up in the mirror block: the plain columns are always the table's own)
+                    s.c_d16 = h2d(st, c_d16, v->pos_d16, n); s.c_b8 = h2d(st, c_b8, v->bases8, n); s.c_span = h2d(st, c_span, v->span_pos, n_spans);
+                    s.c_eidx = h2d(st, c_eidx, v->pos_esc_idx, n_esc); s.c_eval = h2d(st, c_eval, v->pos_esc_val, n_esc);
+                    s.c_eoff = h2d(st, c_eoff, v->pos_esc_off, n_spans + 1);
+                } else {
+                    s.pos = const_cast<int32_t *>(h2d(st, s.pos, v->pos, n)); s.sflags = const_cast<uint8_t *>(h2d(st, s.sflags, v->sflags, n));
+                    s.ref_base = const_cast<uint8_t *>(h2d(st, s.ref_base, v->ref_base, n)); s.alt_base = const_cast<uint8_t *>(h2d(st, s.alt_base, v->alt_base, n));
+                }
                 f.gt = const_cast<uint8_t *>(h2d(st, f.gt, fv->gt, n)); // (bit 6 is written by the library: the mirror is the library's own memory)
                 if (eight) { // (the staged bytes may end up in the mirror block: the 16-bit columns are always the family's own)
                     for (int m = 0; m < 3; m++) {
@@ -668,6 +712,7 @@ int uz_sites_family_upload_async(uz_ctx *c, const uz_sites_view *v, const uz_fam
                     }
             }
             if (eight) { f.widen_pending = true; f.gq_clamped = true; }
+            s.expand_pending = compact && n;
             family_wide(c, st, fv, f, s.n);
             UZ_HIP(hipEventCreateWithFlags(&f.ready, hipEventDisableTiming));
             UZ_HIP(hipEventRecord(f.ready, st));

@@ -1128,4 +1128,90 @@ const char *uz_vcf_line(const uz_vcf *h, int64_t i, int32_t *len) {
     return (const char *)h->text.data() + h->line_at[(size_t)i];
 }
 
+// ---------------------------------------------------------------- compact site form (uz_types.h: uz_sites_view.pos_d16 ...)
+
+static int base3(uint8_t b) {
+    static const char codes[] = UZ_BASE3_CODES;
+    for (int k = 0; k < (int)sizeof(codes) - 1; k++)
+        if ((uint8_t)codes[k] == b) return k;
+    return -1;
+}
+
+int uz_sites_pack(const uz_sites_view *in, uint8_t *out, int64_t cap, uz_sites_view *view, int64_t *bytes) {
+    if (!in || !bytes || (out && !view)) { last_error = "null argument"; return UZ_IO_E_ARG; }
+    return guarded([&] {
+        const int64_t n = in->n_sites;
+        if (n < 0 || n >= ((int64_t)1 << 31) || in->n_contigs < 0) fail(UZ_IO_E_ARG, "bad site count");
+        if (n && (!in->pos || !in->sflags || !in->ref_base || !in->alt_base)) fail(UZ_IO_E_ARG, "uz_sites_pack takes the plain columns");
+        if (!in->contig_off) fail(UZ_IO_E_ARG, "null contig_off");
+        // the first site of every contig escapes (its pos does not follow from the contig before)
+        std::vector<uint8_t> first((size_t)n + 1, 0);
+        for (int32_t c = 0; c < in->n_contigs; c++) {
+            const int64_t a = in->contig_off[c], b = in->contig_off[c + 1];
+            if (a < 0 || b < a || b > n) fail(UZ_IO_E_ARG, "contig_off does not describe the table");
+            if (a < b) first[(size_t)a] = 1;
+        }
+        if (in->contig_off[0] != 0 || in->contig_off[in->n_contigs] != n) fail(UZ_IO_E_ARG, "contig_off does not describe the table");
+        const int64_t n_spans = (n + UZ_SITE_SPAN - 1) / UZ_SITE_SPAN;
+        auto escapes = [&](int64_t i) {
+            if (i % UZ_SITE_SPAN == 0) return false; // (the span's anchor)
+            const int64_t d = (int64_t)in->pos[i] - in->pos[i - 1];
+            return first[(size_t)i] || d < 0 || d >= UZ_POS_D16_LIMIT;
+        };
+        int64_t n_esc = 0;
+        for (int64_t i = 0; i < n; i++) n_esc += escapes(i);
+        auto al = [](int64_t x) { return (x + 255) & ~(int64_t)255; };
+        const int64_t o_d16 = 0, o_b8 = al(o_d16 + 2 * n), o_span = al(o_b8 + n), o_idx = al(o_span + 4 * n_spans), o_val = al(o_idx + 4 * n_esc),
+                      o_off = al(o_val + 4 * n_esc), end = al(o_off + 4 * (n_spans + 1));
+        *bytes = end;
+        if (!out) return;
+        if (cap < end) fail(UZ_IO_E_ARG, "uz_sites_pack: %lld bytes of room for %lld", (long long)cap, (long long)end);
+        if ((uintptr_t)out % 256) fail(UZ_IO_E_ARG, "uz_sites_pack: the block must be 256-byte aligned");
+        uint16_t *d16 = (uint16_t *)(out + o_d16);
+        uint8_t *b8 = out + o_b8;
+        int32_t *span = (int32_t *)(out + o_span), *eidx = (int32_t *)(out + o_idx), *eval = (int32_t *)(out + o_val), *eoff = (int32_t *)(out + o_off);
+        int64_t e = 0;
+        for (int64_t i = 0; i < n; i++) {
+            const int r = base3(in->ref_base[i]), a = base3(in->alt_base[i]);
+            if (r < 0 || a < 0) fail(UZ_IO_E_RANGE, "site %lld: a base outside the three-bit codes", (long long)i);
+            if (in->sflags[i] & ~UZ_SF_COMPLEX) fail(UZ_IO_E_RANGE, "site %lld: a site flag the compact form does not carry", (long long)i);
+            b8[i] = (uint8_t)(r | a << 3 | (in->sflags[i] & UZ_SF_COMPLEX) << 6);
+            if (i % UZ_SITE_SPAN == 0) { span[i / UZ_SITE_SPAN] = in->pos[i]; eoff[i / UZ_SITE_SPAN] = (int32_t)e; }
+            if (escapes(i)) { eidx[e] = (int32_t)i; eval[e] = in->pos[i]; e++; d16[i] = 0; }
+            else d16[i] = (uint16_t)(i % UZ_SITE_SPAN ? in->pos[i] - in->pos[i - 1] : 0);
+        }
+        eoff[n_spans] = (int32_t)e;
+        memset(view, 0, sizeof(*view));
+        view->n_sites = n; view->n_contigs = in->n_contigs; view->contig_off = in->contig_off;
+        view->pos_d16 = d16; view->bases8 = b8; view->span_pos = span;
+        view->n_pos_esc = n_esc; view->pos_esc_idx = eidx; view->pos_esc_val = eval; view->pos_esc_off = eoff;
+    });
+}
+
+int uz_sites_unpack(const uz_sites_view *v, int32_t *pos, uint8_t *sflags, uint8_t *ref_base, uint8_t *alt_base) {
+    if (!v || !pos || !sflags || !ref_base || !alt_base) { last_error = "null argument"; return UZ_IO_E_ARG; }
+    return guarded([&] {
+        static const char codes[] = UZ_BASE3_CODES;
+        const int64_t n = v->n_sites, n_spans = (n + UZ_SITE_SPAN - 1) / UZ_SITE_SPAN;
+        if (n && (!v->pos_d16 || !v->bases8 || !v->span_pos || !v->pos_esc_off)) fail(UZ_IO_E_ARG, "not a compact site view");
+        for (int64_t s = 0; s < n_spans; s++) {
+            const int64_t lo = s * UZ_SITE_SPAN, hi = std::min(n, lo + UZ_SITE_SPAN);
+            int64_t e = v->pos_esc_off[s];
+            const int64_t e1 = v->pos_esc_off[s + 1];
+            if (e < 0 || e1 < e || e1 > v->n_pos_esc) fail(UZ_IO_E_ARG, "bad escape offsets");
+            uint32_t p = (uint32_t)v->span_pos[s];
+            for (int64_t i = lo; i < hi; i++) {
+                if (e < e1 && v->pos_esc_idx[e] == i) p = (uint32_t)v->pos_esc_val[e++];
+                else if (i > lo) p += v->pos_d16[i];
+                pos[i] = (int32_t)p;
+                const uint8_t b = v->bases8[i];
+                ref_base[i] = (uint8_t)codes[std::min(b & 7, 5)];
+                alt_base[i] = (uint8_t)codes[std::min(b >> 3 & 7, 5)];
+                sflags[i] = (uint8_t)(b >> 6 & 1);
+            }
+            if (e != e1) fail(UZ_IO_E_ARG, "span %lld: an escape outside its span", (long long)s);
+        }
+    });
+}
+
 } // extern "C"

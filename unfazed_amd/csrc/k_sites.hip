@@ -744,6 +744,136 @@ void uz_fold_complex(uz_ctx *c, uint8_t *gt, const uint8_t *sflags, int64_t n) {
     UZ_HIP(hipGetLastError());
 }
 
+// The compact site form (uz_sites_view.pos_d16 ...) into the plain columns the kernels read -- one workgroup per span of UZ_SITE_SPAN sites,
+// four consecutive sites per lane, every column read and written in 4-site vectors -- and, in the same launch, the first-use work of the
+// table's family that k_widen8 and k_fold_complex do apart: the eight-bit genotype columns widened, the complex bit folded into gt.  pos: one
+// segmented sum scan over the span -- an anchor (the span's first site, an escape) starts a segment with its absolute pos, every other site
+// adds its difference.  2 KB of LDS: the workgroups fit beside the header build's (k_pack_link holds most of a CU's LDS).
+struct SitesExpand {
+    const uint16_t *d16;
+    const uint8_t *b8;
+    const int32_t *span, *eidx, *eval, *eoff;
+    int32_t *pos;
+    uint8_t *sflags, *ref, *alt;
+    uint8_t *gt; // null: no family
+    int widen;   // the family's nine columns came in eight bits: widen them (w)
+    Widen8 w;
+};
+__device__ __forceinline__ void seg_add(uint32_t &f, uint32_t &v, uint32_t fp, uint32_t vp) { // (fp, vp) before (f, v)
+    v = f ? v : vp + v;
+    f |= fp;
+}
+__global__ __launch_bounds__(256) void k_sites_expand(int64_t n, SitesExpand x) {
+    __shared__ uint16_t mark[UZ_SITE_SPAN]; // escape number within the span + 1 at an escaped site, else 0
+    __shared__ uint32_t wf[4], wv_[4];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int64_t base = (int64_t)blockIdx.x * UZ_SITE_SPAN, i0 = base + 4 * t;
+    for (int j = t; j < UZ_SITE_SPAN; j += 256) mark[j] = 0;
+    __syncthreads();
+    const int32_t e0 = x.eoff[blockIdx.x], e1 = x.eoff[blockIdx.x + 1];
+    for (int32_t e = e0 + t; e < e1; e += 256) {
+        const int64_t l = (int64_t)x.eidx[e] - base; // (inside the span: the host checked the list, uz_sites_family_upload_async)
+        if (l >= 0 && l < UZ_SITE_SPAN) mark[l] = (uint16_t)(e - e0 + 1);
+    }
+    __syncthreads();
+    const bool full = i0 + 3 < n; // (the last lanes of the last span: site by site)
+    uint32_t d[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
+    if (full) {
+        const ushort4 dv = *reinterpret_cast<const ushort4 *>(x.d16 + i0);
+        const uchar4 bv = *reinterpret_cast<const uchar4 *>(x.b8 + i0);
+        d[0] = dv.x; d[1] = dv.y; d[2] = dv.z; d[3] = dv.w;
+        b[0] = bv.x; b[1] = bv.y; b[2] = bv.z; b[3] = bv.w;
+    } else
+        for (int k = 0; k < 4; k++)
+            if (i0 + k < n) { d[k] = x.d16[i0 + k]; b[k] = x.b8[i0 + k]; }
+    uint32_t loc[4], locf[4], f = 0, acc = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int l = 4 * t + k;
+        const uint32_t m = mark[l];
+        if (l == 0) { f = 1; acc = (uint32_t)x.span[blockIdx.x]; }
+        else if (m) { f = 1; acc = (uint32_t)x.eval[e0 + m - 1]; }
+        else acc += d[k];
+        loc[k] = acc; locf[k] = f;
+    }
+    uint32_t fi = f, vi = acc;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t fp = __shfl_up(fi, o, 64), vp = __shfl_up(vi, o, 64);
+        if (lane >= o) seg_add(fi, vi, fp, vp);
+    }
+    uint32_t fx = __shfl_up(fi, 1, 64), vx = __shfl_up(vi, 1, 64);
+    if (lane == 0) { fx = 0; vx = 0; }
+    if (lane == 63) { wf[wv] = fi; wv_[wv] = vi; }
+    __syncthreads();
+    uint32_t fp = 0, vp = 0; // the waves before this one
+    for (int w = 0; w < wv; w++) { uint32_t fw = wf[w], vw = wv_[w]; seg_add(fw, vw, fp, vp); fp = fw; vp = vw; }
+    seg_add(fx, vx, fp, vp);
+    int32_t p[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) p[k] = (int32_t)(locf[k] ? loc[k] : vx + loc[k]);
+    const uint64_t codes = 0x4E4E4E54474341ull << 8; // UZ_BASE3_CODES by code: 0, A, C, G, T, N (6, 7: N, as uz_sites_unpack)
+    uint8_t r8[4], a8[4], s8[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        r8[k] = (uint8_t)(codes >> (8 * (b[k] & 7u)));
+        a8[k] = (uint8_t)(codes >> (8 * (b[k] >> 3 & 7u)));
+        s8[k] = (uint8_t)(b[k] >> 6 & 1u);
+    }
+    if (full) {
+        *reinterpret_cast<int4 *>(x.pos + i0) = make_int4(p[0], p[1], p[2], p[3]);
+        *reinterpret_cast<uchar4 *>(x.ref + i0) = make_uchar4(r8[0], r8[1], r8[2], r8[3]);
+        *reinterpret_cast<uchar4 *>(x.alt + i0) = make_uchar4(a8[0], a8[1], a8[2], a8[3]);
+        *reinterpret_cast<uchar4 *>(x.sflags + i0) = make_uchar4(s8[0], s8[1], s8[2], s8[3]);
+        if (x.gt) {
+            const uchar4 g = *reinterpret_cast<const uchar4 *>(x.gt + i0);
+            *reinterpret_cast<uchar4 *>(x.gt + i0) = make_uchar4((uint8_t)((g.x & 0x3Fu) | (b[0] & 0x40u)), (uint8_t)((g.y & 0x3Fu) | (b[1] & 0x40u)),
+                                                               (uint8_t)((g.z & 0x3Fu) | (b[2] & 0x40u)), (uint8_t)((g.w & 0x3Fu) | (b[3] & 0x40u)));
+        }
+        if (x.widen) {
+#pragma unroll
+            for (int q = 0; q < 9; q++) {
+                const uchar4 v = *reinterpret_cast<const uchar4 *>(x.w.s[q] + i0);
+                const uint32_t miss = q < 6 ? (uint32_t)UZ_U8_MISSING : 255u;
+                auto wd = [&](uint32_t u) { return (uint16_t)(u == miss ? 0xFFFFu : u); };
+                *reinterpret_cast<ushort4 *>(x.w.d[q] + i0) = make_ushort4(wd(v.x), wd(v.y), wd(v.z), wd(v.w));
+            }
+        }
+        return;
+    }
+    for (int k = 0; k < 4; k++) {
+        const int64_t i = i0 + k;
+        if (i >= n) break;
+        x.pos[i] = p[k]; x.ref[i] = r8[k]; x.alt[i] = a8[k]; x.sflags[i] = s8[k];
+        if (x.gt) x.gt[i] = (uint8_t)((x.gt[i] & 0x3Fu) | (b[k] & 0x40u));
+        if (x.widen)
+            for (int q = 0; q < 9; q++) {
+                const uint32_t v = x.w.s[q][i];
+                x.w.d[q][i] = (uint16_t)(v == (q < 6 ? (uint32_t)UZ_U8_MISSING : 255u) ? 0xFFFFu : v);
+            }
+    }
+}
+void uz_sites_expand(uz_ctx *c, SitesDev &s, FamilyDev *f) {
+    if (!s.expand_pending) return;
+    s.expand_pending = false;
+    SitesExpand x{};
+    x.d16 = s.c_d16; x.b8 = s.c_b8; x.span = s.c_span; x.eidx = s.c_eidx; x.eval = s.c_eval; x.eoff = s.c_eoff;
+    x.pos = s.pos; x.sflags = s.sflags; x.ref = s.ref_base; x.alt = s.alt_base;
+    if (f) {
+        x.gt = f->gt;
+        x.widen = f->widen_pending;
+        f->widen_pending = false;
+        for (int m = 0; m < 3; m++) {
+            x.w.s[m] = f->stage8[m]; x.w.s[3 + m] = f->stage8[3 + m]; x.w.s[6 + m] = f->stage8[6 + m];
+            x.w.d[m] = f->rd[m]; x.w.d[3 + m] = f->ad[m]; x.w.d[6 + m] = f->gq[m];
+        }
+    }
+    if (s.n <= 0) return;
+    const unsigned nb = (unsigned)((s.n + UZ_SITE_SPAN - 1) / UZ_SITE_SPAN);
+    hipLaunchKernelGGL(k_sites_expand, dim3(nb), dim3(256), 0, c->stream, s.n, x);
+    UZ_HIP(hipGetLastError());
+}
+
 bool uz_site_scan_fresh(const uz_ctx *c, const FamilyDev &f, bool need_cnv) {
     return f.cls_valid && (f.cls_has_cnv || !need_cnv) && site_params_equal(f.cls_params, c->P);
 }

@@ -106,6 +106,12 @@ struct SitesDev {
     uint8_t *sflags = nullptr, *ref_base = nullptr, *alt_base = nullptr;
     hipEvent_t ready = nullptr; // asynchronous upload: end of the copies on the copy stream; the first use waits for it
     bool pending = false;
+    // compact link form (uz_sites_view.pos_d16 ...): the staged columns, expanded into pos / sflags / ref_base / alt_base at first use
+    // (uz_sites_expand: with the first family of the table in the same launch)
+    bool expand_pending = false;
+    const uint16_t *c_d16 = nullptr;
+    const uint8_t *c_b8 = nullptr;
+    const int32_t *c_span = nullptr, *c_eidx = nullptr, *c_eval = nullptr, *c_eoff = nullptr;
 };
 
 struct FamilyDev {
@@ -461,6 +467,8 @@ void uz_concat_table(uz_ctx *c, hipStream_t st, ReadsDev &dst, const ReadsDev &s
                      int64_t seq_base, uint32_t qname_base);
 void uz_finish_table(uz_ctx *c, hipStream_t st, ReadsDev &r); // coarse index of a table whose headers are in place
 void uz_family_widen(uz_ctx *c, FamilyDev &f, int64_t n_sites); // eight-bit link columns -> the 16-bit ones, on the compute stream (once)
+// compact site columns -> the plain ones, and -- f not null -- the family's first-use work in the same launch (widen, complex bit into gt)
+void uz_sites_expand(uz_ctx *c, SitesDev &s, FamilyDev *f);
 void uz_launch_site_scan(uz_ctx *c, FamilyDev &f, const SitesDev &s, bool with_cnv);
 void uz_launch_site_scan_many(uz_ctx *c, FamilyDev *const *fams, int n_fam, const SitesDev &s, bool with_cnv);
 void uz_launch_find(uz_ctx *c, FamilyDev &f, const SitesDev &s, int mode, bool host_offsets = true);

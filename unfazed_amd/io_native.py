@@ -34,7 +34,7 @@ IO_EXPORTS = [
     "uz_bamsrc_open", "uz_bamsrc_close", "uz_bamsrc_n_contigs", "uz_bamsrc_contig_name", "uz_bamsrc_contig_length", "uz_bamsrc_tlen_head",
     "uz_index_summary", "uz_inflate_backend", "uz_io_default_threads", "uz_io_cpu_quota", "uz_bam_stage_plan", "uz_bam_stage_begin", "uz_bam_stage_finish", "uz_stage_gather_blocks", "uz_stage_set_inflated", "uz_stage_sizes", "uz_stage_io_stats", "uz_stage_timing", "uz_stage_fill", "uz_stage_qname", "uz_stage_qnames",
     "uz_stage_free", "uz_stage_walk_plan_sizes", "uz_stage_walk_plan", "uz_bam_stage_finish_desc", "uz_stage_kept_sizes", "uz_stage_kept", "uz_stage_walk_host", "uz_stage_kept_debug", "uz_stage_name_records", "uz_packed_block_sums", "uz_stage_merge_subtasks", "uz_bam_stage_finish_sub",
-    "uz_stage_walk_flagged", "uz_stage_lookup", "uz_stage_extra", "uz_stage_n_lookup_tasks",
+    "uz_stage_walk_flagged", "uz_stage_lookup", "uz_stage_extra", "uz_stage_n_lookup_tasks", "uz_sites_pack", "uz_sites_unpack",
 ]
 
 
@@ -94,6 +94,8 @@ def load():
     lib.uz_vcf_free.argtypes = [C.c_void_p]
     lib.uz_vcf_free.restype = None
     lib.uz_vcf_view_get.argtypes = [C.c_void_p, C.POINTER(VcfView)]
+    lib.uz_sites_pack.argtypes = [C.POINTER(abi.SitesView), C.c_void_p, C.c_int64, C.POINTER(abi.SitesView), C.POINTER(C.c_int64)]
+    lib.uz_sites_unpack.argtypes = [C.POINTER(abi.SitesView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.uz_vcf_sample.argtypes = [C.c_void_p, C.c_int32]
     lib.uz_vcf_sample.restype = C.c_char_p
     lib.uz_vcf_contig.argtypes = [C.c_void_p, C.c_int32]
@@ -192,6 +194,34 @@ class IoError(RuntimeError):
 def _check(lib, rc: int) -> None:
     if rc != 0:
         raise IoError(rc, (lib.uz_io_last_error() or b"").decode(errors="replace"))
+
+
+def pack_sites(plain: "abi.SitesView", alloc=None):
+    """A site table's plain columns (a SitesView) in the compact link form (uz_sites_pack) -> (SitesView of the form, the block it points
+    into, its bytes).  alloc(nbytes) -> a 256-byte aligned uint8 array (pinned: PinnedPool.alloc); None: numpy memory.  Raises IoError with
+    UZ_IO_E_RANGE when a base or a flag has no place in the form: the caller keeps the plain columns."""
+    lib = load()
+    nb = C.c_int64(0)
+    _check(lib, lib.uz_sites_pack(C.byref(plain), None, 0, None, C.byref(nb)))
+    size = max(256, int(nb.value))
+    if alloc is None:
+        raw = np.zeros(size + 256, np.uint8)
+        k = (-raw.ctypes.data) % 256
+        block = raw[k: k + size]
+    else:
+        block = alloc(size)
+    v = abi.SitesView()
+    _check(lib, lib.uz_sites_pack(C.byref(plain), block.ctypes.data, int(block.nbytes), C.byref(v), C.byref(nb)))
+    return v, block, int(nb.value)
+
+
+def unpack_sites(v: "abi.SitesView"):
+    """the host twin of the device's expansion: a compact SitesView -> (pos, sflags, ref_base, alt_base)"""
+    lib = load()
+    n = int(v.n_sites)
+    pos, sf, rb, ab = np.zeros(n + 1, np.int32), np.zeros(n + 1, np.uint8), np.zeros(n + 1, np.uint8), np.zeros(n + 1, np.uint8)
+    _check(lib, lib.uz_sites_unpack(C.byref(v), pos.ctypes.data, sf.ctypes.data, rb.ctypes.data, ab.ctypes.data))
+    return pos[:n], sf[:n], rb[:n], ab[:n]
 
 
 def read_bam_stream_table(stream: bytes, threads: int = 0, insert_size_max_sample: int = 1000000) -> ReadsTable:
