@@ -45,7 +45,8 @@ extern "C" {
 #define UZ_K_PHASE 3       /* the per-DNM read stage (both builds of k_phase) */
 #define UZ_K_SIZING 4      /* fetch-range sizing pass */
 #define UZ_K_CNV 5         /* K6 allele-balance count + decision */
-#define UZ_K_COUNT 6
+#define UZ_K_FAMILY_PACK 6 /* k_family_gt_pack (+ the wide-depth gather) of uz_families_from_samples */
+#define UZ_K_COUNT 7
 
 typedef struct uz_ctx uz_ctx;
 
@@ -71,6 +72,26 @@ int uz_family_upload(uz_ctx *ctx, int sites_id, const uz_family_view *fam, int *
  * This is how a batch is streamed in sub-batches: the site stage of sub-batch k + 1 rides the link between the record
  * tables of sub-batches k - 1 and k instead of stopping it. */
 int uz_sites_family_upload_async(uz_ctx *ctx, const uz_sites_view *sites, const uz_family_view *fam, int *sites_id, int *fam_id);
+/* Cohort form of the genotype columns (one multi-sample sites VCF, many trios, README.md:208): the columns of every sample
+ * named by a batch's trios -> HBM ONCE, sample-major (uz_samples_view), and the trios made from them on the device.  Replaces the same
+ * gt_types / gt_ref_depths / gt_alt_depths / gt_quals reads (informative_site_finder.py:257-260) and the per-family `vcf(region)` loop
+ * around them (:42, :213, :558-568), which hands every sample's genotypes out again for every family it belongs to.
+ * uz_samples_upload: one pooled block; the copies are queued on the copy stream (pinned host memory for link speed, uz_pinned_alloc)
+ * and the call returns -- the host arrays must stay untouched until a uz_families_from_samples on the table has returned, which
+ * makes the compute stream wait for the copies' event. */
+int uz_samples_upload(uz_ctx *ctx, int sites_id, const uz_samples_view *samples, int *samples_id);
+/* n trios of a sample table in ONE launch sequence: kid / dad / mom [n] are sample indices of the table.  A family's nine 16-bit
+ * columns ARE the three samples' rows (no copy); it owns its packed genotype byte -- kid | dad << 2 | mom << 4 with the site's complex
+ * flag already in bit 6 (k_family_gt_pack) -- its class bytes and the 32-bit depths of its three members at the table's wide sites.
+ * The families are those of uz_family_upload to every later call (uz_site_scan*, uz_find, uz_phase*, uz_phase_cnv) and live until
+ * uz_sites_free.  UZ_E_ARG: an index outside [0, n_samples), n < 0, a samples_id that names no live table of this context. */
+int uz_families_from_samples(uz_ctx *ctx, int samples_id, int32_t n, const int32_t *kid, const int32_t *dad, const int32_t *mom, int *fam_ids /* [n] */);
+/* Any family's device columns back on the host, whatever route made it: gt [S] (complex bit included), cols [9][S] = ref depth of
+ * kid, dad, mom, alt depth of the three, GQ of the three.  For parity tests of the two routes. */
+int uz_family_fetch(uz_ctx *ctx, int fam_id, uint8_t *gt, uint16_t *cols /* [9][S] */);
+/* A table is kept alive by the families made from it: UZ_E_STATE while one exists.  uz_sites_free frees a sites table's families
+ * and then its sample tables. */
+int uz_samples_free(uz_ctx *ctx, int samples_id);
 /* Alignment records of one BAM -> HBM.  Replaces pysam.AlignmentFile + fetch +
  * mate (read_collector.py:372-385, :400, :167, :185).  Whatever form a table arrives in, HBM holds the packed
  * one (uz_reads_packed_view in uz_types.h).

@@ -138,6 +138,15 @@ int uz_sites_pack(const uz_sites_view *in, uint8_t *out, int64_t cap, uz_sites_v
 /* its inverse on the host (what the device's expansion computes): the plain columns of a compact view */
 int uz_sites_unpack(const uz_sites_view *v, int32_t *pos, uint8_t *sflags, uint8_t *ref_base, uint8_t *alt_base);
 
+/* The device-facing columns of samples pick[0 .. n_pick) of a decoded table (uz_types.h: uz_samples_view), made ONCE per sample instead of
+ * once per trio: gt copied, depths in 16 bits (negative = missing -> UZ_U16_MISSING, clamped at 32767), floor(GQ) (NaN or negative =
+ * missing, clamped at 32767) -- rows [n_pick][n_sites] in the caller's memory (pinned for the upload) -- and the table-level wide
+ * list: the sites where any picked sample has a depth above 32767, ascending, with every picked sample's 32-bit depths
+ * [n_pick][n_wide].  Threads share the samples x spans of sites.  *n_wide is always set; the list is written when wide_site is given
+ * (wide_cap entries of room: call again with the row outputs NULL once the count is known).  UZ_IO_E_RANGE: a depth below -1 or above 2^30. */
+int uz_samples_pack(const uz_vcf_view *in, int32_t n_pick, const int32_t *pick, int threads, uint8_t *gt, uint16_t *ref_depth, uint16_t *alt_depth,
+                    uint16_t *gq, int64_t *n_wide, int64_t wide_cap, int64_t *wide_site, int32_t *wide_ref_depth, int32_t *wide_alt_depth);
+
 /* ------------------------------------------------------------------ staged (packed) records
  * uz_reads_packed_view (uz_types.h) is what crosses the host link.  The caller owns the output buffers (pinned
  * memory from uz_pinned_alloc for the upload): the `out` view arrives with every pointer set to a WRITABLE

@@ -160,6 +160,24 @@ typedef struct uz_family_view {
 #define UZ_U8_MISSING 254u
 #define UZ_U8_SEE_WIDE 255u
 
+/* genotype columns of the samples of a cohort, sample-major: every sample's columns lie in HBM once, and a trio's nine 16-bit columns
+ * are nine rows of this table (uz_families_from_samples).  The values mean what the columns of uz_family_view mean: UZ_U16_MISSING,
+ * depths clamped at 32767, floor(GQ).  The wide list is the TABLE's: a site stands in it when any sample of the table has a depth
+ * above 32767 there, with every sample's depths in 32 bits (-1 = missing).  HOST pointers; rows back to back (row s at s * n_sites,
+ * s * n_wide for the wide depths). */
+typedef struct uz_samples_view {
+    int32_t n_samples;
+    int32_t reserved0;
+    const uint8_t *gt;             /* [n_samples][S] cyvcf2 gt_types codes (0 / 1 / 2 / 3) */
+    const uint16_t *ref_depth;     /* [n_samples][S] */
+    const uint16_t *alt_depth;     /* [n_samples][S] */
+    const uint16_t *gq;            /* [n_samples][S] */
+    int64_t n_wide;
+    const int64_t *wide_site;      /* [n_wide] site index, ascending */
+    const int32_t *wide_ref_depth; /* [n_samples][n_wide]; values up to 2^30 */
+    const int32_t *wide_alt_depth; /* [n_samples][n_wide] */
+} uz_samples_view;
+
 /* alignment records of one BAM in file (coordinate) order */
 typedef struct uz_reads_view {
     int64_t n_segs; /* < 2^31 */

@@ -113,6 +113,14 @@ class FamilyView(C.Structure):
     ]
 
 
+class SamplesView(C.Structure):
+    _fields_ = [
+        ("n_samples", C.c_int32), ("reserved0", C.c_int32),
+        ("gt", _p), ("ref_depth", _p), ("alt_depth", _p), ("gq", _p),
+        ("n_wide", C.c_int64), ("wide_site", _p), ("wide_ref_depth", _p), ("wide_alt_depth", _p),
+    ]
+
+
 class ReadsView(C.Structure):
     _fields_ = [
         ("n_segs", C.c_int64),
@@ -583,6 +591,20 @@ def family_view(gt: np.ndarray, rd: np.ndarray, ad: np.ndarray, gq: np.ndarray, 
             v.wide_ref_depth[m], v.wide_alt_depth[m] = _ptr(wr[m]), _ptr(wa[m])
         keep.update(wide_site=ws, wide_rd=wr, wide_ad=wa)
     return Held(v, keep)
+
+
+def samples_view(cols) -> Held:
+    """model.SampleColumns (SitesTable.sample_columns) -> uz_samples_view; the arrays are used in place (pinned rows stay pinned)"""
+    arrs = dict(gt=_c(cols.gt, np.uint8), ref_depth=_c(cols.ref_depth, np.uint16), alt_depth=_c(cols.alt_depth, np.uint16), gq=_c(cols.gq, np.uint16))
+    v = SamplesView()
+    v.n_samples = len(cols.names)
+    for k, a in arrs.items():
+        setattr(v, k, _ptr(a))
+    if cols.wide is not None and len(cols.wide[0]):
+        ws, wr, wa = _c(cols.wide[0], np.int64), _c(cols.wide[1], np.int32), _c(cols.wide[2], np.int32)
+        v.n_wide, v.wide_site, v.wide_ref_depth, v.wide_alt_depth = int(ws.size), _ptr(ws), _ptr(wr), _ptr(wa)
+        arrs.update(wide_site=ws, wide_rd=wr, wide_ad=wa)
+    return Held(v, arrs)
 
 
 def family_columns8(rd, ad, gq, wide=None):

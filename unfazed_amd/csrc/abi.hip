@@ -169,9 +169,20 @@ ReadsDev &reads_of(uz_ctx *c, int id) {
 void free_family(uz_ctx *c, FamilyDev &f) {
     if (f.ready) { (void)hipEventSynchronize(f.ready); (void)hipEventDestroy(f.ready); f.ready = nullptr; }
     f.pending = false;
+    if (f.samples_id >= 0 && f.samples_id < (int)c->samples.size()) c->samples[(size_t)f.samples_id].live_fams--; // (its gt / cls / wide depths lie in a block of the table's)
     uz_block_put(c, f.block);
     uz_block_put(c, f.wide_block);
     f = FamilyDev();
+}
+void free_samples(uz_ctx *c, SamplesDev &m) {
+    if (m.ready) { (void)hipEventSynchronize(m.ready); (void)hipEventDestroy(m.ready); }
+    uz_block_put(c, m.block);
+    for (DevBlock &b : m.fam_blocks) uz_block_put(c, b);
+    m = SamplesDev();
+}
+SamplesDev &samples_of(uz_ctx *c, int id) {
+    UZ_REQUIRE(id >= 0 && id < (int)c->samples.size() && c->samples[id].live, UZ_E_ARG, "unknown sample table handle");
+    return c->samples[id];
 }
 void free_sites(uz_ctx *c, SitesDev &s) {
     if (s.ready) { (void)hipEventSynchronize(s.ready); (void)hipEventDestroy(s.ready); }
@@ -416,6 +427,8 @@ void uz_destroy(uz_ctx *c) {
     uz_prof_drain(c);
     uz_phase_state_free(c);
     for (auto &f : c->fams) if (f.live) free_family(c, f);
+    for (auto &m : c->samples) if (m.live) free_samples(c, m);
+    c->trio_idx.release();
     for (auto &s : c->sites) if (s.live) free_sites(c, s);
     for (auto &r : c->reads) if (r.live) free_reads(c, r);
     for (auto &b : c->block_pool) (void)hipFree(b.p);
@@ -759,6 +772,140 @@ int uz_family_adopt_device(uz_ctx *c, int sites_id, const uz_family_view *v, int
         const int k = new_slot(c->fams);
         c->fams[k] = f;
         *id = k;
+    });
+}
+
+// ---- the cohort form: a sample table, and trios made from it (unfazed_hip.h) ----------------------------------------------------------
+int uz_samples_upload(uz_ctx *c, int sites_id, const uz_samples_view *v, int *id) {
+    return guarded(c, [&] {
+        UZ_REQUIRE(v && id && v->n_samples >= 0 && v->n_wide >= 0, UZ_E_ARG, "bad samples view");
+        SitesDev &s = sites_of(c, sites_id);
+        const size_t n = (size_t)s.n, ns = (size_t)v->n_samples, w = (size_t)v->n_wide;
+        UZ_REQUIRE(!(n && ns) || (v->gt && v->ref_depth && v->alt_depth && v->gq), UZ_E_ARG, "null column pointer");
+        UZ_REQUIRE(!w || v->wide_site, UZ_E_ARG, "n_wide set but wide_site is null");
+        UZ_REQUIRE(!(w && ns) || (v->wide_ref_depth && v->wide_alt_depth), UZ_E_ARG, "null wide depth column");
+        for (size_t k = 0; k < w; k++)
+            UZ_REQUIRE(v->wide_site[k] >= 0 && v->wide_site[k] < s.n && (k == 0 || v->wide_site[k] > v->wide_site[k - 1]), UZ_E_ARG,
+                       "wide_site must be ascending site indices of the table");
+        for (size_t k = 0; k < w * ns; k++) {
+            const int32_t r = v->wide_ref_depth[k], a = v->wide_alt_depth[k];
+            UZ_REQUIRE(r >= -1 && a >= -1 && r <= (1 << 30) && a <= (1 << 30), UZ_E_RANGE, "wide depth outside [-1, 2^30]");
+        }
+        SamplesDev m;
+        m.live = true; m.sites_id = sites_id; m.n_samples = v->n_samples; m.n_wide = v->n_wide;
+        m.stride = (n + 64 + 255) & ~(size_t)255; // every row 256-byte aligned, vector tail reads stay in-bounds
+        for (int pass = 0; pass < 2; pass++) {
+            Carver cv(pass ? m.block.p : nullptr);
+            m.gt = cv.take<uint8_t>(ns * m.stride);
+            m.rd = cv.take<uint16_t>(ns * m.stride); m.ad = cv.take<uint16_t>(ns * m.stride); m.gq = cv.take<uint16_t>(ns * m.stride);
+            m.wide_site = cv.take<int64_t>(w); m.wide_rd = cv.take<int32_t>(ns * w); m.wide_ad = cv.take<int32_t>(ns * w);
+            if (!pass) m.block = uz_block_get(c, cv.off + 256);
+        }
+        try {
+            hipStream_t st = c->copy_stream;
+            if (n && ns) { // one strided copy per column: the host rows lie back to back, the device rows at the aligned stride
+                UZ_HIP(hipMemcpy2DAsync(m.gt, m.stride, v->gt, n, n, ns, hipMemcpyHostToDevice, st));
+                UZ_HIP(hipMemcpy2DAsync(m.rd, m.stride * 2, v->ref_depth, n * 2, n * 2, ns, hipMemcpyHostToDevice, st));
+                UZ_HIP(hipMemcpy2DAsync(m.ad, m.stride * 2, v->alt_depth, n * 2, n * 2, ns, hipMemcpyHostToDevice, st));
+                UZ_HIP(hipMemcpy2DAsync(m.gq, m.stride * 2, v->gq, n * 2, n * 2, ns, hipMemcpyHostToDevice, st));
+            }
+            if (w) {
+                UZ_HIP(hipMemcpyAsync(m.wide_site, v->wide_site, w * sizeof(int64_t), hipMemcpyHostToDevice, st));
+                if (ns) {
+                    UZ_HIP(hipMemcpyAsync(m.wide_rd, v->wide_ref_depth, ns * w * sizeof(int32_t), hipMemcpyHostToDevice, st));
+                    UZ_HIP(hipMemcpyAsync(m.wide_ad, v->wide_alt_depth, ns * w * sizeof(int32_t), hipMemcpyHostToDevice, st));
+                }
+            }
+            UZ_HIP(hipEventCreateWithFlags(&m.ready, hipEventDisableTiming));
+            UZ_HIP(hipEventRecord(m.ready, st));
+            m.pending = true;
+        } catch (...) { if (m.ready) (void)hipEventDestroy(m.ready); (void)hipStreamSynchronize(c->copy_stream); uz_block_put(c, m.block); throw; }
+        const int k = new_slot(c->samples);
+        c->samples[(size_t)k] = m;
+        *id = k;
+    });
+}
+
+int uz_families_from_samples(uz_ctx *c, int samples_id, int32_t n, const int32_t *kid, const int32_t *dad, const int32_t *mom, int *fam_ids) {
+    return guarded(c, [&] {
+        UZ_REQUIRE(n >= 0 && (n == 0 || (kid && dad && mom && fam_ids)), UZ_E_ARG, "bad trio list");
+        SamplesDev &m0 = samples_of(c, samples_id);
+        UZ_REQUIRE(m0.sites_id >= 0 && m0.sites_id < (int)c->sites.size() && c->sites[(size_t)m0.sites_id].live, UZ_E_ARG, "the sample table's sites table is gone");
+        std::vector<int32_t> trio((size_t)n * 3);
+        for (int32_t t = 0; t < n; t++) {
+            const int32_t idx[3] = {kid[t], dad[t], mom[t]};
+            for (int q = 0; q < 3; q++) {
+                UZ_REQUIRE(idx[q] >= 0 && idx[q] < m0.n_samples, UZ_E_ARG, "sample index outside the table");
+                trio[(size_t)t * 3 + q] = idx[q];
+            }
+        }
+        if (n == 0) return;
+        SitesDev &s = sites_of(c, m0.sites_id);
+        if (m0.pending) { m0.pending = false; UZ_HIP(hipStreamWaitEvent(c->stream, m0.ready, 0)); }
+        const size_t S = (size_t)s.n, w = (size_t)m0.n_wide;
+        const size_t A = (S + 64 + 255) & ~(size_t)255; // cls and gt of trio t: t * 2A and t * 2A + A; the wide depths behind them
+        const size_t wide_at = (size_t)n * 2 * A;
+        DevBlock blk = uz_block_get(c, wide_at + (size_t)n * 6 * w * sizeof(int32_t) + 512);
+        int made = 0;
+        try {
+            c->trio_idx.ensure(trio.size());
+            UZ_HIP(hipMemcpyAsync(c->trio_idx.p, trio.data(), trio.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+            int32_t *wide_out = reinterpret_cast<int32_t *>(blk.p + wide_at);
+            uz_launch_family_pack(c, m0, s, n, c->trio_idx.p, blk.p + A, 2 * A, wide_out);
+            UZ_HIP(hipStreamSynchronize(c->stream)); // (`trio` is pageable host memory; the families are ready when the call returns)
+            for (int32_t t = 0; t < n; t++) {
+                const int k = new_slot(c->fams); // (may move c->fams: no reference into it is held across)
+                FamilyDev f;
+                f.live = true; f.owned = true; f.sites_id = m0.sites_id; f.samples_id = samples_id;
+                f.cls = blk.p + (size_t)t * 2 * A;
+                f.gt = blk.p + (size_t)t * 2 * A + A;
+                SamplesDev &m = c->samples[(size_t)samples_id];
+                const int32_t *ix = &trio[(size_t)t * 3];
+                for (int q = 0; q < 3; q++) {
+                    f.rd[q] = m.rd + (size_t)ix[q] * m.stride; f.ad[q] = m.ad + (size_t)ix[q] * m.stride; f.gq[q] = m.gq + (size_t)ix[q] * m.stride;
+                }
+                f.n_wide = m.n_wide;
+                f.wide_site = m.wide_site;
+                f.wide_depth = w ? wide_out + (size_t)t * 6 * w : nullptr;
+                c->fams[(size_t)k] = f;
+                m.live_fams++;
+                fam_ids[t] = k;
+                made++;
+            }
+            c->samples[(size_t)samples_id].fam_blocks.push_back(blk);
+        } catch (...) {
+            (void)hipStreamSynchronize(c->stream);
+            for (int t = 0; t < made; t++) free_family(c, c->fams[(size_t)fam_ids[t]]);
+            uz_block_put(c, blk);
+            throw;
+        }
+    });
+}
+
+int uz_family_fetch(uz_ctx *c, int fam_id, uint8_t *gt, uint16_t *cols) {
+    return guarded(c, [&] {
+        FamilyDev &f = fam_of(c, fam_id);
+        SitesDev &s = sites_of(c, f.sites_id);
+        const size_t n = (size_t)s.n;
+        if (!n) return;
+        UZ_REQUIRE(gt != nullptr && cols != nullptr, UZ_E_ARG, "null output");
+        uz_family_widen(c, f, s.n);
+        UZ_HIP(hipStreamSynchronize(c->stream));
+        UZ_HIP(hipMemcpy(gt, f.gt, n, hipMemcpyDeviceToHost));
+        for (int q = 0; q < 3; q++) {
+            UZ_HIP(hipMemcpy(cols + (size_t)q * n, f.rd[q], n * 2, hipMemcpyDeviceToHost));
+            UZ_HIP(hipMemcpy(cols + (size_t)(3 + q) * n, f.ad[q], n * 2, hipMemcpyDeviceToHost));
+            UZ_HIP(hipMemcpy(cols + (size_t)(6 + q) * n, f.gq[q], n * 2, hipMemcpyDeviceToHost));
+        }
+    });
+}
+
+int uz_samples_free(uz_ctx *c, int samples_id) {
+    return guarded(c, [&] {
+        SamplesDev &m = samples_of(c, samples_id);
+        UZ_REQUIRE(m.live_fams == 0, UZ_E_STATE, "families made from this sample table are alive: uz_sites_free frees them with it");
+        UZ_HIP(hipStreamSynchronize(c->stream));
+        free_samples(c, m);
     });
 }
 
@@ -1414,6 +1561,8 @@ int uz_sites_free(uz_ctx *c, int sites_id) {
         UZ_HIP(hipStreamSynchronize(c->stream));
         for (size_t k = 0; k < c->fams.size(); k++)
             if (c->fams[k].live && c->fams[k].sites_id == sites_id) { find_forget(c, (int)k); free_family(c, c->fams[k]); }
+        for (auto &m : c->samples)
+            if (m.live && m.sites_id == sites_id) free_samples(c, m);
         free_sites(c, s);
     });
 }

@@ -1214,4 +1214,61 @@ int uz_sites_unpack(const uz_sites_view *v, int32_t *pos, uint8_t *sflags, uint8
     });
 }
 
+// ---------------------------------------------------------------- per-sample device columns (uz_types.h: uz_samples_view)
+
+int uz_samples_pack(const uz_vcf_view *in, int32_t n_pick, const int32_t *pick, int threads, uint8_t *gt, uint16_t *ref_depth, uint16_t *alt_depth,
+                    uint16_t *gq, int64_t *n_wide, int64_t wide_cap, int64_t *wide_site, int32_t *wide_ref_depth, int32_t *wide_alt_depth) {
+    if (!in || !n_wide || n_pick < 0 || (n_pick && !pick)) { last_error = "null argument"; return UZ_IO_E_ARG; }
+    return guarded([&] {
+        const int64_t n = in->n_sites;
+        if (n < 0 || in->n_samples < 0) fail(UZ_IO_E_ARG, "bad table sizes");
+        for (int32_t k = 0; k < n_pick; k++)
+            if (pick[k] < 0 || pick[k] >= in->n_samples) fail(UZ_IO_E_ARG, "sample index %d outside the table's %d samples", (int)pick[k], (int)in->n_samples);
+        if (n && n_pick && (!in->gt || !in->ref_depth || !in->alt_depth || !in->gq)) fail(UZ_IO_E_ARG, "null genotype column");
+        const bool rows = gt && ref_depth && alt_depth && gq;
+        if (!rows && (gt || ref_depth || alt_depth || gq)) fail(UZ_IO_E_ARG, "uz_samples_pack: set all four row outputs or none");
+        // work items: sample x span of sites; a site any picked sample is too deep at is marked (several threads may write the same 1)
+        const int64_t span = 1 << 16, n_spans = (n + span - 1) / span, n_items = n_spans * n_pick;
+        std::vector<uint8_t> deep((size_t)n, 0);
+        std::atomic<int> bad{0};
+        const int T = workers_for(n_items, resolve_threads(threads), 1);
+        parallel_dynamic(n_items, T, [&](int64_t item, int) {
+            const int64_t k = item / n_spans, lo = (item % n_spans) * span, hi = std::min(n, lo + span);
+            const size_t src = (size_t)pick[k] * (size_t)n, dst = (size_t)k * (size_t)n;
+            const int32_t *rd = in->ref_depth + src, *ad = in->alt_depth + src;
+            const double *q = in->gq + src;
+            int err = 0;
+            for (int64_t i = lo; i < hi; i++) {
+                const int32_t r = rd[i], a = ad[i];
+                if (r < -1 || a < -1) err |= 1;
+                if (r > (1 << 30) || a > (1 << 30)) err |= 2;
+                if (r > 32767 || a > 32767) deep[(size_t)i] = 1;
+                if (!rows) continue;
+                gt[dst + i] = in->gt[src + i];
+                ref_depth[dst + i] = (uint16_t)(r < 0 ? UZ_U16_MISSING : r > 32767 ? 32767 : r);
+                alt_depth[dst + i] = (uint16_t)(a < 0 ? UZ_U16_MISSING : a > 32767 ? 32767 : a);
+                const double g = std::floor(q[i]); // NaN and anything negative: missing; the rest clamped like the depths
+                gq[dst + i] = (uint16_t)(!(g >= 0.0) ? UZ_U16_MISSING : g > 32767.0 ? 32767 : (int)g);
+            }
+            if (err) bad.fetch_or(err);
+        });
+        if (bad.load() & 1) fail(UZ_IO_E_RANGE, "negative allele depth other than the missing marker -1");
+        if (bad.load() & 2) fail(UZ_IO_E_RANGE, "allele depth above 2^30");
+        int64_t w = 0;
+        for (int64_t i = 0; i < n; i++) w += deep[(size_t)i];
+        *n_wide = w;
+        if (!wide_site || !w) return;
+        if (wide_cap < w || !wide_ref_depth || !wide_alt_depth) fail(UZ_IO_E_ARG, "uz_samples_pack: room for %lld wide sites, %lld found", (long long)wide_cap, (long long)w);
+        int64_t e = 0;
+        for (int64_t i = 0; i < n; i++)
+            if (deep[(size_t)i]) wide_site[e++] = i;
+        for (int32_t k = 0; k < n_pick; k++)
+            for (int64_t j = 0; j < w; j++) {
+                const size_t at = (size_t)pick[k] * (size_t)n + (size_t)wide_site[j];
+                wide_ref_depth[(size_t)k * w + j] = in->ref_depth[at];
+                wide_alt_depth[(size_t)k * w + j] = in->alt_depth[at];
+            }
+    });
+}
+
 } // extern "C"

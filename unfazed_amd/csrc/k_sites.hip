@@ -874,6 +874,72 @@ void uz_sites_expand(uz_ctx *c, SitesDev &s, FamilyDev *f) {
     UZ_HIP(hipGetLastError());
 }
 
+// ---- trios of a sample table (uz_families_from_samples, abi.hip) ---------------------------------------------------------------------
+// The packed genotype byte of n trios in ONE launch: blockIdx.y picks the trio, a lane takes 16 consecutive sites -- three 16-byte loads (the
+// members' gt rows of the sample table), one of the site flags, one 16-byte store.  The complex bit goes in here, so a family made this way
+// needs no k_fold_complex.  Pure streaming: 4 bytes read and 1 written per site and trio, no LDS; the workgroups walk the site chunks
+// grid-stride like k_site_scan's.
+__device__ __forceinline__ uint32_t gt_pack4(uint32_t k, uint32_t d, uint32_t m, uint32_t s) {
+    return (k & 0x03030303u) | ((d & 0x03030303u) << 2) | ((m & 0x03030303u) << 4) | ((s & 0x01010101u * UZ_SF_COMPLEX) << 6);
+}
+__global__ __launch_bounds__(256) void k_family_gt_pack(int64_t n, const uint8_t *__restrict__ gt, size_t stride, const int32_t *__restrict__ trio,
+                                                        const uint8_t *__restrict__ sflags, uint8_t *__restrict__ out, size_t out_stride) {
+    const size_t t = blockIdx.y;
+    const uint8_t *__restrict__ gk = gt + (size_t)trio[3 * t] * stride;
+    const uint8_t *__restrict__ gd = gt + (size_t)trio[3 * t + 1] * stride;
+    const uint8_t *__restrict__ gm = gt + (size_t)trio[3 * t + 2] * stride;
+    uint8_t *__restrict__ o = out + t * out_stride;
+    const int64_t n_chunks = (n + 256 * 16 - 1) / (256 * 16);
+    for (int64_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+        const int64_t base = (chunk * 256 + threadIdx.x) * 16;
+        if (base >= n) continue;
+        if (base + 16 <= n) {
+            const uint4 k = *reinterpret_cast<const uint4 *>(gk + base), d = *reinterpret_cast<const uint4 *>(gd + base);
+            const uint4 m = *reinterpret_cast<const uint4 *>(gm + base), s = *reinterpret_cast<const uint4 *>(sflags + base);
+            *reinterpret_cast<uint4 *>(o + base) = make_uint4(gt_pack4(k.x, d.x, m.x, s.x), gt_pack4(k.y, d.y, m.y, s.y), gt_pack4(k.z, d.z, m.z, s.z),
+                                                              gt_pack4(k.w, d.w, m.w, s.w));
+        } else {
+            for (int64_t i = base; i < n; i++) o[i] = (uint8_t)gt_pack4(gk[i], gd[i], gm[i], sflags[i]);
+        }
+    }
+}
+// the 32-bit depths of every trio's members at the table's wide sites: [6][n_wide] per trio (rd kid, dad, mom, ad kid, dad, mom), what
+// k_site_scan_wide reads; one lane per (wide site, trio)
+__global__ __launch_bounds__(256) void k_family_wide_gather(int64_t n_wide, const int32_t *__restrict__ wrd, const int32_t *__restrict__ wad,
+                                                            const int32_t *__restrict__ trio, int32_t *__restrict__ out) {
+    const size_t t = blockIdx.y;
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n_wide) return;
+    int32_t *__restrict__ o = out + t * 6 * (size_t)n_wide;
+#pragma unroll
+    for (int m = 0; m < 3; m++) {
+        const size_t row = (size_t)trio[3 * t + m] * (size_t)n_wide;
+        o[(size_t)m * n_wide + k] = wrd[row + k];
+        o[(size_t)(3 + m) * n_wide + k] = wad[row + k];
+    }
+}
+void uz_launch_family_pack(uz_ctx *c, const SamplesDev &sm, const SitesDev &s, int32_t n, const int32_t *trio, uint8_t *gt_out, size_t gt_stride, int32_t *wide_out) {
+    if (n <= 0) return;
+    UZ_REQUIRE((uintptr_t)s.sflags % 16 == 0, UZ_E_ARG, "the site flags of an adopted sites table must be 16-byte aligned for uz_families_from_samples");
+    ProfScope ps(c, UZ_K_FAMILY_PACK);
+    const int32_t y_max = 65535; // (grid limit: more trios go in slices)
+    for (int32_t t0 = 0; t0 < n; t0 += y_max) {
+        const int32_t ny = std::min<int32_t>(y_max, n - t0);
+        if (s.n > 0) {
+            const int64_t n_chunks = (s.n + 256 * 16 - 1) / (256 * 16);
+            const int64_t nb = std::max<int64_t>(1, std::min<int64_t>(n_chunks, std::max<int64_t>(4096 / ny, 16))); // the trios fill the chip together
+            hipLaunchKernelGGL(k_family_gt_pack, dim3((unsigned)nb, (unsigned)ny), dim3(256), 0, c->stream, s.n, (const uint8_t *)sm.gt, sm.stride, trio + 3 * (size_t)t0,
+                               (const uint8_t *)s.sflags, gt_out + (size_t)t0 * gt_stride, gt_stride);
+            UZ_HIP(hipGetLastError());
+        }
+        if (sm.n_wide > 0) {
+            hipLaunchKernelGGL(k_family_wide_gather, dim3((unsigned)((sm.n_wide + 255) / 256), (unsigned)ny), dim3(256), 0, c->stream, sm.n_wide, (const int32_t *)sm.wide_rd,
+                               (const int32_t *)sm.wide_ad, trio + 3 * (size_t)t0, wide_out + (size_t)t0 * 6 * (size_t)sm.n_wide);
+            UZ_HIP(hipGetLastError());
+        }
+    }
+}
+
 bool uz_site_scan_fresh(const uz_ctx *c, const FamilyDev &f, bool need_cnv) {
     return f.cls_valid && (f.cls_has_cnv || !need_cnv) && site_params_equal(f.cls_params, c->P);
 }

@@ -137,9 +137,31 @@ struct FamilyDev {
     // eight-bit link form (uz_family_view.ref_depth8 ...): the staged bytes, widened into rd / ad / gq at first use; gq was clamped at 254
     const uint8_t *stage8[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool widen_pending = false, gq_clamped = false;
+    // made by uz_families_from_samples: rd / ad / gq are rows of that sample table, wide_site is the table's, and gt / cls / wide_depth
+    // lie in a block the TABLE owns (one per call, SamplesDev::fam_blocks) -- `block` and `wide_block` stay empty
+    int samples_id = -1;
     bool cls_valid = false;
     bool cls_has_cnv = false; // DEL / DUP codes (bits 3-6) computed
     uz_params cls_params;
+};
+
+// the 16-bit genotype columns of a cohort's samples, sample-major (uz_samples_view): rows are padded to a stride that keeps every row
+// 256-byte aligned (the site scan reads a family's columns -- rows of this table -- in 16-byte vectors)
+struct SamplesDev {
+    bool live = false;
+    int sites_id = -1;
+    int32_t n_samples = 0;
+    DevBlock block;                   // the rows, the wide list
+    std::vector<DevBlock> fam_blocks; // gt / cls / wide depths of the families made from the table: one block per uz_families_from_samples
+    int live_fams = 0;                // families that alias the rows: the table cannot be freed before them
+    size_t stride = 0;                // elements between two rows (of gt and of the 16-bit columns alike)
+    uint8_t *gt = nullptr;
+    uint16_t *rd = nullptr, *ad = nullptr, *gq = nullptr;
+    int64_t n_wide = 0;
+    int64_t *wide_site = nullptr;
+    int32_t *wide_rd = nullptr, *wide_ad = nullptr; // [n_samples][n_wide]
+    hipEvent_t ready = nullptr; // end of the copies on the copy stream; the first uz_families_from_samples makes the compute stream wait for it
+    bool pending = false;
 };
 
 struct ReadsDev {
@@ -248,6 +270,8 @@ struct uz_ctx {
     std::vector<SitesDev> sites;
     std::vector<FamilyDev> fams;
     std::vector<ReadsDev> reads;
+    std::vector<SamplesDev> samples;
+    DevBuf<int32_t> trio_idx; // uz_families_from_samples: kid / dad / mom sample indices of the batch's trios
 
     // allele-balance threshold table of K1 (k_sites.hip), rebuilt when the thresholds change
     DevBuf<int32_t> ab_lut;
@@ -469,6 +493,9 @@ void uz_finish_table(uz_ctx *c, hipStream_t st, ReadsDev &r); // coarse index of
 void uz_family_widen(uz_ctx *c, FamilyDev &f, int64_t n_sites); // eight-bit link columns -> the 16-bit ones, on the compute stream (once)
 // compact site columns -> the plain ones, and -- f not null -- the family's first-use work in the same launch (widen, complex bit into gt)
 void uz_sites_expand(uz_ctx *c, SitesDev &s, FamilyDev *f);
+// n trios of a sample table: packed genotype bytes (complex bit folded in) and the members' depths at the table's wide sites, one launch each;
+// trio: [3 n] sample indices on the device; gt_out / wide_out: trio t at t * gt_stride bytes / t * 6 * n_wide values
+void uz_launch_family_pack(uz_ctx *c, const SamplesDev &sm, const SitesDev &s, int32_t n, const int32_t *trio, uint8_t *gt_out, size_t gt_stride, int32_t *wide_out);
 void uz_launch_site_scan(uz_ctx *c, FamilyDev &f, const SitesDev &s, bool with_cnv);
 void uz_launch_site_scan_many(uz_ctx *c, FamilyDev *const *fams, int n_fam, const SitesDev &s, bool with_cnv);
 void uz_launch_find(uz_ctx *c, FamilyDev &f, const SitesDev &s, int mode, bool host_offsets = true);

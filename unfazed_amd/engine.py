@@ -14,11 +14,11 @@ from . import abi
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("UZ_HIP_LIB", os.path.join(_HERE, "libunfazed_hip.so"))
 
-K_SITE_SCAN, K_WINDOW_COUNT, K_WINDOW_FILL, K_PHASE, K_SIZING, K_CNV = 0, 1, 2, 3, 4, 5
+K_SITE_SCAN, K_WINDOW_COUNT, K_WINDOW_FILL, K_PHASE, K_SIZING, K_CNV, K_FAMILY_PACK = 0, 1, 2, 3, 4, 5, 6
 
 EXPORTS = [
     "uz_create", "uz_destroy", "uz_last_error", "uz_sync", "uz_set_params",
-    "uz_sites_upload", "uz_family_upload", "uz_sites_family_upload_async", "uz_reads_upload", "uz_reads_upload_packed", "uz_reads_wait", "uz_reads_headers", "uz_bgzf_inflate", "uz_bgzf_inflate_to_host", "uz_bam_walk", "uz_crc32_blocks", "uz_bam_walk_fetch", "uz_bam_walk_release", "uz_reads_from_bam",
+    "uz_sites_upload", "uz_family_upload", "uz_sites_family_upload_async", "uz_samples_upload", "uz_families_from_samples", "uz_family_fetch", "uz_samples_free", "uz_reads_upload", "uz_reads_upload_packed", "uz_reads_wait", "uz_reads_headers", "uz_bgzf_inflate", "uz_bgzf_inflate_to_host", "uz_bam_walk", "uz_crc32_blocks", "uz_bam_walk_fetch", "uz_bam_walk_release", "uz_reads_from_bam",
     "uz_bam_walk_flags", "uz_bam_join", "uz_bam_join_needs", "uz_bam_join_fetch", "uz_reads_from_walk", "uz_reads_names", "uz_walk_slot_stats", "uz_walk_reserve",
     "uz_pinned_alloc", "uz_pinned_free",
     "uz_sites_adopt_device", "uz_family_adopt_device", "uz_reads_adopt_device",
@@ -80,6 +80,10 @@ def load_library(path: Optional[str] = None):
     for f in ("uz_family_upload", "uz_family_adopt_device"):
         getattr(L, f).argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int)]
     L.uz_sites_family_upload_async.argtypes = [vp, vp, vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.uz_samples_upload.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int)]
+    L.uz_families_from_samples.argtypes = [vp, C.c_int, C.c_int32, vp, vp, vp, vp]
+    L.uz_family_fetch.argtypes = [vp, C.c_int, vp, vp]
+    L.uz_samples_free.argtypes = [vp, C.c_int]
     L.uz_drop_derived.argtypes = [vp]
     L.uz_sites_free.argtypes = [vp, C.c_int]
     L.uz_reads_free.argtypes = [vp, C.c_int]
@@ -177,6 +181,37 @@ class HipEngine:
         fid = C.c_int(-1)
         self._ck(self.L.uz_family_upload(self.h, int(sites_h), v.ref(), C.byref(fid)), "uz_family_upload")
         return fid.value
+
+    # ---- the cohort form: the samples' columns in HBM once, trios made from them on the device
+    def upload_samples(self, sites_h: int, cols) -> int:
+        """model.SampleColumns (SitesTable.sample_columns; rows in pinned memory -- alloc=PinnedPool.alloc -- for link speed) -> a sample
+        table of the sites table (uz_samples_upload: queued on the copy stream).  The arrays are kept until the table is freed."""
+        v = abi.samples_view(cols)
+        mid = C.c_int(-1)
+        self._ck(self.L.uz_samples_upload(self.h, int(sites_h), v.ref(), C.byref(mid)), "uz_samples_upload")
+        self._samples = getattr(self, "_samples", {})
+        self._samples[mid.value] = (int(sites_h), v)
+        return mid.value
+
+    def families_from_samples(self, samples_h: int, kid, dad, mom) -> list:
+        """the trios (kid[t], dad[t], mom[t]) -- sample indices of the table -- as families, one launch sequence (uz_families_from_samples)"""
+        k, d, m = (np.ascontiguousarray(x, np.int32) for x in (kid, dad, mom))
+        if not (k.size == d.size == m.size):
+            raise ValueError("kid / dad / mom lists of different lengths")
+        out = np.full(max(1, k.size), -1, np.int32)
+        self._ck(self.L.uz_families_from_samples(self.h, int(samples_h), int(k.size), k.ctypes.data, d.ctypes.data, m.ctypes.data, out.ctypes.data),
+                 "uz_families_from_samples")
+        return [int(x) for x in out[: k.size]]
+
+    def family_fetch(self, fam: int, n_sites: int):
+        """a family's device columns, whatever route made it -> (gt u8 [S] with the complex bit, cols u16 [9][S]: rd k d m, ad k d m, gq k d m)"""
+        gt, cols = np.zeros(max(1, n_sites), np.uint8), np.zeros((9, max(1, n_sites)), np.uint16)
+        self._ck(self.L.uz_family_fetch(self.h, int(fam), gt.ctypes.data, cols.ctypes.data), "uz_family_fetch")
+        return gt[:n_sites], cols[:, :n_sites] if n_sites else cols[:, :0]
+
+    def free_samples(self, samples_h: int):
+        self._ck(self.L.uz_samples_free(self.h, int(samples_h)), "uz_samples_free")
+        getattr(self, "_samples", {}).pop(int(samples_h), None)
 
     def upload_sites_family_async(self, held: abi.Held, gt, rd, ad, gq, wide=None):
         """sites + one trio's genotype columns queued on the copy stream (uz_sites_family_upload_async) -> (sites id, family id);
@@ -504,6 +539,7 @@ class HipEngine:
 
     def free_sites(self, sid: int):
         self._ck(self.L.uz_sites_free(self.h, int(sid)), "uz_sites_free")
+        self._samples = {k: x for k, x in getattr(self, "_samples", {}).items() if x[0] != int(sid)}  # (its sample tables went with it)
         self._staged_sites.pop(int(sid), None)
 
     def free_reads(self, rid: int):

@@ -193,16 +193,59 @@ class PhasingHost:
         self._reads_h: Dict[str, object] = {}
         self.cutoffs: Dict[str, float] = {}  # reference snv_phaser.py:14 concordant_upper_lens
         self.capacity_skipped: List[str] = []  # record keys the device refused (UZ_ST_CAPACITY)
+        # the cohort form of the family columns (prepare_families): the sample tables on the device, [(handle, {sample: row})], and which
+        # route made the families -- families_from_samples = made on the device, in families_from_samples_calls calls, from
+        # samples_uploaded rows in sample_tables tables; families_host = made by family_columns + add_family, one at a time
+        self._sample_tabs: List[tuple] = []
+        self.stats: Dict[str, int] = dict(families_from_samples=0, families_from_samples_calls=0, samples_uploaded=0, sample_tables=0, families_host=0)
 
     # ------------------------------------------------------------ handles
     def family(self, kid: str, dad: str, mom: str):
         key = (kid, dad, mom)
         if key not in self._fam_h:
+            self.stats["families_host"] += 1
             gt, rd, ad, gq = self.sites.family_columns(kid, dad, mom)
             wide = getattr(self.sites, "wide_depths", None)  # sites deeper than the 16-bit columns hold: their 32-bit depths
             self._fam_h[key] = self.backend.add_family(self._sites_h, gt, rd, ad, gq, wide=wide) if wide is not None else \
                 self.backend.add_family(self._sites_h, gt, rd, ad, gq)
         return self._fam_h[key]
+
+    def prepare_families(self, trios):
+        """The families of a whole batch up front, by the cohort route: when the batch names two or more kids and the backend keeps sample
+        tables (upload_samples), the columns of the samples its new trios name go to the device ONCE, as one sample table, and all the
+        trios are made there in one call (uz_families_from_samples) -- instead of a dozen numpy passes and ten blocking copies per trio,
+        a shared parent converted once per sibling.  A trio whose three members lie in a table of an earlier call is made from that
+        table; the others' samples form a new table (a member they share with an older table travels again with it).
+        UZ_FAMILY_ROUTE=host, a single kid, or a backend without sample tables: family() makes them one by one, as before."""
+        trios = list(dict.fromkeys(trios))
+        if len({t[0] for t in trios}) < 2 or not hasattr(self.backend, "upload_samples") or __import__("os").environ.get("UZ_FAMILY_ROUTE", "device") == "host":
+            return
+        new = [t for t in trios if t not in self._fam_h]
+        if not new:
+            return
+        by_tab: Dict[int, list] = {}
+        rest = []
+        for t in new:
+            for k, (_, rows) in enumerate(self._sample_tabs):
+                if all(s in rows for s in t):
+                    by_tab.setdefault(k, []).append(t)
+                    break
+            else:
+                rest.append(t)
+        if rest:
+            names = list(dict.fromkeys(s for t in rest for s in t))
+            cols = self.sites.sample_columns(names)
+            self._sample_tabs.append((self.backend.upload_samples(self._sites_h, cols), {s: r for r, s in enumerate(names)}))
+            self.stats["sample_tables"] += 1
+            self.stats["samples_uploaded"] += len(names)
+            by_tab[len(self._sample_tabs) - 1] = rest
+        for k, ts in by_tab.items():
+            h, rows = self._sample_tabs[k]
+            fams = self.backend.families_from_samples(h, [rows[t[0]] for t in ts], [rows[t[1]] for t in ts], [rows[t[2]] for t in ts])
+            self.stats["families_from_samples_calls"] += 1
+            self.stats["families_from_samples"] += len(ts)
+            for t, f in zip(ts, fams):
+                self._fam_h[t] = f
 
     def reads(self, bam: str, min_base_qual: int):
         """device handle of the whole table of a BAM (kept for the life of the host), staged for this base-quality threshold"""
@@ -301,6 +344,7 @@ class PhasingHost:
         for i in scan:
             by_kid.setdefault(dnms[i]["kid"], []).append(i)
         mode = (abi.FIND_WHOLE_REGION if whole_region else 0) | (0 if many else abi.FIND_SECOND_WINDOW)
+        self.prepare_families((kid, pedigrees[kid]["dad"], pedigrees[kid]["mom"]) for kid in by_kid)
         for kid, idxs in by_kid.items():
             dad, mom = pedigrees[kid]["dad"], pedigrees[kid]["mom"]
             fam = self.family(kid, dad, mom)

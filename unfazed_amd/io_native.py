@@ -34,7 +34,7 @@ IO_EXPORTS = [
     "uz_bamsrc_open", "uz_bamsrc_close", "uz_bamsrc_n_contigs", "uz_bamsrc_contig_name", "uz_bamsrc_contig_length", "uz_bamsrc_tlen_head",
     "uz_index_summary", "uz_inflate_backend", "uz_io_default_threads", "uz_io_cpu_quota", "uz_bam_stage_plan", "uz_bam_stage_begin", "uz_bam_stage_finish", "uz_stage_gather_blocks", "uz_stage_set_inflated", "uz_stage_sizes", "uz_stage_io_stats", "uz_stage_timing", "uz_stage_fill", "uz_stage_qname", "uz_stage_qnames",
     "uz_stage_free", "uz_stage_walk_plan_sizes", "uz_stage_walk_plan", "uz_bam_stage_finish_desc", "uz_stage_kept_sizes", "uz_stage_kept", "uz_stage_walk_host", "uz_stage_kept_debug", "uz_stage_name_records", "uz_packed_block_sums", "uz_stage_merge_subtasks", "uz_bam_stage_finish_sub",
-    "uz_stage_walk_flagged", "uz_stage_lookup", "uz_stage_extra", "uz_stage_n_lookup_tasks", "uz_sites_pack", "uz_sites_unpack",
+    "uz_stage_walk_flagged", "uz_stage_lookup", "uz_stage_extra", "uz_stage_n_lookup_tasks", "uz_sites_pack", "uz_sites_unpack", "uz_samples_pack",
 ]
 
 
@@ -96,6 +96,8 @@ def load():
     lib.uz_vcf_view_get.argtypes = [C.c_void_p, C.POINTER(VcfView)]
     lib.uz_sites_pack.argtypes = [C.POINTER(abi.SitesView), C.c_void_p, C.c_int64, C.POINTER(abi.SitesView), C.POINTER(C.c_int64)]
     lib.uz_sites_unpack.argtypes = [C.POINTER(abi.SitesView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.uz_samples_pack.argtypes = [C.POINTER(VcfView), C.c_int32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int64,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]
     lib.uz_vcf_sample.argtypes = [C.c_void_p, C.c_int32]
     lib.uz_vcf_sample.restype = C.c_char_p
     lib.uz_vcf_contig.argtypes = [C.c_void_p, C.c_int32]
@@ -213,6 +215,48 @@ def pack_sites(plain: "abi.SitesView", alloc=None):
     v = abi.SitesView()
     _check(lib, lib.uz_sites_pack(C.byref(plain), block.ctypes.data, int(block.nbytes), C.byref(v), C.byref(nb)))
     return v, block, int(nb.value)
+
+
+def pack_samples(table: SitesTable, pick, threads: int = 0, alloc=None):
+    """The device-facing columns of samples `pick` (indices into table.samples) of a table whose genotype columns are the decoder's
+    ([ns][S]: u8 gt, int32 depths, f64 GQ) -- uz_samples_pack: every sample converted once, threads over samples x site spans.
+    alloc(nbytes) -> uint8 array chooses the memory of the rows (pinned for the upload); None: numpy memory.
+    -> (gt u8 [k][S], ref_depth u16 [k][S], alt_depth, gq, wide): wide = None or (site i64 [w], ref_depth i32 [k][w], alt_depth).
+    A depth below -1 raises ValueError, one above 2^30 OverflowError, as SitesTable.family_columns does."""
+    lib = load()
+    pick = np.ascontiguousarray(pick, np.int32)
+    k, n = int(pick.size), int(table.n_sites)
+    cols = [np.ascontiguousarray(table.gt, np.uint8), np.ascontiguousarray(table.ref_depth, np.int32), np.ascontiguousarray(table.alt_depth, np.int32),
+            np.ascontiguousarray(table.gq, np.float64)]
+    v = VcfView()
+    v.n_sites, v.n_samples, v.n_contigs = n, len(table.samples), 0
+    v.gt, v.ref_depth, v.alt_depth, v.gq = (c.ctypes.data for c in cols)
+
+    def room(nbytes, dtype):
+        a = alloc(max(64, nbytes)) if alloc is not None else np.empty(max(64, nbytes), np.uint8)
+        return a[:nbytes].view(dtype).reshape(k, n)
+
+    gt, rd, ad, gq = room(k * n, np.uint8), room(2 * k * n, np.uint16), room(2 * k * n, np.uint16), room(2 * k * n, np.uint16)
+    nw = C.c_int64(0)
+
+    def call(rc):
+        if rc != 0:
+            msg = (lib.uz_io_last_error() or b"").decode(errors="replace")
+            if "negative allele depth" in msg:
+                raise ValueError(msg)
+            if "above 2^30" in msg:
+                raise OverflowError(msg)
+            raise IoError(rc, msg)
+
+    call(lib.uz_samples_pack(C.byref(v), k, pick.ctypes.data, int(threads), gt.ctypes.data, rd.ctypes.data, ad.ctypes.data, gq.ctypes.data, C.byref(nw), 0,
+                             None, None, None))
+    wide = None
+    w = int(nw.value)
+    if w:
+        ws, wr, wa = np.zeros(w, np.int64), np.zeros((k, w), np.int32), np.zeros((k, w), np.int32)
+        call(lib.uz_samples_pack(C.byref(v), k, pick.ctypes.data, int(threads), None, None, None, None, C.byref(nw), w, ws.ctypes.data, wr.ctypes.data, wa.ctypes.data))
+        wide = (ws, wr, wa)
+    return gt, rd, ad, gq, wide
 
 
 def unpack_sites(v: "abi.SitesView"):

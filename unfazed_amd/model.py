@@ -115,6 +115,23 @@ def _pad16(n: int) -> int:
     return (n + 15) & ~15
 
 
+@dataclass
+class SampleColumns:
+    """What SitesTable.sample_columns returns: row r belongs to names[r]."""
+
+    names: List[str]
+    gt: np.ndarray         # u8 [k][S]
+    ref_depth: np.ndarray  # u16 [k][S]
+    alt_depth: np.ndarray
+    gq: np.ndarray
+    wide: Optional[tuple]  # None, or (site i64 [w], ref_depth i32 [k][w], alt_depth i32 [k][w])
+
+    def row(self, name: str) -> int:
+        if not hasattr(self, "_row"):
+            self._row = {s: r for r, s in enumerate(self.names)}
+        return self._row[name]
+
+
 class SitesTable:
     """SoA columns of a decoded sites VCF (all samples), host side.
 
@@ -230,6 +247,55 @@ class SitesTable:
             depth16(self.alt_depth),
             np.ascontiguousarray(g.astype(np.uint16)),
         )
+
+    def sample_columns(self, names: Sequence[str], alloc=None, impl: Optional[str] = None) -> "SampleColumns":
+        """Device-facing columns of the samples `names`, made ONCE per sample (the cohort form: a trio's nine 16-bit columns are
+        three rows of these, uz_families_from_samples): gt u8 [k][S] (cyvcf2 codes), ref_depth / alt_depth / gq u16 [k][S] by the
+        rules of :meth:`family_columns` -- negative = missing (0xFFFF), depths clamped at 32767, floor(GQ), NaN GQ = missing -- and the
+        table-level wide list: the sites where any of these samples has a depth above 32767, with every sample's 32-bit depths.
+        A decoder's table goes through the native packer (io_native.pack_samples: threads over samples x site spans), one built by
+        from_records through numpy; impl = "native" / "numpy" picks one (both give the same bytes).
+        alloc(nbytes) -> uint8 array: the memory of the rows (pinned for the upload)."""
+        names = list(names)
+        pick = np.asarray([self.samples.index(s) for s in names], np.int64)
+        if impl is None:
+            impl = "native" if hasattr(self, "_native") else "numpy"
+        if impl == "native":
+            from . import io_native
+            gt, rd, ad, gq, wide = io_native.pack_samples(self, pick, alloc=alloc)
+            return SampleColumns(names, gt, rd, ad, gq, wide)
+        k, n = int(pick.size), self.n_sites
+        rdc, adc = self.ref_depth[pick], self.alt_depth[pick]
+        for a in (rdc, adc):
+            if a.size and a.min() < -1:
+                raise ValueError("negative allele depth other than the missing marker -1")
+            if a.size and a.max() > (1 << 30):
+                raise OverflowError("allele depth above 2^30")
+
+        def room(dtype):
+            nb = k * n * np.dtype(dtype).itemsize
+            a = alloc(max(64, nb)) if alloc is not None else np.empty(max(64, nb), np.uint8)
+            return a[:nb].view(dtype).reshape(k, n)
+
+        def depth16(a, out):
+            v = np.minimum(a.astype(np.int64), U16_MAX_VALUE)
+            v[v < 0] = U16_MISSING
+            out[...] = v
+            return out
+
+        gt = room(np.uint8)
+        gt[...] = self.gt[pick]
+        g = np.floor(self.gq[pick])
+        g = np.where(np.isnan(g), -1.0, g)
+        g = np.clip(g, -1, U16_MAX_VALUE).astype(np.int64)
+        g[g < 0] = U16_MISSING
+        gq = room(np.uint16)
+        gq[...] = g
+        wide = None
+        ws = np.nonzero((rdc > U16_MAX_VALUE).any(axis=0) | (adc > U16_MAX_VALUE).any(axis=0))[0].astype(np.int64) if (n and k) else np.zeros(0, np.int64)
+        if ws.size:
+            wide = (ws, np.ascontiguousarray(rdc[:, ws].astype(np.int32)), np.ascontiguousarray(adc[:, ws].astype(np.int32)))
+        return SampleColumns(names, gt, depth16(rdc, room(np.uint16)), depth16(adc, room(np.uint16)), gq, wide)
 
     # ---- host-side interval queries (tabix semantics) -------------------
     def query(self, chrom: str, beg1: int, end1: int) -> np.ndarray:
