@@ -252,6 +252,18 @@ int uz_phase_votes(uz_ctx *ctx, int64_t *vote_off /* [4n+1] */, int32_t *vote_va
 /* Haplotype groups after connect_reads of the last uz_phase (diagnostics / tests):
  * grp_off[2n+1] then grp_q: "ref" set then "alt" set (qname ids, ascending). */
 int uz_phase_groups(uz_ctx *ctx, int64_t *grp_off /* [2n+1] */, int32_t *grp_q);
+/* Test hook: what the sizing pass left for the batch of the last uz_phase / uz_phase_end (n DNMs, n_het = het_off[n] het sites of its
+ * window lists).  bounds: five numbers per DNM -- records of its own fetch, sum of the lengths of its het-site fetch ranges (capped at
+ * 0x7FFFFFF0), het sites, candidates, most het sites within one record's reach.  pre_win: first / one-past-last record of the DNM's own
+ * fetch (an SV's: of both breakpoint fetches).  pre_ha / pre_hl: first record and length of every het site's fetch range, in the order
+ * of het_idx (0 for the sites of a DNM without candidates).  reduced: the batch's reduction of `bounds`, UZ_SIZING_REDUCED_WORDS 8-byte
+ * words: [0] max bounds[0], [1] max bounds[1], [2] max bounds[2], [3] max bounds[3], [4] DNMs with candidates, [5] max of
+ * M = b1 + 4 b0 (b4 + 1), [6] sum of min(M, 4096) + b3, [7 + k], k < 256: DNMs with candidates whose arena estimate
+ * min(((37 b1) / 4 + 10 b0 + 3328 + 255) >> 8, 255) is k.  Any pointer may be NULL.  UZ_E_STATE: no batch has run on the context, or one is
+ * open (uz_phase_begin). */
+#define UZ_SIZING_REDUCED_WORDS 263
+int uz_phase_sizing_fetch(uz_ctx *ctx, int32_t *bounds /* [5n] */, int32_t *pre_win /* [4n] */, int32_t *pre_ha /* [n_het] */,
+                          int32_t *pre_hl /* [n_het] */, int64_t *reduced /* [UZ_SIZING_REDUCED_WORDS] */);
 
 /* ---- allele-balance (CNV) stage ---------------------------------------- */
 /* K6.  Everything run_cnv_phasing does after its find (sv_phaser.py:357-423: phase_by_snvs :71-85,

@@ -12,6 +12,8 @@ _LIB = None
 
 
 def build():
+    if os.environ.get("UZ_EMU_LIB"):  # a sanitizer build of the same source (flags of scripts/sanitize_io.sh)
+        return os.environ["UZ_EMU_LIB"]
     so = os.path.join(_HERE, "libemu_phase.so")
     deps = [os.path.join(_HERE, "emu_phase.cpp"), os.path.join(_ROOT, "unfazed_amd", "csrc", "phase_body.hpp"),
             os.path.join(_ROOT, "unfazed_amd", "csrc", "wg.hpp"), os.path.join(_ROOT, "unfazed_amd", "csrc", "pack.hpp"),
@@ -24,12 +26,35 @@ def build():
     return so
 
 
-def phase(params, sites, reads, dnms, found, no_seq=None, umask=None, bl=None):
-    """Same result layout as oracle.phase(..., keep_lists=True) plus groups."""
+def _lib():
     global _LIB
     if _LIB is None:
         _LIB = C.CDLL(build())
         _LIB.emu_phase.restype = C.c_int
+        _LIB.emu_phase_sizing.restype = C.c_int
+    return _LIB
+
+
+def phase_sizing(params, sites, reads, dnms, found):
+    """The sizing pass in its generic form (uz_phase_bounds over uz_lower_bounds_c): bounds [n, 5], pre_win [n, 4], pre_ha, pre_hl [n_het]."""
+    co, ci, cf, ho, hi = found
+    n = dnms.view.n
+    nh = int(ho[n])
+    hi = np.ascontiguousarray(hi if hi.size else np.zeros(1, np.int32), np.int32)
+    co, ho = np.ascontiguousarray(co, np.int64), np.ascontiguousarray(ho, np.int64)
+    bounds, pre_win = np.zeros(max(1, 5 * n), np.int32), np.zeros(max(1, 4 * n), np.int32)
+    pre_ha, pre_hl = np.zeros(nh + 2, np.int32), np.zeros(nh + 2, np.int32)
+    vp = C.c_void_p
+    rc = _lib().emu_phase_sizing(C.byref(params), vp(sites.arrays["pos"].ctypes.data), reads.ref(), dnms.ref(), vp(co.ctypes.data),
+                                 vp(ho.ctypes.data), vp(hi.ctypes.data), vp(bounds.ctypes.data), vp(pre_win.ctypes.data),
+                                 vp(pre_ha.ctypes.data), vp(pre_hl.ctypes.data))
+    assert rc == 0
+    return dict(bounds=bounds[: 5 * n].reshape(n, 5), pre_win=pre_win[: 4 * n].reshape(n, 4), pre_ha=pre_ha[:nh], pre_hl=pre_hl[:nh])
+
+
+def phase(params, sites, reads, dnms, found, no_seq=None, umask=None, bl=None):
+    """Same result layout as oracle.phase(..., keep_lists=True) plus groups."""
+    _lib()
     co, ci, cf, ho, hi = found
     n = dnms.view.n
     ci = np.ascontiguousarray(ci if ci.size else np.zeros(1, np.int32))

@@ -155,3 +155,44 @@ extern "C" int emu_phase(const uz_params *P, const uz_sites_view *S, const uz_re
     if (base_err_out) *base_err_out = base_err;
     return 0;
 }
+
+// The sizing pass alone, in its generic form (uz_phase_bounds: every lower bound through uz_lower_bounds_c -- uz_lb_level over the three index
+// levels, uz_mid8_refine), over a table of which only the start column, the contigs and the spans matter: what tests/sizingmodel.py is held to on
+// the CPU before the device's staged form is held to it.  bounds [5n], pre_win [4n], pre_ha / pre_hl [het_off[n]] (zeroed by the caller: a DNM
+// without candidates leaves its het ranges untouched, as on the device behind its memset).
+extern "C" int emu_phase_sizing(const uz_params *P, const int32_t *spos, const uz_reads_view *Rv, const uz_dnms_view *D, const int64_t *cand_off,
+                                const int64_t *het_off, const int32_t *het_idx, int32_t *bounds, int32_t *pre_win, int32_t *pre_ha, int32_t *pre_hl) {
+    const int64_t n = Rv->n_segs;
+    std::vector<RecA> ra((size_t)n + 1);
+    for (int64_t i = 0; i < n; i++) { ra[i].start = Rv->start[i]; ra[i].end = Rv->end[i]; ra[i].cigar_off = 0; ra[i].sq_off = 0; }
+    // the three levels as k_build_coarse writes them; mid8 is read a 32-byte cell at a time (uz_mid8_refine)
+    std::vector<int32_t> coarse((size_t)(n >> 12) + 2), mid_idx((size_t)(n >> 6) + 2);
+    int32_t *mid8 = (int32_t *)aligned_alloc(64, (((size_t)(n >> 3) + 16) * sizeof(int32_t) + 63) & ~(size_t)63);
+    if (!mid8) return -1;
+    for (int64_t k = 0; k < (n >> 3) + 16; k++) mid8[k] = 0;
+    for (int64_t k = 0; (k << 3) < n; k++) {
+        const int32_t st = Rv->start[k << 3];
+        mid8[k] = st;
+        if ((k & 7) == 0) mid_idx[k >> 3] = st;
+        if ((k & 511) == 0) coarse[k >> 9] = st;
+    }
+    PhaseArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n = D->n;
+    a.no_extended = P->no_extended; a.cutoff = D->cutoff;
+    a.spos = spos; a.cand_off = cand_off; a.het_off = het_off; a.het_idx = het_idx;
+    a.rcontig = D->rcontig; a.dstart = D->start; a.dend = D->end; a.dflags = D->dflags; a.vartype = D->vartype;
+    a.R.contig_off = Rv->contig_off; a.R.max_span = Rv->max_span; a.R.n_contigs = Rv->n_contigs;
+    a.R.ra = ra.data(); a.R.coarse = coarse.data(); a.R.mid = mid_idx.data(); a.R.mid8 = mid8;
+    a.pre_win = pre_win; a.pre_ha = pre_ha; a.pre_hl = pre_hl;
+    for (int d = 0; d < D->n; d++) {
+        int32_t *b = bounds + 5 * (size_t)d;
+        long long tp = 0;
+        int mhp = 0;
+        uz_phase_bounds(a, d, b, 0, 1, tp, mhp);
+        b[1] = (int32_t)(tp > 0x7FFFFFF0LL ? 0x7FFFFFF0LL : tp);
+        b[4] = mhp;
+    }
+    free(mid8);
+    return 0;
+}

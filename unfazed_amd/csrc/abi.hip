@@ -1931,6 +1931,14 @@ int uz_phase_groups(uz_ctx *c, int64_t *grp_off, int32_t *grp_q) {
     });
     return g ? g : rc;
 }
+int uz_phase_sizing_fetch(uz_ctx *c, int32_t *bounds, int32_t *pre_win, int32_t *pre_ha, int32_t *pre_hl, int64_t *reduced) {
+    int rc = 0;
+    int g = guarded(c, [&] {
+        UZ_REQUIRE(c->phase_valid && !c->phase_open, UZ_E_STATE, "uz_phase_sizing_fetch before uz_phase / uz_phase_end");
+        rc = uz_phase_sizing_fetch_impl(c, bounds, pre_win, pre_ha, pre_hl, reduced);
+    });
+    return g ? g : rc;
+}
 
 int uz_prof_enable(uz_ctx *c, int on) {
     return guarded(c, [&] { c->prof_mask = on == 0 ? 0u : on == 1 ? ~0u : (uint32_t)on >> 1; });

@@ -246,6 +246,7 @@ struct PhaseState {
     std::vector<int32_t> list_len_h;
     bool have_lists = false;
     int32_t n = 0;
+    int64_t n_het = 0; // het sites of the batch the sizing pass last ran on (uz_phase_sizing_fetch)
     // uz_phase_begin left a speculative run in flight: what uz_finish_phase needs to judge it
     bool pending = false;
     Caps pend_caps = {0, 0, 0, 0, 0, 0};
@@ -1699,6 +1700,7 @@ void uz_launch_phase(uz_ctx *c, FamilyDev &f, const SitesDev &s, ReadsDev &r, in
     st->bounds.ensure((size_t)5 * n);
     st->pre_win.ensure((size_t)4 * n); st->pre_h.ensure(2 * ((size_t)c->n_het + 1));
     a.pre_win = st->pre_win.p; a.pre_ha = st->pre_h.p; a.pre_hl = st->pre_h.p + (size_t)c->n_het + 1;
+    st->n_het = c->n_het;
     // DNMs without candidates leave their het ranges untouched: they must read as empty
     UZ_HIP(hipMemsetAsync(st->pre_h.p, 0, 2 * ((size_t)c->n_het + 1) * sizeof(int32_t), c->stream));
     {
@@ -2012,6 +2014,30 @@ static int gather_lists(uz_ctx *c, int k0, int k1, int64_t *off, int32_t *val) {
             }
             src += len;
         }
+    }
+    return 0;
+}
+
+// test hook (unfazed_hip.h: uz_phase_sizing_fetch): what the sizing pass of the last batch left.  k_phase_bounds and k_bounds_reduce are the only
+// writers of these buffers -- k_phase reads pre_win / pre_ha / pre_hl, the host reads the pinned copy of the reduced record -- so they still hold
+// the pass's output when the batch's call has returned.
+int uz_phase_sizing_fetch_impl(uz_ctx *c, int32_t *bounds, int32_t *pre_win, int32_t *pre_ha, int32_t *pre_hl, int64_t *reduced) {
+    PhaseState *st = (PhaseState *)c->phase_state;
+    UZ_REQUIRE(st != nullptr && !st->pending, UZ_E_STATE, "uz_phase_sizing_fetch: no finished batch on this context");
+    const size_t n = (size_t)(st->n > 0 ? st->n : 0), nh = (size_t)st->n_het;
+    if (reduced) memset(reduced, 0, UZ_SIZING_REDUCED_WORDS * sizeof(int64_t));
+    if (!n) return 0;
+    UZ_HIP(hipStreamSynchronize(c->stream));
+    if (bounds) UZ_HIP(hipMemcpy(bounds, st->bounds.p, 5 * n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (pre_win) UZ_HIP(hipMemcpy(pre_win, st->pre_win.p, 4 * n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (pre_ha && nh) UZ_HIP(hipMemcpy(pre_ha, st->pre_h.p, nh * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (pre_hl && nh) UZ_HIP(hipMemcpy(pre_hl, st->pre_h.p + nh + 1, nh * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (reduced) { // from the device's record, not the host's pinned copy of it
+        BoundsRed br;
+        UZ_HIP(hipMemcpy(&br, st->bounds_red.p, sizeof(br), hipMemcpyDeviceToHost));
+        reduced[0] = br.mA; reduced[1] = br.mT; reduced[2] = br.mH; reduced[3] = br.mC; reduced[4] = br.active;
+        reduced[5] = (int64_t)br.mM; reduced[6] = (int64_t)br.sumP;
+        for (int k = 0; k < 256; k++) reduced[7 + k] = br.hist[k];
     }
     return 0;
 }

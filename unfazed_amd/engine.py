@@ -14,6 +14,7 @@ from . import abi
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("UZ_HIP_LIB", os.path.join(_HERE, "libunfazed_hip.so"))
 
+SIZING_REDUCED_WORDS = 263  # unfazed_hip.h UZ_SIZING_REDUCED_WORDS
 K_SITE_SCAN, K_WINDOW_COUNT, K_WINDOW_FILL, K_PHASE, K_SIZING, K_CNV, K_FAMILY_PACK = 0, 1, 2, 3, 4, 5, 6
 
 EXPORTS = [
@@ -24,7 +25,7 @@ EXPORTS = [
     "uz_sites_adopt_device", "uz_family_adopt_device", "uz_reads_adopt_device",
     "uz_sites_free", "uz_reads_free", "uz_drop_derived",
     "uz_site_scan", "uz_site_scan_many", "uz_site_classes", "uz_find", "uz_find_fetch",
-    "uz_phase", "uz_phase_begin", "uz_phase_end", "uz_phase_cohort", "uz_phase_votes", "uz_phase_groups", "uz_phase_cnv", "uz_phase_cnv_sites",
+    "uz_phase", "uz_phase_begin", "uz_phase_end", "uz_phase_cohort", "uz_phase_votes", "uz_phase_groups", "uz_phase_sizing_fetch", "uz_phase_cnv", "uz_phase_cnv_sites",
     "uz_prof_enable", "uz_prof_reset", "uz_prof_get", "uz_prof_units",
 ]
 
@@ -100,6 +101,7 @@ def load_library(path: Optional[str] = None):
     L.uz_phase_cnv_sites.argtypes = [vp, vp, vp]
     L.uz_phase_votes.argtypes = [vp, vp, vp]
     L.uz_phase_groups.argtypes = [vp, vp, vp]
+    L.uz_phase_sizing_fetch.argtypes = [vp, vp, vp, vp, vp, vp]
     L.uz_prof_enable.argtypes = [vp, C.c_int]
     L.uz_prof_reset.argtypes = [vp]
     L.uz_prof_get.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
@@ -672,6 +674,23 @@ class HipEngine:
         gq = np.zeros(max(1, int(go[-1])), dtype=np.int32)
         self._ck(self.L.uz_phase_groups(self.h, go.ctypes.data, gq.ctypes.data), "uz_phase_groups")
         return go, gq[: int(go[-1])]
+
+    def phase_sizing(self, n: int, n_het: int) -> dict:
+        """Test hook (uz_phase_sizing_fetch): the sizing pass's output for the last phase_raw / phase_end -- n DNMs, n_het = het_off[n] of the
+        batch's window lists.  -> bounds [n, 5], pre_win [n, 4], pre_ha [n_het], pre_hl [n_het] and the batch's reduction: mA, mT, mH, mC,
+        active, mM, sumP as ints, hist int64 [256]."""
+        n, n_het = int(n), int(n_het)
+        bounds = np.zeros(max(1, 5 * n), np.int32)
+        pre_win = np.zeros(max(1, 4 * n), np.int32)
+        pre_ha = np.zeros(max(1, n_het), np.int32)
+        pre_hl = np.zeros(max(1, n_het), np.int32)
+        red = np.zeros(SIZING_REDUCED_WORDS, np.int64)
+        self._ck(self.L.uz_phase_sizing_fetch(self.h, bounds.ctypes.data, pre_win.ctypes.data, pre_ha.ctypes.data, pre_hl.ctypes.data,
+                                              red.ctypes.data), "uz_phase_sizing_fetch")
+        out = dict(bounds=bounds[: 5 * n].reshape(n, 5), pre_win=pre_win[: 4 * n].reshape(n, 4), pre_ha=pre_ha[:n_het], pre_hl=pre_hl[:n_het])
+        out.update({k: int(red[j]) for j, k in enumerate(("mA", "mT", "mH", "mC", "active", "mM", "sumP"))})
+        out["hist"] = red[7:].copy()
+        return out
 
     def phase(self, fam: int, reads_h: int, dv: abi.Held, params: abi.Params, found_list, want_lists: bool = True,
               find_mode: int = abi.FIND_SECOND_WINDOW):
