@@ -59,12 +59,15 @@ print("RESULT " + json.dumps(res))
 """
 
 
-def _build(tmp_path, from_memory, n_dnms, breakage="none"):
-    out = str(tmp_path / ("%s_%d_%s.npz" % ("rec" if from_memory else "link", n_dnms, breakage)))
+def _build(tmp_path, from_memory, n_dnms, breakage="none", lazy=False):
+    out = str(tmp_path / ("%s%s_%d_%s.npz" % ("rec" if from_memory else "link", "_lazy" if lazy else "", n_dnms, breakage)))
     env = dict(os.environ, UZ_BUILD_LOG="1")
     env.pop("UZ_BUILD_FROM_MEMORY", None)
+    env.pop("UZ_BUILD_LAZY", None)
     if from_memory:
         env["UZ_BUILD_FROM_MEMORY"] = "1"
+    if lazy:  # the header build at the table's first use, on the compute stream (read once per process: hence the child)
+        env["UZ_BUILD_LAZY"] = "1"
     r = subprocess.run([sys.executable, "-c", _CHILD, ROOT, TESTS, str(n_dnms), breakage, out], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     res = json.loads([x for x in r.stdout.splitlines() if x.startswith("RESULT ")][-1][len("RESULT "):])
@@ -93,3 +96,22 @@ def test_a_contradicting_pair_form_is_refused_by_both_builds(tmp_path, breakage)
     assert link["error"] is not None and rec["error"] is not None
     rc = [re.search(r"failed \((-?\d+)\)", e["error"]).group(1) for e in (link, rec)]
     assert rc[0] == rc[1], (link["error"], rec["error"])
+
+
+def test_the_build_at_first_use_gives_the_same_headers(tmp_path):
+    """The header build that no upload queued (UZ_BUILD_LAZY=1): the table's first use runs it on the compute stream from the columns the
+    upload left with the table -- the same headers as from the build queued behind the copies, in the link form."""
+    queued, want = _build(tmp_path, False, 40)
+    lazy, got = _build(tmp_path, False, 40, lazy=True)
+    assert queued["error"] is None and lazy["error"] is None
+    assert lazy["n"] == queued["n"] > 2048  # several spans of 1024 records
+    for k in ("start", "end", "tlen", "mate", "qname"):
+        assert np.array_equal(got[k], want[k]), k
+
+
+def test_the_build_at_first_use_refuses_a_contradicting_pair_form(tmp_path):
+    queued, _ = _build(tmp_path, False, 40, "orphan_second")
+    lazy, _ = _build(tmp_path, False, 40, "orphan_second", lazy=True)
+    assert queued["error"] is not None and lazy["error"] is not None
+    rc = [re.search(r"failed \((-?\d+)\)", e["error"]).group(1) for e in (queued, lazy)]
+    assert rc[0] == rc[1], (queued["error"], lazy["error"])

@@ -76,7 +76,9 @@ def test_a_pair_form_that_contradicts_itself_is_refused(engine):
             i = int(f[9])
             k = next(int(x) for x in f if 0 < int(x) - i <= 252 and int(x) != i + int(p[i]))
             p[i] = k - i
-        with pytest.raises(UnfazedHipError):
+        # the sentence of the pair form's own code, whichever call meets the flag (a FIRST turned into a SECOND also moves the span's
+        # name-id sum off the packer's row: there the totals' code may be the one that is written last)
+        with pytest.raises(UnfazedHipError, match=None if breakage == "orphan_second" else "pair_d8"):
             rid = engine.upload_reads_packed(part)
             engine.wait_reads(rid)
 

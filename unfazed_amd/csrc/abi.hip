@@ -995,8 +995,24 @@ static void check_packed_view(const uz_reads_packed_view *v) {
     }
 }
 
-// packed columns in HOST memory -> one block; every command goes to stream `st`
-static void reads_from_packed_host(uz_ctx *c, hipStream_t st, const uz_reads_packed_view *v, ReadsDev &r, bool defer_build) {
+// The columns of a table's block, each named ONCE by a staging routine that runs its body three times: pass 0 sizes the block, pass 1 plans
+// the slab copy (h2d only looks at the host addresses), pass 2 places the columns and copies them (or points into the slab's image)
+struct Stager {
+    hipStream_t st;
+    int pass;
+    Carver cv;
+    template <typename T>
+    T *own(size_t n) { return cv.take<T>(n); } // an area that only the device writes
+    template <typename T>
+    const T *col(const T *host, size_t n, size_t room = 0) { // a column off the link (room: elements kept free behind it)
+        T *d = cv.take<T>(n + room);
+        return pass ? h2d(st, d, host, n) : d;
+    }
+};
+
+// packed columns in HOST memory -> one block; every command goes to stream `st`.  The header build is left to the caller: r.cols and
+// r.build_scratch are what uz_build_records takes
+static void reads_from_packed_host(uz_ctx *c, hipStream_t st, const uz_reads_packed_view *v, ReadsDev &r) {
     check_packed_view(v);
     r.live = true;
     r.n = v->n_segs; r.n_contigs = v->n_contigs; r.n_qnames = v->n_qnames;
@@ -1009,8 +1025,6 @@ static void reads_from_packed_host(uz_ctx *c, hipStream_t st, const uz_reads_pac
     const size_t n = (size_t)r.n, nc = (size_t)r.n_cigar_total, nu = (size_t)r.n_row_units, ns = (size_t)r.n_seq_units, ncs = (size_t)v->n_cigar_total;
     const size_t nsl = (size_t)v->n_seq_units; // units on the link
     const size_t nbl = (size_t)r.n_bl, nblp = nbl * (v->bl_wide ? 2 : 1), nblc = (nbl + 3) / 4;
-    uint8_t *bl_n = nullptr, *t_nbl = nullptr, *bl_pos = nullptr, *bl_code = nullptr;
-    uint32_t *cigar_staged = nullptr;
     const bool two_bit = v->seq2 != nullptr;
     const size_t ne = two_bit ? (size_t)v->n_exc : 0;
     const bool t8 = v->tup8 != nullptr; // the dictionary index in one byte: rebuilt into the 16-bit column's place by the header build's first kernel
@@ -1018,203 +1032,107 @@ static void reads_from_packed_host(uz_ctx *c, hipStream_t st, const uz_reads_pac
     const bool lists = v->n_low != nullptr || (tupf && v->tup_n_low); // quality rows only for the records with bases (at their base-row position), written by the header build
     const size_t nt = tupf ? (size_t)v->n_tup : 0;
     const size_t nte = t8 ? (size_t)v->n_tup_esc : 0, ntsp = t8 ? ((size_t)v->n_segs + UZ_TUP8_SPAN - 1) / UZ_TUP8_SPAN + 1 : 0;
-    uint8_t *d_tup8 = nullptr; uint16_t *t_hot = nullptr, *t_esc = nullptr; uint32_t *t_eoff = nullptr;
-    uint16_t *tup = nullptr, *t_flag = nullptr, *t_ls = nullptr, *t_nc = nullptr, *t_um = nullptr; uint8_t *t_mq = nullptr, *t_ax = nullptr, *t_nl = nullptr;
     const size_t nql = lists ? (size_t)v->n_qlow_pos * (v->qlow_pos_wide ? 2 : 1) : 0;
-    uint8_t *n_low = nullptr, *qpos = nullptr;
-    uint16_t *umask_in = nullptr;
     r.n_qlow_pos = lists ? v->n_qlow_pos : 0;
     r.n_plane_units = lists ? r.n_seq_units : v->n_row_units;
-    uint32_t *cigar = nullptr; uint8_t *seq4 = nullptr, *qlow = nullptr, *seq2 = nullptr;
-    uint32_t *exc_rec = nullptr; uint16_t *exc_pos = nullptr; uint8_t *exc_code = nullptr;
-    int32_t *start, *end, *tlen, *mate; uint32_t *qname; uint16_t *flag, *l_seq, *n_cigar; uint8_t *mapq, *aux;
     const bool d8 = v->start_d8 != nullptr;
-    const bool n8 = v->mate_d8 != nullptr;
-    const bool p8 = v->pair_d8 != nullptr;
     const bool d16 = v->start_d != nullptr || d8;
     const size_t nes = d16 ? (size_t)v->n_esc16 : 0;
-    int16_t *d_start = nullptr, *d_tlen = nullptr, *d_mate = nullptr, *d_qname = nullptr;
-    uint8_t *d_start8 = nullptr;
-    int8_t *d_mate8 = nullptr, *d_qname8 = nullptr;
-    uint8_t *d_pair8 = nullptr;
-    unsigned long long *e_key = nullptr; int32_t *e_val = nullptr;
-    unsigned long long *pk = nullptr;
-    const size_t npk = v->pk_sums ? ((size_t)v->n_pk_spans + 1) * UZ_PK_SUMS : 0; // the packer's span sums (checked below)
-    void *scratch = nullptr;
-    for (int pass = 0; pass < 2; pass++) {
-        Carver cv(pass ? r.block.p : nullptr);
-        carve_common(cv, r);
-        cigar = cv.take<uint32_t>(nc);
-        if (ccompact) cigar_staged = cv.take<uint32_t>(ncs);
-        if (d16) {
-            d_start = cv.take<int16_t>(d8 ? 0 : n); d_start8 = cv.take<uint8_t>(d8 ? n : 0);
-            d_tlen = cv.take<int16_t>(p8 ? 0 : n); d_mate = cv.take<int16_t>(n8 || p8 ? 0 : n); d_qname = cv.take<int16_t>(n8 || p8 ? 0 : n);
-            d_mate8 = cv.take<int8_t>(n8 ? n : 0); d_qname8 = cv.take<int8_t>(n8 ? n : 0); d_pair8 = cv.take<uint8_t>(p8 ? n : 0);
-            e_key = cv.take<unsigned long long>(nes); e_val = cv.take<int32_t>(nes);
-        }
-        seq4 = cv.take<uint8_t>(ns * UZ_SEQ4_UNIT_BYTES);
-        qlow = cv.take<uint8_t>((lists ? ns : nu) * UZ_QLOW_UNIT_BYTES);
-        if (lists) { n_low = cv.take<uint8_t>(tupf ? 0 : n); qpos = cv.take<uint8_t>(nql); }
-        if (tupf) {
-            tup = cv.take<uint16_t>(n); t_flag = cv.take<uint16_t>(nt); t_ls = cv.take<uint16_t>(nt); t_nc = cv.take<uint16_t>(nt);
-            t_mq = cv.take<uint8_t>(nt); t_ax = cv.take<uint8_t>(nt); t_nl = cv.take<uint8_t>(nt); t_um = cv.take<uint16_t>(nt);
-            if (t8) { d_tup8 = cv.take<uint8_t>(n); t_hot = cv.take<uint16_t>(256); t_esc = cv.take<uint16_t>(nte); t_eoff = cv.take<uint32_t>(ntsp); }
-        }
-        if (v->umask) umask_in = cv.take<uint16_t>(n);
-        if (blf) { bl_n = cv.take<uint8_t>(v->bl_n ? n : 0); t_nbl = cv.take<uint8_t>(v->tup_n_bl ? nt : 0); bl_pos = cv.take<uint8_t>(nblp); bl_code = cv.take<uint8_t>(nblc + 4); }
-        if (two_bit) {
-            seq2 = cv.take<uint8_t>(nsl * UZ_SEQ2_UNIT_BYTES);
-            exc_rec = cv.take<uint32_t>(ne); exc_pos = cv.take<uint16_t>(ne); exc_code = cv.take<uint8_t>(ne);
-        }
-        const size_t nw = d16 ? 0 : n; // the plain wide columns
-        start = cv.take<int32_t>(nw); end = cv.take<int32_t>(n); tlen = cv.take<int32_t>(nw); mate = cv.take<int32_t>(nw);
-        qname = cv.take<uint32_t>(nw);
-        const size_t npl = tupf ? 0 : n; // the plain small columns
-        flag = cv.take<uint16_t>(npl); l_seq = cv.take<uint16_t>(npl); n_cigar = cv.take<uint16_t>(npl);
-        mapq = cv.take<uint8_t>(npl); aux = cv.take<uint8_t>(npl);
-        if (npk) pk = cv.take<unsigned long long>(npk);
-        scratch = cv.take<uint8_t>(uz_rec_scratch_bytes(r.n));
-        if (!pass) r.block = uz_block_get(c, cv.off + 256);
-    }
+    const size_t npk = v->pk_sums ? ((size_t)v->n_pk_spans + 1) * UZ_PK_SUMS : 0; // the packer's span sums (checked by check_packed_view)
     RecColumns col;
     SlabPlan plan;
     SlabScope slab_scope(&plan);
-    for (int stage_pass = 0; stage_pass < 2; stage_pass++) {
-    if (stage_pass) slab_commit(c, st, plan, r.mirror);
-    col = RecColumns();
-    r.contig_off = const_cast<int64_t *>(h2d(st, r.contig_off, v->contig_off, (size_t)v->n_contigs + 1));
-    r.max_span = const_cast<int32_t *>(h2d(st, r.max_span, v->max_span, (size_t)v->n_contigs));
-    col.end = v->end ? h2d(st, end, v->end, n) : nullptr;
-    if (npk) col.pk_sums = h2d(st, pk, (const unsigned long long *)v->pk_sums, npk);
-    if (d16) { // 16-bit differences + the escape list instead of four 32-bit columns
-        if (d8) col.start_d8 = h2d(st, d_start8, v->start_d8, n);
-        else col.start_d = h2d(st, d_start, v->start_d, n);
-        if (p8) col.pair_d8 = h2d(st, d_pair8, v->pair_d8, n);
-        else {
-            col.tlen_s = h2d(st, d_tlen, v->tlen_s, n);
-            if (n8) { col.mate_d8 = h2d(st, d_mate8, v->mate_d8, n); col.qname_d8 = h2d(st, d_qname8, v->qname_d8, n); }
-            else { col.mate_d = h2d(st, d_mate, v->mate_d, n); col.qname_d = h2d(st, d_qname, v->qname_d, n); }
+    for (int pass = 0; pass < 3; pass++) {
+        if (pass == 2) slab_commit(c, st, plan, r.mirror);
+        Stager S{st, pass, Carver(pass ? r.block.p : nullptr)};
+        col = RecColumns();
+        carve_common(S.cv, r);
+        if (pass) {
+            r.contig_off = const_cast<int64_t *>(h2d(st, r.contig_off, v->contig_off, (size_t)v->n_contigs + 1));
+            r.max_span = const_cast<int32_t *>(h2d(st, r.max_span, v->max_span, (size_t)v->n_contigs));
         }
-        col.esc16_key = h2d(st, e_key, (const unsigned long long *)v->esc16_key, nes); col.esc16_val = h2d(st, e_val, v->esc16_val, nes);
-        col.n_esc16 = (int64_t)nes;
-        col.start = nullptr; col.tlen = nullptr; col.mate = nullptr; col.qname = nullptr;
-    } else {
-        col.start = h2d(st, start, v->start, n); col.tlen = h2d(st, tlen, v->tlen, n);
-        col.mate = h2d(st, mate, v->mate, n); col.qname = h2d(st, qname, v->qname, n);
-    }
-    if (tupf) { // a 16-bit index per record + the table of combinations instead of nine bytes of small columns
-        if (t8) {
-            col.tup8 = h2d(st, d_tup8, v->tup8, n); col.tup_hot = h2d(st, t_hot, v->tup_hot, (size_t)256);
-            col.tup_esc = nte ? h2d(st, t_esc, v->tup_esc, nte) : t_esc; col.tup_esc_off = h2d(st, t_eoff, v->tup_esc_off, ntsp);
-            col.n_tup_esc = (int64_t)nte;
-            col.tup_out = tup; col.tup = tup; // (k_tup_expand writes it before anything reads it)
+        if (v->end) col.end = S.col(v->end, n);
+        if (npk) col.pk_sums = S.col((const unsigned long long *)v->pk_sums, npk);
+        if (d16) { // 16-bit differences + the escape list instead of four 32-bit columns
+            if (d8) col.start_d8 = S.col(v->start_d8, n);
+            else col.start_d = S.col(v->start_d, n);
+            if (v->pair_d8) col.pair_d8 = S.col(v->pair_d8, n);
+            else {
+                col.tlen_s = S.col(v->tlen_s, n);
+                if (v->mate_d8) { col.mate_d8 = S.col(v->mate_d8, n); col.qname_d8 = S.col(v->qname_d8, n); }
+                else { col.mate_d = S.col(v->mate_d, n); col.qname_d = S.col(v->qname_d, n); }
+            }
+            col.esc16_key = S.col((const unsigned long long *)v->esc16_key, nes); col.esc16_val = S.col(v->esc16_val, nes);
+            col.n_esc16 = (int64_t)nes;
+        } else {
+            col.start = S.col(v->start, n); col.tlen = S.col(v->tlen, n);
+            col.mate = S.col(v->mate, n); col.qname = S.col(v->qname, n);
+        }
+        if (tupf) { // a 16-bit index per record + the table of combinations instead of nine bytes of small columns
+            if (t8) {
+                col.tup8 = S.col(v->tup8, n); col.tup_hot = S.col(v->tup_hot, (size_t)256);
+                col.tup_esc = S.col(v->tup_esc, nte); col.tup_esc_off = S.col(v->tup_esc_off, ntsp);
+                col.n_tup_esc = (int64_t)nte;
+                col.tup_out = S.own<uint16_t>(n); col.tup = col.tup_out; // (k_tup_expand writes it before anything reads it)
+            } else
+                col.tup = S.col(v->tup, n);
+            col.n_tup = (int64_t)nt;
+            col.tup_flag = S.col(v->tup_flag, nt); col.tup_l_seq = S.col(v->tup_l_seq, nt); col.tup_n_cigar = S.col(v->tup_n_cigar, nt);
+            col.tup_mapq = S.col(v->tup_mapq, nt); col.tup_aux = S.col(v->tup_aux, nt);
+            if (v->tup_n_low) col.tup_n_low = S.col(v->tup_n_low, nt);
+            if (v->tup_umask) col.tup_umask = S.col(v->tup_umask, nt);
+            if (v->tup_n_bl) col.tup_n_bl = S.col(v->tup_n_bl, nt);
+        } else {
+            col.flag = S.col(v->flag, n);
+            col.l_seq = S.col(v->l_seq, n); col.n_cigar = S.col(v->n_cigar, n);
+            col.mapq = S.col(v->mapq, n); col.aux = S.col(v->aux, n);
+        }
+        col.lists = lists ? 1 : 0;
+        if (ccompact) { // the travelled words land in a staging area; the header build writes the store
+            col.cigar_out = S.own<uint32_t>(nc);
+            col.cigar_staged = S.col(v->cigar, ncs);
+            r.cigar = col.cigar_out;
         } else
-            col.tup = h2d(st, tup, v->tup, n);
-        col.n_tup = (int64_t)nt;
-        col.tup_flag = h2d(st, t_flag, v->tup_flag, nt); col.tup_l_seq = h2d(st, t_ls, v->tup_l_seq, nt); col.tup_n_cigar = h2d(st, t_nc, v->tup_n_cigar, nt);
-        col.tup_mapq = h2d(st, t_mq, v->tup_mapq, nt); col.tup_aux = h2d(st, t_ax, v->tup_aux, nt);
-        if (v->tup_n_low) col.tup_n_low = h2d(st, t_nl, v->tup_n_low, nt);
-        if (v->tup_umask) col.tup_umask = h2d(st, t_um, v->tup_umask, nt);
-        if (v->tup_n_bl) col.tup_n_bl = h2d(st, t_nbl, v->tup_n_bl, nt);
-    } else {
-        col.flag = h2d(st, flag, v->flag, n);
-        col.l_seq = h2d(st, l_seq, v->l_seq, n); col.n_cigar = h2d(st, n_cigar, v->n_cigar, n);
-        col.mapq = h2d(st, mapq, v->mapq, n); col.aux = h2d(st, aux, v->aux, n);
+            r.cigar = S.col(v->cigar, nc);
+        col.cigar_in = r.cigar;
+        if (two_bit) { // half the bytes over the link; the header build expands them into seq4
+            r.seq4 = S.own<uint8_t>(ns * UZ_SEQ4_UNIT_BYTES);
+            r.seq2_staged = S.col(v->seq2, nsl * UZ_SEQ2_UNIT_BYTES);
+            r.n_exc = (int64_t)ne;
+            r.exc_rec = S.col(v->exc_rec, ne); r.exc_pos = S.col(v->exc_pos, ne); r.exc_code = S.col(v->exc_code, ne);
+        } else
+            r.seq4 = S.col(v->seq4, ns * UZ_SEQ4_UNIT_BYTES);
+        if (blf) {
+            if (v->bl_n) col.bl_n = S.col(v->bl_n, n);
+            col.bl_pos = S.col(v->bl_pos, nblp); col.bl_code = S.col(v->bl_code, nblc, 4);
+            col.bl_wide = v->bl_wide;
+            col.n_seq_link = (int64_t)nsl;
+            col.seq4_out = reinterpret_cast<uint32_t *>(const_cast<uint8_t *>(r.seq4));
+        }
+        if (lists) {
+            r.qlow = S.own<uint8_t>(ns * UZ_QLOW_UNIT_BYTES);
+            if (!tupf) col.n_low = S.col(v->n_low, n);
+            col.qlow_pos = S.col(v->qlow_pos, nql);
+            col.qpos_wide = v->qlow_pos_wide;
+            if (v->umask) col.umask = S.col(v->umask, n);
+        } else {
+            r.qlow = const_cast<uint8_t *>(S.col(v->qlow, nu * UZ_QLOW_UNIT_BYTES));
+            col.plane_in = reinterpret_cast<const uint32_t *>(r.qlow);
+        }
+        r.build_scratch = S.own<uint8_t>(uz_rec_scratch_bytes(r.n));
+        if (!pass) r.block = uz_block_get(c, S.cv.off + 256);
     }
-    col.lists = lists ? 1 : 0;
-    if (ccompact) { // the travelled words land in a staging area; the header build writes the store
-        r.cigar = cigar;
-        col.cigar_staged = h2d(st, cigar_staged, v->cigar, ncs);
-        col.cigar_out = cigar;
-    } else
-        r.cigar = h2d(st, cigar, v->cigar, nc);
-    col.cigar_in = r.cigar;
-    if (two_bit) { // half the bytes over the link; the header build expands them into seq4
-        r.seq4 = seq4;
-        r.seq2_staged = h2d(st, seq2, v->seq2, nsl * UZ_SEQ2_UNIT_BYTES);
-        r.n_exc = (int64_t)ne;
-        r.exc_rec = h2d(st, exc_rec, v->exc_rec, ne); r.exc_pos = h2d(st, exc_pos, v->exc_pos, ne); r.exc_code = h2d(st, exc_code, v->exc_code, ne);
-    } else
-        r.seq4 = h2d(st, seq4, v->seq4, ns * UZ_SEQ4_UNIT_BYTES);
-    if (blf) {
-        if (v->bl_n) col.bl_n = h2d(st, bl_n, v->bl_n, n);
-        col.bl_pos = h2d(st, bl_pos, v->bl_pos, nblp); col.bl_code = h2d(st, bl_code, v->bl_code, nblc);
-        col.bl_wide = v->bl_wide;
-        col.n_seq_link = (int64_t)nsl;
-        col.seq4_out = reinterpret_cast<uint32_t *>(seq4);
-        r.seq4 = seq4;
-    }
-    r.qlow = qlow;
-    if (lists) {
-        if (!tupf) col.n_low = h2d(st, n_low, v->n_low, n);
-        col.qlow_pos = h2d(st, qpos, v->qlow_pos, nql);
-        col.qpos_wide = v->qlow_pos_wide;
-        if (v->umask) col.umask = h2d(st, umask_in, v->umask, n);
-    } else {
-        r.qlow = const_cast<uint8_t *>(h2d(st, qlow, v->qlow, nu * UZ_QLOW_UNIT_BYTES));
-        col.plane_in = reinterpret_cast<const uint32_t *>(r.qlow);
-    }
-    } // stage_pass
     r.qlow_thr = v->min_base_qual;
     r.qlow_valid = true;
-    r.col_q[0] = col.plane_in; r.col_q[1] = col.n_low; r.col_q[2] = col.qlow_pos; r.col_q[3] = col.cigar_in; r.col_q[4] = col.umask; r.col_q[5] = col.cigar_staged; r.col_q[6] = col.cigar_out; r.col_qwide = col.qpos_wide;
-    {
-        const void *t[8] = {col.tup, col.tup_flag, col.tup_l_seq, col.tup_n_cigar, col.tup_mapq, col.tup_aux, col.tup_n_low, col.tup_umask};
-        for (int k = 0; k < 8; k++) r.col_t[k] = t[k];
-        r.col_t8[0] = col.tup8; r.col_t8[1] = col.tup_hot; r.col_t8[2] = col.tup_esc; r.col_t8[3] = col.tup_esc_off; r.col_ntesc = col.n_tup_esc;
-        r.col_lists = col.lists;
-        r.col_ntup = col.n_tup;
-        const void *dd[10] = {col.start_d, col.tlen_s, col.mate_d, col.qname_d, col.esc16_key, col.esc16_val, col.start_d8, col.mate_d8, col.qname_d8, col.pair_d8};
-        for (int k = 0; k < 10; k++) r.col_d[k] = dd[k];
-        r.col_nesc = col.n_esc16;
-        const void *bb[4] = {col.bl_n, col.tup_n_bl, col.bl_pos, col.bl_code};
-        for (int k = 0; k < 4; k++) r.col_b[k] = bb[k];
-        r.col_bwide = col.bl_wide;
-        r.col_pk = col.pk_sums;
-    }
-    if (defer_build) { // asynchronous upload: copies only on the copy stream, the header build at first use (uz_reads_make_ready)
-        const void *p[10] = {col.start, col.end, col.tlen, col.mate, col.qname, col.flag, col.l_seq, col.n_cigar, col.mapq, col.aux};
-        for (int k = 0; k < 10; k++) r.col_ptrs[k] = p[k];
-        r.build_scratch = scratch;
-        return;
-    }
-    uz_build_records(c, st, r, col, scratch);
+    r.cols = col;
 }
 
-// the header build of an asynchronously uploaded table, from the staged columns the upload left in its block
-static void build_staged(uz_ctx *c, hipStream_t st, ReadsDev &r) {
-    RecColumns col;
-    col.start = (const int32_t *)r.col_ptrs[0]; col.end = (const int32_t *)r.col_ptrs[1]; col.tlen = (const int32_t *)r.col_ptrs[2];
-    col.mate = (const int32_t *)r.col_ptrs[3]; col.qname = (const uint32_t *)r.col_ptrs[4]; col.flag = (const uint16_t *)r.col_ptrs[5];
-    col.l_seq = (const uint16_t *)r.col_ptrs[6]; col.n_cigar = (const uint16_t *)r.col_ptrs[7]; col.mapq = (const uint8_t *)r.col_ptrs[8];
-    col.aux = (const uint8_t *)r.col_ptrs[9];
-    col.plane_in = (const uint32_t *)r.col_q[0]; col.n_low = (const uint8_t *)r.col_q[1]; col.qlow_pos = (const uint8_t *)r.col_q[2];
-    col.cigar_in = (const uint32_t *)r.col_q[3]; col.umask = (const uint16_t *)r.col_q[4];
-    col.cigar_staged = (const uint32_t *)r.col_q[5]; col.cigar_out = (uint32_t *)const_cast<void *>(r.col_q[6]);
-    col.tup = (const uint16_t *)r.col_t[0]; col.tup_flag = (const uint16_t *)r.col_t[1]; col.tup_l_seq = (const uint16_t *)r.col_t[2];
-    col.tup_n_cigar = (const uint16_t *)r.col_t[3]; col.tup_mapq = (const uint8_t *)r.col_t[4]; col.tup_aux = (const uint8_t *)r.col_t[5];
-    col.tup_n_low = (const uint8_t *)r.col_t[6]; col.tup_umask = (const uint16_t *)r.col_t[7]; col.lists = r.col_lists; col.n_tup = r.col_ntup;
-    col.tup8 = (const uint8_t *)r.col_t8[0]; col.tup_hot = (const uint16_t *)r.col_t8[1]; col.tup_esc = (const uint16_t *)r.col_t8[2];
-    col.tup_esc_off = (const uint32_t *)r.col_t8[3]; col.n_tup_esc = r.col_ntesc;
-    if (col.tup8) col.tup_out = const_cast<uint16_t *>(col.tup);
-    col.start_d = (const int16_t *)r.col_d[0]; col.tlen_s = (const int16_t *)r.col_d[1]; col.mate_d = (const int16_t *)r.col_d[2];
-    col.qname_d = (const int16_t *)r.col_d[3]; col.esc16_key = (const unsigned long long *)r.col_d[4]; col.esc16_val = (const int32_t *)r.col_d[5];
-    col.start_d8 = (const uint8_t *)r.col_d[6];
-    col.mate_d8 = (const int8_t *)r.col_d[7]; col.qname_d8 = (const int8_t *)r.col_d[8]; col.pair_d8 = (const uint8_t *)r.col_d[9];
-    col.n_esc16 = r.col_nesc;
-    col.qpos_wide = r.col_qwide;
-    col.bl_n = (const uint8_t *)r.col_b[0]; col.tup_n_bl = (const uint8_t *)r.col_b[1]; col.bl_pos = (const uint8_t *)r.col_b[2]; col.bl_code = (const uint8_t *)r.col_b[3];
-    col.bl_wide = r.col_bwide;
-    col.pk_sums = (const unsigned long long *)r.col_pk;
-    if (col.bl_form()) { col.n_seq_link = r.n_seq_units - r.n_bl_units; col.seq4_out = reinterpret_cast<uint32_t *>(const_cast<uint8_t *>(r.seq4)); }
-    uz_build_records(c, st, r, col, r.build_scratch);
-}
 void uz_reads_make_ready(uz_ctx *c, ReadsDev &r) {
     if (!r.pending) return;
     if (r.built) UZ_HIP(hipStreamWaitEvent(c->stream, r.built, 0)); // built beside whatever the compute stream was doing
-    else {
+    else { // no build queued with the upload (UZ_BUILD_LAZY): from the staged columns the upload left in the table's block
         UZ_HIP(hipStreamWaitEvent(c->stream, r.ready, 0));
-        build_staged(c, c->stream, r);
+        uz_build_records(c, c->stream, r, r.cols, r.build_scratch);
     }
     r.pending = false;
 }
@@ -1266,12 +1184,152 @@ int uz_reads_upload_impl(uz_ctx *c, const uz_reads_view *v, ReadsDev &r) {
     uz_build_records(c, st, r, col, scratch);
     uz_pack_ascii_rows(c, st, r, cigar_in, cigar_off_in, seq_in, r.qual_off16, cigar, seq4);
     UZ_HIP(hipStreamSynchronize(st));
-    if (c->hflags[0]) {
-        const int f = c->hflags[0];
-        c->hflags[0] = 0;
-        throw UzError{UZ_E_RANGE, f == 2 ? "SEQ holds a character outside BAM's 16-code alphabet" : "inconsistent reads view"};
-    }
+    uz_check_upload_flag(c);
     return 0;
+}
+
+// A table over packed columns that lie in DEVICE memory: cigar, seq4 and the quality plane stay where they are and ARE the device's stores, the
+// headers and the index are built into a block of the library's own (two-bit rows and the list form of the plane are expanded there).  None
+// of the caller's other pointers is kept.  -> the table's id
+static int adopt_device(uz_ctx *c, const uz_reads_packed_view *v) {
+    check_packed_view(v);
+    UZ_REQUIRE(!v->cigar_compact, UZ_E_ARG, "uz_reads_adopt_device takes every CIGAR word (cigar_compact = 0): the caller's column IS the device's store");
+    UZ_REQUIRE(!v->bl_n && !v->tup_n_bl, UZ_E_ARG, "uz_reads_adopt_device takes base rows: the list form of the bases (bl_*) is a form of the host link");
+    UZ_REQUIRE(!v->tup8, UZ_E_ARG, "uz_reads_adopt_device takes the 16-bit dictionary index: the one-byte form (tup8) is a form of the host link");
+    UZ_REQUIRE(((uintptr_t)v->qlow | (uintptr_t)v->seq4 | (uintptr_t)v->seq2 | (uintptr_t)v->cigar) % 16 == 0, UZ_E_ARG, "device columns must be 16-byte aligned");
+    ReadsDev r;
+    r.live = true;
+    r.n = v->n_segs; r.n_contigs = v->n_contigs; r.n_qnames = v->n_qnames;
+    r.n_cigar_total = v->n_cigar_total; r.n_row_units = v->n_row_units; r.n_seq_units = v->n_seq_units;
+    void *scratch = nullptr;
+    uint8_t *seq4_own = nullptr; // two-bit rows are expanded into the library's own block
+    uint8_t *qlow_own = nullptr; // the list form of the quality plane likewise
+    const bool a_lists = v->n_low != nullptr || (v->tup && v->tup_n_low);
+    r.n_qlow_pos = a_lists ? v->n_qlow_pos : 0;
+    r.n_plane_units = a_lists ? v->n_seq_units : v->n_row_units;
+    for (int pass = 0; pass < 2; pass++) {
+        Carver cv(pass ? r.block.p : nullptr);
+        carve_common(cv, r);
+        if (v->seq2) seq4_own = cv.take<uint8_t>((size_t)r.n_seq_units * UZ_SEQ4_UNIT_BYTES);
+        if (a_lists) qlow_own = cv.take<uint8_t>((size_t)r.n_seq_units * UZ_QLOW_UNIT_BYTES);
+        scratch = cv.take<uint8_t>(uz_rec_scratch_bytes(r.n));
+        if (!pass) r.block = uz_block_get(c, cv.off + 256);
+    }
+    try {
+        hipStream_t st = c->stream;
+        UZ_HIP(hipMemcpyAsync(r.contig_off, v->contig_off, ((size_t)v->n_contigs + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+        if (v->n_contigs) UZ_HIP(hipMemcpyAsync(r.max_span, v->max_span, (size_t)v->n_contigs * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        RecColumns col;
+        col.start = v->start; col.end = v->end; col.tlen = v->tlen; col.mate = v->mate; col.qname = v->qname;
+        if (v->start_d || v->start_d8) {
+            col.start_d = v->start_d; col.start_d8 = v->start_d8; col.tlen_s = v->tlen_s; col.mate_d = v->mate_d; col.qname_d = v->qname_d;
+            col.mate_d8 = v->mate_d8; col.qname_d8 = v->qname_d8; col.pair_d8 = v->pair_d8;
+            col.esc16_key = (const unsigned long long *)v->esc16_key; col.esc16_val = v->esc16_val; col.n_esc16 = v->n_esc16;
+        }
+        col.flag = v->flag; col.l_seq = v->l_seq; col.n_cigar = v->n_cigar; col.mapq = v->mapq; col.aux = v->aux;
+        r.cigar = v->cigar; r.seq4 = v->seq4; r.qlow = const_cast<uint8_t *>(v->qlow);
+        col.cigar_in = v->cigar;
+        if (v->seq2) {
+            r.seq4 = seq4_own; r.seq2_staged = v->seq2;
+            r.n_exc = v->n_exc; r.exc_rec = v->exc_rec; r.exc_pos = v->exc_pos; r.exc_code = v->exc_code;
+        }
+        if (v->tup) {
+            col.tup = v->tup; col.tup_flag = v->tup_flag; col.tup_l_seq = v->tup_l_seq; col.tup_n_cigar = v->tup_n_cigar;
+            col.tup_mapq = v->tup_mapq; col.tup_aux = v->tup_aux; col.tup_n_low = v->tup_n_low; col.tup_umask = v->tup_umask; col.n_tup = v->n_tup;
+        }
+        if (a_lists) { r.qlow = qlow_own; col.lists = 1; col.n_low = v->n_low; col.qlow_pos = v->qlow_pos; col.qpos_wide = v->qlow_pos_wide; col.umask = v->umask; }
+        else col.plane_in = reinterpret_cast<const uint32_t *>(v->qlow);
+        r.qlow_thr = v->min_base_qual;
+        r.qlow_valid = true;
+        uz_build_records(c, st, r, col, scratch);
+        UZ_HIP(hipStreamSynchronize(st));
+        r.exc_rec = nullptr; r.exc_pos = nullptr; r.exc_code = nullptr; r.n_exc = 0; // (the caller's memory: not kept)
+        uz_check_upload_flag(c);
+    } catch (...) { uz_block_put(c, r.block); throw; }
+    const int k = new_slot(c->reads);
+    c->reads[k] = r;
+    return k;
+}
+
+// What uz_reads_from_walk and uz_reads_from_bam share.  The records of a walked batch (they lie inflated in its slot) are unpacked into the columns of
+// ONE block (uz_launch_bam_extract), the table adopts the columns where they lie (adopt_device) and keeps the block as its `mirror`; the slot is released.
+struct ExtractJob {
+    const char *who = "";              // the entry point: in front of the error texts
+    const uz_kept_rec *kept = nullptr; // the kept list [n] and the aux bytes of records only the host has seen: device memory, or --
+    const uint8_t *aux = nullptr;      // from_host -- the host's, which then travel into the block first
+    int64_t aux_bytes = 0;
+    bool from_host = false;
+    const int64_t *contig_off = nullptr; // [n_contigs + 1], [n_contigs]: host memory
+    const int32_t *max_span = nullptr;
+    int32_t n_contigs = 0, min_base_qual = 0;
+    int64_t n = 0, n_cigar_total = 0, n_row_units = 0, n_seq_units = 0, names_bytes = 0;
+    uint32_t n_qnames = 0;
+    bool names = false;                 // the read names are unpacked too, and then ...
+    uint8_t *names_out = nullptr;       // ... copied to this host memory, or
+    bool keep_names = false;            // ... kept in the block, with the kept list and ...
+    const uint32_t *name_rec = nullptr; // ... this column (device, [n_qnames]): uz_reads_names answers ids from them
+};
+static int extract_and_adopt(uz_ctx *c, uz_ctx::WalkSlot &w, const ExtractJob &j) {
+    const std::string who = std::string(j.who) + ": ";
+    const size_t n = (size_t)j.n, nctg = (size_t)j.n_contigs;
+    DevBlock blk;
+    uz_kept_rec *d_kept = nullptr;
+    uint8_t *d_aux = nullptr, *mapq = nullptr, *aux_col = nullptr, *seq4 = nullptr, *d_names = nullptr;
+    int64_t *d_coff = nullptr;
+    int32_t *d_span = nullptr, *start = nullptr, *tlen = nullptr, *mate = nullptr, *err = nullptr;
+    uint32_t *qname = nullptr, *cigar = nullptr, *plane = nullptr, *name_rec = nullptr;
+    uint16_t *flag = nullptr, *l_seq = nullptr, *n_cigar = nullptr;
+    for (int pass = 0; pass < 2; pass++) {
+        Carver cv(pass ? blk.p : nullptr);
+        if (j.from_host) { d_kept = cv.take<uz_kept_rec>(n); d_aux = cv.take<uint8_t>((size_t)j.aux_bytes + 64); }
+        d_coff = cv.take<int64_t>(nctg + 1); d_span = cv.take<int32_t>(nctg + 1); err = cv.take<int32_t>(4);
+        start = cv.take<int32_t>(n); tlen = cv.take<int32_t>(n); mate = cv.take<int32_t>(n); qname = cv.take<uint32_t>(n);
+        flag = cv.take<uint16_t>(n); l_seq = cv.take<uint16_t>(n); n_cigar = cv.take<uint16_t>(n);
+        mapq = cv.take<uint8_t>(n); aux_col = cv.take<uint8_t>(n);
+        cigar = cv.take<uint32_t>((size_t)j.n_cigar_total); seq4 = cv.take<uint8_t>((size_t)j.n_seq_units * UZ_SEQ4_UNIT_BYTES);
+        plane = cv.take<uint32_t>((size_t)j.n_row_units);
+        if (j.names) d_names = cv.take<uint8_t>((size_t)j.names_bytes);
+        if (j.keep_names) { d_kept = cv.take<uz_kept_rec>(n); name_rec = cv.take<uint32_t>((size_t)j.n_qnames); }
+        if (!pass) blk = uz_block_get(c, cv.off + 256);
+    }
+    int id = -1;
+    try {
+        hipStream_t st = c->stream;
+        const uz_kept_rec *kept = j.kept;
+        const uint8_t *aux = j.aux;
+        if (j.from_host) {
+            if (n) UZ_HIP(hipMemcpyAsync(d_kept, j.kept, n * sizeof(uz_kept_rec), hipMemcpyHostToDevice, st));
+            if (j.aux_bytes) UZ_HIP(hipMemcpyAsync(d_aux, j.aux, (size_t)j.aux_bytes, hipMemcpyHostToDevice, st));
+            kept = d_kept; aux = d_aux;
+        }
+        UZ_HIP(hipMemcpyAsync(d_coff, j.contig_off, (nctg + 1) * 8, hipMemcpyHostToDevice, st));
+        if (nctg) UZ_HIP(hipMemcpyAsync(d_span, j.max_span, nctg * 4, hipMemcpyHostToDevice, st));
+        UZ_HIP(hipMemsetAsync(err, 0, 16, st));
+        uz_launch_bam_extract(c, st, j.n, w.out.p, w.out_bytes, aux, j.aux_bytes, kept, j.min_base_qual, start, tlen, mate, qname, flag, l_seq, n_cigar, mapq, aux_col,
+                              cigar, seq4, plane, err, d_names, j.n_cigar_total, j.n_row_units, j.n_seq_units, j.names_bytes);
+        if (j.names_out && j.names_bytes) UZ_HIP(hipMemcpyAsync(j.names_out, d_names, (size_t)j.names_bytes, hipMemcpyDeviceToHost, st));
+        if (j.keep_names && n) {
+            UZ_HIP(hipMemcpyAsync(d_kept, kept, n * sizeof(uz_kept_rec), hipMemcpyDeviceToDevice, st));
+            if (j.n_qnames) UZ_HIP(hipMemcpyAsync(name_rec, j.name_rec, (size_t)j.n_qnames * 4, hipMemcpyDeviceToDevice, st));
+        }
+        int32_t e = 0;
+        UZ_HIP(hipMemcpyAsync(&e, err, 4, hipMemcpyDeviceToHost, st));
+        UZ_HIP(hipStreamSynchronize(st));
+        UZ_REQUIRE(e != 2, UZ_E_RANGE, who + "an offset of the kept list points beyond the stores its totals declare");
+        UZ_REQUIRE(e == 0, UZ_E_RANGE, who + "a kept record lies outside the walked bytes, or overruns its block_size");
+        uz_reads_packed_view v;
+        memset(&v, 0, sizeof(v));
+        v.n_segs = j.n; v.n_contigs = j.n_contigs; v.contig_off = d_coff; v.max_span = d_span;
+        v.start = start; v.tlen = tlen; v.mate = mate; v.qname = qname; v.flag = flag; v.l_seq = l_seq; v.n_cigar = n_cigar; v.mapq = mapq; v.aux = aux_col;
+        v.n_cigar_total = j.n_cigar_total; v.cigar = cigar; v.n_row_units = j.n_row_units; v.n_seq_units = j.n_seq_units; v.seq4 = seq4;
+        v.qlow = reinterpret_cast<const uint8_t *>(plane); v.min_base_qual = j.min_base_qual; v.n_qnames = j.n_qnames;
+        id = adopt_device(c, &v);
+        ReadsDev &r = c->reads[(size_t)id];
+        r.mirror = blk;
+        if (j.keep_names) { r.kept_list = d_kept; r.name_rec = name_rec; r.names = d_names; r.names_bytes = j.names_bytes; }
+    } catch (...) { uz_block_put(c, blk); throw; }
+    { std::lock_guard<std::mutex> lk(c->err_mu); w.busy = false; }
+    return id;
 }
 
 extern "C" {
@@ -1292,7 +1350,7 @@ int uz_reads_upload_packed(uz_ctx *c, const uz_reads_packed_view *v, int *id) {
         UZ_REQUIRE(v && id, UZ_E_ARG, "bad reads view");
         ReadsDev r;
         try {
-            reads_from_packed_host(c, c->copy_stream, v, r, true);
+            reads_from_packed_host(c, c->copy_stream, v, r);
             UZ_HIP(hipEventCreateWithFlags(&r.ready, hipEventDisableTiming));
             UZ_HIP(hipEventRecord(r.ready, c->copy_stream));
             r.pending = true;
@@ -1300,7 +1358,7 @@ int uz_reads_upload_packed(uz_ctx *c, const uz_reads_packed_view *v, int *id) {
             if (!lazy) {
                 if (!c->build_stream) UZ_HIP(hipStreamCreateWithFlags(&c->build_stream, hipStreamNonBlocking));
                 UZ_HIP(hipStreamWaitEvent(c->build_stream, r.ready, 0));
-                build_staged(c, c->build_stream, r);
+                uz_build_records(c, c->build_stream, r, r.cols, r.build_scratch);
                 UZ_HIP(hipEventCreateWithFlags(&r.built, hipEventDisableTiming));
                 UZ_HIP(hipEventRecord(r.built, c->build_stream));
             }
@@ -1320,10 +1378,7 @@ int uz_reads_wait(uz_ctx *c, int reads_id) {
         ReadsDev &r = reads_of(c, reads_id);
         uz_reads_make_ready(c, r);
         UZ_HIP(hipStreamSynchronize(c->stream));
-        if (c->hflags[0]) {
-            c->hflags[0] = 0;
-            throw UzError{UZ_E_RANGE, "n_cigar_total / n_row_units of the reads view do not match its columns"};
-        }
+        uz_check_upload_flag(c);
     });
 }
 
@@ -1332,10 +1387,7 @@ int uz_reads_headers(uz_ctx *c, int reads_id, int32_t *start, int32_t *end, int3
         ReadsDev &r = reads_of(c, reads_id);
         uz_reads_make_ready(c, r);
         UZ_HIP(hipStreamSynchronize(c->stream));
-        if (c->hflags[0]) {
-            c->hflags[0] = 0;
-            throw UzError{UZ_E_RANGE, "inconsistent reads view"};
-        }
+        uz_check_upload_flag(c);
         struct HA { int32_t start, end; uint32_t cigar_off, sq_off; }; // the record headers (RecA / RecB of phase_body.hpp)
         struct HB { int32_t mate; uint32_t qname; uint16_t l_seq, n_cigar; int32_t tlen; };
         const size_t n = (size_t)r.n;
@@ -1464,70 +1516,7 @@ int uz_bgzf_inflate_to_host(uz_ctx *c, const uint8_t *comp, int64_t comp_bytes, 
 int uz_reads_adopt_device(uz_ctx *c, const uz_reads_packed_view *v, int *id) {
     return guarded(c, [&] {
         UZ_REQUIRE(v && id, UZ_E_ARG, "bad reads view");
-        check_packed_view(v);
-        UZ_REQUIRE(!v->cigar_compact, UZ_E_ARG, "uz_reads_adopt_device takes every CIGAR word (cigar_compact = 0): the caller's column IS the device's store");
-        UZ_REQUIRE(!v->bl_n && !v->tup_n_bl, UZ_E_ARG, "uz_reads_adopt_device takes base rows: the list form of the bases (bl_*) is a form of the host link");
-        UZ_REQUIRE(!v->tup8, UZ_E_ARG, "uz_reads_adopt_device takes the 16-bit dictionary index: the one-byte form (tup8) is a form of the host link");
-        UZ_REQUIRE(((uintptr_t)v->qlow | (uintptr_t)v->seq4 | (uintptr_t)v->seq2 | (uintptr_t)v->cigar) % 16 == 0, UZ_E_ARG, "device columns must be 16-byte aligned");
-        ReadsDev r;
-        r.live = true;
-        r.n = v->n_segs; r.n_contigs = v->n_contigs; r.n_qnames = v->n_qnames;
-        r.n_cigar_total = v->n_cigar_total; r.n_row_units = v->n_row_units; r.n_seq_units = v->n_seq_units;
-        void *scratch = nullptr;
-        uint8_t *seq4_own = nullptr; // two-bit rows are expanded into the library's own block
-        uint8_t *qlow_own = nullptr; // the list form of the quality plane likewise
-        const bool a_lists = v->n_low != nullptr || (v->tup && v->tup_n_low);
-        r.n_qlow_pos = a_lists ? v->n_qlow_pos : 0;
-        r.n_plane_units = a_lists ? v->n_seq_units : v->n_row_units;
-        for (int pass = 0; pass < 2; pass++) {
-            Carver cv(pass ? r.block.p : nullptr);
-            carve_common(cv, r);
-            if (v->seq2) seq4_own = cv.take<uint8_t>((size_t)r.n_seq_units * UZ_SEQ4_UNIT_BYTES);
-            if (a_lists) qlow_own = cv.take<uint8_t>((size_t)r.n_seq_units * UZ_QLOW_UNIT_BYTES);
-            scratch = cv.take<uint8_t>(uz_rec_scratch_bytes(r.n));
-            if (!pass) r.block = uz_block_get(c, cv.off + 256);
-        }
-        try {
-            hipStream_t st = c->stream;
-            UZ_HIP(hipMemcpyAsync(r.contig_off, v->contig_off, ((size_t)v->n_contigs + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-            if (v->n_contigs) UZ_HIP(hipMemcpyAsync(r.max_span, v->max_span, (size_t)v->n_contigs * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-            RecColumns col;
-            col.start = v->start; col.end = v->end; col.tlen = v->tlen; col.mate = v->mate; col.qname = v->qname;
-            if (v->start_d || v->start_d8) {
-                col.start_d = v->start_d; col.start_d8 = v->start_d8; col.tlen_s = v->tlen_s; col.mate_d = v->mate_d; col.qname_d = v->qname_d;
-                col.mate_d8 = v->mate_d8; col.qname_d8 = v->qname_d8; col.pair_d8 = v->pair_d8;
-                col.esc16_key = (const unsigned long long *)v->esc16_key; col.esc16_val = v->esc16_val; col.n_esc16 = v->n_esc16;
-            }
-            col.flag = v->flag; col.l_seq = v->l_seq; col.n_cigar = v->n_cigar; col.mapq = v->mapq; col.aux = v->aux;
-            r.cigar = v->cigar; r.seq4 = v->seq4; r.qlow = const_cast<uint8_t *>(v->qlow);
-            col.cigar_in = v->cigar;
-            if (v->seq2) {
-                r.seq4 = seq4_own; r.seq2_staged = v->seq2;
-                r.n_exc = v->n_exc; r.exc_rec = v->exc_rec; r.exc_pos = v->exc_pos; r.exc_code = v->exc_code;
-            }
-            if (v->tup) {
-                col.tup = v->tup; col.tup_flag = v->tup_flag; col.tup_l_seq = v->tup_l_seq; col.tup_n_cigar = v->tup_n_cigar;
-                col.tup_mapq = v->tup_mapq; col.tup_aux = v->tup_aux; col.tup_n_low = v->tup_n_low; col.tup_umask = v->tup_umask; col.n_tup = v->n_tup;
-            }
-            if (v->n_low || (v->tup && v->tup_n_low)) { r.qlow = qlow_own; col.lists = 1; col.n_low = v->n_low; col.qlow_pos = v->qlow_pos; col.qpos_wide = v->qlow_pos_wide; col.umask = v->umask; }
-            else col.plane_in = reinterpret_cast<const uint32_t *>(v->qlow);
-            r.qlow_thr = v->min_base_qual;
-            r.qlow_valid = true;
-            uz_build_records(c, st, r, col, scratch);
-            UZ_HIP(hipStreamSynchronize(st));
-            r.exc_rec = nullptr; r.exc_pos = nullptr; r.exc_code = nullptr; r.n_exc = 0; // (the caller's memory: not kept)
-            if (c->hflags[0]) {
-                const int f = c->hflags[0];
-                c->hflags[0] = 0;
-                throw UzError{UZ_E_RANGE, f == 5 ? "umask: a unit beyond the read's length, or a mask on a read longer than 480 bases"
-                                          : f == 4 ? "qlow_pos: positions of a record are not ascending or lie beyond l_seq"
-                                          : f == 3 ? "exc_* columns: an entry names a record without bases, a base beyond l_seq or a code above 15"
-                                                 : "n_cigar_total / n_row_units of the reads view do not match its columns"};
-            }
-        } catch (...) { uz_block_put(c, r.block); uz_block_put(c, r.mirror); throw; }
-        const int k = new_slot(c->reads);
-        c->reads[k] = r;
-        *id = k;
+        *id = adopt_device(c, v);
     });
 }
 
@@ -2255,61 +2244,17 @@ int uz_reads_from_walk(uz_ctx *c, int walk_id, int32_t min_base_qual, int want_n
         uz_ctx::WalkSlot &w = c->walk[walk_id];
         auto &J = w.join;
         UZ_REQUIRE(J.done, UZ_E_STATE, "uz_reads_from_walk: the joins of this batch are not finished (uz_bam_join until it needs nothing)");
-        const int64_t n = J.tot_h[JT_N], n_cigar_total = J.tot_h[JT_CIGAR], n_row_units = J.tot_h[JT_UNITS], n_seq_units = J.tot_h[JT_SEQ_UNITS], names_bytes = J.tot_h[JT_NAME_BYTES];
-        const int64_t n_qnames = J.tot_h[JT_QNAMES];
-        const int32_t n_contigs = J.n_ref;
-        UZ_REQUIRE(n < (int64_t)0x7FFFFFF0 && n_cigar_total < ((int64_t)1 << 32) && n_row_units < ((int64_t)1 << 32) && names_bytes < ((int64_t)1 << 32), UZ_E_RANGE,
+        ExtractJob j;
+        j.who = "uz_reads_from_walk";
+        j.kept = J.kept.p; j.aux = J.aux.p; j.aux_bytes = J.aux_bytes; // (the joins ran on the slot's stream and were waited for: uz_bam_join returns behind them)
+        j.contig_off = J.contig_off_h.data(); j.max_span = J.max_span_h.data(); j.n_contigs = J.n_ref; j.min_base_qual = min_base_qual;
+        j.n = J.tot_h[JT_N]; j.n_cigar_total = J.tot_h[JT_CIGAR]; j.n_row_units = J.tot_h[JT_UNITS]; j.n_seq_units = J.tot_h[JT_SEQ_UNITS];
+        j.names_bytes = J.tot_h[JT_NAME_BYTES]; j.n_qnames = (uint32_t)J.tot_h[JT_QNAMES];
+        UZ_REQUIRE(j.n < (int64_t)0x7FFFFFF0 && j.n_cigar_total < ((int64_t)1 << 32) && j.n_row_units < ((int64_t)1 << 32) && j.names_bytes < ((int64_t)1 << 32), UZ_E_RANGE,
                    "uz_reads_from_walk: the batch does not fit the table's 32-bit offsets");
         if (totals) for (int k = 0; k < 8; k++) totals[k] = J.tot_h[k];
-        DevBlock blk;
-        uz_kept_rec *d_kept = nullptr;
-        uint8_t *mapq = nullptr, *aux_col = nullptr, *seq4 = nullptr, *d_names = nullptr;
-        int64_t *d_coff = nullptr;
-        int32_t *d_span = nullptr, *start = nullptr, *tlen = nullptr, *mate = nullptr, *err = nullptr;
-        uint32_t *qname = nullptr, *cigar = nullptr, *plane = nullptr, *name_rec = nullptr;
-        uint16_t *flag = nullptr, *l_seq = nullptr, *n_cigar = nullptr;
-        for (int pass = 0; pass < 2; pass++) {
-            Carver cv(pass ? blk.p : nullptr);
-            d_coff = cv.take<int64_t>((size_t)n_contigs + 1); d_span = cv.take<int32_t>((size_t)n_contigs + 1); err = cv.take<int32_t>(4);
-            start = cv.take<int32_t>((size_t)n); tlen = cv.take<int32_t>((size_t)n); mate = cv.take<int32_t>((size_t)n); qname = cv.take<uint32_t>((size_t)n);
-            flag = cv.take<uint16_t>((size_t)n); l_seq = cv.take<uint16_t>((size_t)n); n_cigar = cv.take<uint16_t>((size_t)n);
-            mapq = cv.take<uint8_t>((size_t)n); aux_col = cv.take<uint8_t>((size_t)n);
-            cigar = cv.take<uint32_t>((size_t)n_cigar_total); seq4 = cv.take<uint8_t>((size_t)n_seq_units * UZ_SEQ4_UNIT_BYTES);
-            plane = cv.take<uint32_t>((size_t)n_row_units);
-            if (want_names) { d_kept = cv.take<uz_kept_rec>((size_t)n); name_rec = cv.take<uint32_t>((size_t)n_qnames); d_names = cv.take<uint8_t>((size_t)names_bytes); }
-            if (!pass) blk = uz_block_get(c, cv.off + 256);
-        }
-        int id = -1;
-        try {
-            hipStream_t st = c->stream; // (the joins ran on the slot's stream and were waited for: uz_bam_join returns behind them)
-            UZ_HIP(hipMemcpyAsync(d_coff, J.contig_off_h.data(), ((size_t)n_contigs + 1) * 8, hipMemcpyHostToDevice, st));
-            if (n_contigs) UZ_HIP(hipMemcpyAsync(d_span, J.max_span_h.data(), (size_t)n_contigs * 4, hipMemcpyHostToDevice, st));
-            UZ_HIP(hipMemsetAsync(err, 0, 16, st));
-            uz_launch_bam_extract(c, st, n, w.out.p, w.out_bytes, J.aux.p, J.aux_bytes, J.kept.p, min_base_qual, start, tlen, mate, qname, flag, l_seq, n_cigar, mapq, aux_col,
-                                  cigar, seq4, plane, err, want_names ? d_names : nullptr, n_cigar_total, n_row_units, n_seq_units, names_bytes);
-            if (want_names && n) {
-                UZ_HIP(hipMemcpyAsync(d_kept, J.kept.p, (size_t)n * sizeof(uz_kept_rec), hipMemcpyDeviceToDevice, st));
-                if (n_qnames) UZ_HIP(hipMemcpyAsync(name_rec, J.name_rec.p, (size_t)n_qnames * 4, hipMemcpyDeviceToDevice, st));
-            }
-            int32_t e = 0;
-            UZ_HIP(hipMemcpyAsync(&e, err, 4, hipMemcpyDeviceToHost, st));
-            UZ_HIP(hipStreamSynchronize(st));
-            UZ_REQUIRE(e != 2, UZ_E_RANGE, "uz_reads_from_walk: an offset of the kept list points beyond the stores its totals declare");
-            UZ_REQUIRE(e == 0, UZ_E_RANGE, "uz_reads_from_walk: a kept record lies outside the walked bytes, or overruns its block_size");
-            uz_reads_packed_view v;
-            memset(&v, 0, sizeof(v));
-            v.n_segs = n; v.n_contigs = n_contigs; v.contig_off = d_coff; v.max_span = d_span;
-            v.start = start; v.tlen = tlen; v.mate = mate; v.qname = qname; v.flag = flag; v.l_seq = l_seq; v.n_cigar = n_cigar; v.mapq = mapq; v.aux = aux_col;
-            v.n_cigar_total = n_cigar_total; v.cigar = cigar; v.n_row_units = n_row_units; v.n_seq_units = n_seq_units; v.seq4 = seq4;
-            v.qlow = reinterpret_cast<const uint8_t *>(plane); v.min_base_qual = min_base_qual; v.n_qnames = (uint32_t)n_qnames;
-            const int rc = uz_reads_adopt_device(c, &v, &id);
-            if (rc) throw UzError{rc, c->err};
-            ReadsDev &r = c->reads[(size_t)id];
-            r.mirror = blk;
-            if (want_names) { r.kept_list = d_kept; r.name_rec = name_rec; r.names = d_names; r.names_bytes = names_bytes; }
-        } catch (...) { uz_block_put(c, blk); throw; }
-        { std::lock_guard<std::mutex> lk(c->err_mu); w.busy = false; }
-        *reads_id = id;
+        j.names = j.keep_names = want_names != 0; j.name_rec = J.name_rec.p; // the names stay on the device
+        *reads_id = extract_and_adopt(c, w, j);
     });
 }
 
@@ -2372,64 +2317,13 @@ int uz_reads_from_bam(uz_ctx *c, int walk_id, const uz_kept_rec *kept, int64_t n
         UZ_REQUIRE(reads_id && n >= 0 && n < (int64_t)0x7FFFFFF0 && (n == 0 || kept) && aux_bytes >= 0 && (aux_bytes == 0 || aux) && contig_off && max_span && n_contigs >= 0 &&
                        n_cigar_total >= 0 && n_cigar_total < ((int64_t)1 << 32) && n_row_units >= 0 && n_row_units < ((int64_t)1 << 32) && n_seq_units >= 0 && n_seq_units <= n_row_units,
                    UZ_E_ARG, "bad arguments");
-        uz_ctx::WalkSlot &w = c->walk[walk_id];
-        static const bool rfb_log = getenv("UZ_RFB_LOG") != nullptr; // development aid: where the call's time goes
-        const auto t0 = std::chrono::steady_clock::now();
-        auto since = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
-        double t_blk = 0, t_enq = 0, t_sync = 0;
-        // one block for the kept list, the aux bytes and the columns the records are unpacked into; the table adopts the columns in place
-        // (uz_reads_adopt_device: cigar, seq4 and the quality plane ARE the device's stores) and keeps the block as its `mirror`
-        DevBlock blk;
-        uz_kept_rec *d_kept = nullptr;
-        uint8_t *d_aux = nullptr, *mapq = nullptr, *aux_col = nullptr, *seq4 = nullptr, *d_names = nullptr;
-        int64_t *d_coff = nullptr;
-        int32_t *d_span = nullptr, *start = nullptr, *tlen = nullptr, *mate = nullptr, *err = nullptr;
-        uint32_t *qname = nullptr, *cigar = nullptr, *plane = nullptr;
-        uint16_t *flag = nullptr, *l_seq = nullptr, *n_cigar = nullptr;
-        for (int pass = 0; pass < 2; pass++) {
-            Carver cv(pass ? blk.p : nullptr);
-            d_kept = cv.take<uz_kept_rec>((size_t)n); d_aux = cv.take<uint8_t>((size_t)aux_bytes + 64);
-            d_coff = cv.take<int64_t>((size_t)n_contigs + 1); d_span = cv.take<int32_t>((size_t)n_contigs + 1); err = cv.take<int32_t>(4);
-            start = cv.take<int32_t>((size_t)n); tlen = cv.take<int32_t>((size_t)n); mate = cv.take<int32_t>((size_t)n); qname = cv.take<uint32_t>((size_t)n);
-            flag = cv.take<uint16_t>((size_t)n); l_seq = cv.take<uint16_t>((size_t)n); n_cigar = cv.take<uint16_t>((size_t)n);
-            mapq = cv.take<uint8_t>((size_t)n); aux_col = cv.take<uint8_t>((size_t)n);
-            cigar = cv.take<uint32_t>((size_t)n_cigar_total); seq4 = cv.take<uint8_t>((size_t)n_seq_units * UZ_SEQ4_UNIT_BYTES);
-            plane = cv.take<uint32_t>((size_t)n_row_units);
-            if (names_out) d_names = cv.take<uint8_t>((size_t)names_bytes);
-            if (!pass) blk = uz_block_get(c, cv.off + 256);
-        }
-        int id = -1;
-        t_blk = since();
-        try {
-            hipStream_t st = c->stream;
-            if (n) UZ_HIP(hipMemcpyAsync(d_kept, kept, (size_t)n * sizeof(uz_kept_rec), hipMemcpyHostToDevice, st));
-            if (aux_bytes) UZ_HIP(hipMemcpyAsync(d_aux, aux, (size_t)aux_bytes, hipMemcpyHostToDevice, st));
-            UZ_HIP(hipMemcpyAsync(d_coff, contig_off, ((size_t)n_contigs + 1) * 8, hipMemcpyHostToDevice, st));
-            if (n_contigs) UZ_HIP(hipMemcpyAsync(d_span, max_span, (size_t)n_contigs * 4, hipMemcpyHostToDevice, st));
-            UZ_HIP(hipMemsetAsync(err, 0, 16, st));
-            uz_launch_bam_extract(c, st, n, w.out.p, w.out_bytes, d_aux, aux_bytes, d_kept, min_base_qual, start, tlen, mate, qname, flag, l_seq, n_cigar, mapq, aux_col,
-                                  cigar, seq4, plane, err, names_out ? d_names : nullptr, n_cigar_total, n_row_units, n_seq_units, names_bytes);
-            if (names_out && names_bytes) UZ_HIP(hipMemcpyAsync(names_out, d_names, (size_t)names_bytes, hipMemcpyDeviceToHost, st));
-            int32_t e = 0;
-            UZ_HIP(hipMemcpyAsync(&e, err, 4, hipMemcpyDeviceToHost, st));
-            t_enq = since();
-            UZ_HIP(hipStreamSynchronize(st));
-            t_sync = since();
-            UZ_REQUIRE(e != 2, UZ_E_RANGE, "uz_reads_from_bam: an offset of the kept list points beyond the stores its totals declare");
-            UZ_REQUIRE(e == 0, UZ_E_RANGE, "uz_reads_from_bam: a kept record lies outside the walked bytes, or overruns its block_size");
-            uz_reads_packed_view v;
-            memset(&v, 0, sizeof(v));
-            v.n_segs = n; v.n_contigs = n_contigs; v.contig_off = d_coff; v.max_span = d_span;
-            v.start = start; v.tlen = tlen; v.mate = mate; v.qname = qname; v.flag = flag; v.l_seq = l_seq; v.n_cigar = n_cigar; v.mapq = mapq; v.aux = aux_col;
-            v.n_cigar_total = n_cigar_total; v.cigar = cigar; v.n_row_units = n_row_units; v.n_seq_units = n_seq_units; v.seq4 = seq4;
-            v.qlow = reinterpret_cast<const uint8_t *>(plane); v.min_base_qual = min_base_qual; v.n_qnames = n_qnames;
-            const int rc = uz_reads_adopt_device(c, &v, &id);
-            if (rc) throw UzError{rc, c->err};
-            c->reads[(size_t)id].mirror = blk;
-        } catch (...) { uz_block_put(c, blk); throw; }
-        { std::lock_guard<std::mutex> lk(c->err_mu); w.busy = false; }
-        if (rfb_log) fprintf(stderr, "[uz] reads_from_bam n=%lld kept %.1f MB names %.1f MB: block %.2f, enqueue %.2f, sync %.2f, adopt %.2f ms\n", (long long)n, n * 32 / 1e6, names_bytes / 1e6, t_blk, t_enq - t_blk, t_sync - t_enq, since() - t_sync);
-        *reads_id = id;
+        ExtractJob j;
+        j.who = "uz_reads_from_bam";
+        j.kept = kept; j.aux = aux; j.aux_bytes = aux_bytes; j.from_host = true; // the host made the kept list: it travels into the table's block
+        j.contig_off = contig_off; j.max_span = max_span; j.n_contigs = n_contigs; j.min_base_qual = min_base_qual;
+        j.n = n; j.n_cigar_total = n_cigar_total; j.n_row_units = n_row_units; j.n_seq_units = n_seq_units; j.names_bytes = names_bytes; j.n_qnames = n_qnames;
+        j.names = names_out != nullptr; j.names_out = names_out; // the names go back to the host, which keeps them
+        *reads_id = extract_and_adopt(c, c->walk[walk_id], j);
     });
 }
 

@@ -1540,7 +1540,7 @@ void uz_phase_state_free(uz_ctx *c) {
 
 int uz_want_lists = 1; // uz_phase always keeps the lists available for uz_phase_votes / uz_phase_groups
 
-static void phase_check_upload_flags(uz_ctx *c) {
+void uz_check_upload_flag(uz_ctx *c) {
     if (c->hflags[0]) { // set by the header build of an upload (abi.hip) whose commands have now run
         const int f = c->hflags[0];
         c->hflags[0] = 0;
@@ -1730,7 +1730,7 @@ void uz_launch_phase(uz_ctx *c, FamilyDev &f, const SitesDev &s, ReadsDev &r, in
     uz_kcopy(c, st->bounds_h, st->bounds_red.p, sizeof(BoundsRed));
     if (!st->bounds_ready) UZ_HIP(hipEventCreateWithFlags(&st->bounds_ready, hipEventDisableTiming));
     UZ_HIP(hipEventRecord(st->bounds_ready, c->stream));
-    auto check_upload_flags = [&] { phase_check_upload_flags(c); };
+    auto check_upload_flags = [&] { uz_check_upload_flag(c); };
     auto exact_sizes = [&](const BoundsRed *bh) { return phase_exact_sizes(bh, n); };
     if (st->n_cus <= 0) { // asked once: the query is not cheap
         hipDeviceProp_t prop;
@@ -1940,7 +1940,7 @@ bool uz_finish_phase(uz_ctx *c, int32_t *status, int32_t *counts, int32_t *origi
     if (st->pending) {
         st->pending = false;
         UZ_HIP(hipStreamSynchronize(c->stream));
-        phase_check_upload_flags(c);
+        uz_check_upload_flag(c);
         if (c->hflags[1]) {
             c->hflags[1] = 0;
             st->force_exact = true; // (the whole run states the error in full)

@@ -164,6 +164,57 @@ struct SamplesDev {
     bool pending = false;
 };
 
+// the fixed-width columns of a table as DEVICE pointers (staged by an upload, or the caller's for an adopted table)
+struct RecColumns {
+    const int32_t *start = nullptr, *end = nullptr, *tlen = nullptr, *mate = nullptr;
+    const uint32_t *qname = nullptr;
+    const uint16_t *flag = nullptr, *l_seq = nullptr, *n_cigar = nullptr;
+    const uint8_t *mapq = nullptr, *aux = nullptr;
+    // qualities of the staged form: the plane itself (plane_in: the header build counts its bits into nlow) or its list
+    // form (n_low + qlow_pos: the header build copies the counts and writes the plane rows of the listed records); both
+    // null for an ASCII upload, whose plane and counts are built from the quality bytes (uz_build_qlow)
+    const uint32_t *cigar_staged = nullptr; // cigar_compact: the words that travelled (records with a simple code own none); the header build writes
+    uint32_t *cigar_out = nullptr;          // ... every record's words here (the device's CIGAR store).  Both null: `cigar_in` is the store itself
+    const uint32_t *cigar_in = nullptr; // the record's CIGAR words (at its cigar offset): `end` is derived from them when the column is left out (end == nullptr)
+    const uint16_t *umask = nullptr;    // staged units per record (null: every unit)
+    // dictionary form of the small columns (tup set: flag / l_seq / n_cigar / mapq / aux / n_low are read through the table)
+    const uint16_t *tup = nullptr, *tup_flag = nullptr, *tup_l_seq = nullptr, *tup_n_cigar = nullptr;
+    const uint8_t *tup_mapq = nullptr, *tup_aux = nullptr, *tup_n_low = nullptr;
+    const uint16_t *tup_umask = nullptr;
+    int64_t n_tup = 0; // entries of the dictionary (0: not known)
+    // the index in one byte (uz_types.h tup8): the header build first rebuilds the 16-bit column into tup_out (k_tup_expand) and reads it as `tup`
+    const uint8_t *tup8 = nullptr;
+    const uint16_t *tup_hot = nullptr, *tup_esc = nullptr;
+    const uint32_t *tup_esc_off = nullptr;
+    int64_t n_tup_esc = 0;
+    uint16_t *tup_out = nullptr;
+    // bases as lists (uz_types.h: bl_*): per record the number of listed bases (plain column or through the dictionary), their query indices and
+    // two-bit codes; seq4_out: the device's base rows (the header build writes the units of the listed records, behind the n_seq_link units that
+    // travelled as rows)
+    const uint8_t *bl_n = nullptr, *tup_n_bl = nullptr, *bl_pos = nullptr, *bl_code = nullptr;
+    int32_t bl_wide = 0;
+    int64_t n_seq_link = 0;
+    uint32_t *seq4_out = nullptr;
+    __host__ __device__ bool bl_form() const { return bl_n != nullptr || tup_n_bl != nullptr; }
+    // 16-bit difference form of start / tlen / mate / qname (start_d set: the plain four are null)
+    const int16_t *start_d = nullptr, *tlen_s = nullptr, *mate_d = nullptr, *qname_d = nullptr;
+    const uint8_t *start_d8 = nullptr; // the start differences in eight bits (then start_d is null)
+    const int8_t *mate_d8 = nullptr, *qname_d8 = nullptr; // mate / name-id differences in eight bits (then mate_d / qname_d are null)
+    const uint8_t *pair_d8 = nullptr; // the pair form: tlen, mate and name id in one byte (then tlen_s and the four above are null)
+    __host__ __device__ bool diff_form() const { return tlen_s != nullptr || pair_d8 != nullptr; } // start (and the rest) travel as differences
+    const unsigned long long *esc16_key = nullptr;
+    const int32_t *esc16_val = nullptr;
+    int64_t n_esc16 = 0;
+    int64_t esc_lo = 0, esc_hi = 0;   // set by the header build's workgroups: the escape entries of their own span of records
+    int32_t pk_shift = 12;            // set by the header build: records per span of its passes = 1 << pk_shift (a small table gets shorter spans: more workgroups)
+    int32_t lists = 0; // the qualities came as counts (+ positions): n_low, or tup_n_low through the table
+    const uint32_t *plane_in = nullptr;
+    const uint8_t *n_low = nullptr, *qlow_pos = nullptr;
+    int32_t qpos_wide = 0;
+    // the span sums from the packer (uz_types.h pk_sums: [(spans + 1) * UZ_PK_SUMS], exclusive): null -- the header build computes them itself
+    const unsigned long long *pk_sums = nullptr;
+};
+
 struct ReadsDev {
     bool live = false;
     int64_t n = 0;
@@ -200,18 +251,9 @@ struct ReadsDev {
     // sat in the chain of every chunk's read stage.  `built` marks its end; null: no build queued yet, the first use runs it
     // (UZ_BUILD_LAZY=1).
     hipEvent_t built = nullptr;
-    const void *col_ptrs[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    RecColumns cols; // the staged columns of an asynchronous upload, as its header build takes them (an adopted table keeps none of the caller's)
     void *build_scratch = nullptr;
-    const void *col_t[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // tup, tup_flag, tup_l_seq, tup_n_cigar, tup_mapq, tup_aux, tup_n_low, tup_umask
-    const void *col_t8[4] = {nullptr, nullptr, nullptr, nullptr}; // tup8, tup_hot, tup_esc, tup_esc_off (the one-byte index: col_t[0] is then where the 16-bit column is rebuilt)
-    int64_t col_ntesc = 0;
-    int32_t col_lists = 0;
-    int64_t col_ntup = 0;
-    const void *col_d[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // start_d, tlen_s, mate_d, qname_d, esc16_key, esc16_val, start_d8, mate_d8, qname_d8, pair_d8
-    int64_t col_nesc = 0;
-    const void *col_q[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // plane_in / n_low / qlow_pos / cigar_in / umask / cigar_staged / cigar_out of RecColumns, for the deferred header build
     int64_t n_cigar_staged = 0; // cigar_compact: words that travelled (checked by the header build)
-    int32_t col_qwide = 0;
     // a table that arrived with two-bit base rows (uz_reads_packed_view.seq2): the staged rows and the listed bases, expanded
     // into seq4 by the header build (uz_build_records); null afterwards / for four-bit tables
     const uint8_t *seq2_staged = nullptr;
@@ -220,11 +262,8 @@ struct ReadsDev {
     const uint8_t *exc_code = nullptr;
     int64_t n_exc = 0;
     // bases as lists (uz_types.h bl_*): the listed bases and the row units of the records that carry them (inside n_seq_units: their units
-    // lie behind the n_seq_units - n_bl_units that travelled as rows); bl_n / tup_n_bl / bl_pos / bl_code for the deferred header build
+    // lie behind the n_seq_units - n_bl_units that travelled as rows)
     int64_t n_bl = 0, n_bl_units = 0;
-    const void *col_pk = nullptr; // pk_sums of RecColumns, for the deferred header build
-    const void *col_b[4] = {nullptr, nullptr, nullptr, nullptr};
-    int32_t col_bwide = 0;
     // a table built from a batch joined on the device (uz_reads_from_walk with names): the kept list, the record that brought every name id first and
     // the read names of the records, all in `mirror` -- uz_reads_names answers ids from them
     const uz_kept_rec *kept_list = nullptr;
@@ -420,56 +459,6 @@ struct ProfScope {
 DevBlock uz_block_get(uz_ctx *c, size_t bytes);
 void uz_block_put(uz_ctx *c, DevBlock b);
 
-// the fixed-width columns of a table as DEVICE pointers (staged by an upload, or the caller's for an adopted table)
-struct RecColumns {
-    const int32_t *start = nullptr, *end = nullptr, *tlen = nullptr, *mate = nullptr;
-    const uint32_t *qname = nullptr;
-    const uint16_t *flag = nullptr, *l_seq = nullptr, *n_cigar = nullptr;
-    const uint8_t *mapq = nullptr, *aux = nullptr;
-    // qualities of the staged form: the plane itself (plane_in: the header build counts its bits into nlow) or its list
-    // form (n_low + qlow_pos: the header build copies the counts and writes the plane rows of the listed records); both
-    // null for an ASCII upload, whose plane and counts are built from the quality bytes (uz_build_qlow)
-    const uint32_t *cigar_staged = nullptr; // cigar_compact: the words that travelled (records with a simple code own none); the header build writes
-    uint32_t *cigar_out = nullptr;          // ... every record's words here (the device's CIGAR store).  Both null: `cigar_in` is the store itself
-    const uint32_t *cigar_in = nullptr; // the record's CIGAR words (at its cigar offset): `end` is derived from them when the column is left out (end == nullptr)
-    const uint16_t *umask = nullptr;    // staged units per record (null: every unit)
-    // dictionary form of the small columns (tup set: flag / l_seq / n_cigar / mapq / aux / n_low are read through the table)
-    const uint16_t *tup = nullptr, *tup_flag = nullptr, *tup_l_seq = nullptr, *tup_n_cigar = nullptr;
-    const uint8_t *tup_mapq = nullptr, *tup_aux = nullptr, *tup_n_low = nullptr;
-    const uint16_t *tup_umask = nullptr;
-    int64_t n_tup = 0; // entries of the dictionary (0: not known)
-    // the index in one byte (uz_types.h tup8): the header build first rebuilds the 16-bit column into tup_out (k_tup_expand) and reads it as `tup`
-    const uint8_t *tup8 = nullptr;
-    const uint16_t *tup_hot = nullptr, *tup_esc = nullptr;
-    const uint32_t *tup_esc_off = nullptr;
-    int64_t n_tup_esc = 0;
-    uint16_t *tup_out = nullptr;
-    // bases as lists (uz_types.h: bl_*): per record the number of listed bases (plain column or through the dictionary), their query indices and
-    // two-bit codes; seq4_out: the device's base rows (the header build writes the units of the listed records, behind the n_seq_link units that
-    // travelled as rows)
-    const uint8_t *bl_n = nullptr, *tup_n_bl = nullptr, *bl_pos = nullptr, *bl_code = nullptr;
-    int32_t bl_wide = 0;
-    int64_t n_seq_link = 0;
-    uint32_t *seq4_out = nullptr;
-    __host__ __device__ bool bl_form() const { return bl_n != nullptr || tup_n_bl != nullptr; }
-    // 16-bit difference form of start / tlen / mate / qname (start_d set: the plain four are null)
-    const int16_t *start_d = nullptr, *tlen_s = nullptr, *mate_d = nullptr, *qname_d = nullptr;
-    const uint8_t *start_d8 = nullptr; // the start differences in eight bits (then start_d is null)
-    const int8_t *mate_d8 = nullptr, *qname_d8 = nullptr; // mate / name-id differences in eight bits (then mate_d / qname_d are null)
-    const uint8_t *pair_d8 = nullptr; // the pair form: tlen, mate and name id in one byte (then tlen_s and the four above are null)
-    __host__ __device__ bool diff_form() const { return tlen_s != nullptr || pair_d8 != nullptr; } // start (and the rest) travel as differences
-    const unsigned long long *esc16_key = nullptr;
-    const int32_t *esc16_val = nullptr;
-    int64_t n_esc16 = 0;
-    int64_t esc_lo = 0, esc_hi = 0;   // set by the header build's workgroups: the escape entries of their own span of records
-    int32_t pk_shift = 12;            // set by the header build: records per span of its passes = 1 << pk_shift (a small table gets shorter spans: more workgroups)
-    int32_t lists = 0; // the qualities came as counts (+ positions): n_low, or tup_n_low through the table
-    const uint32_t *plane_in = nullptr;
-    const uint8_t *n_low = nullptr, *qlow_pos = nullptr;
-    int32_t qpos_wide = 0;
-    // the span sums from the packer (uz_types.h pk_sums: [(spans + 1) * UZ_PK_SUMS], exclusive): null -- the header build computes them itself
-    const unsigned long long *pk_sums = nullptr;
-};
 // Small transfers on the COMPUTE path go through a copy kernel, one side in pinned host memory, never through
 // hipMemcpyAsync: the DMA engine is in order, and a 2 KB result copy queued behind gigabytes of staged uploads would hold
 // the kernels of the current table back until every later table has landed (measured: copies and kernels did not
@@ -477,6 +466,8 @@ struct RecColumns {
 void uz_kcopy(uz_ctx *c, void *dst, const void *src, size_t bytes);
 // waits for an asynchronous upload and builds its headers, on the compute stream (no-op for a table that is ready)
 void uz_reads_make_ready(uz_ctx *c, ReadsDev &r);
+// hflags[0], the consistency flag of the header builds whose commands have run: read and cleared; set -> UzError (UZ_E_RANGE, what the code says)
+void uz_check_upload_flag(uz_ctx *c);
 // stage launchers
 // offsets (prefix sums of n_cigar / row units), RecA / RecB / fm and the coarse index, on stream `st`;
 // off_scratch: >= uz_rec_scratch_bytes(n) bytes of device memory
