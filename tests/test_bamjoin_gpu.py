@@ -186,3 +186,99 @@ def test_slots_grow_once(engine, workload):
         engine.free_reads(engine.reads_from_bam(dev))
     after = engine.walk_slot_stats()
     assert after["allocations"] == mid["allocations"], (before, mid, after)
+
+
+WALK_SLOTS = 4  # csrc/walk_book.hpp: WalkBook::SLOTS
+
+
+def test_fifth_open_batch_is_refused(engine, workload):
+    """four walked batches wait for their tables: the fifth walk is refused before anything of it is queued, and goes through once a slot is given back"""
+    from unfazed_amd.engine import UnfazedHipError
+    src = io_native.BamSource(workload["bam"], threads=3)
+    f = fetches_of(workload, 3, 4)
+
+    def walked():
+        return src.select_kept(f[0], f[1], f[2], 20, join=engine, release=engine.bam_walk_release)
+
+    held = [walked() for _ in range(WALK_SLOTS)]
+    try:
+        assert sorted(dev.token for dev in held) == list(range(WALK_SLOTS))
+        with pytest.raises(UnfazedHipError, match="four walked batches"):
+            walked()
+        engine.free_reads(engine.reads_from_bam(held.pop()))
+        held.append(walked())  # the slot that was given back
+        assert sorted(dev.token for dev in held) == list(range(WALK_SLOTS))
+    finally:
+        n = [dev.n for dev in held]
+        for dev in held:
+            engine.free_reads(engine.reads_from_bam(dev))
+    assert len(set(n)) == 1 and n[0] > 0
+
+
+def test_walk_id_checks(engine, workload):
+    """every entry point that takes a walk id refuses one out of range and one whose slot is free; uz_bam_walk_release alone takes a free slot"""
+    import ctypes as C
+    from types import SimpleNamespace
+    from unfazed_amd.engine import UnfazedHipError
+    src = io_native.BamSource(workload["bam"], threads=3)
+    f = fetches_of(workload, 3, 4)
+    dev = src.select_kept(f[0], f[1], f[2], 20, join=engine, release=engine.bam_walk_release)
+    freed = dev.token
+    engine.bam_walk_release(freed)
+    dev.token = None
+    L, h = engine.L, engine.h
+    desc, d_first, d_flags, d_walked = np.zeros(4, io_native.WALK_DESC), np.zeros(4, np.int64), np.zeros(4, np.int32), np.zeros(4, np.int64)
+    kept, coff, span, rid = np.zeros(1, io_native.KEPT_REC), np.zeros(2, np.int64), np.zeros(1, np.int32), C.c_int(-1)
+    calls = {
+        "uz_bam_walk_fetch": lambda k: engine._ck(L.uz_bam_walk_fetch(h, k, desc.ctypes.data, d_first.ctypes.data, d_flags.ctypes.data, d_walked.ctypes.data), "uz_bam_walk_fetch"),
+        "uz_bam_walk_flags": lambda k: engine.walk_flags(k, 1),
+        "uz_bam_join": lambda k: engine.join(k, 0, None, 0, False),
+        "uz_bam_join_needs": lambda k: engine.join_needs(k, 1),
+        "uz_bam_join_fetch": lambda k: engine.join_fetch(k, 1, 1),
+        "uz_reads_from_walk": lambda k: engine.reads_from_bam(SimpleNamespace(joined=True, token=k, min_base_qual=20)),
+        "uz_reads_from_bam": lambda k: engine._ck(L.uz_reads_from_bam(h, k, kept.ctypes.data, 0, None, 0, coff.ctypes.data, span.ctypes.data, 1, 0, 0, 0, 0, 20, None, 0,
+                                                                         C.addressof(rid)), "uz_reads_from_bam"),
+    }
+    for name, call in calls.items():
+        for k in (-1, WALK_SLOTS, freed):
+            with pytest.raises(UnfazedHipError, match=name + r" failed .*bad walk id"):
+                call(k)
+    for k in (-1, WALK_SLOTS):
+        with pytest.raises(UnfazedHipError, match="bad walk id"):
+            engine.bam_walk_release(k)
+    engine.bam_walk_release(freed)  # a free slot: legal
+    dev = src.select_kept(f[0], f[1], f[2], 20, join=engine, release=engine.bam_walk_release)
+    assert dev.n > 0
+    engine.free_reads(engine.reads_from_bam(dev))
+
+
+@pytest.mark.parametrize("slack,stride,spread", [(None, 3, 4), ("0", 5, 2)])
+def test_reserve_covers_every_buffer(hip_lib, workload, slack, stride, spread, monkeypatch):
+    """uz_walk_reserve after the first joined batch grows every buffer of every slot: three more batches of the same fetches, open at once on slots
+    only the reserve has touched, allocate nothing.  slack "0": mates only the index can answer (test_mates_only_the_index_can_answer) -- the joins
+    then use the answers' scratch and the need records as well."""
+    from unfazed_amd.engine import HipEngine
+    if slack is not None:
+        monkeypatch.setenv("UZ_STAGE_SLACK", slack)
+    f = fetches_of(workload, stride, spread)
+    eng = HipEngine(0)  # (the allocation counter is the context's)
+    try:
+        src = io_native.BamSource(workload["bam"], threads=3)
+
+        def walked():
+            return src.select_kept(f[0], f[1], f[2], 20, join=eng, release=eng.bam_walk_release)
+
+        dev = walked()
+        if slack is not None:
+            assert dev.io_stats["index_mate_lookups"] > 0 and dev.join_calls > 1
+        eng.free_reads(eng.reads_from_bam(dev))  # the first table of the context: the reserve
+        before = eng.walk_slot_stats()
+        held = [walked() for _ in range(3)]
+        assert sorted(d.token for d in held) == [0, 1, 2]
+        for d in held:
+            eng.free_reads(eng.reads_from_bam(d))
+        after = eng.walk_slot_stats()
+        assert after["allocations"] == before["allocations"] > 0, (before, after)
+        assert len(set(after["slot_room"])) == 1 and after["slot_room"][0] > 0, after
+    finally:
+        eng.close()

@@ -454,17 +454,14 @@ void uz_destroy(uz_ctx *c) {
         if (w.s0) (void)hipStreamDestroy(w.s0);
         if (w.s1) (void)hipStreamDestroy(w.s1);
         if (w.ev) (void)hipEventDestroy(w.ev);
-        w.comp.release(); w.out.release(); w.in_off.release(); w.out_off.release(); w.blk_coff.release(); w.span.release(); w.count.release(); w.first.release();
-        w.walked.release(); w.task.release(); w.reach.release(); w.fetch.release(); w.flags.release(); w.iflags.release(); w.blk_crc.release(); w.desc.release();
-        w.desc_kept.release(); w.n_direct.release(); w.tab_first.release(); w.kcount.release(); w.kfirst.release(); w.tab.release();
-        auto &J = w.join;
-        J.jtask.release(); J.keep.release(); J.mate.release(); J.target.release(); J.h_flags.release(); J.jt_tid.release(); J.reach_a.release(); J.reach_host.release();
-        J.cnt.release(); J.cspan.release(); J.look_tid.release(); J.reach_key.release(); J.totals.release(); J.hkey_in.release(); J.hkey.release(); J.fkey_in.release();
-        J.fkey.release(); J.ccount.release(); J.hval_in.release(); J.hperm.release(); J.inv.release(); J.fval_in.release(); J.fidx.release(); J.front0.release();
-        J.front1.release(); J.need.release(); J.first.release(); J.runid.release(); J.pos_of_k.release(); J.fo.release(); J.name_rec.release(); J.gidx.release();
-        J.tmp.release(); J.aux.release(); J.s5_in.release(); J.s5_out.release(); J.need_rec.release(); J.kept.release();
+#define UZ_X(T, name) w.name.release();
+        UZ_WALK_BUFS(UZ_X)
+#undef UZ_X
+#define UZ_X(T, name) w.join.name.release();
+        UZ_JOIN_BUFS(UZ_X)
+#undef UZ_X
     }
-    for (auto &b : c->walk_park) (void)hipFree(b.first);
+    for (void *b : c->book.take_parked()) (void)hipFree(b);
     for (FindSlot &a : c->find_alt) {
         a.cnt_c.release(); a.cnt_h.release(); a.win_range.release(); a.cand_off.release(); a.het_off.release();
         a.cand_idx.release(); a.het_idx.release(); a.cand_flags.release();
@@ -1251,6 +1248,156 @@ static int adopt_device(uz_ctx *c, const uz_reads_packed_view *v) {
     return k;
 }
 
+// ---- the device slots of walked batches (uz_ctx::WalkSlot; which are held: uz_ctx::book, csrc/walk_book.hpp)
+// the slot of a batch that is held: the look-up of every entry point that takes a walk id
+uz_ctx::WalkSlot &walk_slot(uz_ctx *c, int walk_id) {
+    UZ_REQUIRE(walk_id >= 0 && walk_id < uz_ctx::WALK_SLOTS && c->book.held(walk_id), UZ_E_ARG, "bad walk id");
+    return c->walk[walk_id];
+}
+
+// A claimed slot, given back unless it is handed on (dismiss).  drain: copies into the claimer's locals and kernels on the slot's buffers may
+// still be queued -- nothing of the slot is handed on, and the claimer's frame is not left, before both of its streams have drained.
+struct SlotClaim {
+    uz_ctx *c;
+    int k;
+    bool drain;
+    SlotClaim(uz_ctx *c_, int k_, bool drain_) : c(c_), k(k_), drain(drain_) {}
+    SlotClaim(const SlotClaim &) = delete;
+    SlotClaim &operator=(const SlotClaim &) = delete;
+    void dismiss() { k = -1; }
+    ~SlotClaim() {
+        if (k < 0) return;
+        if (drain) {
+            uz_ctx::WalkSlot &w = c->walk[k];
+            if (w.s0) (void)hipStreamSynchronize(w.s0);
+            if (w.s1) (void)hipStreamSynchronize(w.s1);
+            (void)hipGetLastError();
+        }
+        c->book.release(k);
+    }
+};
+
+// what uz_bam_walk is given, as its steps pass it on
+struct WalkPlan {
+    const uint8_t *comp; int64_t comp_bytes, n_blocks; const int64_t *in_off, *out_off, *blk_coff; const uint32_t *blk_crc;
+    int32_t n_tasks; const int32_t *task; int64_t n_spans; const int64_t *span; int64_t n_reach; const int32_t *reach; int64_t n_fetch; const int32_t *fetch;
+    int64_t out_bytes() const { return n_blocks ? out_off[n_blocks] : 0; }
+};
+
+void check_walk_plan(const WalkPlan &p) {
+    UZ_REQUIRE(p.n_blocks >= 0 && p.comp_bytes >= 0 && p.n_tasks >= 0 && p.n_spans >= 0 && p.n_reach >= 0 && p.n_fetch >= 0, UZ_E_ARG, "bad arguments");
+    UZ_REQUIRE(p.n_blocks == 0 || (p.comp && p.in_off && p.out_off && p.blk_coff), UZ_E_ARG, "null block table");
+    UZ_REQUIRE(p.n_tasks == 0 || (p.task && p.span && p.reach && p.fetch), UZ_E_ARG, "null walk plan");
+    const int64_t *in_off = p.in_off, *out_off = p.out_off;
+    for (int64_t k = 0; k < p.n_blocks; k++)
+        UZ_REQUIRE(in_off[k] >= 0 && in_off[k] < p.comp_bytes && (k == 0 || in_off[k] > in_off[k - 1]) && out_off[k] >= 0 && out_off[k] <= out_off[k + 1] &&
+                       out_off[k + 1] - out_off[k] <= 65536,
+                   UZ_E_ARG, "bad block table (blocks in the order they lie in `comp`; a BGZF block inflates to at most 64 KiB)");
+    // the plan is the kernel's only guard: every index it names must lie inside the arrays it names
+    for (int32_t t = 0; t < p.n_tasks; t++) {
+        const int32_t *tc = p.task + UZ_WALK_TASK_COLS * (size_t)t;
+        UZ_REQUIRE(tc[2] >= 0 && tc[2] <= tc[3] && tc[3] <= p.n_spans && tc[4] >= 0 && tc[4] <= tc[5] && tc[5] <= p.n_reach && tc[6] >= 0 && tc[6] <= tc[7] && tc[7] <= p.n_fetch,
+                   UZ_E_ARG, "walk plan: a task names spans, reach intervals or fetches outside the arrays");
+        // column 9: the stage task a walk task belongs to -- its sub-tasks adjacent and in order (the hash sets of k_tab_insert / k_desc_filter and
+        // the joins find a stage task's first sub-task by walking back over equal values)
+        UZ_REQUIRE(tc[9] >= 0 && (t == 0 ? true : (tc[9] == tc[9 - UZ_WALK_TASK_COLS] || tc[9] == tc[9 - UZ_WALK_TASK_COLS] + 1)), UZ_E_ARG,
+                   "walk plan: column 9 (the stage task of a walk task) must start at or above 0 and go up by at most one from task to task");
+    }
+    for (int64_t k = 0; k < p.n_spans; k++) {
+        const int64_t *sc = p.span + UZ_WALK_SPAN_COLS * (size_t)k;
+        UZ_REQUIRE(sc[4] >= 0 && sc[4] <= sc[5] && sc[5] <= p.n_blocks && (sc[4] == sc[5] || (sc[2] >= out_off[sc[4]] && sc[2] <= sc[3] && sc[3] == out_off[sc[5]])),
+                   UZ_E_ARG, "walk plan: a span names blocks or bytes outside the block table");
+    }
+}
+
+// one pass: every task writes its descriptors into a slice sized for the most records its bytes can hold (a record is at least 36 bytes)
+std::vector<int64_t> desc_slices(const WalkPlan &p) {
+    std::vector<int64_t> first((size_t)p.n_tasks + 1, 0);
+    for (int32_t t = 0; t < p.n_tasks; t++) {
+        const int32_t *tc = p.task + UZ_WALK_TASK_COLS * (size_t)t;
+        int64_t cap = 0;
+        for (int32_t sp = tc[2]; sp < tc[3]; sp++) cap += (p.span[UZ_WALK_SPAN_COLS * (size_t)sp + 3] - p.span[UZ_WALK_SPAN_COLS * (size_t)sp + 2]) / 36 + 1;
+        first[(size_t)t + 1] = first[(size_t)t] + cap;
+    }
+    return first;
+}
+
+// the blocks go up and are inflated in slices of ~8 k: the first block of every slice (+ the end)
+std::vector<int64_t> block_slices(int64_t n_blocks) {
+    std::vector<int64_t> cut{0};
+    for (int64_t b = 1; b <= n_blocks; b++)
+        if (b == n_blocks || (b - cut.back() >= 8192 && n_blocks - b >= 4096)) cut.push_back(b);
+    return cut;
+}
+
+// ... on two streams, as uz_bgzf_inflate_to_host sends them: slice i + 1 goes up while slice i is inflated; then every block against the CRC-32 of
+// its footer.  w.iflags: two words per slice, then the CRC's
+void queue_blocks(uz_ctx *c, uz_ctx::WalkSlot &w, const WalkPlan &p, const std::vector<int64_t> &cut) {
+    const int64_t n_blocks = p.n_blocks, comp_bytes = p.comp_bytes, out_bytes = p.out_bytes();
+    const size_t ns = cut.size() - 1;
+    hipStream_t st = w.s0;
+    UZ_WGROW(w, iflags, 2 * ns + 8); UZ_WGROW(w, blk_crc, (size_t)n_blocks + 1);
+    if (n_blocks == 0) return;
+    hipStream_t s2[2] = {w.s0, w.s1};
+    UZ_HIP(hipMemsetAsync(w.comp.p + comp_bytes, 0, 1024, st));
+    UZ_HIP(hipMemsetAsync(w.out.p + out_bytes, 0, uz_bam_walk_pad(), st));
+    UZ_HIP(hipMemcpyAsync(w.in_off.p, p.in_off, (size_t)n_blocks * 8, hipMemcpyHostToDevice, st));
+    UZ_HIP(hipMemcpyAsync(w.out_off.p, p.out_off, (size_t)(n_blocks + 1) * 8, hipMemcpyHostToDevice, st));
+    UZ_HIP(hipMemcpyAsync(w.blk_coff.p, p.blk_coff, (size_t)n_blocks * 8, hipMemcpyHostToDevice, st));
+    UZ_HIP(hipEventRecord(w.ev, st));
+    UZ_HIP(hipStreamWaitEvent(s2[1], w.ev, 0));
+    for (size_t i = 0; i < ns; i++) {
+        const int64_t b0 = cut[i], b1 = cut[i + 1];
+        const int64_t c0 = i == 0 ? 0 : std::max<int64_t>(p.in_off[b0] - 18, 0), c1 = i + 1 == ns ? comp_bytes : std::max<int64_t>(p.in_off[b1] - 18, c0);
+        UZ_HIP(hipMemcpyAsync(w.comp.p + c0, p.comp + c0, (size_t)(c1 - c0), hipMemcpyHostToDevice, s2[i & 1]));
+        uz_launch_inflate(c, s2[i & 1], b1 - b0, w.comp.p, (comp_bytes + 1024) & ~(int64_t)3, w.in_off.p + b0, w.out_off.p + b0, w.out.p, w.iflags.p + 2 * i);
+    }
+    if (ns > 1) { // the walk (first stream) reads what both streams inflated
+        UZ_HIP(hipEventRecord(w.ev, s2[1]));
+        UZ_HIP(hipStreamWaitEvent(st, w.ev, 0));
+    }
+    if (p.blk_crc) { // as htslib's reader (and the host's walk) holds it
+        UZ_HIP(hipMemcpyAsync(w.blk_crc.p, p.blk_crc, (size_t)n_blocks * 4, hipMemcpyHostToDevice, st));
+        uz_launch_crc32(c, st, n_blocks, w.out.p, w.out_off.p, w.blk_crc.p, w.iflags.p + 2 * ns);
+    }
+}
+
+// the plan up, the walk, and the count of the descriptors the host's joins can need at all (direct, or sharing a name hash with a direct record of
+// the task).  The two counts come down by copies on the slot's stream: they belong to the caller, whose frame outlives the stream's drain (SlotClaim);
+// *kept is valid after the caller's synchronise
+void queue_walk(uz_ctx *c, uz_ctx::WalkSlot &w, const WalkPlan &p, const std::vector<int64_t> &first, int64_t *tab_total_p, int64_t *kept) {
+    const int32_t n_tasks = p.n_tasks;
+    hipStream_t st = w.s0;
+    int64_t &tab_total = *tab_total_p;
+    w.n_desc_all = first.back();
+    UZ_WGROW(w, desc, (size_t)first.back() + 1);
+    UZ_HIP(hipMemcpyAsync(w.first.p, first.data(), ((size_t)n_tasks + 1) * 8, hipMemcpyHostToDevice, st));
+    UZ_HIP(hipMemcpyAsync(w.task.p, p.task, (size_t)n_tasks * UZ_WALK_TASK_COLS * 4, hipMemcpyHostToDevice, st));
+    if (p.n_spans) UZ_HIP(hipMemcpyAsync(w.span.p, p.span, (size_t)p.n_spans * UZ_WALK_SPAN_COLS * 8, hipMemcpyHostToDevice, st));
+    if (p.n_reach) UZ_HIP(hipMemcpyAsync(w.reach.p, p.reach, (size_t)p.n_reach * 8, hipMemcpyHostToDevice, st));
+    if (p.n_fetch) UZ_HIP(hipMemcpyAsync(w.fetch.p, p.fetch, (size_t)p.n_fetch * 12, hipMemcpyHostToDevice, st));
+    uz_launch_bam_walk(c, st, n_tasks, w.out.p, w.out_off.p, w.blk_coff.p, w.task.p, w.span.p, w.reach.p, w.fetch.p, w.count.p, w.first.p, w.walked.p,
+                       w.flags.p, w.desc.p, w.n_direct.p, w.tab_first.p);
+    UZ_HIP(hipMemcpyAsync(&tab_total, w.tab_first.p + n_tasks, 8, hipMemcpyDeviceToHost, st));
+    UZ_HIP(hipStreamSynchronize(st)); // (the pageable `first` has been read; the hash sets' size is known)
+    UZ_WGROW(w, tab, (size_t)tab_total + 1);
+    UZ_HIP(hipMemsetAsync(w.tab.p, 0, (size_t)tab_total * 8, st));
+    uz_launch_desc_filter(c, st, false, n_tasks, w.desc.p, w.first.p, w.count.p, w.task.p, w.tab_first.p, w.tab.p, w.kcount.p, w.kfirst.p, nullptr);
+    UZ_HIP(hipMemcpyAsync(kept, w.kfirst.p + n_tasks, 8, hipMemcpyDeviceToHost, st));
+}
+
+// what the inflate and the CRC check left in iflags (queue_blocks), as the call's error
+void throw_block_errors(const WalkPlan &p, const std::vector<int64_t> &cut, const std::vector<int32_t> &iflags) {
+    const size_t ns = cut.size() - 1;
+    for (size_t i = 0; i < ns; i++)
+        if (iflags[2 * i + 1])
+            throw UzError{UZ_E_RANGE, "BGZF block " + std::to_string(cut[i] + (iflags[2 * i + 1] >> 4)) + " of the batch: not a valid DEFLATE stream of the declared size (code " +
+                                          std::to_string(iflags[2 * i + 1] & 15) + ")"};
+    if (p.blk_crc && p.n_blocks && iflags[2 * ns])
+        throw UzError{UZ_E_RANGE, "CRC mismatch in BGZF block " + std::to_string(iflags[2 * ns] - 1) + " of the batch (file offset " +
+                                      std::to_string((long long)p.blk_coff[iflags[2 * ns] - 1]) + ")"};
+}
+
 // What uz_reads_from_walk and uz_reads_from_bam share.  The records of a walked batch (they lie inflated in its slot) are unpacked into the columns of
 // ONE block (uz_launch_bam_extract), the table adopts the columns where they lie (adopt_device) and keeps the block as its `mirror`; the slot is released.
 struct ExtractJob {
@@ -1269,7 +1416,8 @@ struct ExtractJob {
     bool keep_names = false;            // ... kept in the block, with the kept list and ...
     const uint32_t *name_rec = nullptr; // ... this column (device, [n_qnames]): uz_reads_names answers ids from them
 };
-static int extract_and_adopt(uz_ctx *c, uz_ctx::WalkSlot &w, const ExtractJob &j) {
+static int extract_and_adopt(uz_ctx *c, int walk_id, const ExtractJob &j) {
+    uz_ctx::WalkSlot &w = walk_slot(c, walk_id);
     const std::string who = std::string(j.who) + ": ";
     const size_t n = (size_t)j.n, nctg = (size_t)j.n_contigs;
     DevBlock blk;
@@ -1328,7 +1476,7 @@ static int extract_and_adopt(uz_ctx *c, uz_ctx::WalkSlot &w, const ExtractJob &j
         r.mirror = blk;
         if (j.keep_names) { r.kept_list = d_kept; r.name_rec = name_rec; r.names = d_names; r.names_bytes = j.names_bytes; }
     } catch (...) { uz_block_put(c, blk); throw; }
-    { std::lock_guard<std::mutex> lk(c->err_mu); w.busy = false; }
+    c->book.release(walk_id); // (on success only: a failed batch stays the caller's until its uz_bam_walk_release)
     return id;
 }
 
@@ -1959,172 +2107,61 @@ int uz_bam_walk(uz_ctx *c, const uint8_t *comp, int64_t comp_bytes, int64_t n_bl
                 const uint32_t *blk_crc, int32_t n_tasks, const int32_t *task, int64_t n_spans, const int64_t *span, int64_t n_reach, const int32_t *reach, int64_t n_fetch,
                 const int32_t *fetch, int *walk_id, int64_t *n_desc) {
     return guarded(c, [&] {
-        UZ_REQUIRE(walk_id && n_desc && n_blocks >= 0 && comp_bytes >= 0 && n_tasks >= 0 && n_spans >= 0 && n_reach >= 0 && n_fetch >= 0, UZ_E_ARG, "bad arguments");
-        UZ_REQUIRE(n_blocks == 0 || (comp && in_off && out_off && blk_coff), UZ_E_ARG, "null block table");
-        UZ_REQUIRE(n_tasks == 0 || (task && span && reach && fetch), UZ_E_ARG, "null walk plan");
-        const int64_t out_bytes = n_blocks ? out_off[n_blocks] : 0;
-        for (int64_t k = 0; k < n_blocks; k++)
-            UZ_REQUIRE(in_off[k] >= 0 && in_off[k] < comp_bytes && (k == 0 || in_off[k] > in_off[k - 1]) && out_off[k] >= 0 && out_off[k] <= out_off[k + 1] &&
-                           out_off[k + 1] - out_off[k] <= 65536,
-                       UZ_E_ARG, "bad block table (blocks in the order they lie in `comp`; a BGZF block inflates to at most 64 KiB)");
-        // the plan is the kernel's only guard: every index it names must lie inside the arrays it names
-        for (int32_t t = 0; t < n_tasks; t++) {
-            const int32_t *tc = task + UZ_WALK_TASK_COLS * (size_t)t;
-            UZ_REQUIRE(tc[2] >= 0 && tc[2] <= tc[3] && tc[3] <= n_spans && tc[4] >= 0 && tc[4] <= tc[5] && tc[5] <= n_reach && tc[6] >= 0 && tc[6] <= tc[7] && tc[7] <= n_fetch,
-                       UZ_E_ARG, "walk plan: a task names spans, reach intervals or fetches outside the arrays");
-            // column 9: the stage task a walk task belongs to -- its sub-tasks adjacent and in order (the hash sets of k_tab_insert / k_desc_filter and
-            // the joins find a stage task's first sub-task by walking back over equal values)
-            UZ_REQUIRE(tc[9] >= 0 && (t == 0 ? true : (tc[9] == tc[9 - UZ_WALK_TASK_COLS] || tc[9] == tc[9 - UZ_WALK_TASK_COLS] + 1)), UZ_E_ARG,
-                       "walk plan: column 9 (the stage task of a walk task) must start at or above 0 and go up by at most one from task to task");
-        }
-        for (int64_t k = 0; k < n_spans; k++) {
-            const int64_t *sc = span + UZ_WALK_SPAN_COLS * (size_t)k;
-            UZ_REQUIRE(sc[4] >= 0 && sc[4] <= sc[5] && sc[5] <= n_blocks && (sc[4] == sc[5] || (sc[2] >= out_off[sc[4]] && sc[2] <= sc[3] && sc[3] == out_off[sc[5]])),
-                       UZ_E_ARG, "walk plan: a span names blocks or bytes outside the block table");
-        }
+        UZ_REQUIRE(walk_id && n_desc, UZ_E_ARG, "bad arguments");
+        const WalkPlan p{comp, comp_bytes, n_blocks, in_off, out_off, blk_coff, blk_crc, n_tasks, task, n_spans, span, n_reach, reach, n_fetch, fetch};
+        check_walk_plan(p);
         UZ_HIP(hipSetDevice(c->device));
-        // one pass: every task writes its descriptors into a slice sized for the most records its bytes can hold (a record is at least 36 bytes)
-        std::vector<int64_t> first((size_t)n_tasks + 1, 0);
-        for (int32_t t = 0; t < n_tasks; t++) {
-            const int32_t *tc = task + UZ_WALK_TASK_COLS * (size_t)t;
-            int64_t cap = 0;
-            for (int32_t sp = tc[2]; sp < tc[3]; sp++) cap += (span[UZ_WALK_SPAN_COLS * (size_t)sp + 3] - span[UZ_WALK_SPAN_COLS * (size_t)sp + 2]) / 36 + 1;
-            first[(size_t)t + 1] = first[(size_t)t] + cap;
-        }
-        // The slot: a free one whose large buffers already hold this batch -- the smallest such (best fit) --, else one that has never been
-        // used, else the smallest (it is grown to the largest sizes ANY batch of this context has asked for: a slot grows once).  Nothing is
-        // freed while batches are in flight (hipFree waits for the whole device -- round 5: a process's second call, whose larger last chunk met
-        // another slot than in the first call, stood still for 0.9 s): an outgrown block is parked (DevBuf::ensure_parked).
-        const size_t need_out = (size_t)out_bytes + uz_bam_walk_pad(), need_comp = (size_t)comp_bytes + 1024, need_desc = (size_t)first.back() + 1;
-        int k = -1;
-        {
-            std::lock_guard<std::mutex> lk(c->err_mu);
-            int fit = -1, fresh = -1, small = -1, busy = 0;
-            for (int i = 0; i < uz_ctx::WALK_SLOTS; i++) {
-                const uz_ctx::WalkSlot &s = c->walk[i];
-                if (s.busy) { busy++; continue; }
-                if (s.out.cap >= need_out && s.comp.cap >= need_comp && s.desc.cap >= need_desc) { if (fit < 0 || s.out.cap < c->walk[fit].out.cap) fit = i; }
-                else if (s.out.cap == 0) { if (fresh < 0) fresh = i; }
-                else if (small < 0 || s.out.cap < c->walk[small].out.cap) small = i;
-            }
-            k = fit >= 0 ? fit : fresh >= 0 ? fresh : small;
-            if (k >= 0) c->walk[k].busy = true;
-            if (busy == 0 && k >= 0) { // nothing of an earlier batch is in flight: what was parked can go (only worth a device-wide wait when it is a lot)
-                std::lock_guard<std::mutex> lk2(c->walk_mu);
-                size_t parked = 0;
-                for (auto &b : c->walk_park) parked += b.second;
-                if (parked > ((size_t)24 << 30)) {
-                    for (auto &b : c->walk_park) (void)hipFree(b.first);
-                    c->walk_park.clear();
-                }
-            }
-        }
+        const std::vector<int64_t> first = desc_slices(p), cut = block_slices(n_blocks);
+        const size_t ns = cut.size() - 1;
+        std::vector<int32_t> iflags(2 * ns + 4, 0); // (what the slot's streams copy into is declared before the claim: it outlives their drain)
+        int64_t tab_total = 0, kept = 0;
+        // Nothing is freed while batches are in flight (hipFree waits for the whole device -- round 5: a process's second call, whose larger last
+        // chunk met another slot than in the first call, stood still for 0.9 s): an outgrown block is parked, and the book hands the parked blocks
+        // over only at a claim that finds no other batch in flight (WalkBook::claim).
+        const size_t need_out = (size_t)p.out_bytes() + uz_bam_walk_pad(), need_comp = (size_t)comp_bytes + 1024, need_desc = (size_t)first.back() + 1;
+        std::vector<void *> drained;
+        const int k = c->book.claim([&](int i) { return WalkBook::Caps{c->walk[i].out.cap, c->walk[i].comp.cap, c->walk[i].desc.cap}; }, need_out, need_comp, need_desc, drained);
+        for (void *b : drained) (void)hipFree(b);
         UZ_REQUIRE(k >= 0, UZ_E_STATE, "four walked batches are waiting for uz_reads_from_bam / uz_reads_from_walk / uz_bam_walk_release");
+        SlotClaim claim(c, k, true);
         uz_ctx::WalkSlot &w = c->walk[k];
-        try {
-            // streams of the slot's own: the blocks of the next batch go up and are inflated while this one is still walked (two calls may run at once)
-            if (!w.s0) {
-                UZ_HIP(hipStreamCreateWithFlags(&w.s0, hipStreamNonBlocking));
-                UZ_HIP(hipStreamCreateWithFlags(&w.s1, hipStreamNonBlocking));
-                UZ_HIP(hipEventCreateWithFlags(&w.ev, hipEventDisableTiming));
-            }
-            hipStream_t st = w.s0;
-            w.n_blocks = n_blocks; w.out_bytes = out_bytes; w.n_tasks = n_tasks; w.n_desc = 0; w.n_reach = n_reach;
-            w.max_host = n_tasks ? task[UZ_WALK_TASK_COLS * (size_t)(n_tasks - 1) + 9] : -1;
-            w.join.started = false; w.join.done = false; w.join.n_need = 0; w.join.n_all = 0; w.join.n_dev = 0; w.join.aux_bytes = 0; w.join.n_look = 0;
-            uz_walk_grow(c, w.comp, need_comp, 0); uz_walk_grow(c, w.out, need_out, 1);
-            uz_walk_grow(c, w.in_off, (size_t)n_blocks + 1, 2); uz_walk_grow(c, w.out_off, (size_t)n_blocks + 1, 3); uz_walk_grow(c, w.blk_coff, (size_t)n_blocks + 1, 4);
-            uz_walk_grow(c, w.task, (size_t)n_tasks * UZ_WALK_TASK_COLS + 1, 5); uz_walk_grow(c, w.span, (size_t)n_spans * UZ_WALK_SPAN_COLS + 1, 6);
-            uz_walk_grow(c, w.reach, (size_t)n_reach * 2 + 1, 7); uz_walk_grow(c, w.fetch, (size_t)n_fetch * 3 + 1, 8);
-            uz_walk_grow(c, w.count, (size_t)n_tasks + 1, 9); uz_walk_grow(c, w.first, (size_t)n_tasks + 2, 10); uz_walk_grow(c, w.walked, (size_t)n_tasks + 1, 11);
-            uz_walk_grow(c, w.flags, (size_t)n_tasks + 1, 12);
-            uz_walk_grow(c, w.n_direct, (size_t)n_tasks + 1, 13); uz_walk_grow(c, w.tab_first, (size_t)n_tasks + 2, 14); uz_walk_grow(c, w.kcount, (size_t)n_tasks + 1, 15);
-            uz_walk_grow(c, w.kfirst, (size_t)n_tasks + 2, 16);
-            // the blocks in slices of ~8 k on two streams, as uz_bgzf_inflate_to_host sends them: slice i + 1 goes up while slice i is inflated
-            std::vector<int64_t> cut{0};
-            for (int64_t b = 1; b <= n_blocks; b++)
-                if (b == n_blocks || (b - cut.back() >= 8192 && n_blocks - b >= 4096)) cut.push_back(b);
-            const size_t ns = cut.size() - 1;
-            uz_walk_grow(c, w.iflags, 2 * ns + 8, 17); uz_walk_grow(c, w.blk_crc, (size_t)n_blocks + 1, 18);
-            std::vector<int32_t> iflags(2 * ns + 4, 0);
-            if (n_blocks) {
-                hipStream_t s2[2] = {w.s0, w.s1};
-                UZ_HIP(hipMemsetAsync(w.comp.p + comp_bytes, 0, 1024, st));
-                UZ_HIP(hipMemsetAsync(w.out.p + out_bytes, 0, uz_bam_walk_pad(), st));
-                UZ_HIP(hipMemcpyAsync(w.in_off.p, in_off, (size_t)n_blocks * 8, hipMemcpyHostToDevice, st));
-                UZ_HIP(hipMemcpyAsync(w.out_off.p, out_off, (size_t)(n_blocks + 1) * 8, hipMemcpyHostToDevice, st));
-                UZ_HIP(hipMemcpyAsync(w.blk_coff.p, blk_coff, (size_t)n_blocks * 8, hipMemcpyHostToDevice, st));
-                UZ_HIP(hipEventRecord(w.ev, st));
-                UZ_HIP(hipStreamWaitEvent(s2[1], w.ev, 0));
-                for (size_t i = 0; i < ns; i++) {
-                    const int64_t b0 = cut[i], b1 = cut[i + 1];
-                    const int64_t c0 = i == 0 ? 0 : std::max<int64_t>(in_off[b0] - 18, 0), c1 = i + 1 == ns ? comp_bytes : std::max<int64_t>(in_off[b1] - 18, c0);
-                    UZ_HIP(hipMemcpyAsync(w.comp.p + c0, comp + c0, (size_t)(c1 - c0), hipMemcpyHostToDevice, s2[i & 1]));
-                    uz_launch_inflate(c, s2[i & 1], b1 - b0, w.comp.p, (comp_bytes + 1024) & ~(int64_t)3, w.in_off.p + b0, w.out_off.p + b0, w.out.p, w.iflags.p + 2 * i);
-                }
-                if (ns > 1) { // the walk (first stream) reads what both streams inflated
-                    UZ_HIP(hipEventRecord(w.ev, s2[1]));
-                    UZ_HIP(hipStreamWaitEvent(st, w.ev, 0));
-                }
-                if (blk_crc) { // every block against the CRC-32 of its footer, as htslib's reader (and the host's walk) holds it
-                    UZ_HIP(hipMemcpyAsync(w.blk_crc.p, blk_crc, (size_t)n_blocks * 4, hipMemcpyHostToDevice, st));
-                    uz_launch_crc32(c, st, n_blocks, w.out.p, w.out_off.p, w.blk_crc.p, w.iflags.p + 2 * ns);
-                }
-            }
-            int64_t tab_total = 0, kept = 0;
-            if (n_tasks) {
-                w.n_desc_all = first.back();
-                uz_walk_grow(c, w.desc, need_desc, 19);
-                UZ_HIP(hipMemcpyAsync(w.first.p, first.data(), ((size_t)n_tasks + 1) * 8, hipMemcpyHostToDevice, st));
-                UZ_HIP(hipMemcpyAsync(w.task.p, task, (size_t)n_tasks * UZ_WALK_TASK_COLS * 4, hipMemcpyHostToDevice, st));
-                if (n_spans) UZ_HIP(hipMemcpyAsync(w.span.p, span, (size_t)n_spans * UZ_WALK_SPAN_COLS * 8, hipMemcpyHostToDevice, st));
-                if (n_reach) UZ_HIP(hipMemcpyAsync(w.reach.p, reach, (size_t)n_reach * 8, hipMemcpyHostToDevice, st));
-                if (n_fetch) UZ_HIP(hipMemcpyAsync(w.fetch.p, fetch, (size_t)n_fetch * 12, hipMemcpyHostToDevice, st));
-                uz_launch_bam_walk(c, st, n_tasks, w.out.p, w.out_off.p, w.blk_coff.p, w.task.p, w.span.p, w.reach.p, w.fetch.p, w.count.p, w.first.p, w.walked.p,
-                                   w.flags.p, w.desc.p, w.n_direct.p, w.tab_first.p);
-                UZ_HIP(hipMemcpyAsync(&tab_total, w.tab_first.p + n_tasks, 8, hipMemcpyDeviceToHost, st));
-                UZ_HIP(hipStreamSynchronize(st)); // (the pageable `first` has been read; the hash sets' size is known)
-                // the descriptors the host's joins can need at all (direct, or sharing a name hash with a direct record of the task) are counted
-                uz_walk_grow(c, w.tab, (size_t)tab_total + 1, 20);
-                UZ_HIP(hipMemsetAsync(w.tab.p, 0, (size_t)tab_total * 8, st));
-                uz_launch_desc_filter(c, st, false, n_tasks, w.desc.p, w.first.p, w.count.p, w.task.p, w.tab_first.p, w.tab.p, w.kcount.p, w.kfirst.p, nullptr);
-                UZ_HIP(hipMemcpyAsync(&kept, w.kfirst.p + n_tasks, 8, hipMemcpyDeviceToHost, st));
-            }
-            if (n_blocks) UZ_HIP(hipMemcpyAsync(iflags.data(), w.iflags.p, (2 * ns + (blk_crc ? 1 : 0)) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            UZ_HIP(hipStreamSynchronize(st));
-            for (size_t i = 0; i < ns; i++)
-                if (iflags[2 * i + 1])
-                    throw UzError{UZ_E_RANGE, "BGZF block " + std::to_string(cut[i] + (iflags[2 * i + 1] >> 4)) + " of the batch: not a valid DEFLATE stream of the declared size (code " +
-                                                  std::to_string(iflags[2 * i + 1] & 15) + ")"};
-            if (blk_crc && n_blocks && iflags[2 * ns])
-                throw UzError{UZ_E_RANGE, "CRC mismatch in BGZF block " + std::to_string(iflags[2 * ns] - 1) + " of the batch (file offset " +
-                                              std::to_string((long long)blk_coff[iflags[2 * ns] - 1]) + ")"};
-            w.n_desc = kept;
-            *n_desc = kept;
-            *walk_id = k;
-        } catch (...) {
-            // (copies into this frame's locals and kernels on the slot's buffers may still be queued: nothing of the slot is handed on, and the frame
-            // is not left, before both of its streams have drained)
-            if (w.s0) (void)hipStreamSynchronize(w.s0);
-            if (w.s1) (void)hipStreamSynchronize(w.s1);
-            (void)hipGetLastError();
-            std::lock_guard<std::mutex> lk(c->err_mu);
-            w.busy = false;
-            throw;
+        // streams of the slot's own: the blocks of the next batch go up and are inflated while this one is still walked (two calls may run at once)
+        if (!w.s0) {
+            UZ_HIP(hipStreamCreateWithFlags(&w.s0, hipStreamNonBlocking));
+            UZ_HIP(hipStreamCreateWithFlags(&w.s1, hipStreamNonBlocking));
+            UZ_HIP(hipEventCreateWithFlags(&w.ev, hipEventDisableTiming));
         }
+        w.n_blocks = n_blocks; w.out_bytes = p.out_bytes(); w.n_tasks = n_tasks; w.n_desc = 0; w.n_reach = n_reach;
+        w.max_host = n_tasks ? task[UZ_WALK_TASK_COLS * (size_t)(n_tasks - 1) + 9] : -1;
+        w.join.started = false; w.join.done = false; w.join.n_need = 0; w.join.n_all = 0; w.join.n_dev = 0; w.join.aux_bytes = 0; w.join.n_look = 0;
+        const size_t nb = (size_t)n_blocks + 1, nt = (size_t)n_tasks + 1;
+        UZ_WGROW(w, comp, need_comp); UZ_WGROW(w, out, need_out);
+        UZ_WGROW(w, in_off, nb); UZ_WGROW(w, out_off, nb); UZ_WGROW(w, blk_coff, nb);
+        UZ_WGROW(w, task, (size_t)n_tasks * UZ_WALK_TASK_COLS + 1); UZ_WGROW(w, span, (size_t)n_spans * UZ_WALK_SPAN_COLS + 1);
+        UZ_WGROW(w, reach, (size_t)n_reach * 2 + 1); UZ_WGROW(w, fetch, (size_t)n_fetch * 3 + 1);
+        UZ_WGROW(w, count, nt); UZ_WGROW(w, first, nt + 1); UZ_WGROW(w, walked, nt); UZ_WGROW(w, flags, nt);
+        UZ_WGROW(w, n_direct, nt); UZ_WGROW(w, tab_first, nt + 1); UZ_WGROW(w, kcount, nt); UZ_WGROW(w, kfirst, nt + 1);
+        queue_blocks(c, w, p, cut);
+        if (n_tasks) queue_walk(c, w, p, first, &tab_total, &kept);
+        if (n_blocks) UZ_HIP(hipMemcpyAsync(iflags.data(), w.iflags.p, (2 * ns + (blk_crc ? 1 : 0)) * sizeof(int32_t), hipMemcpyDeviceToHost, w.s0));
+        UZ_HIP(hipStreamSynchronize(w.s0));
+        throw_block_errors(p, cut, iflags);
+        w.n_desc = kept;
+        *n_desc = kept;
+        *walk_id = k;
+        claim.dismiss();
     });
 }
 
 int uz_bam_walk_fetch(uz_ctx *c, int walk_id, uz_walk_desc *desc, int64_t *d_first, int32_t *d_flags, int64_t *d_walked) {
     return guarded(c, [&] {
-        UZ_REQUIRE(walk_id >= 0 && walk_id < uz_ctx::WALK_SLOTS && c->walk[walk_id].busy, UZ_E_ARG, "bad walk id");
-        uz_ctx::WalkSlot &w = c->walk[walk_id];
+        uz_ctx::WalkSlot &w = walk_slot(c, walk_id);
         UZ_REQUIRE(d_first && (w.n_desc == 0 || desc), UZ_E_ARG, "null output");
         UZ_HIP(hipSetDevice(c->device));
         hipStream_t st = w.s0;
         const int32_t nt = w.n_tasks;
         if (nt == 0) { d_first[0] = 0; return; }
-        uz_walk_grow(c, w.desc_kept, (size_t)w.n_desc + 1, 41);
+        UZ_WGROW(w, desc_kept, (size_t)w.n_desc + 1);
         uz_launch_desc_filter(c, st, true, nt, w.desc.p, w.first.p, w.count.p, w.task.p, w.tab_first.p, w.tab.p, w.kcount.p, w.kfirst.p, w.desc_kept.p);
         if (w.n_desc) UZ_HIP(hipMemcpyAsync(desc, w.desc_kept.p, (size_t)w.n_desc * sizeof(uz_walk_desc), hipMemcpyDeviceToHost, st));
         UZ_HIP(hipMemcpyAsync(d_first, w.kfirst.p, (size_t)(nt + 1) * 8, hipMemcpyDeviceToHost, st));
@@ -2136,17 +2173,15 @@ int uz_bam_walk_fetch(uz_ctx *c, int walk_id, uz_walk_desc *desc, int64_t *d_fir
 
 int uz_bam_walk_release(uz_ctx *c, int walk_id) {
     return guarded(c, [&] {
-        UZ_REQUIRE(walk_id >= 0 && walk_id < uz_ctx::WALK_SLOTS, UZ_E_ARG, "bad walk id");
-        std::lock_guard<std::mutex> lk(c->err_mu);
-        c->walk[walk_id].busy = false;
+        UZ_REQUIRE(walk_id >= 0 && walk_id < uz_ctx::WALK_SLOTS, UZ_E_ARG, "bad walk id"); // (a free slot may be released again)
+        c->book.release(walk_id);
     });
 }
 
 // ---- the batch-wide joins on the device (csrc/k_bamjoin.hip)
 int uz_bam_walk_flags(uz_ctx *c, int walk_id, int32_t *d_flags, int64_t *d_walked) {
     return guarded(c, [&] {
-        UZ_REQUIRE(walk_id >= 0 && walk_id < uz_ctx::WALK_SLOTS && c->walk[walk_id].busy, UZ_E_ARG, "bad walk id");
-        uz_ctx::WalkSlot &w = c->walk[walk_id];
+        uz_ctx::WalkSlot &w = walk_slot(c, walk_id);
         if (w.n_tasks == 0) return;
         if (d_flags) UZ_HIP(hipMemcpyAsync(d_flags, w.flags.p, (size_t)w.n_tasks * 4, hipMemcpyDeviceToHost, w.s0));
         if (d_walked) UZ_HIP(hipMemcpyAsync(d_walked, w.walked.p, (size_t)w.n_tasks * 8, hipMemcpyDeviceToHost, w.s0));
@@ -2157,9 +2192,8 @@ int uz_bam_walk_flags(uz_ctx *c, int walk_id, int32_t *d_flags, int64_t *d_walke
 int uz_bam_join(uz_ctx *c, int walk_id, int32_t n_host, const int32_t *h_flags, int32_t n_ref, int all_bases, const uz_walk_desc *xdesc, int64_t n_x, const uint8_t *xaux,
                 int64_t xaux_bytes, const int32_t *look_tid, int64_t n_look, const int32_t *need_jtask, int64_t *n_need, int64_t totals[8]) {
     return guarded(c, [&] {
-        UZ_REQUIRE(walk_id >= 0 && walk_id < uz_ctx::WALK_SLOTS && c->walk[walk_id].busy, UZ_E_ARG, "bad walk id");
+        uz_ctx::WalkSlot &w = walk_slot(c, walk_id);
         UZ_REQUIRE(n_need != nullptr, UZ_E_ARG, "null output");
-        uz_ctx::WalkSlot &w = c->walk[walk_id];
         UZ_REQUIRE(n_host > w.max_host, UZ_E_ARG, "uz_bam_join: the plan names more tasks of the stage (column 9) than n_host");
         for (int64_t k = 0; k < n_x; k++)
             UZ_REQUIRE((xdesc[k].task & UZ_WALK_TASK_JOIN) && (xdesc[k].src & UZ_WALK_SRC_AUX), UZ_E_ARG, "uz_bam_join: a descriptor of the host without its join task or outside the aux bytes");
@@ -2173,15 +2207,15 @@ int uz_bam_join(uz_ctx *c, int walk_id, int32_t n_host, const int32_t *h_flags, 
 
 int uz_bam_join_needs(uz_ctx *c, int walk_id, uz_need_rec *need) {
     return guarded(c, [&] {
-        UZ_REQUIRE(walk_id >= 0 && walk_id < uz_ctx::WALK_SLOTS && c->walk[walk_id].busy && need, UZ_E_ARG, "bad walk id");
-        uz_join_needs(c, c->walk[walk_id], need);
+        uz_ctx::WalkSlot &w = walk_slot(c, walk_id);
+        UZ_REQUIRE(need != nullptr, UZ_E_ARG, "bad walk id");
+        uz_join_needs(c, w, need);
     });
 }
 
 int uz_bam_join_fetch(uz_ctx *c, int walk_id, uint64_t *voff, uint32_t *qname, int32_t *mate, uint8_t *bases, uz_kept_rec *kept, int64_t *contig_off, int32_t *max_span) {
     return guarded(c, [&] {
-        UZ_REQUIRE(walk_id >= 0 && walk_id < uz_ctx::WALK_SLOTS && c->walk[walk_id].busy, UZ_E_ARG, "bad walk id");
-        uz_ctx::WalkSlot &w = c->walk[walk_id];
+        uz_ctx::WalkSlot &w = walk_slot(c, walk_id);
         uz_join_fetch(c, w, voff, qname, mate, bases, kept);
         if (contig_off) for (size_t k = 0; k < w.join.contig_off_h.size(); k++) contig_off[k] = w.join.contig_off_h[k];
         if (max_span) for (int32_t k = 0; k < w.join.n_ref; k++) max_span[k] = w.join.max_span_h[(size_t)k];
@@ -2195,33 +2229,15 @@ int uz_walk_reserve(uz_ctx *c, int n_slots) {
     return guarded(c, [&] {
         UZ_HIP(hipSetDevice(c->device));
         for (int i = 0; i < uz_ctx::WALK_SLOTS && i < n_slots; i++) {
+            if (!c->book.claim_slot(i)) continue;
+            SlotClaim claim(c, i, false); // (nobody takes the slot while it grows)
             uz_ctx::WalkSlot &w = c->walk[i];
-            {
-                std::lock_guard<std::mutex> lk(c->err_mu);
-                if (w.busy) continue;
-                w.busy = true; // (nobody takes it while it grows)
-            }
-            try {
-                auto hi = [&](int kind) { std::lock_guard<std::mutex> lk(c->walk_mu); return c->walk_hi[kind]; };
-                auto &J = w.join;
-#define UZ_RSV(buf, kind) do { const size_t h__ = hi(kind); if (h__) uz_walk_grow(c, buf, h__, kind); } while (0)
-                UZ_RSV(w.comp, 0); UZ_RSV(w.out, 1); UZ_RSV(w.in_off, 2); UZ_RSV(w.out_off, 3); UZ_RSV(w.blk_coff, 4); UZ_RSV(w.task, 5); UZ_RSV(w.span, 6); UZ_RSV(w.reach, 7);
-                UZ_RSV(w.fetch, 8); UZ_RSV(w.count, 9); UZ_RSV(w.first, 10); UZ_RSV(w.walked, 11); UZ_RSV(w.flags, 12); UZ_RSV(w.n_direct, 13); UZ_RSV(w.tab_first, 14);
-                UZ_RSV(w.kcount, 15); UZ_RSV(w.kfirst, 16); UZ_RSV(w.iflags, 17); UZ_RSV(w.blk_crc, 18); UZ_RSV(w.desc, 19); UZ_RSV(w.tab, 20);
-                UZ_RSV(J.tmp, 40); UZ_RSV(w.desc_kept, 41); UZ_RSV(J.jtask, 42); UZ_RSV(J.keep, 43); UZ_RSV(J.mate, 44); UZ_RSV(J.target, 45); UZ_RSV(J.hkey_in, 46);
-                UZ_RSV(J.hval_in, 47); UZ_RSV(J.hkey, 48); UZ_RSV(J.hperm, 49); UZ_RSV(J.inv, 50); UZ_RSV(J.front0, 51); UZ_RSV(J.front1, 52); UZ_RSV(J.need, 53);
-                UZ_RSV(J.cnt, 54); UZ_RSV(J.aux, 55); UZ_RSV(J.jt_tid, 56); UZ_RSV(J.reach_key, 57); UZ_RSV(J.reach_a, 58); UZ_RSV(J.reach_host, 59); UZ_RSV(J.h_flags, 60);
-                UZ_RSV(J.fkey_in, 63); UZ_RSV(J.fkey, 64); UZ_RSV(J.fval_in, 65); UZ_RSV(J.fidx, 66); UZ_RSV(J.first, 67); UZ_RSV(J.runid, 68); UZ_RSV(J.pos_of_k, 69);
-                UZ_RSV(J.fo, 70); UZ_RSV(J.gidx, 71); UZ_RSV(J.s5_in, 72); UZ_RSV(J.s5_out, 73); UZ_RSV(J.kept, 74); UZ_RSV(J.name_rec, 75); UZ_RSV(J.ccount, 76);
-                UZ_RSV(J.cspan, 77); UZ_RSV(J.totals, 78);
-#undef UZ_RSV
-            } catch (...) {
-                std::lock_guard<std::mutex> lk(c->err_mu);
-                w.busy = false;
-                throw;
-            }
-            std::lock_guard<std::mutex> lk(c->err_mu);
-            w.busy = false;
+#define UZ_X(T, name) if (const size_t h = c->book.note(WK_##name, 0)) UZ_WGROW(w, name, h);
+            UZ_WALK_BUFS(UZ_X)
+#undef UZ_X
+#define UZ_X(T, name) if (const size_t h = c->book.note(JK_##name, 0)) UZ_JGROW(w.join, name, h);
+            UZ_JOIN_BUFS(UZ_X)
+#undef UZ_X
         }
     });
 }
@@ -2229,10 +2245,8 @@ int uz_walk_reserve(uz_ctx *c, int n_slots) {
 int uz_walk_slot_stats(uz_ctx *c, int64_t out[8]) {
     return guarded(c, [&] {
         UZ_REQUIRE(out != nullptr, UZ_E_ARG, "null output");
-        std::lock_guard<std::mutex> lk(c->walk_mu);
-        size_t parked = 0;
-        for (auto &b : c->walk_park) parked += b.second;
-        out[0] = c->walk_allocs; out[1] = (int64_t)c->walk_park.size(); out[2] = (int64_t)parked; out[3] = 0;
+        c->book.stats(&out[0], &out[1], &out[2]);
+        out[3] = 0;
         for (int i = 0; i < uz_ctx::WALK_SLOTS && i < 4; i++) out[4 + i] = (int64_t)c->walk[i].out.cap;
     });
 }
@@ -2240,9 +2254,8 @@ int uz_walk_slot_stats(uz_ctx *c, int64_t out[8]) {
 // The table of a batch whose joins ran on the device: the kept list lies in the slot (uz_bam_join), the records are unpacked where they lie.
 int uz_reads_from_walk(uz_ctx *c, int walk_id, int32_t min_base_qual, int want_names, int *reads_id, int64_t totals[8]) {
     return guarded(c, [&] {
-        UZ_REQUIRE(walk_id >= 0 && walk_id < uz_ctx::WALK_SLOTS && c->walk[walk_id].busy && reads_id, UZ_E_ARG, "bad walk id");
-        uz_ctx::WalkSlot &w = c->walk[walk_id];
-        auto &J = w.join;
+        auto &J = walk_slot(c, walk_id).join;
+        UZ_REQUIRE(reads_id != nullptr, UZ_E_ARG, "bad walk id");
         UZ_REQUIRE(J.done, UZ_E_STATE, "uz_reads_from_walk: the joins of this batch are not finished (uz_bam_join until it needs nothing)");
         ExtractJob j;
         j.who = "uz_reads_from_walk";
@@ -2254,7 +2267,7 @@ int uz_reads_from_walk(uz_ctx *c, int walk_id, int32_t min_base_qual, int want_n
                    "uz_reads_from_walk: the batch does not fit the table's 32-bit offsets");
         if (totals) for (int k = 0; k < 8; k++) totals[k] = J.tot_h[k];
         j.names = j.keep_names = want_names != 0; j.name_rec = J.name_rec.p; // the names stay on the device
-        *reads_id = extract_and_adopt(c, w, j);
+        *reads_id = extract_and_adopt(c, walk_id, j);
     });
 }
 
@@ -2312,7 +2325,7 @@ int uz_reads_from_bam(uz_ctx *c, int walk_id, const uz_kept_rec *kept, int64_t n
                       const int32_t *max_span, int32_t n_contigs, int64_t n_cigar_total, int64_t n_row_units, int64_t n_seq_units, uint32_t n_qnames,
                       int32_t min_base_qual, uint8_t *names_out, int64_t names_bytes, int *reads_id) {
     return guarded(c, [&] {
-        UZ_REQUIRE(walk_id >= 0 && walk_id < uz_ctx::WALK_SLOTS && c->walk[walk_id].busy, UZ_E_ARG, "bad walk id");
+        (void)walk_slot(c, walk_id);
         UZ_REQUIRE(names_bytes >= 0 && (names_out == nullptr || names_bytes < ((int64_t)1 << 32)), UZ_E_ARG, "bad name store size");
         UZ_REQUIRE(reads_id && n >= 0 && n < (int64_t)0x7FFFFFF0 && (n == 0 || kept) && aux_bytes >= 0 && (aux_bytes == 0 || aux) && contig_off && max_span && n_contigs >= 0 &&
                        n_cigar_total >= 0 && n_cigar_total < ((int64_t)1 << 32) && n_row_units >= 0 && n_row_units < ((int64_t)1 << 32) && n_seq_units >= 0 && n_seq_units <= n_row_units,
@@ -2323,7 +2336,7 @@ int uz_reads_from_bam(uz_ctx *c, int walk_id, const uz_kept_rec *kept, int64_t n
         j.contig_off = contig_off; j.max_span = max_span; j.n_contigs = n_contigs; j.min_base_qual = min_base_qual;
         j.n = n; j.n_cigar_total = n_cigar_total; j.n_row_units = n_row_units; j.n_seq_units = n_seq_units; j.names_bytes = names_bytes; j.n_qnames = n_qnames;
         j.names = names_out != nullptr; j.names_out = names_out; // the names go back to the host, which keeps them
-        *reads_id = extract_and_adopt(c, c->walk[walk_id], j);
+        *reads_id = extract_and_adopt(c, walk_id, j);
     });
 }
 

@@ -412,14 +412,11 @@ __global__ __launch_bounds__(256) void k_name_gather(int64_t n_ids, const uint32
 
 inline unsigned grid_of(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + 255) / 256); }
 
-template <typename T>
-void grow(uz_ctx *c, DevBuf<T> &b, size_t n, int kind, size_t used = 0, hipStream_t st = nullptr) { uz_walk_grow(c, b, n, kind, used, st); }
-
 void sort_pairs(uz_ctx *c, uz_ctx::WalkSlot &w, hipStream_t st, const unsigned long long *kin, unsigned long long *kout, const uint32_t *vin, uint32_t *vout, int64_t n) {
     if (n <= 0) return;
     size_t bytes = 0;
     UZ_HIP(rocprim::radix_sort_pairs(nullptr, bytes, kin, kout, vin, vout, (size_t)n, 0u, 64u, st));
-    grow(c, w.join.tmp, bytes + 256, 40);
+    UZ_JGROW(w.join, tmp, bytes + 256);
     UZ_HIP(rocprim::radix_sort_pairs((void *)w.join.tmp.p, bytes, kin, kout, vin, vout, (size_t)n, 0u, 64u, st));
 }
 
@@ -456,21 +453,21 @@ void uz_join_run(uz_ctx *c, uz_ctx::WalkSlot &w, const JoinPlanHost &P, const uz
     // ---- room
     const size_t N = (size_t)n_new + 64;
     const size_t carry = first_call ? 0 : (size_t)n_old; // (what a grown buffer takes along: nothing is in them before the first call)
-    grow(c, w.desc_kept, N, 41, carry, st);
-    grow(c, J.jtask, N, 42, carry, st); grow(c, J.keep, N, 43, carry, st); grow(c, J.mate, N, 44, carry, st); grow(c, J.target, N, 45, carry, st);
-    grow(c, J.hkey_in, N, 46, carry, st); grow(c, J.hval_in, N, 47, carry, st);
-    grow(c, J.hkey, N, 48); grow(c, J.hperm, N, 49); grow(c, J.inv, N, 50);
-    grow(c, J.front0, N, 51, carry, st); grow(c, J.front1, N, 52, carry, st); grow(c, J.need, N, 53, carry, st);
-    grow(c, J.cnt, C_COUNT + 8, 54, first_call ? 0 : (size_t)C_COUNT, st);
-    grow(c, J.aux, (size_t)(J.aux_bytes + xaux_bytes) + 1024, 55, (size_t)J.aux_bytes, st);
-    grow(c, J.jt_tid, (size_t)(J.n_host + n_look) + 64, 56, first_call ? 0 : (size_t)(J.n_host + J.n_look), st);
+    UZ_WGROW(w, desc_kept, N, carry, st);
+    UZ_JGROW(J, jtask, N, carry, st); UZ_JGROW(J, keep, N, carry, st); UZ_JGROW(J, mate, N, carry, st); UZ_JGROW(J, target, N, carry, st);
+    UZ_JGROW(J, hkey_in, N, carry, st); UZ_JGROW(J, hval_in, N, carry, st);
+    UZ_JGROW(J, hkey, N); UZ_JGROW(J, hperm, N); UZ_JGROW(J, inv, N);
+    UZ_JGROW(J, front0, N, carry, st); UZ_JGROW(J, front1, N, carry, st); UZ_JGROW(J, need, N, carry, st);
+    UZ_JGROW(J, cnt, C_COUNT + 8, first_call ? 0 : (size_t)C_COUNT, st);
+    UZ_JGROW(J, aux, (size_t)(J.aux_bytes + xaux_bytes) + 1024, (size_t)J.aux_bytes, st);
+    UZ_JGROW(J, jt_tid, (size_t)(J.n_host + n_look) + 64, first_call ? 0 : (size_t)(J.n_host + J.n_look), st);
     if (first_call) {
         int64_t nr = 0; // reach intervals of the plan: the last walk task's column 5
         // (the plan's arrays were checked by uz_bam_walk; their sizes are the slot's)
         nr = (int64_t)w.n_reach;
         n_reach = nr;
-        grow(c, J.reach_key, (size_t)nr + 64, 57); grow(c, J.reach_a, (size_t)nr + 64, 58); grow(c, J.reach_host, (size_t)nr + 64, 59);
-        grow(c, J.h_flags, (size_t)J.n_host + 64, 60);
+        UZ_JGROW(J, reach_key, (size_t)nr + 64); UZ_JGROW(J, reach_a, (size_t)nr + 64); UZ_JGROW(J, reach_host, (size_t)nr + 64);
+        UZ_JGROW(J, h_flags, (size_t)J.n_host + 64);
         UZ_HIP(hipMemsetAsync(J.cnt.p, 0, (C_COUNT + 8) * sizeof(int32_t), st));
         if (J.n_host) UZ_HIP(hipMemcpyAsync(J.h_flags.p, P.h_flags, (size_t)J.n_host * 4, hipMemcpyHostToDevice, st));
         // the filtered descriptors (uz_bam_walk counted them): filled here, in walk-task order
@@ -495,7 +492,7 @@ void uz_join_run(uz_ctx *c, uz_ctx::WalkSlot &w, const JoinPlanHost &P, const uz
     }
     if (!first_call && J.n_need) { // the answers: the askers are this round's frontier
         DevBuf<int32_t> &ans = J.look_tid; // (scratch of the right type)
-        grow(c, ans, (size_t)J.n_need + 64, 61);
+        UZ_JGROW(J, look_tid, (size_t)J.n_need + 64);
         UZ_HIP(hipMemcpyAsync(ans.p, need_jtask, (size_t)J.n_need * 4, hipMemcpyHostToDevice, st));
         const int cur = J.round % 3;
         hipLaunchKernelGGL(k_set_targets, dim3(grid_of(J.n_need)), dim3(256), 0, st, J.n_need, (const uint32_t *)J.need.p, (const int32_t *)ans.p, a.n_jt, J.target.p,
@@ -519,17 +516,17 @@ void uz_join_run(uz_ctx *c, uz_ctx::WalkSlot &w, const JoinPlanHost &P, const uz
     }
     J.n_need = cnt[C_NEED];
     if (J.n_need) { // the host's turn (uz_join_needs -> uz_stage_lookup)
-        grow(c, J.need_rec, (size_t)J.n_need + 64, 62);
+        UZ_JGROW(J, need_rec, (size_t)J.n_need + 64);
         hipLaunchKernelGGL(k_need_recs, dim3(grid_of(J.n_need)), dim3(256), 0, st, J.n_need, (const uint32_t *)J.need.p, (const uz_walk_desc *)w.desc_kept.p, J.need_rec.p);
         return;
     }
     // ---- the kept records, their order, ids and offsets
     const int64_t n = n_new;
-    grow(c, J.fkey_in, N, 63); grow(c, J.fkey, N, 64); grow(c, J.fval_in, N, 65); grow(c, J.fidx, N, 66);
-    grow(c, J.first, N, 67); grow(c, J.runid, N, 68); grow(c, J.pos_of_k, N, 69); grow(c, J.fo, N, 70); grow(c, J.gidx, N, 71);
-    grow(c, J.s5_in, N * sizeof(S5), 72); grow(c, J.s5_out, N * sizeof(S5), 73);
-    grow(c, J.kept, N, 74); grow(c, J.name_rec, N, 75);
-    grow(c, J.ccount, (size_t)J.n_ref + 64, 76); grow(c, J.cspan, (size_t)J.n_ref + 64, 77); grow(c, J.totals, 64, 78);
+    UZ_JGROW(J, fkey_in, N); UZ_JGROW(J, fkey, N); UZ_JGROW(J, fval_in, N); UZ_JGROW(J, fidx, N);
+    UZ_JGROW(J, first, N); UZ_JGROW(J, runid, N); UZ_JGROW(J, pos_of_k, N); UZ_JGROW(J, fo, N); UZ_JGROW(J, gidx, N);
+    UZ_JGROW(J, s5_in, N * sizeof(S5)); UZ_JGROW(J, s5_out, N * sizeof(S5));
+    UZ_JGROW(J, kept, N); UZ_JGROW(J, name_rec, N);
+    UZ_JGROW(J, ccount, (size_t)J.n_ref + 64); UZ_JGROW(J, cspan, (size_t)J.n_ref + 64); UZ_JGROW(J, totals, 64);
     FinalArgs f;
     f.D = w.desc_kept.p; f.n = n; f.jtask = J.jtask.p; f.keep = J.keep.p; f.mate = J.mate.p; f.jt_tid = J.jt_tid.p;
     f.hkey = J.hkey.p; f.hperm = J.hperm.p; f.inv = J.inv.p; f.fkey_in = J.fkey_in.p; f.fval_in = J.fval_in.p; f.fkey = J.fkey.p; f.fidx = J.fidx.p;
@@ -542,13 +539,13 @@ void uz_join_run(uz_ctx *c, uz_ctx::WalkSlot &w, const JoinPlanHost &P, const uz
         hipLaunchKernelGGL(k_final_keys, dim3(grid_of(n)), dim3(256), 0, st, f);
         sort_pairs(c, w, st, J.fkey_in.p, J.fkey.p, J.fval_in.p, J.fidx.p, n);
         hipLaunchKernelGGL(k_final_first, dim3(grid_of(n)), dim3(256), 0, st, f);
-        uz_scan_u32(c, st, J.first.p, J.runid.p, n, J.tmp);
+        uz_scan_u32(c, st, J.first.p, J.runid.p, n, J);
         hipLaunchKernelGGL(k_final_gidx, dim3(grid_of(n)), dim3(256), 0, st, f);
         hipLaunchKernelGGL(k_final_names, dim3(grid_of(n)), dim3(256), 0, st, f);
         size_t bytes = 0;
         const S5 zero = {{0u, 0u, 0u, 0u, 0u}};
         UZ_HIP(rocprim::exclusive_scan(nullptr, bytes, f.s5_in, reinterpret_cast<S5 *>(J.s5_out.p), zero, (size_t)n, S5Plus(), st));
-        grow(c, J.tmp, bytes + 256, 40);
+        UZ_JGROW(J, tmp, bytes + 256);
         UZ_HIP(rocprim::exclusive_scan((void *)J.tmp.p, bytes, f.s5_in, reinterpret_cast<S5 *>(J.s5_out.p), zero, (size_t)n, S5Plus(), st));
         hipLaunchKernelGGL(k_final_check, dim3(grid_of(n)), dim3(256), 0, st, f);
         hipLaunchKernelGGL(k_final_out, dim3(grid_of(n)), dim3(256), 0, st, f);
@@ -602,12 +599,12 @@ void uz_join_fetch(uz_ctx *c, uz_ctx::WalkSlot &w, uint64_t *voff, uint32_t *qna
         UZ_HIP(hipStreamSynchronize(st));
 }
 
-void uz_scan_u32(uz_ctx *c, hipStream_t st, const uint32_t *in, uint32_t *out, int64_t n, DevBuf<uint8_t> &tmp) {
+void uz_scan_u32(uz_ctx *c, hipStream_t st, const uint32_t *in, uint32_t *out, int64_t n, uz_ctx::WalkSlot::Join &J) {
     if (n <= 0) return;
     size_t bytes = 0;
     UZ_HIP(rocprim::exclusive_scan(nullptr, bytes, in, out, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
-    uz_walk_grow(c, tmp, bytes + 256, 40);
-    UZ_HIP(rocprim::exclusive_scan((void *)tmp.p, bytes, in, out, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
+    UZ_JGROW(J, tmp, bytes + 256);
+    UZ_HIP(rocprim::exclusive_scan((void *)J.tmp.p, bytes, in, out, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
 }
 
 void uz_launch_name_lens(uz_ctx *c, hipStream_t st, int64_t n_ids, const uint32_t *ids, const uint32_t *name_rec, const uz_kept_rec *kept, int64_t n_recs, int64_t names_bytes,

@@ -11,6 +11,7 @@
 
 #include "unfazed_hip.h"
 #include "uz_bamwalk.h"
+#include "walk_book.hpp"
 
 struct UzError {
     int code;
@@ -48,20 +49,20 @@ struct DevBuf {
         cap = 0;
     }
     // The same for buffers that grow while OTHER work is running on the device (the slots of walked batches: uz_bam_walk on a decoder's thread,
-    // beside the read stage of another chunk): hipFree waits for the whole device, so the block that was outgrown is parked, not freed (the
-    // context frees the parked blocks when it is destroyed, or at a moment no walked batch is in flight), and the new one is sized for the largest
-    // request any buffer of this kind has seen (*hi: a slot that grows once then fits every batch the process has staged).
-    // used > 0: the first `used` elements are carried over (on stream st).
-    void ensure_parked(size_t n, size_t *hi, std::vector<std::pair<void *, size_t>> &park, size_t used = 0, hipStream_t st = nullptr) {
-        if (hi && n > *hi) *hi = n;
-        if (n <= cap) return;
-        const size_t base = hi ? *hi : n, want = base + base / 4 + 64;
+    // beside the read stage of another chunk): hipFree waits for the whole device, so the block that was outgrown is not freed but handed back in
+    // *old for the caller to park (uz_walk_grow), and the new one is sized for the largest request any buffer of this kind has seen (hi >= n: a
+    // slot that grows once then fits every batch the process has staged).  used > 0: the first `used` elements are carried over (on stream st).
+    // -> false: it fitted, nothing was allocated.
+    bool ensure_parked(size_t n, size_t hi, std::pair<void *, size_t> *old, size_t used = 0, hipStream_t st = nullptr) {
+        if (n <= cap) return false;
+        const size_t want = hi + hi / 4 + 64;
         T *q = nullptr;
         UZ_HIP(hipMalloc((void **)&q, want * sizeof(T)));
         if (p && used) UZ_HIP(hipMemcpyAsync(q, p, used * sizeof(T), hipMemcpyDeviceToDevice, st));
-        if (p) park.push_back({(void *)p, cap * sizeof(T)});
+        *old = {(void *)p, cap * sizeof(T)};
         p = q;
         cap = want;
+        return true;
     }
 };
 
@@ -370,15 +371,9 @@ struct uz_ctx {
 
     // the record walk on the device (k_bamwalk.hip, uz_bam_walk): a batch's inflated blocks stay in HBM from the walk until the batch's table has
     // been packed from them (uz_reads_from_bam); four batches can be in flight (a feed pipeline walks up to three chunks ahead of the read stage)
-    struct WalkSlot {
-        bool busy = false;
-        DevBuf<uint8_t> comp, out;
-        DevBuf<int64_t> in_off, out_off, blk_coff, span, count, first, walked;
-        DevBuf<int32_t> task, reach, fetch, flags, iflags;
-        DevBuf<uint32_t> blk_crc;
-        DevBuf<uz_walk_desc> desc, desc_kept;
-        DevBuf<int64_t> n_direct, tab_first, kcount, kfirst;
-        DevBuf<unsigned long long> tab;
+    struct WalkSlot { // (held or free: uz_ctx::book)
+#define UZ_X(T, name) DevBuf<T> name;
+        UZ_WALK_BUFS(UZ_X) // walk_book.hpp: the one table of the slot's buffers
         int64_t n_blocks = 0, out_bytes = 0, n_desc = 0, n_desc_all = 0, n_reach = 0;
         int32_t n_tasks = 0, max_host = -1; // (max_host: the last walk task's stage task, column 9 of the plan)
         hipStream_t s0 = nullptr, s1 = nullptr; // the slot's own streams (blocks up + inflate in slices on both, the walk on the first)
@@ -390,26 +385,16 @@ struct uz_ctx {
             int32_t n_host = 0, n_look = 0, n_ref = 0, round = 0;
             int64_t n_need = 0;
             bool filled = false, started = false, done = false, all_bases = false;
-            DevBuf<int32_t> jtask, keep, mate, target, h_flags, jt_tid, reach_a, reach_host, cnt, cspan, look_tid;
-            DevBuf<int64_t> reach_key, totals;
-            DevBuf<unsigned long long> hkey_in, hkey, fkey_in, fkey, ccount;
-            DevBuf<uint32_t> hval_in, hperm, inv, fval_in, fidx, front0, front1, need, first, runid, pos_of_k, fo, name_rec;
-            DevBuf<int32_t> gidx;
-            DevBuf<uint8_t> tmp, aux, s5_in, s5_out;
-            DevBuf<uz_need_rec> need_rec;
-            DevBuf<uz_kept_rec> kept;
+            UZ_JOIN_BUFS(UZ_X)
+#undef UZ_X
             int64_t tot_h[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // the totals of the finished join (k_bamjoin.hip: JT_*)
             std::vector<int64_t> contig_off_h;
             std::vector<int32_t> max_span_h;
         } join;
     };
-    static constexpr int WALK_SLOTS = 4;
+    static constexpr int WALK_SLOTS = WalkBook::SLOTS;
     WalkSlot walk[WALK_SLOTS];
-    // growth of the slots' buffers (DevBuf::ensure_parked): the largest request every kind of buffer has seen, and the blocks that were outgrown
-    size_t walk_hi[96] = {0};
-    std::vector<std::pair<void *, size_t>> walk_park;
-    int64_t walk_allocs = 0; // device allocations the slots have made (uz_walk_slot_stats: a process whose batches stopped growing makes none)
-    std::mutex walk_mu;      // guards the three above (walks and joins of different slots run on different decoder threads)
+    WalkBook book; // which slots are held, the largest request every kind of buffer has seen, the blocks that were outgrown (its own lock)
 
     // uz_reads_names: ids / lengths / offsets / bytes on the device and one page-locked staging block, kept from call to call
     DevBuf<uint32_t> nm_ids, nm_len, nm_off;
@@ -430,17 +415,16 @@ struct uz_ctx {
     std::vector<hipEvent_t> event_pool;
 };
 
-// a buffer of a walk slot grown without a hipFree (DevBuf::ensure_parked); kind: which of uz_ctx::walk_hi remembers the largest request
+// A buffer of a walk slot grown without a hipFree (DevBuf::ensure_parked), to the largest request its kind has seen.  A grow site names the
+// buffer once -- UZ_WGROW(w, comp, n), UZ_JGROW(J, jtask, N, carry, st) -- and the kind follows from the name (`c`: the context, in scope).
 template <typename T>
-inline void uz_walk_grow(uz_ctx *c, DevBuf<T> &b, size_t n, int kind, size_t used = 0, hipStream_t st = nullptr) {
-    if (n <= b.cap) {
-        if (n > c->walk_hi[kind]) { std::lock_guard<std::mutex> lk(c->walk_mu); if (n > c->walk_hi[kind]) c->walk_hi[kind] = n; }
-        return;
-    }
-    std::lock_guard<std::mutex> lk(c->walk_mu);
-    b.ensure_parked(n, &c->walk_hi[kind], c->walk_park, used, st);
-    c->walk_allocs++;
+inline void uz_walk_grow(uz_ctx *c, DevBuf<T> &b, WalkKind kind, size_t n, size_t used = 0, hipStream_t st = nullptr) {
+    const size_t hi = c->book.note(kind, n);
+    std::pair<void *, size_t> old;
+    if (b.ensure_parked(n, hi, &old, used, st)) c->book.grew(old.first, old.second);
 }
+#define UZ_WGROW(w, name, ...) uz_walk_grow(c, (w).name, WK_##name, __VA_ARGS__)
+#define UZ_JGROW(J, name, ...) uz_walk_grow(c, (J).name, JK_##name, __VA_ARGS__)
 
 // profiling helpers (abi.hip)
 void uz_prof_begin(uz_ctx *c, int kernel, hipEvent_t *a, hipEvent_t *b);
@@ -526,7 +510,7 @@ void uz_launch_name_lens(uz_ctx *c, hipStream_t st, int64_t n_ids, const uint32_
                          uint32_t *len);
 void uz_launch_name_gather(uz_ctx *c, hipStream_t st, int64_t n_ids, const uint32_t *ids, const uint32_t *name_rec, const uz_kept_rec *kept, const uint8_t *names,
                            const uint32_t *len, const uint32_t *off, uint8_t *out);
-void uz_scan_u32(uz_ctx *c, hipStream_t st, const uint32_t *in, uint32_t *out, int64_t n, DevBuf<uint8_t> &tmp); // exclusive sum
+void uz_scan_u32(uz_ctx *c, hipStream_t st, const uint32_t *in, uint32_t *out, int64_t n, uz_ctx::WalkSlot::Join &J); // exclusive sum (scratch: J.tmp)
 void uz_launch_bam_extract(uz_ctx *c, hipStream_t st, int64_t n, const uint8_t *buf, int64_t buf_bytes, const uint8_t *aux, int64_t aux_bytes, const uz_kept_rec *kept,
                            int thr, int32_t *start, int32_t *tlen, int32_t *mate, uint32_t *qname, uint16_t *flag, uint16_t *l_seq, uint16_t *n_cigar, uint8_t *mapq,
                            uint8_t *aux_col, uint32_t *cigar, uint8_t *seq4, uint32_t *plane, int32_t *err, uint8_t *names, int64_t n_cigar_total, int64_t n_row_units,

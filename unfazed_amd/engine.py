@@ -135,6 +135,8 @@ class HipEngine:
         self._params = None
         import threading
         self._inflate_lock = threading.Lock()
+        self._walked = 0  # tables built from joined batches (reads_from_bam, from whichever thread): the slots are reserved after the 1st, 2nd and 4th
+        self._walked_lock = threading.Lock()
         # walked batches on the device at once, each on its slot's own streams.  Round 5 (the host's joins the bound): two measured 10 % slower than
         # one; with the joins on the device the device's chain is the bound and a batch's walk -- a latency-bound kernel of ~1 900 wavefronts -- leaves
         # the chip to the next batch's inflate: 1 / 2 / 3 at once = 117 / 130 / 128 k DNMs/s in bench.py's feed pass
@@ -507,8 +509,10 @@ class HipEngine:
             kb.token = None
             # a batch is through and its sizes are known: the other slots a pipeline will use grow to them now, not inside a later batch's walk
             # (a no-op once they have)
-            self._walked = getattr(self, "_walked", 0) + 1
-            if self._walked in (1, 2, 4):
+            with self._walked_lock:
+                self._walked += 1
+                walked = self._walked
+            if walked in (1, 2, 4):
                 self._ck(self.L.uz_walk_reserve(self.h, 4), "uz_walk_reserve")
             if names:
                 kb.qnames = io_native.DeviceNames(self, rid.value, int(kb.n_qnames))
