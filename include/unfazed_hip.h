@@ -46,7 +46,8 @@ extern "C" {
 #define UZ_K_SIZING 4      /* fetch-range sizing pass */
 #define UZ_K_CNV 5         /* K6 allele-balance count + decision */
 #define UZ_K_FAMILY_PACK 6 /* k_family_gt_pack (+ the wide-depth gather) of uz_families_from_samples */
-#define UZ_K_COUNT 7
+#define UZ_K_CNV_DENSE 7   /* dense site lists of K6: scan of the 2n counts + k_cnv_dense */
+#define UZ_K_COUNT 8
 
 typedef struct uz_ctx uz_ctx;
 
@@ -210,6 +211,15 @@ int uz_site_classes(uz_ctx *ctx, int fam_id, uint8_t *cls_out /* [n_sites] */);
 int uz_find(uz_ctx *ctx, int fam_id, const uz_dnms_view *dnms, int mode,
             int64_t *cand_off /* [n+1] */, int64_t *het_off /* [n+1] */);
 int uz_find_fetch(uz_ctx *ctx, int32_t *cand_idx, uint8_t *cand_flags, int32_t *het_idx);
+/* Cohort form: the window emit for the DNMs of many kids -- each group with its own trio columns -- in ONE launch sequence instead of one
+ * uz_find per kid (the per-family loop of find, informative_site_finder.py:213, :558-568).  `groups` as in uz_phase_cohort, but only fam_id,
+ * dnm_first and dnm_count count (reads_id and cutoff are ignored); `dnms` holds all groups' DNMs.  The groups must cover [0, dnms->n) exactly
+ * once, in any order; empty groups are allowed and one family may serve several groups.  UZ_E_ARG: a gap, an overlap, a group outside the
+ * batch, families of different sites tables.  Families whose classes are stale (for UZ_FIND_WHOLE_REGION: or lack the DEL / DUP codes) are
+ * classified in one launch first.  Every mode of uz_find; the offsets and, through uz_find_fetch, the lists are those of one uz_find per
+ * group laid end to end in DNM order.  The lists are kept under no key: a later uz_phase over the same DNMs computes its own. */
+int uz_find_cohort(uz_ctx *ctx, const uz_cohort_group *groups, int32_t n_groups, const uz_dnms_view *dnms, int mode,
+                   int64_t *cand_off /* [n+1] */, int64_t *het_off /* [n+1] */);
 /* (The lists of the last THREE finds stay in HBM: a uz_phase / uz_phase_begin over a batch -- same family, DNMs, mode and parameters --
  * that one of them covered takes its lists instead of running the window emit again.  A staged pass calls uz_find for chunk k + 1,
  * whose het lists tell the decoder what to stage, before it queues the read stage of chunk k.) */
@@ -277,8 +287,14 @@ int uz_phase_sizing_fetch(uz_ctx *ctx, int32_t *bounds /* [5n] */, int32_t *pre_
  * etype = UZ_ET_* mask. */
 int uz_phase_cnv(uz_ctx *ctx, int fam_id, const uz_dnms_view *dnms, const int32_t *rb_counts, int32_t *cnv_counts /* [2n] */,
                  int32_t *origin /* [n] */, int32_t *evidence /* [n] */, int32_t *etype /* [n] */);
-/* Site lists of the last uz_phase_cnv: off[2n+1], then pos: cnv_dad_sites, cnv_mom_sites per DNM (positions in
- * candidate-list order).  pos == NULL: offsets only. */
+/* Cohort form: the DEL / DUP of many kids in ONE whole-region find (a family per DNM) and one K6 launch instead of one uz_phase_cnv per
+ * kid (the per-kid loop of run_cnv_phasing, sv_phaser.py:357-423).  Groups as in uz_find_cohort; rb_counts and the results as in
+ * uz_phase_cnv, in DNM order. */
+int uz_phase_cnv_cohort(uz_ctx *ctx, const uz_cohort_group *groups, int32_t n_groups, const uz_dnms_view *dnms, const int32_t *rb_counts,
+                        int32_t *cnv_counts /* [2n] */, int32_t *origin /* [n] */, int32_t *evidence /* [n] */, int32_t *etype /* [n] */);
+/* Site lists of the last uz_phase_cnv / uz_phase_cnv_cohort: off[2n+1], then pos: cnv_dad_sites, cnv_mom_sites per DNM (positions in
+ * candidate-list order).  pos == NULL: offsets only.  The lists lie back to back on the device (k_cnv_dense): off[2n] positions are
+ * copied, not the batch's candidates. */
 int uz_phase_cnv_sites(uz_ctx *ctx, int64_t *off /* [2n+1] */, int32_t *pos);
 
 /* ---- measurement ------------------------------------------------------ */

@@ -1,0 +1,153 @@
+"""uz_find_cohort: the window emit for the DNMs of several kids -- a family per DNM -- in one launch sequence gives, byte for byte, the lists of
+one uz_find per kid laid end to end, in every mode, through the refill path and on families whose classes are stale or lack the DEL / DUP
+codes; the lists are the CPU oracle's; a batch whose groups do not cover it exactly once is refused and leaves the context as it was."""
+import numpy as np
+import pytest
+
+import cohortcases as cc
+from oracle import oracle as orc
+from unfazed_amd import abi
+
+pytestmark = pytest.mark.gpu
+
+E_ARG = -1
+MODES = (abi.FIND_SECOND_WINDOW, 0, abi.FIND_WHOLE_REGION)
+NAMES = ("cand_off", "cand_idx", "cand_flags", "het_off", "het_idx")
+
+
+@pytest.fixture(scope="module")
+def second(hip_lib):
+    """a second context: the per-kid finds run where no cohort call has been"""
+    from unfazed_amd.engine import HipEngine
+    e = HipEngine(0)
+    yield e
+    e.close()
+
+
+@pytest.fixture(scope="module")
+def P():
+    return abi.make_params(search_dist=cc.SEARCH_DIST)
+
+
+def _joined(parts, order):
+    """per-group results (in `order` of their first DNM) -> one batch's five arrays"""
+    co, ho = [np.zeros(1, np.int64)], [np.zeros(1, np.int64)]
+    for g in order:
+        a = parts[g]
+        co.append(a[0][1:] + co[-1][-1])
+        ho.append(a[3][1:] + ho[-1][-1])
+    cat = lambda k, dt: np.concatenate([parts[g][k] for g in order] + [np.zeros(0, dt)]).astype(dt)  # noqa: E731
+    return np.concatenate(co), cat(1, np.int32), cat(2, np.uint8), np.concatenate(ho), cat(4, np.int32)
+
+
+def _order(groups):
+    return sorted(range(len(groups)), key=lambda g: (groups[g][1], groups[g][2]))
+
+
+@pytest.fixture(scope="module")
+def want(second, P):
+    """mode -> the five arrays of one uz_find per group on the second context, joined in DNM order; computed once"""
+    rows, groups = cc.find_batch()
+    sid = second.upload_sites(cc.table())
+    fams = cc.make_families(second, sid)
+    out = {}
+    for mode in MODES:
+        parts = [second.find(fams[t], cc.view(rows[f: f + n], mode), P, mode) for t, f, n in groups]
+        out[mode] = tuple(np.array(x) for x in _joined(parts, _order(groups)))
+    out["fams"] = fams
+    return out
+
+
+def _same(got, exp, what):
+    for name, x, y in zip(NAMES, got, exp):
+        assert x.dtype == y.dtype and x.tobytes() == y.tobytes(), (what, name)
+
+
+def _cohort(engine, fams, P, mode):
+    rows, groups = cc.find_batch()
+    return engine.find_cohort([(fams[t], f, n) for t, f, n in groups], cc.view(rows, mode), P, mode)
+
+
+def test_the_batch_reaches_the_paths_it_names(want):
+    rows, groups = cc.find_batch()
+    assert sorted(n for _, _, n in groups) == [0, 1, 5, 6] and groups[-1][0] == groups[-2][0] and len(rows) == 12
+    co, _, _, ho, _ = want[abi.FIND_WHOLE_REGION]
+    n_c = np.diff(co)
+    assert n_c[6] > 130 and n_c[7] == 0 and n_c[0] == 0
+    for mode in MODES:
+        co, _, _, ho, _ = want[mode]
+        assert co[4] - co[3] == 0 and ho[4] - ho[3] == 0  # no site in reach
+        assert co[-1] > 0 and ho[-1] > 0 and ho[2] - ho[1] > 0  # ... and the second contig has some
+    a, b = want[abi.FIND_SECOND_WINDOW], want[0]
+    assert b[0][5] - b[0][4] == 2 * (a[0][5] - a[0][4]) > 0 and b[3][6] - b[3][5] == 3 * (a[3][6] - a[3][5]) > 0  # mult 2 and 3
+    assert a[0][3] - a[0][2] > b[0][3] - b[0][2]  # the overlapping second window lists sites again
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_cohort_find_equals_per_kid_finds(engine, want, P, mode):
+    sid = engine.upload_sites(cc.table())
+    fams = cc.make_families(engine, sid)  # never scanned: the call classifies them
+    _same(_cohort(engine, fams, P, mode), want[mode], mode)
+    _same(_cohort(engine, fams, P, mode), want[mode], (mode, "again"))  # fresh classes now
+    engine.free_sites(sid)
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_cohort_find_through_the_refill(engine, want, P, mode, monkeypatch):
+    monkeypatch.setenv("UZ_TEST_FIND_CAP", "8")
+    sid = engine.upload_sites(cc.table())
+    fams = cc.make_families(engine, sid)
+    _same(_cohort(engine, fams, P, mode), want[mode], mode)
+    engine.free_sites(sid)
+
+
+def test_classes_without_cnv_codes_are_scanned_again(engine, want, P):
+    """a point-mode find leaves a family's classes without the DEL / DUP codes (uz_site_scan itself always writes them): fresh for a
+    point-mode find, stale for a whole-region one"""
+    rows, groups = cc.find_batch()
+    sid = engine.upload_sites(cc.table())
+    fams = cc.make_families(engine, sid)
+    engine.find(fams[0], cc.view(rows[:5], 0), P, abi.FIND_SECOND_WINDOW)
+    _same(_cohort(engine, fams, P, abi.FIND_WHOLE_REGION), want[abi.FIND_WHOLE_REGION], "whole region after a point-mode scan")
+    _same(_cohort(engine, fams, P, abi.FIND_SECOND_WINDOW), want[abi.FIND_SECOND_WINDOW], "and back")
+    engine.free_sites(sid)
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_cohort_find_equals_the_oracle(want, P, mode):
+    rows, groups = cc.find_batch()
+    sites_h = abi.sites_view(cc.table())
+    parts = [orc.find(P, sites_h, cc.family_held(cc.TRIOS[t]), cc.view(rows[f: f + n], mode), mode) for t, f, n in groups]
+    exp = _joined(parts, _order(groups))
+    for name, x, y in zip(NAMES, want[mode], exp):
+        assert np.array_equal(x, y), (mode, name)
+
+
+def test_refusals_leave_the_context_usable(engine, second, want, P):
+    rows, groups = cc.find_batch()
+    sid = engine.upload_sites(cc.table())
+    fams = cc.make_families(engine, sid)
+    sid2 = engine.upload_sites(cc.table())
+    other = cc.make_families(engine, sid2)
+    dv = cc.view(rows, abi.FIND_SECOND_WINDOW)
+    engine.set_params(P)
+    co, ho = np.zeros(13, np.int64), np.zeros(13, np.int64)
+    A, B = fams[0], fams[1]
+    bad = {
+        "gap": [(A, 0, 5), (B, 6, 6)],
+        "overlap": [(A, 0, 6), (B, 5, 7)],
+        "past n": [(A, 0, 6), (B, 6, 7)],
+        "two sites tables": [(A, 0, 6), (other[1], 6, 6)],
+    }
+    sub = cc.view(rows[:5], abi.FIND_SECOND_WINDOW)
+    plain = [np.array(x) for x in second.find(want["fams"][0], sub, P, abi.FIND_SECOND_WINDOW)]
+    for what, g in bad.items():
+        rc = engine.L.uz_find_cohort(engine.h, engine._find_groups(g), len(g), dv.ref(), abi.FIND_SECOND_WINDOW, co.ctypes.data, ho.ctypes.data)
+        assert rc == E_ARG, what
+        assert engine.L.uz_last_error(engine.h)
+        # a plain find afterwards is what it is on a context that never saw a cohort call: no family-per-DNM state is left behind
+        _same(engine.find(A, sub, P, abi.FIND_SECOND_WINDOW), plain, what)
+    _same(_cohort(engine, fams, P, abi.FIND_SECOND_WINDOW), want[abi.FIND_SECOND_WINDOW], "after the refusals")
+    _same(engine.find(A, sub, P, abi.FIND_SECOND_WINDOW), plain, "after a cohort find")
+    engine.free_sites(sid2)
+    engine.free_sites(sid)

@@ -443,7 +443,7 @@ void uz_destroy(uz_ctx *c) {
     c->nm_ids.release(); c->nm_len.release(); c->nm_off.release(); c->nm_out.release();
     c->ab_lut.release(); c->win_range.release();
     c->dn_fam.release(); c->dn_cutoff.release(); c->fam_cls.release();
-    c->cnv_counts.release(); c->cnv_pos.release(); c->cnv_origin.release(); c->cnv_evidence.release(); c->cnv_etype.release(); c->cnv_rb.release();
+    c->cnv_counts.release(); c->cnv_pos.release(); c->cnv_origin.release(); c->cnv_evidence.release(); c->cnv_etype.release(); c->cnv_rb.release(); c->cnv_off.release(); c->cnv_dense.release();
     c->cnt_c.release(); c->cnt_h.release(); c->cand_off.release(); c->het_off.release();
     c->cand_idx.release(); c->het_idx.release(); c->cand_flags.release(); c->win_range.release();
     c->inf_comp.release(); c->inf_out.release(); c->inf_in.release(); c->inf_off.release(); c->inf_flags.release();
@@ -1990,6 +1990,92 @@ int uz_phase_cohort(uz_ctx *c, const uz_cohort_group *groups, int32_t n_groups, 
     });
 }
 
+// What a cohort find and a cohort allele-balance stage share (unfazed_hip.h: uz_find_cohort): the groups checked, the stale families
+// classified in one launch, the batch staged with a family per DNM (dn_fam = the DNM's group, fam_cls = the class column of every group,
+// as uz_phase_cohort stages them).  Nothing of the context is touched before every check has passed.
+static void cohort_find_stage(uz_ctx *c, const uz_cohort_group *groups, int32_t n_groups, const uz_dnms_view *d, bool cnv, FamilyDev *&f0, SitesDev *&s0) {
+    UZ_REQUIRE(groups && n_groups > 0 && d && d->n >= 0, UZ_E_ARG, "bad cohort batch");
+    const int32_t n = d->n;
+    f0 = &fam_of(c, groups[0].fam_id);
+    s0 = &sites_of(c, f0->sites_id);
+    std::vector<std::pair<int32_t, int32_t>> spans;
+    for (int32_t g = 0; g < n_groups; g++) {
+        UZ_REQUIRE(groups[g].dnm_first >= 0 && groups[g].dnm_count >= 0 && (int64_t)groups[g].dnm_first + groups[g].dnm_count <= n, UZ_E_ARG,
+                   "cohort group outside the DNM batch");
+        UZ_REQUIRE(fam_of(c, groups[g].fam_id).sites_id == f0->sites_id, UZ_E_ARG, "the families of a cohort batch must share a sites table");
+        if (groups[g].dnm_count) spans.push_back({groups[g].dnm_first, groups[g].dnm_count});
+    }
+    std::sort(spans.begin(), spans.end());
+    int64_t next = 0;
+    for (const auto &sp : spans) {
+        UZ_REQUIRE(sp.first == next, UZ_E_ARG, "the groups of a cohort batch must cover its DNMs exactly once");
+        next += sp.second;
+    }
+    UZ_REQUIRE(next == n, UZ_E_ARG, "the groups of a cohort batch must cover its DNMs exactly once");
+    std::vector<FamilyDev *> stale; // (each family once: a family may serve several groups)
+    for (int32_t g = 0; g < n_groups; g++) {
+        FamilyDev *f = &fam_of(c, groups[g].fam_id);
+        if (!uz_site_scan_fresh(c, *f, cnv) && std::find(stale.begin(), stale.end(), f) == stale.end()) stale.push_back(f);
+    }
+    if (!stale.empty()) uz_launch_site_scan_many(c, stale.data(), (int)stale.size(), *s0, cnv);
+    std::vector<int32_t> fam_h((size_t)n, 0);
+    std::vector<uint8_t *> cls_h((size_t)n_groups);
+    for (int32_t g = 0; g < n_groups; g++) {
+        cls_h[(size_t)g] = fam_of(c, groups[g].fam_id).cls;
+        for (int32_t k = groups[g].dnm_first; k < groups[g].dnm_first + groups[g].dnm_count; k++) fam_h[(size_t)k] = g;
+    }
+    find_target(c); c->phase_valid = false; // (the cohort's lists take the place of the oldest set, under no key)
+    uz_stage_dnms(c, d);
+    c->dn_fam.ensure((size_t)n + 1); c->fam_cls.ensure((size_t)n_groups + 1);
+    if (n) UZ_HIP(hipMemcpyAsync(c->dn_fam.p, fam_h.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    UZ_HIP(hipMemcpyAsync(c->fam_cls.p, cls_h.data(), (size_t)n_groups * sizeof(uint8_t *), hipMemcpyHostToDevice, c->stream));
+    UZ_HIP(hipStreamSynchronize(c->stream)); // the staging vectors above are locals
+}
+
+int uz_find_cohort(uz_ctx *c, const uz_cohort_group *groups, int32_t n_groups, const uz_dnms_view *d, int mode, int64_t *cand_off, int64_t *het_off) {
+    return guarded(c, [&] {
+        FamilyDev *f0 = nullptr;
+        SitesDev *s = nullptr;
+        cohort_find_stage(c, groups, n_groups, d, (mode & UZ_FIND_WHOLE_REGION) != 0, f0, s);
+        c->cohort_on = true;
+        try { uz_launch_find(c, *f0, *s, mode); } catch (...) { c->cohort_on = false; throw; }
+        c->cohort_on = false;
+        c->find_fam = groups[0].fam_id;
+        if (cand_off) memcpy(cand_off, c->cand_off_h.data(), ((size_t)d->n + 1) * sizeof(int64_t));
+        if (het_off) memcpy(het_off, c->het_off_h.data(), ((size_t)d->n + 1) * sizeof(int64_t));
+    });
+}
+
+// K6 over the whole-region lists of the context, the dense site lists behind it, the results back: the counts and the lists' offsets stay
+// on the host for uz_phase_cnv_sites
+static void cnv_after_find(uz_ctx *c, const SitesDev &s, size_t n, const int32_t *rb_counts, int32_t *cnv_counts, int32_t *origin, int32_t *evidence,
+                           int32_t *etype) {
+    c->cnv_n = (int32_t)n;
+    c->cnv_counts.ensure(2 * n + 2); c->cnv_pos.ensure((size_t)c->n_cand + 1); c->cnv_origin.ensure(n + 1);
+    c->cnv_evidence.ensure(n + 1); c->cnv_etype.ensure(n + 1);
+    c->cnv_off.ensure(2 * n + 2); c->cnv_dense.ensure((size_t)c->n_cand + 1);
+    const int32_t *rb = nullptr;
+    if (rb_counts && n) {
+        c->cnv_rb.ensure(4 * n);
+        UZ_HIP(hipMemcpyAsync(c->cnv_rb.p, rb_counts, 4 * n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        rb = c->cnv_rb.p;
+    }
+    uz_launch_cnv(c, s, rb, c->cnv_counts.p, c->cnv_pos.p, c->cnv_origin.p, c->cnv_evidence.p, c->cnv_etype.p);
+    uz_launch_cnv_dense(c, c->cnv_counts.p, c->cnv_pos.p, c->cnv_off.p, c->cnv_dense.p);
+    c->cnv_counts_h.resize(2 * n + 2);
+    c->cnv_off_h.assign(2 * n + 1, 0);
+    if (n) {
+        UZ_HIP(hipMemcpyAsync(c->cnv_counts_h.data(), c->cnv_counts.p, 2 * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        UZ_HIP(hipMemcpyAsync(c->cnv_off_h.data(), c->cnv_off.p, (2 * n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        if (origin) UZ_HIP(hipMemcpyAsync(origin, c->cnv_origin.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        if (evidence) UZ_HIP(hipMemcpyAsync(evidence, c->cnv_evidence.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        if (etype) UZ_HIP(hipMemcpyAsync(etype, c->cnv_etype.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    UZ_HIP(hipStreamSynchronize(c->stream));
+    if (cnv_counts && n) memcpy(cnv_counts, c->cnv_counts_h.data(), 2 * n * sizeof(int32_t));
+    c->cnv_valid = true;
+}
+
 int uz_phase_cnv(uz_ctx *c, int fam_id, const uz_dnms_view *d, const int32_t *rb_counts, int32_t *cnv_counts, int32_t *origin,
                  int32_t *evidence, int32_t *etype) {
     return guarded(c, [&] {
@@ -1998,33 +2084,31 @@ int uz_phase_cnv(uz_ctx *c, int fam_id, const uz_dnms_view *d, const int32_t *rb
         UZ_REQUIRE(d != nullptr, UZ_E_ARG, "null DNM view");
         find_target(c); c->phase_valid = false; c->cnv_valid = false;
         uz_stage_dnms(c, d);
-        const size_t n = (size_t)d->n;
         if (!uz_site_scan_fresh(c, f, true)) uz_launch_site_scan(c, f, s, true);
         const int32_t sd = c->P.search_dist;
         c->P.search_dist = 0; // run_cnv_phasing calls find(..., search_dist=0, whole_region=True), sv_phaser.py:375-389
         try { uz_launch_find(c, f, s, UZ_FIND_WHOLE_REGION, false); } catch (...) { c->P.search_dist = sd; throw; }
         c->P.search_dist = sd;
         c->find_fam = fam_id;
-        c->cnv_n = d->n;
-        c->cnv_counts.ensure(2 * n + 2); c->cnv_pos.ensure((size_t)c->n_cand + 1); c->cnv_origin.ensure(n + 1);
-        c->cnv_evidence.ensure(n + 1); c->cnv_etype.ensure(n + 1);
-        const int32_t *rb = nullptr;
-        if (rb_counts && n) {
-            c->cnv_rb.ensure(4 * n);
-            UZ_HIP(hipMemcpyAsync(c->cnv_rb.p, rb_counts, 4 * n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-            rb = c->cnv_rb.p;
-        }
-        uz_launch_cnv(c, s, rb, c->cnv_counts.p, c->cnv_pos.p, c->cnv_origin.p, c->cnv_evidence.p, c->cnv_etype.p);
-        c->cnv_counts_h.resize(2 * n + 2);
-        if (n) {
-            UZ_HIP(hipMemcpyAsync(c->cnv_counts_h.data(), c->cnv_counts.p, 2 * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-            if (origin) UZ_HIP(hipMemcpyAsync(origin, c->cnv_origin.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-            if (evidence) UZ_HIP(hipMemcpyAsync(evidence, c->cnv_evidence.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-            if (etype) UZ_HIP(hipMemcpyAsync(etype, c->cnv_etype.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        }
-        UZ_HIP(hipStreamSynchronize(c->stream));
-        if (cnv_counts && n) memcpy(cnv_counts, c->cnv_counts_h.data(), 2 * n * sizeof(int32_t));
-        c->cnv_valid = true;
+        cnv_after_find(c, s, (size_t)d->n, rb_counts, cnv_counts, origin, evidence, etype);
+    });
+}
+
+int uz_phase_cnv_cohort(uz_ctx *c, const uz_cohort_group *groups, int32_t n_groups, const uz_dnms_view *d, const int32_t *rb_counts, int32_t *cnv_counts,
+                        int32_t *origin, int32_t *evidence, int32_t *etype) {
+    return guarded(c, [&] {
+        FamilyDev *f0 = nullptr;
+        SitesDev *s = nullptr;
+        cohort_find_stage(c, groups, n_groups, d, true, f0, s);
+        c->cnv_valid = false;
+        const int32_t sd = c->P.search_dist;
+        c->P.search_dist = 0; // as uz_phase_cnv
+        c->cohort_on = true;
+        try { uz_launch_find(c, *f0, *s, UZ_FIND_WHOLE_REGION, false); } catch (...) { c->cohort_on = false; c->P.search_dist = sd; throw; }
+        c->cohort_on = false;
+        c->P.search_dist = sd;
+        c->find_fam = groups[0].fam_id;
+        cnv_after_find(c, *s, (size_t)d->n, rb_counts, cnv_counts, origin, evidence, etype);
     });
 }
 
@@ -2033,22 +2117,11 @@ int uz_phase_cnv_sites(uz_ctx *c, int64_t *off, int32_t *pos) {
         UZ_REQUIRE(c->cnv_valid && c->find_valid, UZ_E_STATE, "uz_phase_cnv_sites before uz_phase_cnv");
         UZ_REQUIRE(off != nullptr, UZ_E_ARG, "null output");
         const size_t n = (size_t)c->cnv_n;
-        // the lists keep the layout of the device array: the DNM's slice of the candidate list, dad's sites then mom's
-        std::vector<int64_t> co(n + 1);
-        if (n) UZ_HIP(hipMemcpy(co.data(), c->cand_off.p, (n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
-        int64_t total = 0;
-        for (size_t d = 0; d < n; d++) {
-            off[2 * d] = total; total += c->cnv_counts_h[2 * d];
-            off[2 * d + 1] = total; total += c->cnv_counts_h[2 * d + 1];
-        }
-        off[2 * n] = total;
+        // dad's sites then mom's per DNM, back to back on the device (k_cnv_dense): their offsets came back with the counts
+        memcpy(off, c->cnv_off_h.data(), (2 * n + 1) * sizeof(int64_t));
+        const int64_t total = off[2 * n];
         if (!pos || total == 0) return;
-        std::vector<int32_t> all((size_t)c->n_cand + 1);
-        UZ_HIP(hipMemcpy(all.data(), c->cnv_pos.p, (size_t)c->n_cand * sizeof(int32_t), hipMemcpyDeviceToHost));
-        for (size_t d = 0; d < n; d++) {
-            const int64_t len = off[2 * d + 2] - off[2 * d];
-            if (len) memcpy(pos + off[2 * d], all.data() + co[d], (size_t)len * sizeof(int32_t));
-        }
+        UZ_HIP(hipMemcpy(pos, c->cnv_dense.p, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost));
     });
 }
 

@@ -686,6 +686,84 @@ __global__ __launch_bounds__(256) void k_cnv_count(int32_t n, const int64_t *__r
     origin[d] = org; evidence[d] = (int32_t)ev; etype[d] = et;
 }
 
+// Dense site lists of K6.  k_cnv_count leaves a DNM's voted positions at the head of its slice of the candidate-length array
+// (dad's sites, then mom's): the host would have to take the whole array to cut them out.  An exclusive scan of the 2n counts
+// (k_scan2's tiles, one array) gives every list its place in an array of exactly `total` positions, and one wave per DNM moves
+// its n_dad + n_mom positions there -- lane i element i, 64 consecutive words read and written per round.
+__global__ __launch_bounds__(1024) void k_scan1_sums(int32_t m, const int32_t *c0, int64_t *part /* [tiles] */) {
+    __shared__ long long wsum[16];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int32_t i0 = (int32_t)blockIdx.x * 4096 + 4 * t;
+    long long s = 0;
+    if (i0 + 3 < m) {
+        const int4 a = *reinterpret_cast<const int4 *>(c0 + i0);
+        s = (long long)a.x + a.y + a.z + a.w;
+    } else {
+        for (int k = 0; k < 4; k++) if (i0 + k < m) s += c0[i0 + k];
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    if (lane == 0) wsum[wv] = s;
+    __syncthreads();
+    if (t == 0) {
+        long long a = 0;
+        for (int w = 0; w < 16; w++) a += wsum[w];
+        part[blockIdx.x] = a;
+    }
+}
+__global__ __launch_bounds__(1024) void k_scan1(int32_t m, const int32_t *c0, const int64_t *__restrict__ part, int64_t *o0 /* [m + 1] */) {
+    __shared__ int wsum[16];
+    __shared__ long long csum[16];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int32_t i0 = (int32_t)blockIdx.x * 4096 + 4 * t;
+    int v[4] = {0, 0, 0, 0};
+    if (i0 + 3 < m) {
+        const int4 a = *reinterpret_cast<const int4 *>(c0 + i0);
+        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+    } else {
+        for (int k = 0; k < 4; k++) if (i0 + k < m) v[k] = c0[i0 + k];
+    }
+    long long q = 0; // the tiles before this one
+    for (int b = t; b < (int)blockIdx.x; b += 1024) q += part[b];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) q += __shfl_xor(q, off, 64);
+    const int s = v[0] + v[1] + v[2] + v[3];
+    int in = s;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int u = __shfl_up(in, off, 64);
+        if (lane >= off) in += u;
+    }
+    if (lane == 63) wsum[wv] = in;
+    if (lane == 0) csum[wv] = q;
+    __syncthreads();
+    int64_t base = 0, pre = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < 16; w++) {
+        const int a = wsum[w];
+        if (w < wv) pre += a;
+        tot += a;
+        base += csum[w];
+    }
+    int64_t p = base + pre + (in - s);
+    for (int k = 0; k < 4; k++) {
+        if (i0 + k < m) o0[i0 + k] = p;
+        p += v[k];
+    }
+    if (t == 0 && blockIdx.x == gridDim.x - 1) o0[m] = base + tot;
+}
+__global__ __launch_bounds__(256) void k_cnv_dense(int32_t n, const int64_t *__restrict__ cand_off, const int64_t *__restrict__ cnv_off /* [2n + 1] */,
+                                                   const int32_t *__restrict__ cnv_pos, int32_t *__restrict__ dense) {
+    const int32_t d = (int32_t)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const int lane = threadIdx.x & 63;
+    if (d >= n) return;
+    const int64_t src = cand_off[d], dst = cnv_off[2 * (int64_t)d];
+    int64_t len = cnv_off[2 * (int64_t)d + 2] - dst;
+    const int64_t room = cand_off[d + 1] - src; // (n_dad + n_mom <= the DNM's candidates: every candidate votes at most once)
+    if (len > room) len = room;
+    for (int64_t i = lane; i < len; i += 64) dense[dst + i] = cnv_pos[src + i];
+}
+
 SiteParams make_site_params(const uz_params &p) {
     SiteParams s;
     s.min_gt_qual = p.min_gt_qual;
@@ -1157,5 +1235,24 @@ void uz_launch_cnv(uz_ctx *c, const SitesDev &s, const int32_t *rb_counts_dev, i
     hipLaunchKernelGGL(k_cnv_count, dim3((unsigned)(((int64_t)n * 64 + 255) / 256)), dim3(256), 0, c->stream, n, (const int64_t *)c->cand_off.p,
                        (const int32_t *)c->cand_idx.p, (const uint8_t *)c->cand_flags.p, (const int32_t *)s.pos, (const uint8_t *)c->dn.vartype.p,
                        rb_counts_dev, (int)c->P.evidence_min_ratio, cnv_counts, cnv_pos, origin, evidence, etype);
+    UZ_HIP(hipGetLastError());
+}
+
+// cnv_counts [2n] (k_cnv_count) -> cnv_off [2n + 1], and the lists out of cnv_pos (candidate-list layout) back to back in `dense`
+// (room for the batch's candidates: the total is not known on the host yet)
+void uz_launch_cnv_dense(uz_ctx *c, const int32_t *cnv_counts, const int32_t *cnv_pos, int64_t *cnv_off, int32_t *dense) {
+    const int32_t n = c->dn.n;
+    if (n <= 0) return;
+    UZ_REQUIRE(n < (1 << 30), UZ_E_RANGE, "too many DNMs for one allele-balance batch");
+    const int32_t m = 2 * n;
+    const unsigned tiles = (unsigned)(((int64_t)m + 4095) / 4096);
+    c->scan_part.ensure((size_t)2 * tiles);
+    ProfScope ps(c, UZ_K_CNV_DENSE);
+    hipLaunchKernelGGL(k_scan1_sums, dim3(tiles), dim3(1024), 0, c->stream, m, cnv_counts, c->scan_part.p);
+    UZ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_scan1, dim3(tiles), dim3(1024), 0, c->stream, m, cnv_counts, (const int64_t *)c->scan_part.p, cnv_off);
+    UZ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_cnv_dense, dim3((unsigned)(((int64_t)n * 64 + 255) / 256)), dim3(256), 0, c->stream, n, (const int64_t *)c->cand_off.p,
+                       (const int64_t *)cnv_off, cnv_pos, dense);
     UZ_HIP(hipGetLastError());
 }

@@ -359,7 +359,10 @@ struct uz_ctx {
     bool cnv_valid = false;
     int32_t cnv_n = 0;
     DevBuf<int32_t> cnv_counts, cnv_pos, cnv_origin, cnv_evidence, cnv_etype, cnv_rb;
+    DevBuf<int64_t> cnv_off;   // [2n + 1] exclusive scan of cnv_counts: where every site list starts in cnv_dense
+    DevBuf<int32_t> cnv_dense; // the site lists back to back (k_cnv_dense): what uz_phase_cnv_sites copies
     std::vector<int32_t> cnv_counts_h;
+    std::vector<int64_t> cnv_off_h;
 
     // BGZF inflate (k_inflate.hip, uz_bgzf_inflate_to_host): buffers kept from call to call, a stream of its own (a batch's blocks can
     // be inflated while the read stage of the batch before is still queued on the compute stream)
@@ -477,6 +480,7 @@ void uz_launch_find(uz_ctx *c, FamilyDev &f, const SitesDev &s, int mode, bool h
 void uz_stage_dnms(uz_ctx *c, const uz_dnms_view *d);
 void uz_launch_cnv(uz_ctx *c, const SitesDev &s, const int32_t *rb_counts_dev, int32_t *cnv_counts, int32_t *cnv_pos, int32_t *origin,
                    int32_t *evidence, int32_t *etype);
+void uz_launch_cnv_dense(uz_ctx *c, const int32_t *cnv_counts, const int32_t *cnv_pos, int64_t *cnv_off, int32_t *dense);
 void uz_launch_phase(uz_ctx *c, FamilyDev &f, const SitesDev &s, ReadsDev &r, int32_t *status, int32_t *counts,
                      int32_t *origin, int32_t *evidence, bool defer = false);
 bool uz_finish_phase(uz_ctx *c, int32_t *status, int32_t *counts, int32_t *origin, int32_t *evidence);

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("UZ_HIP_LIB", os.path.join(_HERE, "libunfazed_hip.so"))
 
 SIZING_REDUCED_WORDS = 263  # unfazed_hip.h UZ_SIZING_REDUCED_WORDS
-K_SITE_SCAN, K_WINDOW_COUNT, K_WINDOW_FILL, K_PHASE, K_SIZING, K_CNV, K_FAMILY_PACK = 0, 1, 2, 3, 4, 5, 6
+K_SITE_SCAN, K_WINDOW_COUNT, K_WINDOW_FILL, K_PHASE, K_SIZING, K_CNV, K_FAMILY_PACK, K_CNV_DENSE = 0, 1, 2, 3, 4, 5, 6, 7
 
 EXPORTS = [
     "uz_create", "uz_destroy", "uz_last_error", "uz_sync", "uz_set_params",
@@ -24,8 +24,8 @@ EXPORTS = [
     "uz_pinned_alloc", "uz_pinned_free",
     "uz_sites_adopt_device", "uz_family_adopt_device", "uz_reads_adopt_device",
     "uz_sites_free", "uz_reads_free", "uz_drop_derived",
-    "uz_site_scan", "uz_site_scan_many", "uz_site_classes", "uz_find", "uz_find_fetch",
-    "uz_phase", "uz_phase_begin", "uz_phase_end", "uz_phase_cohort", "uz_phase_votes", "uz_phase_groups", "uz_phase_sizing_fetch", "uz_phase_cnv", "uz_phase_cnv_sites",
+    "uz_site_scan", "uz_site_scan_many", "uz_site_classes", "uz_find", "uz_find_fetch", "uz_find_cohort",
+    "uz_phase", "uz_phase_begin", "uz_phase_end", "uz_phase_cohort", "uz_phase_votes", "uz_phase_groups", "uz_phase_sizing_fetch", "uz_phase_cnv", "uz_phase_cnv_cohort", "uz_phase_cnv_sites",
     "uz_prof_enable", "uz_prof_reset", "uz_prof_get", "uz_prof_units",
 ]
 
@@ -93,11 +93,13 @@ def load_library(path: Optional[str] = None):
     L.uz_site_classes.argtypes = [vp, C.c_int, vp]
     L.uz_find.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp]
     L.uz_find_fetch.argtypes = [vp, vp, vp, vp]
+    L.uz_find_cohort.argtypes = [vp, vp, C.c_int32, vp, C.c_int, vp, vp]
     L.uz_phase.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]
     L.uz_phase_begin.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int]
     L.uz_phase_end.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]
     L.uz_phase_cohort.argtypes = [vp, vp, C.c_int32, vp, C.c_int, vp, vp, vp, vp]
     L.uz_phase_cnv.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.uz_phase_cnv_cohort.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp]
     L.uz_phase_cnv_sites.argtypes = [vp, vp, vp]
     L.uz_phase_votes.argtypes = [vp, vp, vp]
     L.uz_phase_groups.argtypes = [vp, vp, vp]
@@ -586,6 +588,28 @@ class HipEngine:
         ci, cf, hi = self._fetch(int(co[n]), int(ho[n]), transient=transient)
         return co, ci, cf, ho, hi
 
+    @staticmethod
+    def _find_groups(groups):
+        """[(fam, first, count)] -> uz_cohort_group array (reads_id and cutoff are not read by the find-side cohort calls)"""
+        arr = (abi.CohortGroup * max(1, len(groups)))()
+        for k, (fam, first, count) in enumerate(groups):
+            arr[k].fam_id, arr[k].reads_id, arr[k].dnm_first, arr[k].dnm_count, arr[k].cutoff = int(fam), -1, int(first), int(count), 0.0
+        return arr
+
+    def find_cohort(self, groups, dv: abi.Held, params: abi.Params, mode: int, fetch: bool = True):
+        """Cohort form of find(): groups = [(fam, first, count)] covering the DNMs of `dv` exactly once (several kids, each with its own
+        family columns), one launch sequence (uz_find_cohort).  Same result layout as find(), in DNM order."""
+        self.set_params(params)
+        n = dv.view.n
+        co = np.zeros(n + 1, dtype=np.int64)
+        ho = np.zeros(n + 1, dtype=np.int64)
+        self._ck(self.L.uz_find_cohort(self.h, self._find_groups(groups), len(groups), dv.ref(), int(mode), co.ctypes.data, ho.ctypes.data),
+                 "uz_find_cohort")
+        if not fetch:
+            return co, None, None, ho, None
+        ci, cf, hi = self._fetch(int(co[n]), int(ho[n]))
+        return co, ci, cf, ho, hi
+
     def _fetch(self, nc: int, nh: int, transient: bool = False):
         if transient:
             # Into page-locked memory kept from call to call (three sets in turn: the lists of a find are read before the find after next
@@ -725,6 +749,26 @@ class HipEngine:
             assert rb.size == 4 * n
         self._ck(self.L.uz_phase_cnv(self.h, int(fam), dv.ref(), rb.ctypes.data if rb is not None else None, cnt.ctypes.data,
                                      origin.ctypes.data, evidence.ctypes.data, etype.ctypes.data), "uz_phase_cnv")
+        return self._cnv_result(n, cnt, origin, evidence, etype, want_lists)
+
+    def phase_cnv_cohort(self, groups, dv: abi.Held, params: abi.Params, rb_counts=None, want_lists: bool = True):
+        """Cohort form of phase_cnv(): groups = [(fam, first, count)] covering the DNMs of `dv` exactly once, one whole-region find with a
+        family per DNM and one K6 launch (uz_phase_cnv_cohort).  Same result layout as phase_cnv(), in DNM order."""
+        self.set_params(params)
+        n = dv.view.n
+        cnt = np.zeros(max(1, 2 * n), np.int32)
+        origin = np.zeros(max(1, n), np.int32)
+        evidence = np.zeros(max(1, n), np.int32)
+        etype = np.zeros(max(1, n), np.int32)
+        rb = None
+        if rb_counts is not None:
+            rb = np.ascontiguousarray(rb_counts, np.int32).reshape(-1)
+            assert rb.size == 4 * n
+        self._ck(self.L.uz_phase_cnv_cohort(self.h, self._find_groups(groups), len(groups), dv.ref(), rb.ctypes.data if rb is not None else None,
+                                            cnt.ctypes.data, origin.ctypes.data, evidence.ctypes.data, etype.ctypes.data), "uz_phase_cnv_cohort")
+        return self._cnv_result(n, cnt, origin, evidence, etype, want_lists)
+
+    def _cnv_result(self, n, cnt, origin, evidence, etype, want_lists):
         r = dict(cnv_counts=cnt[: 2 * n].reshape(n, 2), origin=origin[:n], evidence=evidence[:n], etype=etype[:n], lists=None)
         if want_lists:
             off = np.zeros(2 * n + 1, np.int64)

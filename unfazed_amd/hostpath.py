@@ -12,6 +12,7 @@ Mirrors, by name and argument meaning:
 """
 from __future__ import annotations
 
+import os
 import sys
 import types
 from typing import Dict, List, Optional, Sequence
@@ -180,6 +181,18 @@ class _VoteLists:
         return np.unique(self.vv[idx].astype(np.int64))
 
 
+class _Stats(dict):
+    """PhasingHost.stats: the counters of calls a host has not made yet (find_cohort_calls, find_kid_calls, cnv_cohort_calls,
+    cnv_kid_calls) read as 0 and are entered by their first increment"""
+
+    ROUTE_KEYS = ("find_cohort_calls", "find_kid_calls", "cnv_cohort_calls", "cnv_kid_calls")
+
+    def __missing__(self, key):
+        if key in self.ROUTE_KEYS:
+            return 0
+        raise KeyError(key)
+
+
 class PhasingHost:
     """Drives one backend over one sites table and the reads tables of the kids."""
 
@@ -197,7 +210,10 @@ class PhasingHost:
         # route made the families -- families_from_samples = made on the device, in families_from_samples_calls calls, from
         # samples_uploaded rows in sample_tables tables; families_host = made by family_columns + add_family, one at a time
         self._sample_tabs: List[tuple] = []
-        self.stats: Dict[str, int] = dict(families_from_samples=0, families_from_samples_calls=0, samples_uploaded=0, sample_tables=0, families_host=0)
+        # ... and which route the find and the allele-balance stage took (_cohort_route): *_cohort_calls = device calls over all kids of a
+        # batch at once, *_kid_calls = device calls over one kid's DNMs.  These four are entered with their first call (_Stats: one
+        # that has not been made reads as 0), so a host that has only made families shows the family counters alone
+        self.stats: Dict[str, int] = _Stats(families_from_samples=0, families_from_samples_calls=0, samples_uploaded=0, sample_tables=0, families_host=0)
 
     # ------------------------------------------------------------ handles
     def family(self, kid: str, dad: str, mom: str):
@@ -345,11 +361,10 @@ class PhasingHost:
             by_kid.setdefault(dnms[i]["kid"], []).append(i)
         mode = (abi.FIND_WHOLE_REGION if whole_region else 0) | (0 if many else abi.FIND_SECOND_WINDOW)
         self.prepare_families((kid, pedigrees[kid]["dad"], pedigrees[kid]["mom"]) for kid in by_kid)
-        for kid, idxs in by_kid.items():
-            dad, mom = pedigrees[kid]["dad"], pedigrees[kid]["mom"]
-            fam = self.family(kid, dad, mom)
+
+        def view(idxs):
             n = len(idxs)
-            dv = abi.dnms_view(
+            return abi.dnms_view(
                 contig=[contig_of[i] for i in idxs],
                 rcontig=[-1] * n,
                 start=[int(dnms[i]["start"]) for i in idxs],
@@ -360,10 +375,8 @@ class PhasingHost:
                 cutoff=0.0,
                 mult=[mult_of[i] for i in idxs],
             )
-            if not fetch and not attach:
-                continue  # the caller runs its own device stage over the batch (K6): no lists on the host
-            co, ci, cf, ho, hi = self.backend.find(fam, dv, params, mode)
-            col, hol = co.tolist(), ho.tolist()
+
+        def take(idxs, ci, cf, hi, col, hol, dad, mom):
             for k, i in enumerate(idxs):
                 found[i] = dict(
                     mult=mult_of[i],
@@ -373,6 +386,28 @@ class PhasingHost:
                 )
             if attach:
                 pending_attach.append((idxs, ci, cf, hi, col, hol, dad, mom))
+
+        fams = {kid: self.family(kid, pedigrees[kid]["dad"], pedigrees[kid]["mom"]) for kid in by_kid}
+        if not fetch and not attach:
+            pass  # the caller runs its own device stage over the batch (K6): no lists on the host
+        elif self._cohort_route(by_kid, "find_cohort"):
+            # all kids in ONE device call (uz_find_cohort): the kids' DNMs back to back in by_kid order, then every kid's slice of the lists
+            groups, all_idx = [], []
+            for kid, idxs in by_kid.items():
+                groups.append((fams[kid], len(all_idx), len(idxs)))
+                all_idx += idxs
+            co, ci, cf, ho, hi = self.backend.find_cohort(groups, view(all_idx), params, mode)
+            self.stats["find_cohort_calls"] += 1
+            col, hol = co.tolist(), ho.tolist()
+            for (kid, idxs), (_, first, n) in zip(by_kid.items(), groups):
+                c0, c1, h0, h1 = col[first], col[first + n], hol[first], hol[first + n]
+                take(idxs, ci[c0:c1], cf[c0:c1], hi[h0:h1], [x - c0 for x in col[first : first + n + 1]], [x - h0 for x in hol[first : first + n + 1]],
+                     pedigrees[kid]["dad"], pedigrees[kid]["mom"])
+        else:
+            for kid, idxs in by_kid.items():
+                co, ci, cf, ho, hi = self.backend.find(fams[kid], view(idxs), params, mode)
+                self.stats["find_kid_calls"] += 1
+                take(idxs, ci, cf, hi, co.tolist(), ho.tolist(), pedigrees[kid]["dad"], pedigrees[kid]["mom"])
 
         def attach_now():
             # the site dicts the reference leaves on every DNM (:262-343): the columns of the whole batch's sites become Python values in
@@ -401,6 +436,11 @@ class PhasingHost:
         # (defer_attach: the caller runs info["attach"]() itself -- the read stage needs the index lists, not the dicts, so a staged batch builds
         # them beside the native decode of its first chunks instead of in front of it)
         return ret, {"order": ret_idx, "found": found, "many": many, "mode": mode, "scanned": scan, "contig_of": contig_of, "attach": attach_now}
+
+    def _cohort_route(self, by_kid, method: str) -> bool:
+        """do the kids of a batch go to the device in one call?  Two or more kids and a backend that has the cohort call (the CPU oracle
+        has none); UZ_FIND_ROUTE=kid forces one call per kid"""
+        return len(by_kid) >= 2 and hasattr(self.backend, method) and os.environ.get("UZ_FIND_ROUTE", "cohort") != "kid"
 
     def _site_dicts(self, idx, flags, dad, mom, with_kid_allele):
         s = self.sites
@@ -974,17 +1014,30 @@ class PhasingHost:
             for i in info["scanned"]:
                 if dnms[i]["vartype"] in ["DEL", "DUP"]:
                     by_kid.setdefault(dnms[i]["kid"], []).append(i)
-            for kid, idxs in by_kid.items():
-                fam = self.family(kid, pedigrees[kid]["dad"], pedigrees[kid]["mom"])
+
+            def view(idxs):
                 n = len(idxs)
-                dv = abi.dnms_view(
+                return abi.dnms_view(
                     contig=[info["contig_of"][i] for i in idxs], rcontig=[-1] * n,
                     start=[int(dnms[i]["start"]) for i in idxs], end=[int(dnms[i]["end"]) for i in idxs],
                     vartype=[vartype_code(dnms[i]["vartype"]) for i in idxs], refs=[b""] * n, alts=[b""] * n, cutoff=0.0,
                 )
-                res = self.backend.phase_cnv(fam, dv, params)
-                for k, i in enumerate(idxs):
+            fams = {kid: self.family(kid, pedigrees[kid]["dad"], pedigrees[kid]["mom"]) for kid in by_kid}
+            if self._cohort_route(by_kid, "phase_cnv_cohort"):
+                groups, all_idx = [], []
+                for kid, idxs in by_kid.items():
+                    groups.append((fams[kid], len(all_idx), len(idxs)))
+                    all_idx += idxs
+                res = self.backend.phase_cnv_cohort(groups, view(all_idx), params)
+                self.stats["cnv_cohort_calls"] += 1
+                for k, i in enumerate(all_idx):
                     device_lists[i] = res["lists"][k]
+            else:
+                for kid, idxs in by_kid.items():
+                    res = self.backend.phase_cnv(fams[kid], view(idxs), params)
+                    self.stats["cnv_kid_calls"] += 1
+                    for k, i in enumerate(idxs):
+                        device_lists[i] = res["lists"][k]
         for i in info["order"]:
             dn = dnms[i]
             dad_id, mom_id = pedigrees[dn["kid"]]["dad"], pedigrees[dn["kid"]]["mom"]
