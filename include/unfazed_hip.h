@@ -47,7 +47,10 @@ extern "C" {
 #define UZ_K_CNV 5         /* K6 allele-balance count + decision */
 #define UZ_K_FAMILY_PACK 6 /* k_family_gt_pack (+ the wide-depth gather) of uz_families_from_samples */
 #define UZ_K_CNV_DENSE 7   /* dense site lists of K6: scan of the 2n counts + k_cnv_dense */
-#define UZ_K_COUNT 8
+#define UZ_K_VCF_TABS 8    /* k_vcf_tabs: field starts of the picked sample columns (uz_samples_from_text), one launch per chunk of text */
+#define UZ_K_VCF_CELLS 9   /* k_vcf_cells: the cells parsed into the sample table's rows, one launch per chunk */
+#define UZ_K_VCF_COPY 10   /* not a kernel: the chunks' host-to-device copies on the copy stream, timed beside the two kernels */
+#define UZ_K_COUNT 11
 
 typedef struct uz_ctx uz_ctx;
 
@@ -90,6 +93,23 @@ int uz_families_from_samples(uz_ctx *ctx, int samples_id, int32_t n, const int32
 /* Any family's device columns back on the host, whatever route made it: gt [S] (complex bit included), cols [9][S] = ref depth of
  * kid, dad, mom, alt depth of the three, GQ of the three.  For parity tests of the two routes. */
 int uz_family_fetch(uz_ctx *ctx, int fam_id, uint8_t *gt, uint16_t *cols /* [9][S] */);
+/* The same sample table WITHOUT the host parsing a sample cell: the record text of a lazily decoded text VCF (unfazed_io.h:
+ * uz_vcf_decode_regions_lazy, uz_vcf_samples_text) goes up in bounded chunks cut at line ends -- chunk k + 1 copied while chunk k is parsed
+ * -- and two kernels (csrc/k_vcf.hip) read GT, AD (or RO / AO) and GQ of the picked sample columns into rows [n_pick][S] of the layout
+ * above.  Replaces gt_types / gt_ref_depths / gt_alt_depths / gt_quals of every sample at every record (informative_site_finder.py:257-260)
+ * behind `vcf(region)` (:42, :213).  pick[r]: the file's sample column of row r, in any order.  text->n_records must equal the sites table's S.
+ * The device settles only a plain grammar (csrc/vcf_cell.hpp); a record with any picked cell outside it -- or beyond a limit of the
+ * kernels' formats: a FORMAT slot above 127, a sample region of 4 GiB -- is handed back: *n_unsettled of them, listed by
+ * uz_samples_unsettled (site indices, ascending).  While there are any, the table answers uz_families_from_samples with UZ_E_STATE.
+ * uz_samples_settle takes exactly those sites, in that order, and their cells as a sample table of n sites -- uz_samples_pack of
+ * uz_vcf_record_samples: the host's own reader -- overwrites the rows there and builds the table's wide list from cells' wide list (whose
+ * wide_site indexes the n sites).  A table with no unsettled site is ready at once (and has no wide site: a depth above 32767 is never
+ * settled on the device).  The call returns when the rows are in place; the text may be freed then.
+ * Chunks are 32 MiB of text; the environment variable UZ_VCF_CHUNK_BYTES, read per call, sets another size (a line longer than a
+ * chunk gets a chunk of its own). */
+int uz_samples_from_text(uz_ctx *ctx, int sites_id, const uz_vcf_text_view *text, int32_t n_pick, const int32_t *pick, int *samples_id, int64_t *n_unsettled);
+int uz_samples_unsettled(uz_ctx *ctx, int samples_id, int64_t *site /* [n_unsettled] */);
+int uz_samples_settle(uz_ctx *ctx, int samples_id, int64_t n, const int64_t *site, const uz_samples_view *cells);
 /* A table is kept alive by the families made from it: UZ_E_STATE while one exists.  uz_sites_free frees a sites table's families
  * and then its sample tables. */
 int uz_samples_free(uz_ctx *ctx, int samples_id);

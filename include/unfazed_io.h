@@ -104,6 +104,26 @@ int uz_vcf_decode(const char *path, int threads, uz_vcf **out);
  * (`bcftools index`): its references are the header's contigs by id, a record overlaps by POS and rlen. */
 int uz_vcf_decode_regions(const char *path, const char *tbi_path, int64_t n_iv, const int32_t *ref, const int32_t *lo, const int32_t *hi,
                           int threads, uz_vcf **out);
+/* The same decode WITHOUT the sample cells: every fixed column, REF / ALT, the header and the lines as uz_vcf_decode_regions makes them, but
+ * the four genotype columns ([n_samples][n_sites]: 17 bytes per cell, more than 99 % of a cohort file's decode time) are neither allocated
+ * nor parsed -- the cohort route reads the cells on the device from the text (uz_vcf_samples_text -> unfazed_hip.h: uz_samples_from_text),
+ * replacing gt_types / gt_ref_depths / gt_alt_depths / gt_quals of every sample at every record (informative_site_finder.py:257-260) behind
+ * `vcf(region)` (:42, :213).  uz_vcf_view_get of such a table has NULL genotype columns until uz_vcf_fill_samples.  A BCF is decoded
+ * eagerly as before (uz_vcf_is_lazy: 0). */
+int uz_vcf_decode_regions_lazy(const char *path, const char *tbi_path, int64_t n_iv, const int32_t *ref, const int32_t *lo, const int32_t *hi,
+                               int threads, uz_vcf **out);
+int uz_vcf_is_lazy(const uz_vcf *h); /* 1: decoded lazily and not filled yet */
+/* The genotype columns of a lazily decoded table, from its kept text: the values of the eager decode, by the same cell reader
+ * (csrc/io_vcf_cell.hpp).  Idempotent (a filled or eagerly decoded table: nothing to do); raises what the eager decode raises, and the
+ * table stays lazy then. */
+int uz_vcf_fill_samples(uz_vcf *h, int threads);
+/* the text of a text table and its per-record sample-column offsets and FORMAT slots (uz_types.h: uz_vcf_text_view), lazy or not */
+int uz_vcf_samples_text(const uz_vcf *h, uz_vcf_text_view *out);
+/* What the eager decode holds for records rec[0 .. n_rec) and sample columns pick[0 .. n_pick): gt u8, int32 depths, f64 GQ, each
+ * [n_pick][n_rec] -- the input of uz_samples_pack for the records the device hands back (uz_samples_unsettled).  Raises what the eager
+ * decode raises (UZ_IO_E_FORMAT on an unparsable genotype allele). */
+int uz_vcf_record_samples(const uz_vcf *h, int64_t n_rec, const int64_t *rec, int32_t n_pick, const int32_t *pick, uint8_t *gt, int32_t *ref_depth,
+                          int32_t *alt_depth, double *gq);
 /* sequence names of the index, each NUL-terminated, into buf -- a text file's in the order of their first record in the file (the
  * TBI's, or the CSI's aux block), a BCF's the header's contigs by id; returns the bytes needed (call with cap 0 first) or a negative UZ_IO_E_* */
 int64_t uz_vcf_index_names(const char *path, const char *tbi_path, char *buf, int64_t cap);

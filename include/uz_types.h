@@ -178,6 +178,20 @@ typedef struct uz_samples_view {
     const int32_t *wide_alt_depth; /* [n_samples][n_wide] */
 } uz_samples_view;
 
+/* The record text of a decoded text VCF and where every record's sample columns lie in it (unfazed_io.h: uz_vcf_samples_text; taken by
+ * unfazed_hip.h: uz_samples_from_text, which parses the sample cells on the device).  HOST pointers into the decoder's table: they live
+ * as long as it does. */
+typedef struct uz_vcf_text_view {
+    const uint8_t *text;
+    int64_t text_bytes;
+    int64_t n_records;
+    int32_t n_samples;       /* sample columns the header names */
+    int32_t reserved0;
+    const uint64_t *samp_at;  /* [n_records] offset of the first byte of column 10 (the line end when the line has none) */
+    const uint64_t *line_end; /* [n_records] offset of the record's '\n' (the text's end for a last line without one) */
+    const int32_t *fmt_slot;  /* [n_records][5] FORMAT slots of GT, AD, RO, AO, GQ; -1: absent (all five on a line without a sample column) */
+} uz_vcf_text_view;
+
 /* alignment records of one BAM in file (coordinate) order */
 typedef struct uz_reads_view {
     int64_t n_segs; /* < 2^31 */

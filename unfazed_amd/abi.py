@@ -121,6 +121,14 @@ class SamplesView(C.Structure):
     ]
 
 
+class VcfTextView(C.Structure):
+    """uz_types.h: uz_vcf_text_view"""
+    _fields_ = [
+        ("text", _p), ("text_bytes", C.c_int64), ("n_records", C.c_int64), ("n_samples", C.c_int32), ("reserved0", C.c_int32),
+        ("samp_at", _p), ("line_end", _p), ("fmt_slot", _p),
+    ]
+
+
 class ReadsView(C.Structure):
     _fields_ = [
         ("n_segs", C.c_int64),

@@ -177,6 +177,7 @@ void free_family(uz_ctx *c, FamilyDev &f) {
 void free_samples(uz_ctx *c, SamplesDev &m) {
     if (m.ready) { (void)hipEventSynchronize(m.ready); (void)hipEventDestroy(m.ready); }
     uz_block_put(c, m.block);
+    uz_block_put(c, m.wide_block);
     for (DevBlock &b : m.fam_blocks) uz_block_put(c, b);
     m = SamplesDev();
 }
@@ -429,6 +430,7 @@ void uz_destroy(uz_ctx *c) {
     for (auto &f : c->fams) if (f.live) free_family(c, f);
     for (auto &m : c->samples) if (m.live) free_samples(c, m);
     c->trio_idx.release();
+    for (int b = 0; b < 2; b++) if (c->vcf_pin[b]) (void)hipHostFree(c->vcf_pin[b]);
     for (auto &s : c->sites) if (s.live) free_sites(c, s);
     for (auto &r : c->reads) if (r.live) free_reads(c, r);
     for (auto &b : c->block_pool) (void)hipFree(b.p);
@@ -823,10 +825,124 @@ int uz_samples_upload(uz_ctx *c, int sites_id, const uz_samples_view *v, int *id
     });
 }
 
+int uz_samples_from_text(uz_ctx *c, int sites_id, const uz_vcf_text_view *t, int32_t n_pick, const int32_t *pick, int *id, int64_t *n_unsettled) {
+    return guarded(c, [&] {
+        UZ_REQUIRE(t && id && n_unsettled && n_pick >= 0 && (n_pick == 0 || pick) && t->n_samples >= 0, UZ_E_ARG, "bad text view or pick list");
+        SitesDev &s = sites_of(c, sites_id);
+        UZ_REQUIRE(t->n_records == s.n, UZ_E_ARG, "the text's records are not the sites of the table");
+        UZ_REQUIRE(s.n == 0 || (t->text && t->samp_at && t->line_end && t->fmt_slot && t->text_bytes >= 0), UZ_E_ARG, "null pointer in the text view");
+        for (int32_t r = 0; r < n_pick; r++) UZ_REQUIRE(pick[r] >= 0 && pick[r] < t->n_samples, UZ_E_ARG, "picked sample column outside the file's");
+        size_t chunk = (size_t)32 << 20;
+        if (const char *e = getenv("UZ_VCF_CHUNK_BYTES")) { // (read per call: a test hook for the multi-chunk path)
+            const long long v = atoll(e);
+            if (v > 0) chunk = (size_t)v;
+        }
+        chunk = std::min<size_t>(chunk, (size_t)1 << 31);
+        const size_t n = (size_t)s.n, ns = (size_t)n_pick;
+        SamplesDev m;
+        m.live = true; m.sites_id = sites_id; m.n_samples = n_pick; m.n_wide = 0;
+        m.stride = (n + 64 + 255) & ~(size_t)255;
+        for (int pass = 0; pass < 2; pass++) {
+            Carver cv(pass ? m.block.p : nullptr);
+            m.gt = cv.take<uint8_t>(ns * m.stride);
+            m.rd = cv.take<uint16_t>(ns * m.stride); m.ad = cv.take<uint16_t>(ns * m.stride); m.gq = cv.take<uint16_t>(ns * m.stride);
+            if (!pass) m.block = uz_block_get(c, cv.off + 256);
+        }
+        try {
+            uz_vcf_parse_text(c, t, n_pick, pick, m, chunk, m.unsettled);
+        } catch (...) { uz_block_put(c, m.block); throw; }
+        m.need_settle = !m.unsettled.empty();
+        *n_unsettled = (int64_t)m.unsettled.size();
+        const int k = new_slot(c->samples);
+        c->samples[(size_t)k] = m;
+        *id = k;
+    });
+}
+
+int uz_samples_unsettled(uz_ctx *c, int samples_id, int64_t *site) {
+    return guarded(c, [&] {
+        SamplesDev &m = samples_of(c, samples_id);
+        UZ_REQUIRE(m.unsettled.empty() || site, UZ_E_ARG, "null output");
+        for (size_t k = 0; k < m.unsettled.size(); k++) site[k] = m.unsettled[k];
+    });
+}
+
+int uz_samples_settle(uz_ctx *c, int samples_id, int64_t n, const int64_t *site, const uz_samples_view *v) {
+    return guarded(c, [&] {
+        SamplesDev &m = samples_of(c, samples_id);
+        UZ_REQUIRE(n >= 0 && (n == 0 || (site && v)), UZ_E_ARG, "bad settle arguments");
+        UZ_REQUIRE(m.need_settle || n == 0, UZ_E_STATE, "the sample table has no unsettled sites");
+        UZ_REQUIRE((size_t)n == m.unsettled.size() && std::equal(m.unsettled.begin(), m.unsettled.end(), site), UZ_E_ARG,
+                   "uz_samples_settle takes exactly the sites of uz_samples_unsettled, in that order");
+        if (n == 0) return;
+        const size_t un = (size_t)n, ns = (size_t)m.n_samples, w = (size_t)v->n_wide;
+        UZ_REQUIRE(v->n_samples == m.n_samples && v->n_wide >= 0, UZ_E_ARG, "the cells are not a sample table of the table's rows");
+        UZ_REQUIRE(!ns || (v->gt && v->ref_depth && v->alt_depth && v->gq), UZ_E_ARG, "null column pointer");
+        UZ_REQUIRE(!w || v->wide_site, UZ_E_ARG, "n_wide set but wide_site is null");
+        UZ_REQUIRE(!(w && ns) || (v->wide_ref_depth && v->wide_alt_depth), UZ_E_ARG, "null wide depth column");
+        std::vector<int64_t> wide_site(w);
+        for (size_t k = 0; k < w; k++) {
+            UZ_REQUIRE(v->wide_site[k] >= 0 && v->wide_site[k] < n && (k == 0 || v->wide_site[k] > v->wide_site[k - 1]), UZ_E_ARG,
+                       "wide_site must be ascending indices of the settled sites");
+            wide_site[k] = site[v->wide_site[k]];
+        }
+        for (size_t k = 0; k < w * ns; k++) {
+            const int32_t r = v->wide_ref_depth[k], a = v->wide_alt_depth[k];
+            UZ_REQUIRE(r >= -1 && a >= -1 && r <= (1 << 30) && a <= (1 << 30), UZ_E_RANGE, "wide depth outside [-1, 2^30]");
+        }
+        DevBlock tmp, wide;
+        try {
+            int64_t *d_site = nullptr;
+            uint8_t *d_gt = nullptr;
+            uint16_t *d_rd = nullptr, *d_ad = nullptr, *d_gq = nullptr;
+            for (int pass = 0; pass < 2; pass++) {
+                Carver cv(pass ? tmp.p : nullptr);
+                d_site = cv.take<int64_t>(un); d_gt = cv.take<uint8_t>(ns * un);
+                d_rd = cv.take<uint16_t>(ns * un); d_ad = cv.take<uint16_t>(ns * un); d_gq = cv.take<uint16_t>(ns * un);
+                if (!pass) tmp = uz_block_get(c, cv.off + 256);
+            }
+            UZ_HIP(hipMemcpyAsync(d_site, site, un * 8, hipMemcpyHostToDevice, c->stream));
+            if (ns) {
+                UZ_HIP(hipMemcpyAsync(d_gt, v->gt, ns * un, hipMemcpyHostToDevice, c->stream));
+                UZ_HIP(hipMemcpyAsync(d_rd, v->ref_depth, ns * un * 2, hipMemcpyHostToDevice, c->stream));
+                UZ_HIP(hipMemcpyAsync(d_ad, v->alt_depth, ns * un * 2, hipMemcpyHostToDevice, c->stream));
+                UZ_HIP(hipMemcpyAsync(d_gq, v->gq, ns * un * 2, hipMemcpyHostToDevice, c->stream));
+            }
+            uz_launch_vcf_settle(c, n, m.n_samples, d_site, d_gt, d_rd, d_ad, d_gq, m);
+            if (w) {
+                int64_t *ws = nullptr;
+                int32_t *wr = nullptr, *wa = nullptr;
+                for (int pass = 0; pass < 2; pass++) {
+                    Carver cv(pass ? wide.p : nullptr);
+                    ws = cv.take<int64_t>(w); wr = cv.take<int32_t>(ns * w); wa = cv.take<int32_t>(ns * w);
+                    if (!pass) wide = uz_block_get(c, cv.off + 256);
+                }
+                UZ_HIP(hipMemcpyAsync(ws, wide_site.data(), w * 8, hipMemcpyHostToDevice, c->stream));
+                if (ns) {
+                    UZ_HIP(hipMemcpyAsync(wr, v->wide_ref_depth, ns * w * 4, hipMemcpyHostToDevice, c->stream));
+                    UZ_HIP(hipMemcpyAsync(wa, v->wide_alt_depth, ns * w * 4, hipMemcpyHostToDevice, c->stream));
+                }
+                m.wide_site = ws; m.wide_rd = wr; m.wide_ad = wa;
+            }
+            UZ_HIP(hipStreamSynchronize(c->stream)); // (the host arrays are the caller's)
+        } catch (...) {
+            (void)hipStreamSynchronize(c->stream);
+            uz_block_put(c, tmp); uz_block_put(c, wide);
+            m.wide_site = nullptr; m.wide_rd = m.wide_ad = nullptr;
+            throw;
+        }
+        uz_block_put(c, tmp);
+        m.wide_block = wide;
+        m.n_wide = (int64_t)w;
+        m.need_settle = false;
+    });
+}
+
 int uz_families_from_samples(uz_ctx *c, int samples_id, int32_t n, const int32_t *kid, const int32_t *dad, const int32_t *mom, int *fam_ids) {
     return guarded(c, [&] {
         UZ_REQUIRE(n >= 0 && (n == 0 || (kid && dad && mom && fam_ids)), UZ_E_ARG, "bad trio list");
         SamplesDev &m0 = samples_of(c, samples_id);
+        UZ_REQUIRE(!m0.need_settle, UZ_E_STATE, "the sample table has unsettled sites: uz_samples_settle first");
         UZ_REQUIRE(m0.sites_id >= 0 && m0.sites_id < (int)c->sites.size() && c->sites[(size_t)m0.sites_id].live, UZ_E_ARG, "the sample table's sites table is gone");
         std::vector<int32_t> trio((size_t)n * 3);
         for (int32_t t = 0; t < n; t++) {

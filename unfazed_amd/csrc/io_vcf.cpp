@@ -15,6 +15,7 @@
 
 #include "io_common.hpp"
 #include "io_index.hpp"
+#include "io_vcf_cell.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -42,87 +43,21 @@ struct uz_vcf {
     std::vector<uint32_t> n_info;
     std::vector<std::string> dict;     // BCF: FILTER / INFO / FORMAT string dictionary
     int64_t io_stats[4] = {0, 0, 0, 0}; // compressed bytes read, BGZF blocks inflated (region decode), lines walked, records kept
+    // Text tables: where every record's sample columns lie and how they are read -- the absolute offset of the first byte of column 10 (the
+    // line end when the line has none), the line end, and the FORMAT slots of GT, AD, RO, AO, GQ (-1: absent, or no sample column to read).
+    // A lazily decoded table (uz_vcf_decode_regions_lazy) keeps these INSTEAD of the four genotype columns, which uz_vcf_fill_samples
+    // makes from them when someone asks.
+    std::vector<uint64_t> samp_at, line_end;
+    std::vector<int32_t> fmt_slot; // [n][5]
+    bool lazy = false;             // the genotype columns have not been filled
+    std::mutex fill_mu;
 };
 
 namespace {
 
-struct Str {
-    const char *p;
-    size_t n;
-    bool eq(const char *s) const { return strlen(s) == n && memcmp(p, s, n) == 0; }
-};
-
-// Python int(x) for the plain forms a VCF holds: optional sign, decimal digits
-bool parse_int(Str s, long long &out) {
-    if (s.n == 0 || s.n > 18) return false;
-    size_t i = 0;
-    bool neg = false;
-    if (s.p[0] == '-' || s.p[0] == '+') { neg = s.p[0] == '-'; i = 1; }
-    if (i >= s.n) return false;
-    long long v = 0;
-    for (; i < s.n; i++) {
-        if (s.p[i] < '0' || s.p[i] > '9') return false;
-        v = v * 10 + (s.p[i] - '0');
-    }
-    out = neg ? -v : v;
-    return true;
-}
-
-long long num_int(Str s) { // io_vcf._num(x, int): "." / "" / unparsable -> -1
-    long long v;
-    if (s.n == 0 || s.eq(".")) return -1;
-    return parse_int(s, v) ? v : -1;
-}
-
-double num_float(Str s) { // io_vcf._num(x, float, -1.0)
-    if (s.n == 0 || s.eq(".") || s.n > 63) return -1.0;
-    char buf[64];
-    memcpy(buf, s.p, s.n);
-    buf[s.n] = 0;
-    char *e = nullptr;
-    const double v = strtod(buf, &e);
-    if (e == buf || *e != 0) return -1.0;
-    return v;
-}
-
-// k-th ':'-separated piece of a sample column (or of FORMAT)
-bool piece(Str col, int k, Str &out) {
-    const char *p = col.p, *end = col.p + col.n;
-    for (int i = 0;; i++) {
-        const char *q = (const char *)memchr(p, ':', (size_t)(end - p));
-        const char *stop = q ? q : end;
-        if (i == k) { out = Str{p, (size_t)(stop - p)}; return true; }
-        if (!q) return false;
-        p = q + 1;
-    }
-}
-
-int parse_gt(Str g) {
-    if (g.eq(".") || g.eq("./.") || g.eq(".|.")) return UZ_GT_UNKNOWN;
-    long long al[2] = {-1, -1};
-    int na = 0;
-    const char *p = g.p, *end = g.p + g.n;
-    while (p <= end) {
-        const char *q = p;
-        while (q < end && *q != '/' && *q != '|') q++;
-        if (na < 2) {
-            const Str a{p, (size_t)(q - p)};
-            long long v = -1;
-            if (!a.eq(".")) { if (!parse_int(a, v)) fail(UZ_IO_E_FORMAT, "unparsable genotype allele '%.*s'", (int)a.n, a.p); }
-            al[na] = v;
-        }
-        na++;
-        if (q >= end) break;
-        p = q + 1;
-    }
-    if (na == 1) return al[0] < 0 ? UZ_GT_UNKNOWN : (al[0] == 0 ? 0 : 3);
-    const long long a = al[0], b = al[1];
-    if (a < 0 && b < 0) return UZ_GT_UNKNOWN;
-    if (a < 0 || b < 0) { const long long c = b < 0 ? a : b; return c == 0 ? 0 : 1; }
-    if (a != b) return 1;
-    return a == 0 ? 0 : 3;
-}
-
+using uzcell::Str;
+using uzcell::parse_int;
+using uzcell::piece;
 
 // ------------------------------------------------------------------ BCF2
 struct BcfVal { // one typed value: `n` elements of `type` at `p`
@@ -380,7 +315,7 @@ void decode_bcf(uz_vcf &V, int threads) {
     V.contig_off.push_back(n);
 }
 
-void decode_text(uz_vcf &V, int threads);
+void decode_text(uz_vcf &V, int threads, bool lazy = false);
 
 void decode(uz_vcf &V, const char *path, int threads) {
     {
@@ -582,7 +517,7 @@ RegionIndex load_region_index(const char *path, const char *idx_path, int thread
 }
 
 void decode_regions(uz_vcf &V, const char *path, const char *tbi_path, int64_t n_iv, const int32_t *iv_ref, const int32_t *iv_lo,
-                    const int32_t *iv_hi, int threads) {
+                    const int32_t *iv_hi, int threads, bool lazy = false) {
     const RegionIndex tbi = load_region_index(path, tbi_path, threads);
     const int32_t n_ref = (int32_t)tbi.n_refs();
     std::vector<std::vector<Iv>> ivs((size_t)n_ref);
@@ -767,11 +702,68 @@ void decode_regions(uz_vcf &V, const char *path, const char *tbi_path, int64_t n
         });
     } catch (...) { inflateEnd(&z); throw; }
     inflateEnd(&z);
-    decode_text(V, threads);
+    decode_text(V, threads, lazy);
     V.io_stats[0] = file_bytes; V.io_stats[1] = blocks; V.io_stats[2] = walked; V.io_stats[3] = kept;
 }
 
-void decode_text(uz_vcf &V, int threads) {
+// The sample columns of record i in file order, the line walked once: fn(s, column) for every sample s the header names (a column the
+// line is too short for reads as ".")
+template <typename F>
+void each_sample_col(const uz_vcf &V, int64_t i, F fn) {
+    const char *T = (const char *)V.text.data();
+    const char *p = T + V.samp_at[(size_t)i], *e = T + V.line_end[(size_t)i];
+    bool more = true;
+    for (size_t s = 0; s < V.samples.size(); s++) {
+        Str col{".", 1};
+        if (more) {
+            const char *tb = (const char *)memchr(p, '\t', (size_t)(e - p));
+            col = Str{p, (size_t)((tb ? tb : e) - p)};
+            more = tb != nullptr;
+            if (tb) p = tb + 1;
+        }
+        fn(s, col);
+    }
+}
+// one cell into the decoder's value types: the one place the host reads a genotype cell (uzcell::sample_cell) -- the eager decode,
+// uz_vcf_fill_samples and uz_vcf_record_samples all come through here
+void read_cell(const uz_vcf &V, int64_t i, Str col, uint8_t &gt, int32_t &rd, int32_t &ad, double &gq) {
+    const int32_t *f = &V.fmt_slot[(size_t)i * 5];
+    const int slot[5] = {f[0], f[1], f[2], f[3], f[4]};
+    try {
+        uzcell::sample_cell(col, slot, gt, rd, ad, gq);
+    } catch (const uzcell::BadAllele &b) {
+        fail(UZ_IO_E_FORMAT, "unparsable genotype allele '%.*s'", (int)b.text.size(), b.text.data());
+    }
+}
+// all sample columns of records [lo, hi) into the four genotype columns
+void fill_records(uz_vcf &V, int64_t lo, int64_t hi) {
+    const size_t un = (size_t)V.n;
+    for (int64_t i = lo; i < hi; i++) {
+        const int32_t *f = &V.fmt_slot[(size_t)i * 5];
+        if (f[0] < 0 && f[1] < 0 && f[2] < 0 && f[3] < 0 && f[4] < 0) continue; // (the columns hold their defaults)
+        each_sample_col(V, i, [&](size_t s, Str col) {
+            const size_t o = s * un + (size_t)i;
+            read_cell(V, i, col, V.gt[o], V.ref_depth[o], V.alt_depth[o], V.gq[o]);
+        });
+    }
+}
+void fill_samples(uz_vcf &V, int threads) {
+    std::lock_guard<std::mutex> g(V.fill_mu);
+    if (!V.lazy) return;
+    const size_t un = (size_t)V.n, ns = V.samples.size();
+    V.gt.assign(ns * un, UZ_GT_UNKNOWN);
+    V.ref_depth.assign(ns * un, -1); V.alt_depth.assign(ns * un, -1);
+    V.gq.assign(ns * un, -1.0);
+    try {
+        parallel_slices(V.n, workers_for(V.n, threads, 256), [&](int64_t lo, int64_t hi, int) { fill_records(V, lo, hi); });
+    } catch (...) {
+        V.gt.clear(); V.ref_depth.clear(); V.alt_depth.clear(); V.gq.clear();
+        throw;
+    }
+    V.lazy = false;
+}
+
+void decode_text(uz_vcf &V, int threads, bool lazy) {
     const char *T = (const char *)V.text.data();
     const size_t N = V.text.size();
     if (N >= 5 && memcmp(T, "BCF\2", 4) == 0) { decode_bcf(V, threads); return; }
@@ -832,9 +824,13 @@ void decode_text(uz_vcf &V, int threads) {
     V.line_len.resize(un); V.ref_at.resize(un); V.ref_len.resize(un); V.alt_at.resize(un); V.alt_len.resize(un);
     V.chrom_len.resize(un);
     V.pos.resize(un); V.end.resize(un); V.sflags.resize(un); V.ref_base.resize(un); V.alt_base.resize(un);
-    V.gt.assign(ns * un, UZ_GT_UNKNOWN);
-    V.ref_depth.assign(ns * un, -1); V.alt_depth.assign(ns * un, -1);
-    V.gq.assign(ns * un, -1.0);
+    V.samp_at.resize(un); V.line_end.resize(un); V.fmt_slot.assign(un * 5, -1);
+    V.lazy = lazy;
+    if (!lazy) {
+        V.gt.assign(ns * un, UZ_GT_UNKNOWN);
+        V.ref_depth.assign(ns * un, -1); V.alt_depth.assign(ns * un, -1);
+        V.gq.assign(ns * un, -1.0);
+    }
     parallel_slices(n, threads, [&](int64_t lo, int64_t hi, int) {
         std::vector<Str> f;
         for (int64_t i = lo; i < hi; i++) {
@@ -898,41 +894,15 @@ void decode_text(uz_vcf &V, int threads) {
             V.sflags[(size_t)i] = cx ? UZ_SF_COMPLEX : 0;
             V.ref_base[(size_t)i] = cx || ref.n != 1 ? 0 : (uint8_t)ref.p[0];
             V.alt_base[(size_t)i] = cx || alt.n != 1 ? 0 : (uint8_t)alt.p[0];
-            if (ns == 0 || f.size() <= 8) continue;
-            // FORMAT keys: the last occurrence of a key wins
-            int k_gt = -1, k_ad = -1, k_ro = -1, k_ao = -1, k_gq = -1;
-            {
-                Str pc;
-                for (int k = 0; piece(f[8], k, pc); k++) {
-                    if (pc.eq("GT")) k_gt = k; else if (pc.eq("AD")) k_ad = k; else if (pc.eq("RO")) k_ro = k;
-                    else if (pc.eq("AO")) k_ao = k; else if (pc.eq("GQ")) k_gq = k;
-                }
-            }
-            for (size_t s = 0; s < ns; s++) {
-                const Str col = 9 + s < f.size() ? f[9 + s] : Str{".", 1};
-                const size_t o = s * un + (size_t)i;
-                Str v;
-                if (k_gt >= 0 && piece(col, k_gt, v)) V.gt[o] = (uint8_t)parse_gt(v);
-                bool ad_done = false;
-                if (k_ad >= 0 && piece(col, k_ad, v) && !v.eq(".")) {
-                    const char *cm = (const char *)memchr(v.p, ',', v.n);
-                    const Str a0{v.p, cm ? (size_t)(cm - v.p) : v.n};
-                    V.ref_depth[o] = (int32_t)num_int(a0);
-                    if (cm) {
-                        const char *c2 = (const char *)memchr(cm + 1, ',', (size_t)(v.p + v.n - cm - 1));
-                        const Str a1{cm + 1, c2 ? (size_t)(c2 - cm - 1) : (size_t)(v.p + v.n - cm - 1)};
-                        V.alt_depth[o] = (int32_t)num_int(a1);
-                    } else V.alt_depth[o] = -1;
-                    ad_done = true;
-                }
-                Str ro, ao;
-                if (!ad_done && k_ro >= 0 && k_ao >= 0 && piece(col, k_ro, ro) && piece(col, k_ao, ao)) {
-                    V.ref_depth[o] = (int32_t)num_int(ro);
-                    const char *cm = (const char *)memchr(ao.p, ',', ao.n);
-                    V.alt_depth[o] = (int32_t)num_int(Str{ao.p, cm ? (size_t)(cm - ao.p) : ao.n});
-                }
-                if (k_gq >= 0 && piece(col, k_gq, v)) V.gq[o] = num_float(v);
-            }
+            // where the sample columns lie, and the FORMAT keys they are read by (uzcell::format_slots: the last occurrence of a key wins).  A
+            // line without a sample column keeps no slot: every cell of it holds the defaults whatever its FORMAT says.
+            V.line_end[(size_t)i] = (uint64_t)e;
+            V.samp_at[(size_t)i] = f.size() > 9 ? (uint64_t)(f[9].p - T) : (uint64_t)e;
+            if (ns == 0 || f.size() <= 9) continue;
+            int slot[5];
+            uzcell::format_slots(f[8], slot);
+            for (int k = 0; k < 5; k++) V.fmt_slot[(size_t)i * 5 + k] = slot[k];
+            if (!lazy) fill_records(V, i, i + 1);
         }
     });
     // contigs in order of appearance; records must be grouped by contig and sorted inside one
@@ -993,6 +963,61 @@ int uz_vcf_decode_regions(const char *path, const char *tbi_path, int64_t n_iv, 
         std::unique_ptr<uz_vcf> V(new uz_vcf());
         decode_regions(*V, path, tbi_path, n_iv, ref, lo, hi, resolve_threads(threads));
         *out = V.release();
+    });
+}
+
+int uz_vcf_decode_regions_lazy(const char *path, const char *tbi_path, int64_t n_iv, const int32_t *ref, const int32_t *lo, const int32_t *hi,
+                               int threads, uz_vcf **out) {
+    return guarded([&] {
+        if (!path || !out || n_iv < 0 || (n_iv && (!ref || !lo || !hi))) fail(UZ_IO_E_ARG, "uz_vcf_decode_regions_lazy: bad arguments");
+        std::unique_ptr<uz_vcf> V(new uz_vcf());
+        decode_regions(*V, path, tbi_path, n_iv, ref, lo, hi, resolve_threads(threads), true);
+        *out = V.release();
+    });
+}
+
+int uz_vcf_is_lazy(const uz_vcf *h) { return h && h->lazy ? 1 : 0; }
+
+int uz_vcf_fill_samples(uz_vcf *h, int threads) {
+    if (!h) { last_error = "null argument"; return UZ_IO_E_ARG; }
+    return guarded([&] { fill_samples(*h, resolve_threads(threads)); });
+}
+
+int uz_vcf_samples_text(const uz_vcf *h, uz_vcf_text_view *v) {
+    if (!h || !v) { last_error = "null argument"; return UZ_IO_E_ARG; }
+    return guarded([&] {
+        if (h->is_bcf) fail(UZ_IO_E_ARG, "uz_vcf_samples_text: a BCF has no text");
+        memset(v, 0, sizeof(*v));
+        v->text = h->text.data();
+        v->text_bytes = (int64_t)h->text.size();
+        v->n_records = h->n;
+        v->n_samples = (int32_t)h->samples.size();
+        v->samp_at = h->samp_at.data(); v->line_end = h->line_end.data(); v->fmt_slot = h->fmt_slot.data();
+    });
+}
+
+int uz_vcf_record_samples(const uz_vcf *h, int64_t n_rec, const int64_t *rec, int32_t n_pick, const int32_t *pick, uint8_t *gt, int32_t *ref_depth,
+                          int32_t *alt_depth, double *gq) {
+    if (!h || n_rec < 0 || n_pick < 0 || (n_rec && !rec) || (n_pick && !pick)) { last_error = "null argument"; return UZ_IO_E_ARG; }
+    return guarded([&] {
+        if (h->is_bcf) fail(UZ_IO_E_ARG, "uz_vcf_record_samples: a BCF has no text");
+        if (n_rec && n_pick && (!gt || !ref_depth || !alt_depth || !gq)) fail(UZ_IO_E_ARG, "uz_vcf_record_samples: null output");
+        for (int32_t k = 0; k < n_pick; k++)
+            if (pick[k] < 0 || (size_t)pick[k] >= h->samples.size()) fail(UZ_IO_E_ARG, "sample index %d outside the table's %zu samples", (int)pick[k], h->samples.size());
+        // a record's columns are split once (a column is found by walking the tabs before it), the records shared among the threads
+        std::vector<int32_t> row_of(h->samples.size(), -1), next_row((size_t)n_pick, -1); // rows that picked a column: first, then chained
+        for (int32_t k = n_pick - 1; k >= 0; k--) { next_row[(size_t)k] = row_of[(size_t)pick[k]]; row_of[(size_t)pick[k]] = k; }
+        for (int64_t j = 0; j < n_rec; j++)
+            if (rec[j] < 0 || rec[j] >= h->n) fail(UZ_IO_E_ARG, "record index %lld outside the table", (long long)rec[j]);
+        parallel_slices(n_rec, workers_for(n_rec, resolve_threads(0), 64), [&](int64_t lo, int64_t hi, int) {
+            for (int64_t j = lo; j < hi; j++)
+                each_sample_col(*h, rec[j], [&](size_t s, Str col) {
+                    for (int32_t k = row_of[s]; k >= 0; k = next_row[(size_t)k]) {
+                        const size_t o = (size_t)k * (size_t)n_rec + (size_t)j;
+                        read_cell(*h, rec[j], col, gt[o], ref_depth[o], alt_depth[o], gq[o]);
+                    }
+                });
+        });
     });
 }
 

@@ -163,6 +163,12 @@ struct SamplesDev {
     int32_t *wide_rd = nullptr, *wide_ad = nullptr; // [n_samples][n_wide]
     hipEvent_t ready = nullptr; // end of the copies on the copy stream; the first uz_families_from_samples makes the compute stream wait for it
     bool pending = false;
+    // a table parsed from the text on the device (uz_samples_from_text): the sites handed back to the host's reader, ascending; while
+    // need_settle the rows of those sites are void and the table makes no family (uz_samples_settle overwrites them and brings the wide
+    // list, which lies in a block of its own: its size is known only then)
+    std::vector<int64_t> unsettled;
+    bool need_settle = false;
+    DevBlock wide_block;
 };
 
 // the fixed-width columns of a table as DEVICE pointers (staged by an upload, or the caller's for an adopted table)
@@ -312,6 +318,8 @@ struct uz_ctx {
     std::vector<ReadsDev> reads;
     std::vector<SamplesDev> samples;
     DevBuf<int32_t> trio_idx; // uz_families_from_samples: kid / dad / mom sample indices of the batch's trios
+    uint8_t *vcf_pin[2] = {nullptr, nullptr}; // uz_samples_from_text: the two page-locked chunk images, kept from call to call
+    size_t vcf_pin_cap[2] = {0, 0};
 
     // allele-balance threshold table of K1 (k_sites.hip), rebuilt when the thresholds change
     DevBuf<int32_t> ab_lut;
@@ -474,6 +482,11 @@ void uz_sites_expand(uz_ctx *c, SitesDev &s, FamilyDev *f);
 // n trios of a sample table: packed genotype bytes (complex bit folded in) and the members' depths at the table's wide sites, one launch each;
 // trio: [3 n] sample indices on the device; gt_out / wide_out: trio t at t * gt_stride bytes / t * 6 * n_wide values
 void uz_launch_family_pack(uz_ctx *c, const SamplesDev &sm, const SitesDev &s, int32_t n, const int32_t *trio, uint8_t *gt_out, size_t gt_stride, int32_t *wide_out);
+// the sample cells of a text VCF parsed into the rows of `m` (k_vcf.hip): chunks of at most chunk_bytes of text, cut at line ends; -> the records
+// handed back to the host, ascending.  uz_launch_vcf_settle: their cells ([n_rows][n], device memory) over the rows
+void uz_vcf_parse_text(uz_ctx *c, const uz_vcf_text_view *t, int32_t n_pick, const int32_t *pick, SamplesDev &m, size_t chunk_bytes, std::vector<int64_t> &unsettled);
+void uz_launch_vcf_settle(uz_ctx *c, int64_t n, int32_t n_rows, const int64_t *site, const uint8_t *gt_in, const uint16_t *rd_in, const uint16_t *ad_in,
+                          const uint16_t *gq_in, SamplesDev &m);
 void uz_launch_site_scan(uz_ctx *c, FamilyDev &f, const SitesDev &s, bool with_cnv);
 void uz_launch_site_scan_many(uz_ctx *c, FamilyDev *const *fams, int n_fam, const SitesDev &s, bool with_cnv);
 void uz_launch_find(uz_ctx *c, FamilyDev &f, const SitesDev &s, int mode, bool host_offsets = true);

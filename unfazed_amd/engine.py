@@ -16,10 +16,11 @@ LIB_PATH = os.environ.get("UZ_HIP_LIB", os.path.join(_HERE, "libunfazed_hip.so")
 
 SIZING_REDUCED_WORDS = 263  # unfazed_hip.h UZ_SIZING_REDUCED_WORDS
 K_SITE_SCAN, K_WINDOW_COUNT, K_WINDOW_FILL, K_PHASE, K_SIZING, K_CNV, K_FAMILY_PACK, K_CNV_DENSE = 0, 1, 2, 3, 4, 5, 6, 7
+K_VCF_TABS, K_VCF_CELLS, K_VCF_COPY = 8, 9, 10  # uz_samples_from_text: the two kernels and (not a kernel) the chunks' copies
 
 EXPORTS = [
     "uz_create", "uz_destroy", "uz_last_error", "uz_sync", "uz_set_params",
-    "uz_sites_upload", "uz_family_upload", "uz_sites_family_upload_async", "uz_samples_upload", "uz_families_from_samples", "uz_family_fetch", "uz_samples_free", "uz_reads_upload", "uz_reads_upload_packed", "uz_reads_wait", "uz_reads_headers", "uz_bgzf_inflate", "uz_bgzf_inflate_to_host", "uz_bam_walk", "uz_crc32_blocks", "uz_bam_walk_fetch", "uz_bam_walk_release", "uz_reads_from_bam",
+    "uz_sites_upload", "uz_family_upload", "uz_sites_family_upload_async", "uz_samples_upload", "uz_samples_from_text", "uz_samples_unsettled", "uz_samples_settle", "uz_families_from_samples", "uz_family_fetch", "uz_samples_free", "uz_reads_upload", "uz_reads_upload_packed", "uz_reads_wait", "uz_reads_headers", "uz_bgzf_inflate", "uz_bgzf_inflate_to_host", "uz_bam_walk", "uz_crc32_blocks", "uz_bam_walk_fetch", "uz_bam_walk_release", "uz_reads_from_bam",
     "uz_bam_walk_flags", "uz_bam_join", "uz_bam_join_needs", "uz_bam_join_fetch", "uz_reads_from_walk", "uz_reads_names", "uz_walk_slot_stats", "uz_walk_reserve",
     "uz_pinned_alloc", "uz_pinned_free",
     "uz_sites_adopt_device", "uz_family_adopt_device", "uz_reads_adopt_device",
@@ -83,6 +84,9 @@ def load_library(path: Optional[str] = None):
     L.uz_sites_family_upload_async.argtypes = [vp, vp, vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.uz_samples_upload.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int)]
     L.uz_families_from_samples.argtypes = [vp, C.c_int, C.c_int32, vp, vp, vp, vp]
+    L.uz_samples_from_text.argtypes = [vp, C.c_int, vp, C.c_int32, vp, C.POINTER(C.c_int), C.POINTER(C.c_int64)]
+    L.uz_samples_unsettled.argtypes = [vp, C.c_int, vp]
+    L.uz_samples_settle.argtypes = [vp, C.c_int, C.c_int64, vp, vp]
     L.uz_family_fetch.argtypes = [vp, C.c_int, vp, vp]
     L.uz_samples_free.argtypes = [vp, C.c_int]
     L.uz_drop_derived.argtypes = [vp]
@@ -198,6 +202,46 @@ class HipEngine:
         self._samples = getattr(self, "_samples", {})
         self._samples[mid.value] = (int(sites_h), v)
         return mid.value
+
+    def samples_from_text(self, sites_h: int, table, pick, settle: bool = True):
+        """The sample table of a natively decoded text VCF without the host parsing its sample cells: the table's record text goes to the
+        device in chunks and two kernels read GT, AD (or RO / AO) and GQ of the sample columns `pick` (indices into table.samples) into the
+        rows (uz_samples_from_text).  The records the device will not vouch for come back (uz_samples_unsettled) and are read by the host's
+        own reader -- io_native.vcf_record_samples, then pack_samples: errors are the eager decode's -- and settled (uz_samples_settle).
+            -> (handle, number of sites handed back).  settle=False leaves the round trip to the caller (settle_samples)."""
+        from . import io_native
+        pick = np.ascontiguousarray(pick, np.int32)
+        text = io_native.vcf_samples_text(table)
+        mid, nu = C.c_int(-1), C.c_int64(0)
+        self._ck(self.L.uz_samples_from_text(self.h, int(sites_h), C.byref(text), int(pick.size), pick.ctypes.data, C.byref(mid), C.byref(nu)), "uz_samples_from_text")
+        self._samples = getattr(self, "_samples", {})
+        self._samples[mid.value] = (int(sites_h), None)
+        if settle and nu.value:
+            try:
+                self.settle_samples(mid.value, table, pick, nu.value)
+            except Exception:
+                self.free_samples(mid.value)
+                raise
+        return mid.value, int(nu.value)
+
+    def unsettled_sites(self, samples_h: int, n: int):
+        """the n sites a table made by samples_from_text handed back, ascending"""
+        site = np.zeros(max(1, int(n)), np.int64)
+        self._ck(self.L.uz_samples_unsettled(self.h, int(samples_h), site.ctypes.data), "uz_samples_unsettled")
+        return site[: int(n)]
+
+    def settle_samples(self, samples_h: int, table, pick, n: int) -> None:
+        """the n handed-back sites of a table made by samples_from_text, read by the host's reader and written over the device's rows"""
+        from . import io_native
+        from .model import SampleColumns, SitesTable
+        pick = np.ascontiguousarray(pick, np.int32)
+        site = self.unsettled_sites(samples_h, n)
+        sub = SitesTable(["row%d" % r for r in range(pick.size)], [])  # the decoder's columns of those sites alone, rows in pick order
+        sub.pos = np.zeros(site.size, np.int32)
+        sub.gt, sub.ref_depth, sub.alt_depth, sub.gq = io_native.vcf_record_samples(table, site, pick)
+        cols = SampleColumns(list(sub.samples), *io_native.pack_samples(sub, np.arange(pick.size)))
+        v = abi.samples_view(cols)
+        self._ck(self.L.uz_samples_settle(self.h, int(samples_h), int(site.size), site.ctypes.data, v.ref()), "uz_samples_settle")
 
     def families_from_samples(self, samples_h: int, kid, dad, mom) -> list:
         """the trios (kid[t], dad[t], mom[t]) -- sample indices of the table -- as families, one launch sequence (uz_families_from_samples)"""

@@ -181,11 +181,18 @@ class _VoteLists:
         return np.unique(self.vv[idx].astype(np.int64))
 
 
+def samples_route() -> str:
+    """UZ_SAMPLES_ROUTE: "device" (default) -- the sample cells of a cohort batch's text VCF are parsed on the device from the record text
+    (session.lazy_samples, PhasingHost.prepare_families); "host" -- the decoder parses them and the packed columns are uploaded"""
+    return "host" if __import__("os").environ.get("UZ_SAMPLES_ROUTE", "device").lower() == "host" else "device"
+
+
 class _Stats(dict):
     """PhasingHost.stats: the counters of calls a host has not made yet (find_cohort_calls, find_kid_calls, cnv_cohort_calls,
-    cnv_kid_calls) read as 0 and are entered by their first increment"""
+    cnv_kid_calls, and samples_parsed_device / sites_unsettled of the sample tables the device parsed from the text) read as 0 and are
+    entered by their first increment"""
 
-    ROUTE_KEYS = ("find_cohort_calls", "find_kid_calls", "cnv_cohort_calls", "cnv_kid_calls")
+    ROUTE_KEYS = ("find_cohort_calls", "find_kid_calls", "cnv_cohort_calls", "cnv_kid_calls", "samples_parsed_device", "sites_unsettled")
 
     def __missing__(self, key):
         if key in self.ROUTE_KEYS:
@@ -232,6 +239,8 @@ class PhasingHost:
         trios are made there in one call (uz_families_from_samples) -- instead of a dozen numpy passes and ten blocking copies per trio,
         a shared parent converted once per sibling.  A trio whose three members lie in a table of an earlier call is made from that
         table; the others' samples form a new table (a member they share with an older table travels again with it).
+        A table whose sample cells were left unparsed (a lazily decoded text VCF) gets its sample table from the text on the device
+        (samples_from_text) instead of sample_columns + upload_samples.
         UZ_FAMILY_ROUTE=host, a single kid, or a backend without sample tables: family() makes them one by one, as before."""
         trios = list(dict.fromkeys(trios))
         if len({t[0] for t in trios}) < 2 or not hasattr(self.backend, "upload_samples") or __import__("os").environ.get("UZ_FAMILY_ROUTE", "device") == "host":
@@ -250,8 +259,15 @@ class PhasingHost:
                 rest.append(t)
         if rest:
             names = list(dict.fromkeys(s for t in rest for s in t))
-            cols = self.sites.sample_columns(names)
-            self._sample_tabs.append((self.backend.upload_samples(self._sites_h, cols), {s: r for r, s in enumerate(names)}))
+            if getattr(self.sites, "genotypes_deferred", False) and hasattr(self.backend, "samples_from_text") and samples_route() == "device":
+                # a lazily decoded text VCF (session.host_for): the device reads the sample cells from the record text, and the host's reader
+                # only the records it hands back -- the table's own genotype columns are never made
+                h, n_back = self.backend.samples_from_text(self._sites_h, self.sites, [self.sites.samples.index(s) for s in names])
+                self.stats["samples_parsed_device"] += len(names)
+                self.stats["sites_unsettled"] += n_back
+            else:
+                h = self.backend.upload_samples(self._sites_h, self.sites.sample_columns(names))
+            self._sample_tabs.append((h, {s: r for r, s in enumerate(names)}))
             self.stats["sample_tables"] += 1
             self.stats["samples_uploaded"] += len(names)
             by_tab[len(self._sample_tabs) - 1] = rest

@@ -35,6 +35,7 @@ IO_EXPORTS = [
     "uz_index_summary", "uz_inflate_backend", "uz_io_default_threads", "uz_io_cpu_quota", "uz_bam_stage_plan", "uz_bam_stage_begin", "uz_bam_stage_finish", "uz_stage_gather_blocks", "uz_stage_set_inflated", "uz_stage_sizes", "uz_stage_io_stats", "uz_stage_timing", "uz_stage_fill", "uz_stage_qname", "uz_stage_qnames",
     "uz_stage_free", "uz_stage_walk_plan_sizes", "uz_stage_walk_plan", "uz_bam_stage_finish_desc", "uz_stage_kept_sizes", "uz_stage_kept", "uz_stage_walk_host", "uz_stage_kept_debug", "uz_stage_name_records", "uz_packed_block_sums", "uz_stage_merge_subtasks", "uz_bam_stage_finish_sub",
     "uz_stage_walk_flagged", "uz_stage_lookup", "uz_stage_extra", "uz_stage_n_lookup_tasks", "uz_sites_pack", "uz_sites_unpack", "uz_samples_pack",
+    "uz_vcf_decode_regions_lazy", "uz_vcf_is_lazy", "uz_vcf_fill_samples", "uz_vcf_samples_text", "uz_vcf_record_samples",
 ]
 
 
@@ -87,6 +88,11 @@ def load():
     lib.uz_bam_timing.restype = None
     lib.uz_vcf_decode.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
     lib.uz_vcf_decode_regions.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+    lib.uz_vcf_decode_regions_lazy.argtypes = lib.uz_vcf_decode_regions.argtypes
+    lib.uz_vcf_is_lazy.argtypes = [C.c_void_p]
+    lib.uz_vcf_fill_samples.argtypes = [C.c_void_p, C.c_int]
+    lib.uz_vcf_samples_text.argtypes = [C.c_void_p, C.POINTER(abi.VcfTextView)]
+    lib.uz_vcf_record_samples.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.uz_vcf_index_names.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_int64]
     lib.uz_vcf_index_names.restype = C.c_int64
     lib.uz_vcf_io_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
@@ -421,18 +427,21 @@ def tabix_contigs(path: str, tbi: str = None) -> list:
     return [x.decode() for x in buf.raw[: int(n)].split(b"\0")[:-1]]
 
 
-def read_vcf_table_regions(path: str, ref, lo, hi, threads: int = 0, tbi: str = None) -> SitesTable:
+def read_vcf_table_regions(path: str, ref, lo, hi, threads: int = 0, tbi: str = None, lazy: bool = False) -> SitesTable:
     """Index-driven decode: the records overlapping the intervals [lo[k], hi[k]) (0-based) of sequence ref[k] (an index into
     tabix_contigs) -- what cyvcf2's vcf(region) hands the reference, without inflating the rest of the file.  `.io_stats`:
-    compressed bytes read, BGZF blocks inflated, lines walked, records kept."""
+    compressed bytes read, BGZF blocks inflated, lines walked, records kept.
+    lazy: the sample cells are not parsed (uz_vcf_decode_regions_lazy) -- the table's gt / ref_depth / alt_depth / gq are made on their first
+    access (uz_vcf_fill_samples), and a table that is never asked never pays; `samples_text` / `record_samples` serve the device route."""
     lib = load()
     ref = np.ascontiguousarray(ref, np.int32)
     lo = np.ascontiguousarray(lo, np.int32)
     hi = np.ascontiguousarray(hi, np.int32)
     hp = C.c_void_p()
-    _check(lib, lib.uz_vcf_decode_regions(os.fsencode(path), os.fsencode(tbi) if tbi else None, int(ref.size), ref.ctypes.data,
-                                          lo.ctypes.data, hi.ctypes.data, int(threads), C.byref(hp)))
-    t = _vcf_table_from_handle(lib, _Handle(hp.value, lib.uz_vcf_free))
+    decode = lib.uz_vcf_decode_regions_lazy if lazy else lib.uz_vcf_decode_regions
+    _check(lib, decode(os.fsencode(path), os.fsencode(tbi) if tbi else None, int(ref.size), ref.ctypes.data,
+                       lo.ctypes.data, hi.ctypes.data, int(threads), C.byref(hp)))
+    t = _vcf_table_from_handle(lib, _Handle(hp.value, lib.uz_vcf_free), threads=threads)
     names = tabix_contigs(path, tbi)
     # utils.py:46-52 get_prefix: the first record of the FILE decides, not the first record of this subset
     t.file_prefix = (names[0][:3] if "chr" in names[0].lower() else "") if names else ""
@@ -448,7 +457,28 @@ def read_vcf_table(path: str, threads: int = 0) -> SitesTable:
     return _vcf_table_from_handle(lib, _Handle(hp.value, lib.uz_vcf_free))
 
 
-def _vcf_table_from_handle(lib, h) -> SitesTable:
+def vcf_samples_text(table: SitesTable) -> "abi.VcfTextView":
+    """the record text of a natively decoded text table and where its sample columns lie (uz_vcf_samples_text): what
+    HipEngine.samples_from_text sends to the device.  The view points into the table, which must outlive it."""
+    lib = load()
+    v = abi.VcfTextView()
+    _check(lib, lib.uz_vcf_samples_text(table._native.ptr, C.byref(v)))
+    return v
+
+
+def vcf_record_samples(table: SitesTable, rec, pick):
+    """what the eager decode holds for records `rec` and sample columns `pick` (uz_vcf_record_samples) -> gt u8 [k][r], ref_depth i32,
+    alt_depth i32, gq f64 -- without filling the table.  Raises IoError as the eager decode would (an unparsable genotype allele)."""
+    lib = load()
+    rec, pick = np.ascontiguousarray(rec, np.int64), np.ascontiguousarray(pick, np.int32)
+    k, r = int(pick.size), int(rec.size)
+    gt, rd, ad, gq = np.zeros((k, r), np.uint8), np.zeros((k, r), np.int32), np.zeros((k, r), np.int32), np.zeros((k, r), np.float64)
+    _check(lib, lib.uz_vcf_record_samples(table._native.ptr, r, rec.ctypes.data, k, pick.ctypes.data, gt.ctypes.data, rd.ctypes.data, ad.ctypes.data,
+                                          gq.ctypes.data))
+    return gt, rd, ad, gq
+
+
+def _vcf_table_from_handle(lib, h, threads: int = 0) -> SitesTable:
     v = VcfView()
     _check(lib, lib.uz_vcf_view_get(h.ptr, C.byref(v)))
     n, ns, nc = int(v.n_sites), int(v.n_samples), int(v.n_contigs)
@@ -457,10 +487,22 @@ def _vcf_table_from_handle(lib, h) -> SitesTable:
     t.contig_off = _arr(v.contig_off, nc + 1, np.int64).copy()
     t.pos, t.end = _arr(v.pos, n, np.int32), _arr(v.end, n, np.int32)
     t.sflags, t.ref_base, t.alt_base = (_arr(getattr(v, k), n, np.uint8) for k in ("sflags", "ref_base", "alt_base"))
-    t.gt = _arr(v.gt, ns * n, np.uint8).reshape(ns, n)
-    t.ref_depth = _arr(v.ref_depth, ns * n, np.int32).reshape(ns, n)
-    t.alt_depth = _arr(v.alt_depth, ns * n, np.int32).reshape(ns, n)
-    t.gq = _arr(v.gq, ns * n, np.float64).reshape(ns, n)
+
+    def genotype_columns():
+        w = VcfView()
+        _check(lib, lib.uz_vcf_view_get(h.ptr, C.byref(w)))
+        t.gt = _arr(w.gt, ns * n, np.uint8).reshape(ns, n)
+        t.ref_depth = _arr(w.ref_depth, ns * n, np.int32).reshape(ns, n)
+        t.alt_depth = _arr(w.alt_depth, ns * n, np.int32).reshape(ns, n)
+        t.gq = _arr(w.gq, ns * n, np.float64).reshape(ns, n)
+
+    if lib.uz_vcf_is_lazy(h.ptr):
+        def fill():  # first access of a genotype column (model.SitesTable): the host parses the cells after all
+            _check(lib, lib.uz_vcf_fill_samples(h.ptr, int(threads)))
+            genotype_columns()
+        t.defer_genotypes(fill)
+    else:
+        genotype_columns()
     t.ref_str = _Strings(lib.uz_vcf_ref, h, n, lambda s: s)
     t.alt_strs = _Strings(lib.uz_vcf_alt, h, n, lambda s: [] if s == "." else s.split(","))
     t.lines = _Strings(lib.uz_vcf_line, h, n, lambda s: s)

@@ -132,11 +132,43 @@ class SampleColumns:
         return self._row[name]
 
 
+def _genotype_column(name):
+    """gt / ref_depth / alt_depth / gq of a SitesTable: plain attributes, except that a lazily decoded table (defer_genotypes) makes all
+    four on the first read of any of them"""
+    key = "_" + name
+
+    def get(self):
+        fill = self.__dict__.get("_fill_genotypes")
+        if fill is not None:
+            fill()  # (sets the four columns; raises what the eager decode would have raised, and the table stays lazy then)
+            self.__dict__.pop("_fill_genotypes", None)
+        return self.__dict__[key]
+
+    def put(self, value):
+        self.__dict__[key] = value
+
+    return property(get, put)
+
+
 class SitesTable:
     """SoA columns of a decoded sites VCF (all samples), host side.
 
     Device-facing per-family columns are produced by :meth:`family_columns`.
     """
+
+    gt = _genotype_column("gt")
+    ref_depth = _genotype_column("ref_depth")
+    alt_depth = _genotype_column("alt_depth")
+    gq = _genotype_column("gq")
+
+    def defer_genotypes(self, fill) -> None:
+        """the four genotype columns are not there yet: fill() makes them (assigns all four) when one is first read"""
+        self.__dict__["_fill_genotypes"] = fill
+
+    @property
+    def genotypes_deferred(self) -> bool:
+        """True while a lazily decoded table has not been asked for a genotype column"""
+        return "_fill_genotypes" in self.__dict__
 
     def __init__(self, samples: Sequence[str], contigs: Sequence[str]):
         self.samples = list(samples)

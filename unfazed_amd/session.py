@@ -91,7 +91,18 @@ def site_regions(name, dnms, search_dist):
     return tuple(sorted(out))
 
 
-def load_sites(name_or_table, regions=None) -> (str, SitesTable):
+def lazy_samples(backend, dnms) -> bool:
+    """Should the region decode of a batch's sites file leave the sample cells unparsed?  When the batch names two or more kids and the
+    backend parses them on the device (samples_from_text): the cohort route then never reads the host's genotype columns, which are
+    more than 99 % of a cohort file's decode.  UZ_SAMPLES_ROUTE=host: the host parses them, as before.  (Only a text VCF is decoded
+    lazily -- a BCF comes back eager whatever is asked -- and any other consumer of such a table fills it on first access.)"""
+    from .hostpath import samples_route
+    if samples_route() == "host" or os.environ.get("UZ_FAMILY_ROUTE", "device") == "host":
+        return False
+    return dnms is not None and hasattr(backend, "samples_from_text") and len({dn.get("kid") for dn in dnms}) >= 2
+
+
+def load_sites(name_or_table, regions=None, lazy: bool = False) -> (str, SitesTable):
     if isinstance(name_or_table, SitesTable):
         key = "table@%d" % id(name_or_table)
         _SITES[key] = name_or_table
@@ -101,7 +112,7 @@ def load_sites(name_or_table, regions=None) -> (str, SitesTable):
         if key not in _SITES:
             from .io_native import read_vcf_table_regions
             _SITES[key] = read_vcf_table_regions(name_or_table, [r[0] for r in regions], [r[1] for r in regions],
-                                                 [r[2] for r in regions], threads=_io_threads())
+                                                 [r[2] for r in regions], threads=_io_threads(), lazy=lazy)
         return key, _SITES[key]
     if name_or_table not in _SITES:
         if _python_io():
@@ -211,8 +222,8 @@ class _LazyReads(dict):
 def host_for(sites, insert_size_max_sample: int = 1000000, dnms=None, search_dist=None) -> PhasingHost:
     """dnms + search_dist: the batch the host will serve -- a sites file with a tabix index next to it is then decoded through
     the index for the batch's windows only (one table, one host per distinct batch)"""
-    key, table = load_sites(sites, site_regions(sites, dnms, search_dist))
     backend = get_backend()
+    key, table = load_sites(sites, site_regions(sites, dnms, search_dist), lazy=lazy_samples(backend, dnms))
     hk = (key, id(backend))
     if hk not in _HOSTS:
         _HOSTS[hk] = PhasingHost(backend, table, _LazyReads(insert_size_max_sample))
