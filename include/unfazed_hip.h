@@ -50,7 +50,9 @@ extern "C" {
 #define UZ_K_VCF_TABS 8    /* k_vcf_tabs: field starts of the picked sample columns (uz_samples_from_text), one launch per chunk of text */
 #define UZ_K_VCF_CELLS 9   /* k_vcf_cells: the cells parsed into the sample table's rows, one launch per chunk */
 #define UZ_K_VCF_COPY 10   /* not a kernel: the chunks' host-to-device copies on the copy stream, timed beside the two kernels */
-#define UZ_K_COUNT 11
+#define UZ_K_BCF_CELLS 11  /* k_bcf_cells: the values of a BCF's five FORMAT fields read into the sample table's rows (uz_samples_from_bcf), one launch per chunk */
+#define UZ_K_BCF_COPY 12   /* not a kernel: the copies of that route's chunks on the copy stream */
+#define UZ_K_COUNT 13
 
 typedef struct uz_ctx uz_ctx;
 
@@ -108,6 +110,15 @@ int uz_family_fetch(uz_ctx *ctx, int fam_id, uint8_t *gt, uint16_t *cols /* [9][
  * Chunks are 32 MiB of text; the environment variable UZ_VCF_CHUNK_BYTES, read per call, sets another size (a line longer than a
  * chunk gets a chunk of its own). */
 int uz_samples_from_text(uz_ctx *ctx, int sites_id, const uz_vcf_text_view *text, int32_t n_pick, const int32_t *pick, int *samples_id, int64_t *n_unsettled);
+/* The same from a BCF (unfazed_io.h: uz_vcf_decode_regions_lazy on a .bcf + .csi, uz_vcf_samples_bcf; informative_site_finder.py:41-43, :213):
+ * a FORMAT field's values lie at a fixed stride per sample, so there is nothing to find -- only the value arrays of GT, AD, RO, AO and GQ go
+ * up, gathered back to back (each on a 4-byte boundary) with five 32-bit offsets and five descriptors per record, in chunks cut at record
+ * boundaries and bounded by UZ_VCF_CHUNK_BYTES (of gathered bytes; a record beyond it gets a chunk of its own), double buffered like the text's.
+ * One kernel per chunk (csrc/k_bcf.hip: k_bcf_cells, the body of csrc/bcf_cell.hpp) writes the rows of the same table: same stride, same block,
+ * the same uz_samples_unsettled / uz_samples_settle round trip and UZ_E_STATE until settled.  Handed back: a record with a picked cell whose
+ * depth lies above 32767 or below 0, a record with one of the five fields in a type other than int8 / int16 / int32 (float for GQ), a record
+ * whose five arrays exceed 4 GiB. */
+int uz_samples_from_bcf(uz_ctx *ctx, int sites_id, const uz_vcf_bcf_view *bcf, int32_t n_pick, const int32_t *pick, int *samples_id, int64_t *n_unsettled);
 int uz_samples_unsettled(uz_ctx *ctx, int samples_id, int64_t *site /* [n_unsettled] */);
 int uz_samples_settle(uz_ctx *ctx, int samples_id, int64_t n, const int64_t *site, const uz_samples_view *cells);
 /* A table is kept alive by the families made from it: UZ_E_STATE while one exists.  uz_sites_free frees a sites table's families

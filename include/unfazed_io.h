@@ -108,8 +108,9 @@ int uz_vcf_decode_regions(const char *path, const char *tbi_path, int64_t n_iv, 
  * the four genotype columns ([n_samples][n_sites]: 17 bytes per cell, more than 99 % of a cohort file's decode time) are neither allocated
  * nor parsed -- the cohort route reads the cells on the device from the text (uz_vcf_samples_text -> unfazed_hip.h: uz_samples_from_text),
  * replacing gt_types / gt_ref_depths / gt_alt_depths / gt_quals of every sample at every record (informative_site_finder.py:257-260) behind
- * `vcf(region)` (:42, :213).  uz_vcf_view_get of such a table has NULL genotype columns until uz_vcf_fill_samples.  A BCF is decoded
- * eagerly as before (uz_vcf_is_lazy: 0). */
+ * `vcf(region)` (:42, :213).  uz_vcf_view_get of such a table has NULL genotype columns until uz_vcf_fill_samples.  A BCF (:41-43) is
+ * decoded the same way: everything but the per-sample values, of which it keeps, per record, where the value arrays of GT, AD, RO, AO and GQ
+ * lie and their type and per-sample count (uz_vcf_samples_bcf -> uz_samples_from_bcf); every bounds check of the eager decode stays. */
 int uz_vcf_decode_regions_lazy(const char *path, const char *tbi_path, int64_t n_iv, const int32_t *ref, const int32_t *lo, const int32_t *hi,
                                int threads, uz_vcf **out);
 int uz_vcf_is_lazy(const uz_vcf *h); /* 1: decoded lazily and not filled yet */
@@ -117,11 +118,15 @@ int uz_vcf_is_lazy(const uz_vcf *h); /* 1: decoded lazily and not filled yet */
  * (csrc/io_vcf_cell.hpp).  Idempotent (a filled or eagerly decoded table: nothing to do); raises what the eager decode raises, and the
  * table stays lazy then. */
 int uz_vcf_fill_samples(uz_vcf *h, int threads);
-/* the text of a text table and its per-record sample-column offsets and FORMAT slots (uz_types.h: uz_vcf_text_view), lazy or not */
+/* the text of a text table and its per-record sample-column offsets and FORMAT slots (uz_types.h: uz_vcf_text_view), lazy or not;
+ * UZ_IO_E_ARG on a BCF */
 int uz_vcf_samples_text(const uz_vcf *h, uz_vcf_text_view *out);
+/* the bytes of a BCF table and its per-record value arrays of GT, AD, RO, AO, GQ (uz_types.h: uz_vcf_bcf_view), lazy or not; UZ_IO_E_ARG on a
+ * text table */
+int uz_vcf_samples_bcf(const uz_vcf *h, uz_vcf_bcf_view *out);
 /* What the eager decode holds for records rec[0 .. n_rec) and sample columns pick[0 .. n_pick): gt u8, int32 depths, f64 GQ, each
  * [n_pick][n_rec] -- the input of uz_samples_pack for the records the device hands back (uz_samples_unsettled).  Raises what the eager
- * decode raises (UZ_IO_E_FORMAT on an unparsable genotype allele). */
+ * decode raises (UZ_IO_E_FORMAT on an unparsable genotype allele).  Text or BCF, lazy or not. */
 int uz_vcf_record_samples(const uz_vcf *h, int64_t n_rec, const int64_t *rec, int32_t n_pick, const int32_t *pick, uint8_t *gt, int32_t *ref_depth,
                           int32_t *alt_depth, double *gq);
 /* sequence names of the index, each NUL-terminated, into buf -- a text file's in the order of their first record in the file (the

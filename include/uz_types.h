@@ -192,6 +192,20 @@ typedef struct uz_vcf_text_view {
     const int32_t *fmt_slot;  /* [n_records][5] FORMAT slots of GT, AD, RO, AO, GQ; -1: absent (all five on a line without a sample column) */
 } uz_vcf_text_view;
 
+/* The bytes of a decoded BCF and where the per-sample value arrays of GT, AD, RO, AO and GQ of every record lie in them (unfazed_io.h:
+ * uz_vcf_samples_bcf; taken by unfazed_hip.h: uz_samples_from_bcf, which reads the values on the device).  A field's array holds, sample after
+ * sample, `count` values of one BCF type: sample s starts at fld_at + s * count * size(type).  The decode has proven every array to lie inside
+ * its record.  HOST pointers into the decoder's table: they live as long as it does. */
+typedef struct uz_vcf_bcf_view {
+    const uint8_t *data;
+    int64_t data_bytes;
+    int64_t n_records;
+    int32_t n_samples;        /* samples the header names (= samples of every record that has FORMAT fields) */
+    int32_t reserved0;
+    const uint64_t *fld_at;   /* [n_records][5] offset of the value array of GT, AD, RO, AO, GQ in `data` */
+    const uint32_t *fld_desc; /* [n_records][5] BCF type (1 int8, 2 int16, 3 int32, 5 float, 7 char) | values per sample << 4; 0: absent */
+} uz_vcf_bcf_view;
+
 /* alignment records of one BAM in file (coordinate) order */
 typedef struct uz_reads_view {
     int64_t n_segs; /* < 2^31 */

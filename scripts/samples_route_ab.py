@@ -7,6 +7,8 @@ process under its own `timeout -k 10`; the routes alternate, --runs of each.  Re
 chunks' copies reached, per-chunk kernel time beside per-chunk copy time, host CPU-seconds of both routes.  The bar: every run of the device
 route beats every run of the host route (exit status 1 otherwise).
     python scripts/samples_route_ab.py [--samples 600] [--sites 20000] [--runs 3] [--out profiles/samples_route_ab.json]
+--bcf: the same table written as BCF + CSI (int8 GT, int16 AD -- int32 in the records with a depth above 32767 --, float GQ), the device route
+through uz_samples_from_bcf / k_bcf_cells; the result goes to profiles/samples_route_bcf_ab.json, with the bytes each route sends over the link.
 A child that ends by a signal, an abort or its time limit ends the whole measurement: nothing more is started on the device."""
 import argparse
 import hashlib
@@ -51,11 +53,52 @@ def write_vcf(path, n_samples, n_sites, seed=7):
     return len(text)
 
 
+def write_bcf(path, n_samples, n_sites, seed=7):
+    """the same plain cohort table as BCF + CSI, built with numpy: GT int8 x 2, AD int16 x 2, GQ float per sample, sites 50 bases apart on 20
+    contigs; every 97th record has a first sample with a depth of 40000 and carries its AD as int32 (the wide list and the settle round trip
+    stay in play)"""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    sys.path.insert(0, ROOT)
+    import bcfcases
+    rng = np.random.default_rng(seed)
+    n_contigs = min(20, max(1, n_sites // 64))
+    per = (n_sites + n_contigs - 1) // n_contigs
+    i = np.arange(n_sites)
+    codes = np.array([[2, 2], [2, 4], [4, 4], [0, 0], [2, 5]], np.int8)  # 0/0 0/1 1/1 ./. 0|1
+    gt = codes[rng.integers(0, 5, (n_sites, n_samples))]
+    ad = rng.integers(0, 60, (n_sites, n_samples, 2)).astype(np.int16)
+    gq = rng.integers(0, 100, (n_sites, n_samples)).astype(np.float32)
+    samples = ["s%04d" % s for s in range(n_samples)]
+    data = bytearray(bcfcases.table_bcf_bytes(samples, ["chr%d" % (c + 1) for c in range(n_contigs)], i // per, 100 + 50 * (i % per), gt, ad, gq))
+    # the deep records: AD as int32, 40000 in the first sample -- the record grows by 4 bytes per sample, so the file is stitched from slices
+    head = len(bcfcases.header_bytes(samples, ["chr%d" % (c + 1) for c in range(n_contigs)]))
+    rec_len = (len(data) - head) // n_sites
+    out = bytearray(data[:head])
+    ad_at = rec_len - 4 * n_samples - 3 - 4 * n_samples  # the AD values of a record: behind them the GQ key, its descriptor and the GQ values
+    done = head
+    for k in range(5, n_sites, 97):
+        at = head + k * rec_len
+        out += data[done:at]
+        r = data[at: at + rec_len]
+        wide = ad[k].astype("<i4")
+        wide[0, 0] = 40000
+        assert r[ad_at - 1] == 0x22
+        r = r[:ad_at - 1] + bytes([0x23]) + wide.tobytes() + r[ad_at + 4 * n_samples:]
+        r[4:8] = (int.from_bytes(r[4:8], "little") + 4 * n_samples).to_bytes(4, "little")
+        out += r
+        done = at + rec_len
+    out += data[done:]
+    bcfcases.write_indexed(path, bytes(out))
+    return len(out)
+
+
 def child(route, path):
     sys.path.insert(0, os.getcwd())
     import numpy as np
     from unfazed_amd import abi, io_native
-    from unfazed_amd.engine import K_VCF_CELLS, K_VCF_COPY, K_VCF_TABS, HipEngine
+    from unfazed_amd.engine import K_BCF_CELLS, K_BCF_COPY, K_VCF_CELLS, K_VCF_COPY, K_VCF_TABS, HipEngine
+    bcf = path.endswith(".bcf")
     threads = int(os.environ.get("UZ_IO_THREADS", "0"))
     eng = HipEngine(0)
     eng.sync()
@@ -72,10 +115,14 @@ def child(route, path):
         t2 = time.perf_counter()
         mid = eng.upload_samples(sid, cols)
         n_back = 0
-        res.update(pack_s=t2 - t1)
+        res.update(pack_s=t2 - t1, link_bytes=int(7 * ns * n + (0 if cols.wide is None else cols.wide[0].size * (8 + 8 * ns))))
     else:
-        eng.prof_enable([K_VCF_TABS, K_VCF_CELLS, K_VCF_COPY])
-        mid, n_back = eng.samples_from_text(sid, table, np.arange(ns), settle=False)
+        if bcf:
+            eng.prof_enable([K_BCF_CELLS, K_BCF_COPY])
+            mid, n_back = eng.samples_from_bcf(sid, table, np.arange(ns), settle=False)
+        else:
+            eng.prof_enable([K_VCF_TABS, K_VCF_CELLS, K_VCF_COPY])
+            mid, n_back = eng.samples_from_text(sid, table, np.arange(ns), settle=False)
         t2 = time.perf_counter()
         if n_back:
             eng.settle_samples(mid, table, np.arange(ns), n_back)
@@ -84,7 +131,18 @@ def child(route, path):
     eng.sync()
     t3, c3 = time.perf_counter(), time.process_time()
     res.update(samples=ns, sites=n, total_s=t3 - t0, decode_s=t1 - t0, table_s=t3 - t1, host_cpu_s=c3 - c0, sites_unsettled=n_back)
-    if route == "device":
+    if route == "device" and bcf:
+        import ctypes as C
+        assert table.genotypes_deferred and table.is_bcf
+        v = io_native.vcf_samples_bcf(table)
+        desc = np.ctypeslib.as_array(C.cast(v.fld_desc, C.POINTER(C.c_uint32)), (n, 5)).astype(np.int64)
+        size = np.array([0, 1, 2, 4, 0, 4, 0, 0], np.int64)[desc & 15]
+        values = int((((desc >> 4) * size * ns + 3) // 4 * 4).sum())  # the five arrays of every record, each on a 4-byte boundary
+        (cells_ms, chunks), (copy_ms, _) = eng.prof_get(K_BCF_CELLS), eng.prof_get(K_BCF_COPY)
+        res.update(value_bytes=values, link_bytes=values + 40 * n + int(n_back) * ns * 7, chunks=int(chunks), cells_ms_per_chunk=cells_ms / max(1, chunks),
+                   copy_ms_per_chunk=copy_ms / max(1, chunks), h2d_GBps=(values / (copy_ms / 1e3) / 1e9) if copy_ms > 0 else None,
+                   parse_no_longer_than_copy=cells_ms <= copy_ms)
+    elif route == "device":
         assert table.genotypes_deferred
         text = io_native.vcf_samples_text(table)
         (tabs_ms, chunks), (cells_ms, _), (copy_ms, _) = eng.prof_get(K_VCF_TABS), eng.prof_get(K_VCF_CELLS), eng.prof_get(K_VCF_COPY)
@@ -107,20 +165,22 @@ def main():
     ap.add_argument("--samples", type=int, default=600)
     ap.add_argument("--sites", type=int, default=20000)
     ap.add_argument("--runs", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "samples_route_ab.json"))
+    ap.add_argument("--bcf", action="store_true", help="the table as BCF + CSI (device route: uz_samples_from_bcf)")
+    ap.add_argument("--out", default=None, help="default: profiles/samples_route_ab.json, with --bcf profiles/samples_route_bcf_ab.json")
     ap.add_argument("--limit", type=int, default=0, help="seconds a child may take (default: sized by the file)")
     ap.add_argument("--child", choices=["host", "device"])
     ap.add_argument("--path")
     a = ap.parse_args()
     if a.child:
         return child(a.child, a.path)
+    a.out = a.out or os.path.join(ROOT, "profiles", "samples_route_bcf_ab.json" if a.bcf else "samples_route_ab.json")
     limit = a.limit or int(120 + a.samples * a.sites / 12e6 * 30)
     runs = {"host": [], "device": []}
     with tempfile.TemporaryDirectory() as d:
-        path = os.path.join(d, "cohort.vcf.gz")
+        path = os.path.join(d, "cohort.bcf" if a.bcf else "cohort.vcf.gz")
         t0 = time.perf_counter()
-        text_bytes = write_vcf(path, a.samples, a.sites)
-        print("wrote %d bytes of text as %d bytes of BGZF in %.1f s" % (text_bytes, os.path.getsize(path), time.perf_counter() - t0), flush=True)
+        text_bytes = (write_bcf if a.bcf else write_vcf)(path, a.samples, a.sites)
+        print("wrote %d bytes as %d bytes of BGZF in %.1f s" % (text_bytes, os.path.getsize(path), time.perf_counter() - t0), flush=True)
         for k in range(a.runs):
             for route in ("host", "device"):
                 cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--child", route, "--path", path]
@@ -136,12 +196,13 @@ def main():
     bar = max(dev_t) < min(host_t)
     same = len({r["rows_sha"] for r in runs["host"] + runs["device"]}) == 1
     keys = ("decode_s", "table_s", "host_cpu_s")
-    out = dict(what="sample table ready on the device from an indexed BGZF VCF: eager decode + pack + upload (host) against lazy decode + text up + "
-                    "parse + settle (device); fresh process per run, alternating; UZ_IO_THREADS=%s" % os.environ.get("UZ_IO_THREADS", "0 (every CPU the process may use)"),
+    what = ("sample table ready on the device from a BCF with its CSI: eager decode + pack + upload (host) against lazy decode + value arrays up + k_bcf_cells + settle (device)"
+            if a.bcf else "sample table ready on the device from an indexed BGZF VCF: eager decode + pack + upload (host) against lazy decode + text up + parse + settle (device)")
+    out = dict(what=what + "; fresh process per run, alternating; UZ_IO_THREADS=%s" % os.environ.get("UZ_IO_THREADS", "0 (every CPU the process may use)"),
                samples=a.samples, sites=a.sites, text_bytes=text_bytes, host_total_s=host_t, device_total_s=dev_t,
-               host={k: [r[k] for r in runs["host"]] for k in keys + ("pack_s",)},
+               host={k: [r.get(k) for r in runs["host"]] for k in keys + ("pack_s", "link_bytes")},
                device={k: [r.get(k) for r in runs["device"]] for k in keys + ("parse_s", "settle_s", "sites_unsettled", "chunks", "tabs_ms_per_chunk", "cells_ms_per_chunk", "copy_ms_per_chunk",
-                                                                              "h2d_GBps", "parse_no_longer_than_copy")},
+                                                                              "h2d_GBps", "parse_no_longer_than_copy", "value_bytes", "link_bytes")},
                every_device_run_beats_every_host_run=bar, same_rows_and_class_bytes_on_both_routes=same)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     json.dump(out, open(a.out, "w"), indent=1)

@@ -129,6 +129,14 @@ class VcfTextView(C.Structure):
     ]
 
 
+class VcfBcfView(C.Structure):
+    """uz_types.h: uz_vcf_bcf_view"""
+    _fields_ = [
+        ("data", _p), ("data_bytes", C.c_int64), ("n_records", C.c_int64), ("n_samples", C.c_int32), ("reserved0", C.c_int32),
+        ("fld_at", _p), ("fld_desc", _p),
+    ]
+
+
 class ReadsView(C.Structure):
     _fields_ = [
         ("n_segs", C.c_int64),

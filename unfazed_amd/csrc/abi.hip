@@ -213,6 +213,35 @@ struct Carver {
     }
 };
 
+// the table of uz_samples_from_text / uz_samples_from_bcf: rows carved at the stride of uz_samples_upload, filled by parse(m, chunk bytes)
+template <typename F>
+void samples_from_records(uz_ctx *c, int sites_id, int64_t n_sites, int32_t n_pick, int *id, int64_t *n_unsettled, F parse) {
+    size_t chunk = (size_t)32 << 20;
+    if (const char *e = getenv("UZ_VCF_CHUNK_BYTES")) { // (read per call: a test hook for the multi-chunk path)
+        const long long v = atoll(e);
+        if (v > 0) chunk = (size_t)v;
+    }
+    chunk = std::min<size_t>(chunk, (size_t)1 << 31);
+    const size_t n = (size_t)n_sites, ns = (size_t)n_pick;
+    SamplesDev m;
+    m.live = true; m.sites_id = sites_id; m.n_samples = n_pick; m.n_wide = 0;
+    m.stride = (n + 64 + 255) & ~(size_t)255;
+    for (int pass = 0; pass < 2; pass++) {
+        Carver cv(pass ? m.block.p : nullptr);
+        m.gt = cv.take<uint8_t>(ns * m.stride);
+        m.rd = cv.take<uint16_t>(ns * m.stride); m.ad = cv.take<uint16_t>(ns * m.stride); m.gq = cv.take<uint16_t>(ns * m.stride);
+        if (!pass) m.block = uz_block_get(c, cv.off + 256);
+    }
+    try {
+        parse(m, chunk);
+    } catch (...) { uz_block_put(c, m.block); throw; }
+    m.need_settle = !m.unsettled.empty();
+    *n_unsettled = (int64_t)m.unsettled.size();
+    const int k = new_slot(c->samples);
+    c->samples[(size_t)k] = m;
+    *id = k;
+}
+
 } // namespace
 
 // ---------------------------------------------------------------- copy kernel (see uz_ctx.hpp)
@@ -832,30 +861,18 @@ int uz_samples_from_text(uz_ctx *c, int sites_id, const uz_vcf_text_view *t, int
         UZ_REQUIRE(t->n_records == s.n, UZ_E_ARG, "the text's records are not the sites of the table");
         UZ_REQUIRE(s.n == 0 || (t->text && t->samp_at && t->line_end && t->fmt_slot && t->text_bytes >= 0), UZ_E_ARG, "null pointer in the text view");
         for (int32_t r = 0; r < n_pick; r++) UZ_REQUIRE(pick[r] >= 0 && pick[r] < t->n_samples, UZ_E_ARG, "picked sample column outside the file's");
-        size_t chunk = (size_t)32 << 20;
-        if (const char *e = getenv("UZ_VCF_CHUNK_BYTES")) { // (read per call: a test hook for the multi-chunk path)
-            const long long v = atoll(e);
-            if (v > 0) chunk = (size_t)v;
-        }
-        chunk = std::min<size_t>(chunk, (size_t)1 << 31);
-        const size_t n = (size_t)s.n, ns = (size_t)n_pick;
-        SamplesDev m;
-        m.live = true; m.sites_id = sites_id; m.n_samples = n_pick; m.n_wide = 0;
-        m.stride = (n + 64 + 255) & ~(size_t)255;
-        for (int pass = 0; pass < 2; pass++) {
-            Carver cv(pass ? m.block.p : nullptr);
-            m.gt = cv.take<uint8_t>(ns * m.stride);
-            m.rd = cv.take<uint16_t>(ns * m.stride); m.ad = cv.take<uint16_t>(ns * m.stride); m.gq = cv.take<uint16_t>(ns * m.stride);
-            if (!pass) m.block = uz_block_get(c, cv.off + 256);
-        }
-        try {
-            uz_vcf_parse_text(c, t, n_pick, pick, m, chunk, m.unsettled);
-        } catch (...) { uz_block_put(c, m.block); throw; }
-        m.need_settle = !m.unsettled.empty();
-        *n_unsettled = (int64_t)m.unsettled.size();
-        const int k = new_slot(c->samples);
-        c->samples[(size_t)k] = m;
-        *id = k;
+        samples_from_records(c, sites_id, s.n, n_pick, id, n_unsettled, [&](SamplesDev &m, size_t chunk) { uz_vcf_parse_text(c, t, n_pick, pick, m, chunk, m.unsettled); });
+    });
+}
+
+int uz_samples_from_bcf(uz_ctx *c, int sites_id, const uz_vcf_bcf_view *t, int32_t n_pick, const int32_t *pick, int *id, int64_t *n_unsettled) {
+    return guarded(c, [&] {
+        UZ_REQUIRE(t && id && n_unsettled && n_pick >= 0 && (n_pick == 0 || pick) && t->n_samples >= 0, UZ_E_ARG, "bad BCF view or pick list");
+        SitesDev &s = sites_of(c, sites_id);
+        UZ_REQUIRE(t->n_records == s.n, UZ_E_ARG, "the BCF's records are not the sites of the table");
+        UZ_REQUIRE(s.n == 0 || (t->data && t->fld_at && t->fld_desc && t->data_bytes >= 0), UZ_E_ARG, "null pointer in the BCF view");
+        for (int32_t r = 0; r < n_pick; r++) UZ_REQUIRE(pick[r] >= 0 && pick[r] < t->n_samples, UZ_E_ARG, "picked sample outside the file's");
+        samples_from_records(c, sites_id, s.n, n_pick, id, n_unsettled, [&](SamplesDev &m, size_t chunk) { uz_vcf_parse_bcf(c, t, n_pick, pick, m, chunk, m.unsettled); });
     });
 }
 

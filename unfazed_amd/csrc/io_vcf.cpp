@@ -50,6 +50,11 @@ struct uz_vcf {
     std::vector<uint64_t> samp_at, line_end;
     std::vector<int32_t> fmt_slot; // [n][5]
     bool lazy = false;             // the genotype columns have not been filled
+    // BCF tables: where the value arrays of GT, AD, RO, AO, GQ of every record lie in `text` and their descriptors (uz_types.h:
+    // uz_vcf_bcf_view) -- every array proven to lie inside its record by the decode.  A lazily decoded BCF keeps these INSTEAD of the four
+    // genotype columns, like a text table its offsets.
+    std::vector<uint64_t> fld_at;   // [n][5]
+    std::vector<uint32_t> fld_desc; // [n][5] type | values per sample << 4; 0: absent
     std::mutex fill_mu;
 };
 
@@ -99,8 +104,78 @@ long long bcf_scalar_int(const BcfVal &v) {
     return x;
 }
 
-void decode_bcf(uz_vcf &V, int threads) {
+// One sample's cell of a BCF record into the decoder's value types: the one place the host reads a BCF's per-sample values -- the eager
+// decode, uz_vcf_fill_samples and uz_vcf_record_samples all come through here (tests/bcf_cell_main.cpp holds the device's body, bcf_cell.hpp,
+// against a restatement of it).  fv: the value arrays of GT, AD, RO, AO, GQ (p null or n 0: absent -- the output keeps what it holds, the
+// caller's default); s: the sample.
+void bcf_sample_cell(const BcfVal fv[5], size_t s, uint8_t &gt, int32_t &ref_depth, int32_t &alt_depth, double &gq) {
+    auto at = [&](const BcfVal &d) { return d.p + s * (size_t)d.n * BCF_SZ[d.type]; };
+    if (fv[0].p && fv[0].n) { // GT: (allele + 1) << 1 | phased; 0 = missing allele
+        long long al[2] = {-1, -1};
+        int na = 0;
+        for (uint32_t k = 0; k < fv[0].n; k++) {
+            long long x;
+            const int st = bcf_int(fv[0].type, at(fv[0]), k, x);
+            if (st == BCF_EOV) break;
+            if (na < 2) al[na] = st == BCF_OK ? (x >> 1) - 1 : -1;
+            na++;
+            if (na >= 2) break; // (further entries change nothing)
+        }
+        int code = UZ_GT_UNKNOWN;
+        if (na == 1) code = al[0] < 0 ? UZ_GT_UNKNOWN : (al[0] == 0 ? 0 : 3);
+        else if (na >= 2) {
+            const long long a = al[0], b = al[1];
+            if (a < 0 && b < 0) code = UZ_GT_UNKNOWN;
+            else if (a < 0 || b < 0) code = (b < 0 ? a : b) == 0 ? 0 : 1;
+            else if (a != b) code = 1;
+            else code = a == 0 ? 0 : 3;
+        }
+        gt = (uint8_t)code;
+    }
+    bool ad_done = false;
+    if (fv[1].p && fv[1].n) { // AD: "." (all missing) falls through to RO / AO, as in the text form
+        long long x0 = -1, x1 = -1;
+        const int s0 = bcf_int(fv[1].type, at(fv[1]), 0, x0);
+        const int s1 = fv[1].n > 1 ? bcf_int(fv[1].type, at(fv[1]), 1, x1) : BCF_EOV;
+        if (!(s0 != BCF_OK && s1 == BCF_EOV)) {
+            ref_depth = s0 == BCF_OK ? (int32_t)x0 : -1;
+            alt_depth = s1 == BCF_OK ? (int32_t)x1 : -1;
+            ad_done = true;
+        }
+    }
+    if (!ad_done && fv[2].p && fv[3].p && fv[2].n && fv[3].n) {
+        long long x;
+        ref_depth = bcf_int(fv[2].type, at(fv[2]), 0, x) == BCF_OK ? (int32_t)x : -1;
+        alt_depth = bcf_int(fv[3].type, at(fv[3]), 0, x) == BCF_OK ? (int32_t)x : -1;
+    }
+    if (fv[4].p && fv[4].n) {
+        if (fv[4].type == 5) {
+            uint32_t bits;
+            memcpy(&bits, at(fv[4]), 4);
+            float fl;
+            memcpy(&fl, &bits, 4);
+            gq = (bits == 0x7F800001u || bits == 0x7F800002u) ? -1.0 : (double)fl;
+        } else {
+            long long x;
+            gq = bcf_int(fv[4].type, at(fv[4]), 0, x) == BCF_OK ? (double)x : -1.0;
+        }
+    }
+}
+// the five value arrays of record i from the kept offsets and descriptors
+void bcf_fields(const uz_vcf &V, int64_t i, BcfVal fv[5]) {
+    for (int k = 0; k < 5; k++) {
+        const uint32_t d = V.fld_desc[(size_t)i * 5 + k];
+        fv[k] = BcfVal();
+        if (!d) continue;
+        fv[k].type = (int)(d & 15u);
+        fv[k].n = d >> 4;
+        fv[k].p = V.text.data() + V.fld_at[(size_t)i * 5 + k];
+    }
+}
+
+void decode_bcf(uz_vcf &V, int threads, bool lazy) {
     V.is_bcf = true;
+    V.lazy = lazy;
     const uint8_t *D = V.text.data();
     const size_t N = V.text.size();
     if (N < 9 || D[4] != 2) fail(UZ_IO_E_FORMAT, "unsupported BCF version");
@@ -177,9 +252,12 @@ void decode_bcf(uz_vcf &V, int threads) {
     V.ref_at.resize(un); V.ref_len.resize(un); V.alt_at.assign(un, 0); V.alt_len.resize(un);
     V.chrom_len.assign(un, 0); V.alt_pool_at.resize(un); V.info_at.resize(un); V.n_info.resize(un);
     V.pos.resize(un); V.end.resize(un); V.sflags.resize(un); V.ref_base.resize(un); V.alt_base.resize(un);
-    V.gt.assign(ns * un, UZ_GT_UNKNOWN);
-    V.ref_depth.assign(ns * un, -1); V.alt_depth.assign(ns * un, -1);
-    V.gq.assign(ns * un, -1.0);
+    V.fld_at.assign(un * 5, 0); V.fld_desc.assign(un * 5, 0);
+    if (!lazy) {
+        V.gt.assign(ns * un, UZ_GT_UNKNOWN);
+        V.ref_depth.assign(ns * un, -1); V.alt_depth.assign(ns * un, -1);
+        V.gq.assign(ns * un, -1.0);
+    }
     std::vector<int32_t> chrom(un);
     std::vector<std::string> alts(un);
     threads = workers_for(n, threads, 2048);
@@ -241,58 +319,19 @@ void decode_bcf(uz_vcf &V, int threads) {
                 if (kid == k_gt) fv[0] = d; else if (kid == k_ad) fv[1] = d; else if (kid == k_ro) fv[2] = d;
                 else if (kid == k_ao) fv[3] = d; else if (kid == k_gq) fv[4] = d;
             }
-            for (size_t s = 0; s < ns && n_fmt; s++) {
+            // what the lazy form keeps: offset and descriptor of the five arrays.  The descriptor holds the count in 28 bits (a field without
+            // values -- type 0 -- has no stride, and nothing reads behind its second entry)
+            for (int k = 0; k < 5 && n_fmt; k++) {
+                if (!fv[k].p || !fv[k].n) continue;
+                uint32_t cnt = fv[k].n;
+                if (fv[k].type == 0) cnt = std::min<uint32_t>(cnt, 2);
+                else if (cnt >= (1u << 28)) { if (lazy) fail(UZ_IO_E_FORMAT, "BCF FORMAT vector of %u values per sample", cnt); continue; }
+                V.fld_at[(size_t)i * 5 + k] = (uint64_t)(fv[k].p - D);
+                V.fld_desc[(size_t)i * 5 + k] = (uint32_t)fv[k].type | cnt << 4;
+            }
+            for (size_t s = 0; s < ns && n_fmt && !lazy; s++) {
                 const size_t o = s * un + (size_t)i;
-                auto at = [&](const BcfVal &d) { return d.p + s * (size_t)d.n * BCF_SZ[d.type]; };
-                if (fv[0].p && fv[0].n) { // GT: (allele + 1) << 1 | phased; 0 = missing allele
-                    long long al[2] = {-1, -1};
-                    int na = 0;
-                    for (uint32_t k = 0; k < fv[0].n; k++) {
-                        long long x;
-                        const int st = bcf_int(fv[0].type, at(fv[0]), k, x);
-                        if (st == BCF_EOV) break;
-                        if (na < 2) al[na] = st == BCF_OK ? (x >> 1) - 1 : -1;
-                        na++;
-                    }
-                    int code = UZ_GT_UNKNOWN;
-                    if (na == 1) code = al[0] < 0 ? UZ_GT_UNKNOWN : (al[0] == 0 ? 0 : 3);
-                    else if (na >= 2) {
-                        const long long a = al[0], b = al[1];
-                        if (a < 0 && b < 0) code = UZ_GT_UNKNOWN;
-                        else if (a < 0 || b < 0) code = (b < 0 ? a : b) == 0 ? 0 : 1;
-                        else if (a != b) code = 1;
-                        else code = a == 0 ? 0 : 3;
-                    }
-                    V.gt[o] = (uint8_t)code;
-                }
-                bool ad_done = false;
-                if (fv[1].p && fv[1].n) { // AD: "." (all missing) falls through to RO / AO, as in the text form
-                    long long x0 = -1, x1 = -1;
-                    const int s0 = bcf_int(fv[1].type, at(fv[1]), 0, x0);
-                    const int s1 = fv[1].n > 1 ? bcf_int(fv[1].type, at(fv[1]), 1, x1) : BCF_EOV;
-                    if (!(s0 != BCF_OK && s1 == BCF_EOV)) {
-                        V.ref_depth[o] = s0 == BCF_OK ? (int32_t)x0 : -1;
-                        V.alt_depth[o] = s1 == BCF_OK ? (int32_t)x1 : -1;
-                        ad_done = true;
-                    }
-                }
-                if (!ad_done && fv[2].p && fv[3].p && fv[2].n && fv[3].n) {
-                    long long x;
-                    V.ref_depth[o] = bcf_int(fv[2].type, at(fv[2]), 0, x) == BCF_OK ? (int32_t)x : -1;
-                    V.alt_depth[o] = bcf_int(fv[3].type, at(fv[3]), 0, x) == BCF_OK ? (int32_t)x : -1;
-                }
-                if (fv[4].p && fv[4].n) {
-                    if (fv[4].type == 5) {
-                        uint32_t bits;
-                        memcpy(&bits, at(fv[4]), 4);
-                        float fl;
-                        memcpy(&fl, &bits, 4);
-                        V.gq[o] = (bits == 0x7F800001u || bits == 0x7F800002u) ? -1.0 : (double)fl;
-                    } else {
-                        long long x;
-                        V.gq[o] = bcf_int(fv[4].type, at(fv[4]), 0, x) == BCF_OK ? (double)x : -1.0;
-                    }
-                }
+                bcf_sample_cell(fv, s, V.gt[o], V.ref_depth[o], V.alt_depth[o], V.gq[o]);
             }
         }
     });
@@ -738,6 +777,16 @@ void read_cell(const uz_vcf &V, int64_t i, Str col, uint8_t &gt, int32_t &rd, in
 // all sample columns of records [lo, hi) into the four genotype columns
 void fill_records(uz_vcf &V, int64_t lo, int64_t hi) {
     const size_t un = (size_t)V.n;
+    for (int64_t i = lo; i < hi && V.is_bcf; i++) {
+        BcfVal fv[5];
+        bcf_fields(V, i, fv);
+        if (!fv[0].p && !fv[1].p && !fv[2].p && !fv[3].p && !fv[4].p) continue;
+        for (size_t s = 0; s < V.samples.size(); s++) {
+            const size_t o = s * un + (size_t)i;
+            bcf_sample_cell(fv, s, V.gt[o], V.ref_depth[o], V.alt_depth[o], V.gq[o]);
+        }
+    }
+    if (V.is_bcf) return;
     for (int64_t i = lo; i < hi; i++) {
         const int32_t *f = &V.fmt_slot[(size_t)i * 5];
         if (f[0] < 0 && f[1] < 0 && f[2] < 0 && f[3] < 0 && f[4] < 0) continue; // (the columns hold their defaults)
@@ -766,7 +815,7 @@ void fill_samples(uz_vcf &V, int threads) {
 void decode_text(uz_vcf &V, int threads, bool lazy) {
     const char *T = (const char *)V.text.data();
     const size_t N = V.text.size();
-    if (N >= 5 && memcmp(T, "BCF\2", 4) == 0) { decode_bcf(V, threads); return; }
+    if (N >= 5 && memcmp(T, "BCF\2", 4) == 0) { decode_bcf(V, threads, lazy); return; }
     // line starts: header first (serial, short), then records
     size_t p = 0;
     bool have_chrom_line = false;
@@ -996,14 +1045,42 @@ int uz_vcf_samples_text(const uz_vcf *h, uz_vcf_text_view *v) {
     });
 }
 
+int uz_vcf_samples_bcf(const uz_vcf *h, uz_vcf_bcf_view *v) {
+    if (!h || !v) { last_error = "null argument"; return UZ_IO_E_ARG; }
+    return guarded([&] {
+        if (!h->is_bcf) fail(UZ_IO_E_ARG, "uz_vcf_samples_bcf: a text table has no BCF records");
+        memset(v, 0, sizeof(*v));
+        v->data = h->text.data();
+        v->data_bytes = (int64_t)h->text.size();
+        v->n_records = h->n;
+        v->n_samples = (int32_t)h->samples.size();
+        v->fld_at = h->fld_at.data(); v->fld_desc = h->fld_desc.data();
+    });
+}
+
 int uz_vcf_record_samples(const uz_vcf *h, int64_t n_rec, const int64_t *rec, int32_t n_pick, const int32_t *pick, uint8_t *gt, int32_t *ref_depth,
                           int32_t *alt_depth, double *gq) {
     if (!h || n_rec < 0 || n_pick < 0 || (n_rec && !rec) || (n_pick && !pick)) { last_error = "null argument"; return UZ_IO_E_ARG; }
     return guarded([&] {
-        if (h->is_bcf) fail(UZ_IO_E_ARG, "uz_vcf_record_samples: a BCF has no text");
         if (n_rec && n_pick && (!gt || !ref_depth || !alt_depth || !gq)) fail(UZ_IO_E_ARG, "uz_vcf_record_samples: null output");
         for (int32_t k = 0; k < n_pick; k++)
             if (pick[k] < 0 || (size_t)pick[k] >= h->samples.size()) fail(UZ_IO_E_ARG, "sample index %d outside the table's %zu samples", (int)pick[k], h->samples.size());
+        if (h->is_bcf) { // a field's values lie at a fixed stride per sample: every picked cell is read where it lies
+            for (int64_t j = 0; j < n_rec; j++)
+                if (rec[j] < 0 || rec[j] >= h->n) fail(UZ_IO_E_ARG, "record index %lld outside the table", (long long)rec[j]);
+            parallel_slices(n_rec, workers_for(n_rec, resolve_threads(0), 64), [&](int64_t lo, int64_t hi, int) {
+                for (int64_t j = lo; j < hi; j++) {
+                    BcfVal fv[5];
+                    bcf_fields(*h, rec[j], fv);
+                    for (int32_t k = 0; k < n_pick; k++) {
+                        const size_t o = (size_t)k * (size_t)n_rec + (size_t)j;
+                        gt[o] = UZ_GT_UNKNOWN; ref_depth[o] = alt_depth[o] = -1; gq[o] = -1.0;
+                        bcf_sample_cell(fv, (size_t)pick[k], gt[o], ref_depth[o], alt_depth[o], gq[o]);
+                    }
+                }
+            });
+            return;
+        }
         // a record's columns are split once (a column is found by walking the tabs before it), the records shared among the threads
         std::vector<int32_t> row_of(h->samples.size(), -1), next_row((size_t)n_pick, -1); // rows that picked a column: first, then chained
         for (int32_t k = n_pick - 1; k >= 0; k--) { next_row[(size_t)k] = row_of[(size_t)pick[k]]; row_of[(size_t)pick[k]] = k; }

@@ -318,7 +318,7 @@ struct uz_ctx {
     std::vector<ReadsDev> reads;
     std::vector<SamplesDev> samples;
     DevBuf<int32_t> trio_idx; // uz_families_from_samples: kid / dad / mom sample indices of the batch's trios
-    uint8_t *vcf_pin[2] = {nullptr, nullptr}; // uz_samples_from_text: the two page-locked chunk images, kept from call to call
+    uint8_t *vcf_pin[2] = {nullptr, nullptr}; // uz_samples_from_text / _from_bcf: the two page-locked chunk images, kept from call to call
     size_t vcf_pin_cap[2] = {0, 0};
 
     // allele-balance threshold table of K1 (k_sites.hip), rebuilt when the thresholds change
@@ -485,6 +485,8 @@ void uz_launch_family_pack(uz_ctx *c, const SamplesDev &sm, const SitesDev &s, i
 // the sample cells of a text VCF parsed into the rows of `m` (k_vcf.hip): chunks of at most chunk_bytes of text, cut at line ends; -> the records
 // handed back to the host, ascending.  uz_launch_vcf_settle: their cells ([n_rows][n], device memory) over the rows
 void uz_vcf_parse_text(uz_ctx *c, const uz_vcf_text_view *t, int32_t n_pick, const int32_t *pick, SamplesDev &m, size_t chunk_bytes, std::vector<int64_t> &unsettled);
+// the same from a BCF's value arrays (k_bcf.hip): chunks of at most chunk_bytes of gathered values, cut at record boundaries
+void uz_vcf_parse_bcf(uz_ctx *c, const uz_vcf_bcf_view *t, int32_t n_pick, const int32_t *pick, SamplesDev &m, size_t chunk_bytes, std::vector<int64_t> &unsettled);
 void uz_launch_vcf_settle(uz_ctx *c, int64_t n, int32_t n_rows, const int64_t *site, const uint8_t *gt_in, const uint16_t *rd_in, const uint16_t *ad_in,
                           const uint16_t *gq_in, SamplesDev &m);
 void uz_launch_site_scan(uz_ctx *c, FamilyDev &f, const SitesDev &s, bool with_cnv);

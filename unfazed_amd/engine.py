@@ -17,10 +17,11 @@ LIB_PATH = os.environ.get("UZ_HIP_LIB", os.path.join(_HERE, "libunfazed_hip.so")
 SIZING_REDUCED_WORDS = 263  # unfazed_hip.h UZ_SIZING_REDUCED_WORDS
 K_SITE_SCAN, K_WINDOW_COUNT, K_WINDOW_FILL, K_PHASE, K_SIZING, K_CNV, K_FAMILY_PACK, K_CNV_DENSE = 0, 1, 2, 3, 4, 5, 6, 7
 K_VCF_TABS, K_VCF_CELLS, K_VCF_COPY = 8, 9, 10  # uz_samples_from_text: the two kernels and (not a kernel) the chunks' copies
+K_BCF_CELLS, K_BCF_COPY = 11, 12  # uz_samples_from_bcf: its kernel and (not a kernel) its chunks' copies
 
 EXPORTS = [
     "uz_create", "uz_destroy", "uz_last_error", "uz_sync", "uz_set_params",
-    "uz_sites_upload", "uz_family_upload", "uz_sites_family_upload_async", "uz_samples_upload", "uz_samples_from_text", "uz_samples_unsettled", "uz_samples_settle", "uz_families_from_samples", "uz_family_fetch", "uz_samples_free", "uz_reads_upload", "uz_reads_upload_packed", "uz_reads_wait", "uz_reads_headers", "uz_bgzf_inflate", "uz_bgzf_inflate_to_host", "uz_bam_walk", "uz_crc32_blocks", "uz_bam_walk_fetch", "uz_bam_walk_release", "uz_reads_from_bam",
+    "uz_sites_upload", "uz_family_upload", "uz_sites_family_upload_async", "uz_samples_upload", "uz_samples_from_text", "uz_samples_from_bcf", "uz_samples_unsettled", "uz_samples_settle", "uz_families_from_samples", "uz_family_fetch", "uz_samples_free", "uz_reads_upload", "uz_reads_upload_packed", "uz_reads_wait", "uz_reads_headers", "uz_bgzf_inflate", "uz_bgzf_inflate_to_host", "uz_bam_walk", "uz_crc32_blocks", "uz_bam_walk_fetch", "uz_bam_walk_release", "uz_reads_from_bam",
     "uz_bam_walk_flags", "uz_bam_join", "uz_bam_join_needs", "uz_bam_join_fetch", "uz_reads_from_walk", "uz_reads_names", "uz_walk_slot_stats", "uz_walk_reserve",
     "uz_pinned_alloc", "uz_pinned_free",
     "uz_sites_adopt_device", "uz_family_adopt_device", "uz_reads_adopt_device",
@@ -85,6 +86,7 @@ def load_library(path: Optional[str] = None):
     L.uz_samples_upload.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int)]
     L.uz_families_from_samples.argtypes = [vp, C.c_int, C.c_int32, vp, vp, vp, vp]
     L.uz_samples_from_text.argtypes = [vp, C.c_int, vp, C.c_int32, vp, C.POINTER(C.c_int), C.POINTER(C.c_int64)]
+    L.uz_samples_from_bcf.argtypes = L.uz_samples_from_text.argtypes
     L.uz_samples_unsettled.argtypes = [vp, C.c_int, vp]
     L.uz_samples_settle.argtypes = [vp, C.c_int, C.c_int64, vp, vp]
     L.uz_family_fetch.argtypes = [vp, C.c_int, vp, vp]
@@ -210,10 +212,19 @@ class HipEngine:
         own reader -- io_native.vcf_record_samples, then pack_samples: errors are the eager decode's -- and settled (uz_samples_settle).
             -> (handle, number of sites handed back).  settle=False leaves the round trip to the caller (settle_samples)."""
         from . import io_native
+        return self._samples_from(self.L.uz_samples_from_text, "uz_samples_from_text", io_native.vcf_samples_text(table), sites_h, table, pick, settle)
+
+    def samples_from_bcf(self, sites_h: int, table, pick, settle: bool = True):
+        """The same from a natively decoded BCF (uz_samples_from_bcf): only the value arrays of GT, AD, RO, AO and GQ go to the device, in chunks,
+        and one kernel reads the samples `pick` into the rows.  Handed back and settled like the text's: records with a depth the 16-bit rows
+        cannot hold or a field in a type the kernel does not take.  -> (handle, number of sites handed back)"""
+        from . import io_native
+        return self._samples_from(self.L.uz_samples_from_bcf, "uz_samples_from_bcf", io_native.vcf_samples_bcf(table), sites_h, table, pick, settle)
+
+    def _samples_from(self, call, name, view, sites_h, table, pick, settle):
         pick = np.ascontiguousarray(pick, np.int32)
-        text = io_native.vcf_samples_text(table)
         mid, nu = C.c_int(-1), C.c_int64(0)
-        self._ck(self.L.uz_samples_from_text(self.h, int(sites_h), C.byref(text), int(pick.size), pick.ctypes.data, C.byref(mid), C.byref(nu)), "uz_samples_from_text")
+        self._ck(call(self.h, int(sites_h), C.byref(view), int(pick.size), pick.ctypes.data, C.byref(mid), C.byref(nu)), name)
         self._samples = getattr(self, "_samples", {})
         self._samples[mid.value] = (int(sites_h), None)
         if settle and nu.value:
@@ -225,13 +236,13 @@ class HipEngine:
         return mid.value, int(nu.value)
 
     def unsettled_sites(self, samples_h: int, n: int):
-        """the n sites a table made by samples_from_text handed back, ascending"""
+        """the n sites a table made by samples_from_text / samples_from_bcf handed back, ascending"""
         site = np.zeros(max(1, int(n)), np.int64)
         self._ck(self.L.uz_samples_unsettled(self.h, int(samples_h), site.ctypes.data), "uz_samples_unsettled")
         return site[: int(n)]
 
     def settle_samples(self, samples_h: int, table, pick, n: int) -> None:
-        """the n handed-back sites of a table made by samples_from_text, read by the host's reader and written over the device's rows"""
+        """the n handed-back sites of a table made by samples_from_text / samples_from_bcf, read by the host's reader and written over the device's rows"""
         from . import io_native
         from .model import SampleColumns, SitesTable
         pick = np.ascontiguousarray(pick, np.int32)

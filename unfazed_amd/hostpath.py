@@ -181,10 +181,17 @@ class _VoteLists:
         return np.unique(self.vv[idx].astype(np.int64))
 
 
-def samples_route() -> str:
-    """UZ_SAMPLES_ROUTE: "device" (default) -- the sample cells of a cohort batch's text VCF are parsed on the device from the record text
-    (session.lazy_samples, PhasingHost.prepare_families); "host" -- the decoder parses them and the packed columns are uploaded"""
-    return "host" if __import__("os").environ.get("UZ_SAMPLES_ROUTE", "device").lower() == "host" else "device"
+BCF_SAMPLES_DEFAULT = "device"  # the route of a BCF when UZ_SAMPLES_ROUTE is not set: what profiles/samples_route_bcf_ab.json admits
+
+
+def samples_route(is_bcf: bool = False) -> str:
+    """UZ_SAMPLES_ROUTE: "device" (default) -- the sample cells of a cohort batch's sites file are read on the device, from the record text of
+    a text VCF or from the value arrays of a BCF (session.lazy_samples, PhasingHost.prepare_families); "host" -- the decoder parses them and
+    the packed columns are uploaded.  Not set, a BCF takes BCF_SAMPLES_DEFAULT."""
+    v = __import__("os").environ.get("UZ_SAMPLES_ROUTE", "").lower()
+    if v == "host":
+        return "host"
+    return BCF_SAMPLES_DEFAULT if (is_bcf and v != "device") else "device"
 
 
 class _Stats(dict):
@@ -239,8 +246,8 @@ class PhasingHost:
         trios are made there in one call (uz_families_from_samples) -- instead of a dozen numpy passes and ten blocking copies per trio,
         a shared parent converted once per sibling.  A trio whose three members lie in a table of an earlier call is made from that
         table; the others' samples form a new table (a member they share with an older table travels again with it).
-        A table whose sample cells were left unparsed (a lazily decoded text VCF) gets its sample table from the text on the device
-        (samples_from_text) instead of sample_columns + upload_samples.
+        A table whose sample cells were left unparsed (a lazily decoded text VCF or BCF) gets its sample table from the text (samples_from_text)
+        or from the BCF's value arrays (samples_from_bcf) on the device instead of sample_columns + upload_samples.
         UZ_FAMILY_ROUTE=host, a single kid, or a backend without sample tables: family() makes them one by one, as before."""
         trios = list(dict.fromkeys(trios))
         if len({t[0] for t in trios}) < 2 or not hasattr(self.backend, "upload_samples") or __import__("os").environ.get("UZ_FAMILY_ROUTE", "device") == "host":
@@ -259,10 +266,12 @@ class PhasingHost:
                 rest.append(t)
         if rest:
             names = list(dict.fromkeys(s for t in rest for s in t))
-            if getattr(self.sites, "genotypes_deferred", False) and hasattr(self.backend, "samples_from_text") and samples_route() == "device":
-                # a lazily decoded text VCF (session.host_for): the device reads the sample cells from the record text, and the host's reader
-                # only the records it hands back -- the table's own genotype columns are never made
-                h, n_back = self.backend.samples_from_text(self._sites_h, self.sites, [self.sites.samples.index(s) for s in names])
+            is_bcf = bool(getattr(self.sites, "is_bcf", False))
+            from_records = "samples_from_bcf" if is_bcf else "samples_from_text"
+            if getattr(self.sites, "genotypes_deferred", False) and hasattr(self.backend, from_records) and samples_route(is_bcf) == "device":
+                # a lazily decoded text VCF or BCF (session.host_for): the device reads the sample cells from the record text (the value arrays
+                # of a BCF), and the host's reader only the records it hands back -- the table's own genotype columns are never made
+                h, n_back = getattr(self.backend, from_records)(self._sites_h, self.sites, [self.sites.samples.index(s) for s in names])
                 self.stats["samples_parsed_device"] += len(names)
                 self.stats["sites_unsettled"] += n_back
             else:

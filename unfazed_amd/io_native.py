@@ -35,7 +35,7 @@ IO_EXPORTS = [
     "uz_index_summary", "uz_inflate_backend", "uz_io_default_threads", "uz_io_cpu_quota", "uz_bam_stage_plan", "uz_bam_stage_begin", "uz_bam_stage_finish", "uz_stage_gather_blocks", "uz_stage_set_inflated", "uz_stage_sizes", "uz_stage_io_stats", "uz_stage_timing", "uz_stage_fill", "uz_stage_qname", "uz_stage_qnames",
     "uz_stage_free", "uz_stage_walk_plan_sizes", "uz_stage_walk_plan", "uz_bam_stage_finish_desc", "uz_stage_kept_sizes", "uz_stage_kept", "uz_stage_walk_host", "uz_stage_kept_debug", "uz_stage_name_records", "uz_packed_block_sums", "uz_stage_merge_subtasks", "uz_bam_stage_finish_sub",
     "uz_stage_walk_flagged", "uz_stage_lookup", "uz_stage_extra", "uz_stage_n_lookup_tasks", "uz_sites_pack", "uz_sites_unpack", "uz_samples_pack",
-    "uz_vcf_decode_regions_lazy", "uz_vcf_is_lazy", "uz_vcf_fill_samples", "uz_vcf_samples_text", "uz_vcf_record_samples",
+    "uz_vcf_decode_regions_lazy", "uz_vcf_is_lazy", "uz_vcf_fill_samples", "uz_vcf_samples_text", "uz_vcf_samples_bcf", "uz_vcf_record_samples",
 ]
 
 
@@ -92,6 +92,7 @@ def load():
     lib.uz_vcf_is_lazy.argtypes = [C.c_void_p]
     lib.uz_vcf_fill_samples.argtypes = [C.c_void_p, C.c_int]
     lib.uz_vcf_samples_text.argtypes = [C.c_void_p, C.POINTER(abi.VcfTextView)]
+    lib.uz_vcf_samples_bcf.argtypes = [C.c_void_p, C.POINTER(abi.VcfBcfView)]
     lib.uz_vcf_record_samples.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.uz_vcf_index_names.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_int64]
     lib.uz_vcf_index_names.restype = C.c_int64
@@ -432,7 +433,8 @@ def read_vcf_table_regions(path: str, ref, lo, hi, threads: int = 0, tbi: str = 
     tabix_contigs) -- what cyvcf2's vcf(region) hands the reference, without inflating the rest of the file.  `.io_stats`:
     compressed bytes read, BGZF blocks inflated, lines walked, records kept.
     lazy: the sample cells are not parsed (uz_vcf_decode_regions_lazy) -- the table's gt / ref_depth / alt_depth / gq are made on their first
-    access (uz_vcf_fill_samples), and a table that is never asked never pays; `samples_text` / `record_samples` serve the device route."""
+    access (uz_vcf_fill_samples), and a table that is never asked never pays; `vcf_samples_text` (a text VCF) / `vcf_samples_bcf` (a BCF) and
+    `vcf_record_samples` serve the device route."""
     lib = load()
     ref = np.ascontiguousarray(ref, np.int32)
     lo = np.ascontiguousarray(lo, np.int32)
@@ -463,6 +465,15 @@ def vcf_samples_text(table: SitesTable) -> "abi.VcfTextView":
     lib = load()
     v = abi.VcfTextView()
     _check(lib, lib.uz_vcf_samples_text(table._native.ptr, C.byref(v)))
+    return v
+
+
+def vcf_samples_bcf(table: SitesTable) -> "abi.VcfBcfView":
+    """the bytes of a natively decoded BCF table and where the value arrays of GT, AD, RO, AO, GQ of its records lie (uz_vcf_samples_bcf): what
+    HipEngine.samples_from_bcf sends to the device.  The view points into the table, which must outlive it."""
+    lib = load()
+    v = abi.VcfBcfView()
+    _check(lib, lib.uz_vcf_samples_bcf(table._native.ptr, C.byref(v)))
     return v
 
 

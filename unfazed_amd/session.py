@@ -91,15 +91,16 @@ def site_regions(name, dnms, search_dist):
     return tuple(sorted(out))
 
 
-def lazy_samples(backend, dnms) -> bool:
+def lazy_samples(backend, dnms, sites=None) -> bool:
     """Should the region decode of a batch's sites file leave the sample cells unparsed?  When the batch names two or more kids and the
-    backend parses them on the device (samples_from_text): the cohort route then never reads the host's genotype columns, which are
-    more than 99 % of a cohort file's decode.  UZ_SAMPLES_ROUTE=host: the host parses them, as before.  (Only a text VCF is decoded
-    lazily -- a BCF comes back eager whatever is asked -- and any other consumer of such a table fills it on first access.)"""
+    backend reads them on the device (samples_from_text for a text VCF, samples_from_bcf for NAME.bcf): the cohort route then never reads
+    the host's genotype columns, which are more than 99 % of a cohort file's decode.  UZ_SAMPLES_ROUTE=host: the host parses them, as
+    before.  (Any other consumer of such a table fills it on first access.)"""
     from .hostpath import samples_route
-    if samples_route() == "host" or os.environ.get("UZ_FAMILY_ROUTE", "device") == "host":
+    is_bcf = isinstance(sites, str) and sites.endswith(".bcf")
+    if samples_route(is_bcf) == "host" or os.environ.get("UZ_FAMILY_ROUTE", "device") == "host":
         return False
-    return dnms is not None and hasattr(backend, "samples_from_text") and len({dn.get("kid") for dn in dnms}) >= 2
+    return dnms is not None and hasattr(backend, "samples_from_bcf" if is_bcf else "samples_from_text") and len({dn.get("kid") for dn in dnms}) >= 2
 
 
 def load_sites(name_or_table, regions=None, lazy: bool = False) -> (str, SitesTable):
@@ -223,7 +224,7 @@ def host_for(sites, insert_size_max_sample: int = 1000000, dnms=None, search_dis
     """dnms + search_dist: the batch the host will serve -- a sites file with a tabix index next to it is then decoded through
     the index for the batch's windows only (one table, one host per distinct batch)"""
     backend = get_backend()
-    key, table = load_sites(sites, site_regions(sites, dnms, search_dist), lazy=lazy_samples(backend, dnms))
+    key, table = load_sites(sites, site_regions(sites, dnms, search_dist), lazy=lazy_samples(backend, dnms, sites))
     hk = (key, id(backend))
     if hk not in _HOSTS:
         _HOSTS[hk] = PhasingHost(backend, table, _LazyReads(insert_size_max_sample))
