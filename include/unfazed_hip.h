@@ -176,6 +176,17 @@ int uz_bam_walk(uz_ctx *ctx, const uint8_t *comp, int64_t comp_bytes, int64_t n_
 /* k_bgzf_crc32 alone (the parity tests hold it against zlib): blocks data[off[k] .. off[k + 1]) of at most 64 KiB (host memory), want[k] their CRC-32;
  * *first_bad = -1, or a block whose checksum differs */
 int uz_crc32_blocks(uz_ctx *ctx, const uint8_t *data, int64_t n_blocks, const int64_t *off, const uint32_t *want, int64_t *first_bad);
+/* uz_bam_walk over the blocks of MANY files presented as one (unfazed_io.h: uz_bamsrc_open_many -- blk_coff, the spans and the tasks' references are
+ * the set's).  file_base / ref_base [n_files + 1], salt1 / salt2 [n_files]: uz_bamsrc_files.  A task's file is the one its first block lies in; the
+ * walk adds the file's ref_base to refID / next_refID of its records and mixes the salts into h1 / h2 (uz_bamwalk.h: uz_walk_file), so that the joins,
+ * uz_reads_from_walk and uz_reads_names see one file.  Refused when a task's reference is not one of its file's. */
+int uz_bam_walk_many(uz_ctx *ctx, const uint8_t *comp, int64_t comp_bytes, int64_t n_blocks, const int64_t *in_off, const int64_t *out_off, const int64_t *blk_coff,
+                     const uint32_t *blk_crc, int32_t n_tasks, const int32_t *task, int64_t n_spans, const int64_t *span, int64_t n_reach, const int32_t *reach,
+                     int64_t n_fetch, const int32_t *fetch, int32_t n_files, const int64_t *file_base, const int32_t *ref_base, const uint64_t *salt1,
+                     const uint32_t *salt2, int *walk_id, int64_t *n_desc);
+/* A table built from such a batch (uz_reads_from_walk / uz_reads_from_bam): per file its first record and its first name id -- rec_first /
+ * name_first [n_files + 1], from ref_base [n_files + 1].  A file's names must be one range of ids, the ranges in file order: UZ_E_STATE otherwise. */
+int uz_reads_files(uz_ctx *ctx, int reads_id, int32_t n_files, const int32_t *ref_base, int64_t *rec_first, int64_t *name_first);
 int uz_bam_walk_fetch(uz_ctx *ctx, int walk_id, uz_walk_desc *desc, int64_t *d_first, int32_t *d_flags, int64_t *d_walked);
 int uz_bam_walk_release(uz_ctx *ctx, int walk_id);
 /* ---- The batch-wide joins of a walked batch ON THE DEVICE (csrc/k_bamjoin.hip): mate() for every fetched record and every mate of a mate
@@ -285,6 +296,13 @@ int uz_phase_end(uz_ctx *ctx, int fam_id, int reads_id, const uz_dnms_view *dnms
  * order; uz_phase_votes / uz_phase_groups afterwards give query-name ids of the group's own table. */
 int uz_phase_cohort(uz_ctx *ctx, const uz_cohort_group *groups, int32_t n_groups, const uz_dnms_view *dnms, int find_mode,
                     int32_t *status, int32_t *counts, int32_t *origin, int32_t *evidence);
+/* The same run on a table that already IS the groups' tables end to end: one built over the groups' alignment files presented as one file
+ * (uz_bam_walk_many ... uz_reads_from_walk).  group_ref_base [n_groups]: where each group's file starts among the table's contigs (its contigs
+ * reach to the next larger base of any group, or to the table's end); `rcontig` of a DNM is the file's own number and becomes -1 outside the
+ * file.  groups[g].reads_id is not looked at.  Nothing is concatenated and nothing copied per group; uz_phase_votes / uz_phase_groups give the
+ * TABLE's name ids (uz_reads_files: where each file's begin). */
+int uz_phase_cohort_joined(uz_ctx *ctx, int reads_id, const uz_cohort_group *groups, int32_t n_groups, const int32_t *group_ref_base, const uz_dnms_view *dnms,
+                           int find_mode, int32_t *status, int32_t *counts, int32_t *origin, int32_t *evidence);
 /* Vote lists of the last uz_phase (for --verbose and the records dict):
  * vote_off[4n+1] then vote_val: dad_reads (qname ids, ascending), mom_reads,
  * dad_sites (positions, ascending), mom_sites.  Call with vote_val == NULL to get

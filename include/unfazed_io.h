@@ -263,6 +263,18 @@ void uz_select_free(uz_select *s);
 typedef struct uz_bamsrc uz_bamsrc; /* an opened BAM + its BAI (mapped; header and the head of the file read once) */
 typedef struct uz_stage uz_stage;   /* one batch planned: sizes known, columns not written yet */
 int uz_bamsrc_open(const char *path, const char *bai_path, int64_t head_records, uz_bamsrc **out);
+/* Many indexed BAMs as ONE source (a cohort's files walked as one batch).  The source's references are those of file 0, then file 1, ... (files
+ * may differ in their headers): ref_base[f] is the running sum of their counts, and refID / next_refID of a record of file f have ref_base[f]
+ * added wherever a record is parsed.  A compressed offset of file f is file_base[f] + its offset in the file, file_base the running sum of the
+ * file sizes rounded up to 64 KiB (the set is refused when the total does not fit 48 bits); every offset of the file's index is shifted the same
+ * way.  The end of a file ends a chain of blocks.  Both name hashes of a record are mixed with its file's salt (0 for file 0): the same read
+ * name in two files is two names.  bai_paths: NULL, or per file NULL = beside the BAM.  head_records: as uz_bamsrc_open for ONE path -- whose
+ * source is then exactly uz_bamsrc_open's; a set keeps no template lengths (they are per file). */
+int uz_bamsrc_open_many(const char *const *paths, const char *const *bai_paths, int32_t n, int64_t head_records, uz_bamsrc **out);
+int32_t uz_bamsrc_n_files(const uz_bamsrc *s);
+/* file_base [n_files + 1], ref_base [n_files + 1], salt1 / salt2 [n_files] (what h1 / h2 of uz_walk_desc are XOR-ed with); any may be NULL */
+int uz_bamsrc_files(const uz_bamsrc *s, int64_t *file_base, int32_t *ref_base, uint64_t *salt1, uint32_t *salt2);
+int32_t uz_bamsrc_ref_file(const uz_bamsrc *s, int32_t ref); /* the file of a reference of the source, -1 outside */
 void uz_bamsrc_close(uz_bamsrc *s);
 int32_t uz_bamsrc_n_contigs(const uz_bamsrc *s);
 const char *uz_bamsrc_contig_name(const uz_bamsrc *s, int32_t i);

@@ -44,6 +44,15 @@ typedef struct uz_need_rec {
     uint32_t pad;
 } uz_need_rec;
 
+/* A batch over many files presented as one (unfazed_io.h: uz_bamsrc_open_many): what the walk needs of the file a walk task lies in, per task
+ * (uz_bam_walk_many derives it from the per-file table and the task's first block).  A record's refID / next_refID that the file's header knows
+ * (0 <= r < n_ref) get ref_base added, one it does not know becomes INT32_MAX; h1 / h2 are XOR-ed with the salts. */
+typedef struct uz_walk_file {
+    uint64_t salt1;
+    int32_t ref_base, n_ref;
+    uint32_t salt2, pad;
+} uz_walk_file;
+
 /* the walk plan as flat arrays (uz_stage_walk_plan fills them, uz_bam_walk reads them) */
 #define UZ_WALK_TASK_COLS 10 /* int32 per task: tid, b (first position behind its reach), span0, span1, reach0, reach1, fetch0, fetch1, fetch_max_len, host */
 /* host (column 9): the task of the stage this walk task is a part of (uz_stage_walk_plan cuts a stage task into sub-tasks: groups of its reach

@@ -471,7 +471,7 @@ void uz_destroy(uz_ctx *c) {
     if (c->dn_stage) (void)hipHostFree(c->dn_stage);
     if (c->find_pin) (void)hipHostFree(c->find_pin);
     if (c->nm_pin) (void)hipHostFree(c->nm_pin);
-    c->nm_ids.release(); c->nm_len.release(); c->nm_off.release(); c->nm_out.release();
+    c->nm_ids.release(); c->nm_len.release(); c->nm_off.release(); c->nm_out.release(); c->rf_first.release(); c->rf_mm.release();
     c->ab_lut.release(); c->win_range.release();
     c->dn_fam.release(); c->dn_cutoff.release(); c->fam_cls.release();
     c->cnv_counts.release(); c->cnv_pos.release(); c->cnv_origin.release(); c->cnv_evidence.release(); c->cnv_etype.release(); c->cnv_rb.release(); c->cnv_off.release(); c->cnv_dense.release();
@@ -1415,7 +1415,31 @@ struct WalkPlan {
     const uint8_t *comp; int64_t comp_bytes, n_blocks; const int64_t *in_off, *out_off, *blk_coff; const uint32_t *blk_crc;
     int32_t n_tasks; const int32_t *task; int64_t n_spans; const int64_t *span; int64_t n_reach; const int32_t *reach; int64_t n_fetch; const int32_t *fetch;
     int64_t out_bytes() const { return n_blocks ? out_off[n_blocks] : 0; }
+    // a batch over many files (uz_bam_walk_many): the per-file table, NULL for one file
+    int32_t n_files = 0; const int64_t *file_base = nullptr; const int32_t *ref_base = nullptr; const uint64_t *salt1 = nullptr; const uint32_t *salt2 = nullptr;
 };
+
+// the file of every walk task (uz_bamwalk.h: uz_walk_file): the one its first gathered block lies in -- whose references must hold the task's
+std::vector<uz_walk_file> task_files(const WalkPlan &p) {
+    UZ_REQUIRE(p.n_files >= 1 && p.file_base && p.ref_base && p.salt1 && p.salt2, UZ_E_ARG, "uz_bam_walk_many: null file table");
+    UZ_REQUIRE(p.file_base[0] == 0 && p.ref_base[0] == 0, UZ_E_ARG, "uz_bam_walk_many: file_base and ref_base start at 0");
+    for (int32_t f = 0; f < p.n_files; f++)
+        UZ_REQUIRE(p.file_base[f + 1] >= p.file_base[f] && p.ref_base[f + 1] >= p.ref_base[f], UZ_E_ARG, "uz_bam_walk_many: file_base and ref_base are running sums");
+    std::vector<uz_walk_file> out((size_t)p.n_tasks);
+    for (int32_t t = 0; t < p.n_tasks; t++) {
+        const int32_t *tc = p.task + UZ_WALK_TASK_COLS * (size_t)t;
+        int32_t f = -1;
+        for (int32_t sp = tc[2]; sp < tc[3] && f < 0; sp++) {
+            const int64_t *sc = p.span + UZ_WALK_SPAN_COLS * (size_t)sp;
+            if (sc[4] < sc[5]) f = (int32_t)(std::upper_bound(p.file_base, p.file_base + p.n_files + 1, p.blk_coff[sc[4]]) - p.file_base) - 1;
+        }
+        if (f < 0) f = (int32_t)(std::upper_bound(p.ref_base, p.ref_base + p.n_files + 1, tc[0]) - p.ref_base) - 1; // (no block: nothing is walked)
+        UZ_REQUIRE(f >= 0 && f < p.n_files && tc[0] >= p.ref_base[f] && tc[0] < p.ref_base[f + 1], UZ_E_ARG,
+                   "uz_bam_walk_many: a task's first block lies in another file than its reference");
+        out[(size_t)t] = uz_walk_file{p.salt1[f], p.ref_base[f], p.ref_base[f + 1] - p.ref_base[f], p.salt2[f], 0u};
+    }
+    return out;
+}
 
 void check_walk_plan(const WalkPlan &p) {
     UZ_REQUIRE(p.n_blocks >= 0 && p.comp_bytes >= 0 && p.n_tasks >= 0 && p.n_spans >= 0 && p.n_reach >= 0 && p.n_fetch >= 0, UZ_E_ARG, "bad arguments");
@@ -1498,7 +1522,8 @@ void queue_blocks(uz_ctx *c, uz_ctx::WalkSlot &w, const WalkPlan &p, const std::
 // the plan up, the walk, and the count of the descriptors the host's joins can need at all (direct, or sharing a name hash with a direct record of
 // the task).  The two counts come down by copies on the slot's stream: they belong to the caller, whose frame outlives the stream's drain (SlotClaim);
 // *kept is valid after the caller's synchronise
-void queue_walk(uz_ctx *c, uz_ctx::WalkSlot &w, const WalkPlan &p, const std::vector<int64_t> &first, int64_t *tab_total_p, int64_t *kept) {
+void queue_walk(uz_ctx *c, uz_ctx::WalkSlot &w, const WalkPlan &p, const std::vector<int64_t> &first, const std::vector<uz_walk_file> &tfile, int64_t *tab_total_p,
+                int64_t *kept) {
     const int32_t n_tasks = p.n_tasks;
     hipStream_t st = w.s0;
     int64_t &tab_total = *tab_total_p;
@@ -1509,8 +1534,12 @@ void queue_walk(uz_ctx *c, uz_ctx::WalkSlot &w, const WalkPlan &p, const std::ve
     if (p.n_spans) UZ_HIP(hipMemcpyAsync(w.span.p, p.span, (size_t)p.n_spans * UZ_WALK_SPAN_COLS * 8, hipMemcpyHostToDevice, st));
     if (p.n_reach) UZ_HIP(hipMemcpyAsync(w.reach.p, p.reach, (size_t)p.n_reach * 8, hipMemcpyHostToDevice, st));
     if (p.n_fetch) UZ_HIP(hipMemcpyAsync(w.fetch.p, p.fetch, (size_t)p.n_fetch * 12, hipMemcpyHostToDevice, st));
+    if (!tfile.empty()) { // (pageable, as `first`: read by the time the synchronise below returns)
+        UZ_WGROW(w, tfile, (size_t)n_tasks + 1);
+        UZ_HIP(hipMemcpyAsync(w.tfile.p, tfile.data(), (size_t)n_tasks * sizeof(uz_walk_file), hipMemcpyHostToDevice, st));
+    }
     uz_launch_bam_walk(c, st, n_tasks, w.out.p, w.out_off.p, w.blk_coff.p, w.task.p, w.span.p, w.reach.p, w.fetch.p, w.count.p, w.first.p, w.walked.p,
-                       w.flags.p, w.desc.p, w.n_direct.p, w.tab_first.p);
+                       w.flags.p, w.desc.p, w.n_direct.p, w.tab_first.p, tfile.empty() ? nullptr : w.tfile.p);
     UZ_HIP(hipMemcpyAsync(&tab_total, w.tab_first.p + n_tasks, 8, hipMemcpyDeviceToHost, st));
     UZ_HIP(hipStreamSynchronize(st)); // (the pageable `first` has been read; the hash sets' size is known)
     UZ_WGROW(w, tab, (size_t)tab_total + 1);
@@ -1995,6 +2024,48 @@ int uz_phase_end(uz_ctx *c, int fam_id, int reads_id, const uz_dnms_view *d, int
     });
 }
 
+// The run of a cohort batch over ONE table whose contigs are "group x contig" -- the merged table of uz_phase_cohort, or a table built over the
+// groups' files at once (uz_phase_cohort_joined): reads contigs renumbered into that table (contig_base[g] + the file's own number, -1 outside the
+// nc_g[g] contigs of the group's file), family / cutoff / name base per DNM, then find and the read stage.
+static void cohort_run(uz_ctx *c, const uz_cohort_group *groups, int32_t n_groups, const uz_dnms_view *d, int find_mode, FamilyDev &f0, SitesDev &s, ReadsDev &R,
+                   const int64_t *contig_base, const int32_t *nc_g, const uint32_t *q_base, int32_t *status, int32_t *counts, int32_t *origin, int32_t *evidence) {
+    const int32_t n = d->n;
+    // ---- the batch: reads contigs renumbered into the merged table, family / cutoff / name base per DNM
+    std::vector<int32_t> rc((size_t)n), fam_h((size_t)n, 0);
+    std::vector<double> cut_h((size_t)n, 0.0);
+    c->phase_qbase.assign((size_t)n, 0);
+    for (int32_t k = 0; k < n; k++) rc[(size_t)k] = -1;
+    std::vector<uint8_t *> cls_h((size_t)n_groups);
+    for (int32_t g = 0; g < n_groups; g++) {
+        FamilyDev &f = fam_of(c, groups[g].fam_id);
+        if (!uz_site_scan_fresh(c, f, false)) uz_launch_site_scan(c, f, s, false);
+        cls_h[(size_t)g] = f.cls;
+        for (int32_t k = groups[g].dnm_first; k < groups[g].dnm_first + groups[g].dnm_count; k++) {
+            const int32_t t = d->rcontig[k];
+            rc[(size_t)k] = (t >= 0 && t < nc_g[g]) ? (int32_t)(contig_base[g] + t) : -1;
+            fam_h[(size_t)k] = g; cut_h[(size_t)k] = groups[g].cutoff; c->phase_qbase[(size_t)k] = q_base ? q_base[g] : 0u;
+        }
+    }
+    uz_dnms_view dv = *d;
+    dv.rcontig = rc.data();
+    find_target(c); c->phase_valid = false; // (the cohort's lists take the place of the older set, under no key)
+    uz_stage_dnms(c, &dv);
+    c->dn_fam.ensure((size_t)n + 1); c->dn_cutoff.ensure((size_t)n + 1); c->fam_cls.ensure((size_t)n_groups + 1);
+    if (n) {
+        UZ_HIP(hipMemcpyAsync(c->dn_fam.p, fam_h.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        UZ_HIP(hipMemcpyAsync(c->dn_cutoff.p, cut_h.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
+    UZ_HIP(hipMemcpyAsync(c->fam_cls.p, cls_h.data(), (size_t)n_groups * sizeof(uint8_t *), hipMemcpyHostToDevice, c->stream));
+    UZ_HIP(hipStreamSynchronize(c->stream)); // the staging vectors above are locals
+    c->cohort_on = true;
+    try {
+        uz_launch_find(c, f0, s, find_mode, false);
+        c->find_fam = groups[0].fam_id;
+        uz_launch_phase(c, f0, s, R, status, counts, origin, evidence);
+    } catch (...) { c->cohort_on = false; throw; }
+    c->cohort_on = false;
+}
+
 int uz_phase_cohort(uz_ctx *c, const uz_cohort_group *groups, int32_t n_groups, const uz_dnms_view *d, int find_mode, int32_t *status,
                     int32_t *counts, int32_t *origin, int32_t *evidence) {
     return guarded(c, [&] {
@@ -2085,41 +2156,45 @@ int uz_phase_cohort(uz_ctx *c, const uz_cohort_group *groups, int32_t n_groups, 
             c->cohort_ids = ids;
         }
         ReadsDev &R = c->reads[(size_t)c->cohort_reads];
-        // ---- the batch: reads contigs renumbered into the merged table, family / cutoff / name base per DNM
-        std::vector<int32_t> rc((size_t)n), fam_h((size_t)n, 0);
-        std::vector<double> cut_h((size_t)n, 0.0);
-        c->phase_qbase.assign((size_t)n, 0);
-        for (int32_t k = 0; k < n; k++) rc[(size_t)k] = -1;
-        std::vector<uint8_t *> cls_h((size_t)n_groups);
+        std::vector<int32_t> nc_g((size_t)n_groups);
+        for (int32_t g = 0; g < n_groups; g++) nc_g[(size_t)g] = reads_of(c, groups[g].reads_id).n_contigs;
+        cohort_run(c, groups, n_groups, d, find_mode, f0, s, R, contig_base.data(), nc_g.data(), q_base.data(), status, counts, origin, evidence);
+    });
+}
+
+// uz_phase_cohort's run on a table that already IS the groups' tables end to end: one built over the groups' files presented as one
+// (uz_bam_walk_many -> uz_reads_from_walk).  group_ref_base [n_groups]: where each group's file starts among the table's contigs; the file's contigs
+// reach to the next larger base of any group, or to the table's last.  No concatenation, no copy per group; the vote lists carry the table's own
+// name ids (uz_reads_files says where each file's start).  groups[g].reads_id is not looked at.
+int uz_phase_cohort_joined(uz_ctx *c, int reads_id, const uz_cohort_group *groups, int32_t n_groups, const int32_t *group_ref_base, const uz_dnms_view *d,
+                           int find_mode, int32_t *status, int32_t *counts, int32_t *origin, int32_t *evidence) {
+    return guarded(c, [&] {
+        UZ_REQUIRE(groups && n_groups > 0 && d && group_ref_base, UZ_E_ARG, "bad cohort batch");
+        UZ_REQUIRE(!(find_mode & UZ_FIND_WHOLE_REGION), UZ_E_ARG, "the read stage runs on SNV / breakpoint windows");
+        const int32_t n = d->n;
+        FamilyDev &f0 = fam_of(c, groups[0].fam_id);
+        SitesDev &s = sites_of(c, f0.sites_id);
+        ReadsDev &R = reads_of(c, reads_id);
+        UZ_REQUIRE(reads_id != c->cohort_reads, UZ_E_ARG, "the merged cohort table of uz_phase_cohort is not a joined table");
+        std::vector<int32_t> bases(group_ref_base, group_ref_base + n_groups);
+        std::sort(bases.begin(), bases.end());
+        std::vector<int64_t> contig_base((size_t)n_groups);
+        std::vector<int32_t> nc_g((size_t)n_groups);
         for (int32_t g = 0; g < n_groups; g++) {
-            FamilyDev &f = fam_of(c, groups[g].fam_id);
-            if (!uz_site_scan_fresh(c, f, false)) uz_launch_site_scan(c, f, s, false);
-            cls_h[(size_t)g] = f.cls;
-            const int32_t nc_g = reads_of(c, groups[g].reads_id).n_contigs;
-            for (int32_t k = groups[g].dnm_first; k < groups[g].dnm_first + groups[g].dnm_count; k++) {
-                const int32_t t = d->rcontig[k];
-                rc[(size_t)k] = (t >= 0 && t < nc_g) ? (int32_t)(contig_base[(size_t)g] + t) : -1;
-                fam_h[(size_t)k] = g; cut_h[(size_t)k] = groups[g].cutoff; c->phase_qbase[(size_t)k] = q_base[(size_t)g];
-            }
+            UZ_REQUIRE(groups[g].dnm_first >= 0 && groups[g].dnm_count >= 0 && groups[g].dnm_first + groups[g].dnm_count <= n, UZ_E_ARG,
+                       "cohort group outside the DNM batch");
+            UZ_REQUIRE(fam_of(c, groups[g].fam_id).sites_id == f0.sites_id, UZ_E_ARG, "the families of a cohort batch must share a sites table");
+            UZ_REQUIRE(group_ref_base[g] >= 0 && group_ref_base[g] <= R.n_contigs, UZ_E_ARG, "a group's file starts outside the table's contigs");
+            const auto nx = std::upper_bound(bases.begin(), bases.end(), group_ref_base[g]);
+            contig_base[(size_t)g] = group_ref_base[g];
+            nc_g[(size_t)g] = (nx == bases.end() ? R.n_contigs : *nx) - group_ref_base[g];
         }
-        uz_dnms_view dv = *d;
-        dv.rcontig = rc.data();
-        find_target(c); c->phase_valid = false; // (the cohort's lists take the place of the older set, under no key)
-        uz_stage_dnms(c, &dv);
-        c->dn_fam.ensure((size_t)n + 1); c->dn_cutoff.ensure((size_t)n + 1); c->fam_cls.ensure((size_t)n_groups + 1);
-        if (n) {
-            UZ_HIP(hipMemcpyAsync(c->dn_fam.p, fam_h.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-            UZ_HIP(hipMemcpyAsync(c->dn_cutoff.p, cut_h.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        uz_reads_make_ready(c, R);
+        if (!R.qlow_valid || R.qlow_thr != c->P.min_gt_qual) {
+            UZ_REQUIRE(R.qual8 != nullptr, UZ_E_STATE, "the joined reads table was packed for another --min-gt-qual");
+            uz_build_qlow(c, c->stream, R, c->P.min_gt_qual);
         }
-        UZ_HIP(hipMemcpyAsync(c->fam_cls.p, cls_h.data(), (size_t)n_groups * sizeof(uint8_t *), hipMemcpyHostToDevice, c->stream));
-        UZ_HIP(hipStreamSynchronize(c->stream)); // the staging vectors above are locals
-        c->cohort_on = true;
-        try {
-            uz_launch_find(c, f0, s, find_mode, false);
-            c->find_fam = groups[0].fam_id;
-            uz_launch_phase(c, f0, s, R, status, counts, origin, evidence);
-        } catch (...) { c->cohort_on = false; throw; }
-        c->cohort_on = false;
+        cohort_run(c, groups, n_groups, d, find_mode, f0, s, R, contig_base.data(), nc_g.data(), nullptr, status, counts, origin, evidence);
     });
 }
 
@@ -2309,13 +2384,15 @@ int uz_prof_units(uz_ctx *c, int kernel, int64_t *units) {
 }
 
 // ---- the record walk on the device (include/uz_bamwalk.h, csrc/k_bamwalk.hip)
-int uz_bam_walk(uz_ctx *c, const uint8_t *comp, int64_t comp_bytes, int64_t n_blocks, const int64_t *in_off, const int64_t *out_off, const int64_t *blk_coff,
-                const uint32_t *blk_crc, int32_t n_tasks, const int32_t *task, int64_t n_spans, const int64_t *span, int64_t n_reach, const int32_t *reach, int64_t n_fetch,
-                const int32_t *fetch, int *walk_id, int64_t *n_desc) {
+static int bam_walk(uz_ctx *c, const WalkPlan &p, int *walk_id, int64_t *n_desc) {
+    const int64_t n_blocks = p.n_blocks, comp_bytes = p.comp_bytes, n_spans = p.n_spans, n_reach = p.n_reach, n_fetch = p.n_fetch;
+    const int32_t n_tasks = p.n_tasks;
+    const int32_t *task = p.task;
+    const uint32_t *blk_crc = p.blk_crc;
     return guarded(c, [&] {
         UZ_REQUIRE(walk_id && n_desc, UZ_E_ARG, "bad arguments");
-        const WalkPlan p{comp, comp_bytes, n_blocks, in_off, out_off, blk_coff, blk_crc, n_tasks, task, n_spans, span, n_reach, reach, n_fetch, fetch};
         check_walk_plan(p);
+        const std::vector<uz_walk_file> tfile = p.n_files ? task_files(p) : std::vector<uz_walk_file>();
         UZ_HIP(hipSetDevice(c->device));
         const std::vector<int64_t> first = desc_slices(p), cut = block_slices(n_blocks);
         const size_t ns = cut.size() - 1;
@@ -2348,7 +2425,7 @@ int uz_bam_walk(uz_ctx *c, const uint8_t *comp, int64_t comp_bytes, int64_t n_bl
         UZ_WGROW(w, count, nt); UZ_WGROW(w, first, nt + 1); UZ_WGROW(w, walked, nt); UZ_WGROW(w, flags, nt);
         UZ_WGROW(w, n_direct, nt); UZ_WGROW(w, tab_first, nt + 1); UZ_WGROW(w, kcount, nt); UZ_WGROW(w, kfirst, nt + 1);
         queue_blocks(c, w, p, cut);
-        if (n_tasks) queue_walk(c, w, p, first, &tab_total, &kept);
+        if (n_tasks) queue_walk(c, w, p, first, tfile, &tab_total, &kept);
         if (n_blocks) UZ_HIP(hipMemcpyAsync(iflags.data(), w.iflags.p, (2 * ns + (blk_crc ? 1 : 0)) * sizeof(int32_t), hipMemcpyDeviceToHost, w.s0));
         UZ_HIP(hipStreamSynchronize(w.s0));
         throw_block_errors(p, cut, iflags);
@@ -2357,6 +2434,23 @@ int uz_bam_walk(uz_ctx *c, const uint8_t *comp, int64_t comp_bytes, int64_t n_bl
         *walk_id = k;
         claim.dismiss();
     });
+}
+
+int uz_bam_walk(uz_ctx *c, const uint8_t *comp, int64_t comp_bytes, int64_t n_blocks, const int64_t *in_off, const int64_t *out_off, const int64_t *blk_coff,
+                const uint32_t *blk_crc, int32_t n_tasks, const int32_t *task, int64_t n_spans, const int64_t *span, int64_t n_reach, const int32_t *reach, int64_t n_fetch,
+                const int32_t *fetch, int *walk_id, int64_t *n_desc) {
+    const WalkPlan p{comp, comp_bytes, n_blocks, in_off, out_off, blk_coff, blk_crc, n_tasks, task, n_spans, span, n_reach, reach, n_fetch, fetch};
+    return bam_walk(c, p, walk_id, n_desc);
+}
+
+// the same over the blocks of many files laid end to end as one (unfazed_io.h: uz_bamsrc_open_many; uz_bamwalk.h: uz_walk_file)
+int uz_bam_walk_many(uz_ctx *c, const uint8_t *comp, int64_t comp_bytes, int64_t n_blocks, const int64_t *in_off, const int64_t *out_off, const int64_t *blk_coff,
+                     const uint32_t *blk_crc, int32_t n_tasks, const int32_t *task, int64_t n_spans, const int64_t *span, int64_t n_reach, const int32_t *reach, int64_t n_fetch,
+                     const int32_t *fetch, int32_t n_files, const int64_t *file_base, const int32_t *ref_base, const uint64_t *salt1, const uint32_t *salt2, int *walk_id,
+                     int64_t *n_desc) {
+    WalkPlan p{comp, comp_bytes, n_blocks, in_off, out_off, blk_coff, blk_crc, n_tasks, task, n_spans, span, n_reach, reach, n_fetch, fetch};
+    p.n_files = n_files < 1 ? -1 : n_files; p.file_base = file_base; p.ref_base = ref_base; p.salt1 = salt1; p.salt2 = salt2; // (-1: refused by task_files)
+    return bam_walk(c, p, walk_id, n_desc);
 }
 
 int uz_bam_walk_fetch(uz_ctx *c, int walk_id, uz_walk_desc *desc, int64_t *d_first, int32_t *d_flags, int64_t *d_walked) {
@@ -2524,6 +2618,44 @@ int uz_reads_names(uz_ctx *c, int reads_id, const uint32_t *ids, int64_t n, int6
         uz_kcopy(c, c->nm_pin, c->nm_out.p, ((size_t)total + 3) & ~(size_t)3);
         UZ_HIP(hipStreamSynchronize(st));
         *bytes = c->nm_pin;
+    });
+}
+
+// A table built over many files presented as one (uz_bam_walk_many): per file its first record and its first name id.  ref_base [n_files + 1]: the
+// files' references among the table's contigs.  rec_first follows from contig_off; name_first is the smallest name id of the file's records
+// (k_reads_files), for a file without records the next file's.  The names of a file must be ONE range of ids, the ranges in file order and
+// together every id of the table: that is what lets one name map serve every file, and a table that breaks it is refused.
+int uz_reads_files(uz_ctx *c, int reads_id, int32_t n_files, const int32_t *ref_base, int64_t *rec_first, int64_t *name_first) {
+    return guarded(c, [&] {
+        ReadsDev &r = reads_of(c, reads_id);
+        UZ_REQUIRE(n_files >= 1 && ref_base && rec_first && name_first, UZ_E_ARG, "uz_reads_files: bad arguments");
+        UZ_REQUIRE(ref_base[0] == 0 && ref_base[n_files] == r.n_contigs, UZ_E_ARG, "uz_reads_files: ref_base must run from 0 to the table's contigs");
+        for (int32_t f = 0; f < n_files; f++) UZ_REQUIRE(ref_base[f + 1] >= ref_base[f], UZ_E_ARG, "uz_reads_files: ref_base is a running sum");
+        uz_reads_make_ready(c, r);
+        hipStream_t st = c->stream;
+        std::vector<int64_t> coff((size_t)r.n_contigs + 1);
+        UZ_HIP(hipMemcpyAsync(coff.data(), r.contig_off, coff.size() * 8, hipMemcpyDeviceToHost, st));
+        UZ_HIP(hipStreamSynchronize(st));
+        uz_check_upload_flag(c);
+        for (int32_t f = 0; f <= n_files; f++) rec_first[f] = coff[(size_t)ref_base[f]];
+        UZ_REQUIRE(rec_first[0] == 0 && rec_first[n_files] == r.n, UZ_E_STATE, "uz_reads_files: the table's contig offsets do not cover its records");
+        for (int32_t f = 0; f < n_files; f++) UZ_REQUIRE(rec_first[f + 1] >= rec_first[f], UZ_E_STATE, "uz_reads_files: the table's contig offsets descend");
+        c->rf_first.ensure((size_t)n_files + 1); c->rf_mm.ensure(2 * (size_t)n_files);
+        std::vector<uint32_t> mm(2 * (size_t)n_files);
+        UZ_HIP(hipMemcpyAsync(c->rf_first.p, rec_first, ((size_t)n_files + 1) * 8, hipMemcpyHostToDevice, st));
+        uz_launch_reads_files(c, st, n_files, r.rec_b, c->rf_first.p, c->rf_mm.p, c->rf_mm.p + n_files);
+        UZ_HIP(hipMemcpyAsync(mm.data(), c->rf_mm.p, mm.size() * 4, hipMemcpyDeviceToHost, st));
+        UZ_HIP(hipStreamSynchronize(st));
+        int64_t next = 0;
+        for (int32_t f = 0; f < n_files; f++) {
+            name_first[f] = next;
+            if (rec_first[f + 1] == rec_first[f]) continue;
+            UZ_REQUIRE((int64_t)mm[(size_t)f] == next && mm[(size_t)n_files + (size_t)f] >= mm[(size_t)f], UZ_E_STATE,
+                       "uz_reads_files: the name ids of file " + std::to_string(f) + " do not start where those of the files before it end");
+            next = (int64_t)mm[(size_t)n_files + (size_t)f] + 1;
+        }
+        name_first[n_files] = next;
+        UZ_REQUIRE(next == (int64_t)r.n_qnames, UZ_E_STATE, "uz_reads_files: the files' name ids are not the table's");
     });
 }
 

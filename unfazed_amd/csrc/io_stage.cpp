@@ -86,6 +86,19 @@ struct uz_bamsrc {
     std::vector<std::string> contigs;
     std::vector<int32_t> contig_len;
     std::vector<int32_t> tlen_head;
+    // A source over many files (uz_bamsrc_open_many) is ONE virtual file: `map` is a reserved address range in which file f is mapped at
+    // file_base[f] (the running sum of the sizes rounded up to 64 KiB), `size` the whole range; contigs / contig_len / refs are those of file 0, then
+    // file 1, ... (ref_base: the running sum of their counts), every offset of a file's index shifted by its base.  A record's refID and next_refID
+    // get the file's ref_base added where they are parsed, and both name hashes are mixed with the file's salt: equal names of two files are two names.
+    // One file: the same tables with one entry, salt 0 -- nothing below takes another path for it.
+    struct Part { size_t size; };
+    std::vector<Part> parts;        // (many files only: the mapping needs no descriptor once it is made -- a cohort's set holds none open)
+    std::vector<int64_t> file_base; // [n_files + 1]
+    std::vector<int32_t> ref_base;  // [n_files + 1]
+    std::vector<int32_t> ref_file;  // [references]: the file of every reference
+    std::vector<uint64_t> salt1;    // [n_files]
+    std::vector<uint32_t> salt2;
+    bool many = false;
     ~uz_bamsrc() {
         if (map && size) munmap(const_cast<uint8_t *>(map), size);
         if (fd >= 0) close(fd);
@@ -96,13 +109,31 @@ namespace {
 
 struct BlockHdr { size_t cdata, clen, blen; uint32_t crc, isize; };
 
-// header of the BGZF block at compressed offset coff; false at the end of the file
-bool block_at(const uz_bamsrc &S, int64_t coff, BlockHdr &b) {
-    if (coff < 0 || (size_t)coff + 18 > S.size) return false;
+// what a record's fields and names of one file of the source are shifted and salted by
+struct FileKey { int32_t ref_base, n_ref; uint64_t s1; uint32_t s2; };
+inline FileKey file_key(const uz_bamsrc &S, int32_t ref) { // ref: a reference of the (virtual) source
+    if (!S.many) return FileKey{0, (int32_t)S.contigs.size(), 0, 0};
+    const size_t f = (size_t)S.ref_file[(size_t)ref];
+    return FileKey{S.ref_base[f], S.ref_base[f + 1] - S.ref_base[f], S.salt1[f], S.salt2[f]};
+}
+// refID / next_refID as the file has it -> the source's: shifted; one the file's header does not know stays outside every file's
+inline int32_t shift_ref(int32_t r, const FileKey &k) { return r < 0 ? r : (r < k.n_ref ? r + k.ref_base : INT32_MAX); }
+
+// where the chain of blocks that starts at compressed offset coff ends: the end of the file that holds it (a chain never runs into the next file)
+inline size_t chain_end(const uz_bamsrc &S, int64_t coff) {
+    if (!S.many) return S.size;
+    if (coff < 0 || coff >= S.file_base.back()) return 0;
+    const size_t f = (size_t)(std::upper_bound(S.file_base.begin(), S.file_base.end(), coff) - S.file_base.begin()) - 1;
+    return (size_t)S.file_base[f] + S.parts[f].size;
+}
+
+// header of the BGZF block at compressed offset coff; false at the end of the file (lim: chain_end of the chain the block belongs to)
+bool block_at(const uz_bamsrc &S, int64_t coff, size_t lim, BlockHdr &b) {
+    if (coff < 0 || (size_t)coff + 18 > lim) return false;
     const uint8_t *h = S.map + coff;
     if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4)) fail(UZ_IO_E_FORMAT, "not a BGZF block at byte %lld", (long long)coff);
     const size_t xlen = rd16(h + 10);
-    if ((size_t)coff + 12 + xlen > S.size) fail(UZ_IO_E_FORMAT, "truncated BGZF block");
+    if ((size_t)coff + 12 + xlen > lim) fail(UZ_IO_E_FORMAT, "truncated BGZF block");
     size_t q = 12, bsize = 0;
     bool found = false;
     while (q + 4 <= 12 + xlen) {
@@ -113,7 +144,7 @@ bool block_at(const uz_bamsrc &S, int64_t coff, BlockHdr &b) {
     }
     if (!found) fail(UZ_IO_E_FORMAT, "BGZF block without a BC field at byte %lld", (long long)coff);
     b.blen = bsize + 1;
-    if (b.blen < 12 + xlen + 8 || (size_t)coff + b.blen > S.size) fail(UZ_IO_E_FORMAT, "truncated BGZF block at byte %lld", (long long)coff);
+    if (b.blen < 12 + xlen + 8 || (size_t)coff + b.blen > lim) fail(UZ_IO_E_FORMAT, "truncated BGZF block at byte %lld", (long long)coff);
     b.cdata = (size_t)coff + 12 + xlen;
     b.clen = b.blen - 12 - xlen - 8;
     b.crc = rd32(h + b.blen - 8);
@@ -151,6 +182,7 @@ struct Stream {
     size_t cur = 0;        // next unread byte of buf
     size_t blk = 0;        // block holding `cur`
     int64_t next_coff = 0;
+    size_t lim = 0;        // the end of the file the stream was sought in (chain_end)
     int64_t file_bytes = 0, n_blocks = 0, n_pre = 0;
     bool eof = false;
     Stream(const uz_bamsrc &s, Inflater &i) : S(s), inf(i), buf(own_buf) {}
@@ -158,8 +190,9 @@ struct Stream {
     void seek(uint64_t voff) {
         buf.clear(); blks.clear(); cur = 0; blk = 0; eof = false;
         next_coff = (int64_t)(voff >> 16);
+        lim = chain_end(S, next_coff);
         if (!more()) { // exactly the end of the file: an empty stream (next() says so); anywhere else the index does not belong to this file
-            if ((voff >> 16) != (uint64_t)S.size || (voff & 0xFFFF)) fail(UZ_IO_E_FORMAT, "virtual offset %llu points past the end of the file (a stale or truncated index?)", (unsigned long long)voff);
+            if ((voff >> 16) != (uint64_t)lim || (voff & 0xFFFF)) fail(UZ_IO_E_FORMAT, "virtual offset %llu points past the end of the file (a stale or truncated index?)", (unsigned long long)voff);
             return;
         }
         cur = (size_t)(voff & 0xFFFF);
@@ -181,7 +214,7 @@ struct Stream {
             }
         }
         BlockHdr h;
-        if (!block_at(S, next_coff, h)) { eof = true; return false; }
+        if (!block_at(S, next_coff, lim, h)) { eof = true; return false; }
         if (h.isize > 65536u) fail(UZ_IO_E_FORMAT, "BGZF block at byte %lld declares %u inflated bytes (a block holds at most 65536)", (long long)next_coff, h.isize);
         const size_t at = buf.size();
         buf.resize(at + h.isize);
@@ -280,6 +313,70 @@ void open_source(uz_bamsrc &S, const char *path, const char *bai_path, int64_t h
         if (!s.next(voff, p, bs)) break;
         S.tlen_head.push_back(rdi32(p + 28));
         s.advance(bs);
+    }
+    const int64_t FILE_ALIGN = 65536;
+    S.file_base = {0, ((int64_t)S.size + FILE_ALIGN - 1) / FILE_ALIGN * FILE_ALIGN};
+    S.ref_base = {0, (int32_t)S.contigs.size()};
+    S.ref_file.assign(S.contigs.size(), 0);
+    S.salt1 = {0}; S.salt2 = {0};
+}
+
+inline uint64_t mix64(uint64_t x) { // splitmix64's finaliser
+    x += 0x9E3779B97F4A7C15ULL;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBULL;
+    return x ^ (x >> 31);
+}
+
+// Many files as one source.  Every file is opened as a source of its own first (header, index, every check of open_source) and closed again; then
+// each is mapped at its place in one reserved address range, so that `S.map + coff` reaches a block of any file, and its index is shifted there.
+void open_many(uz_bamsrc &S, int n, const char *const *paths, const char *const *bai_paths) {
+    const int64_t FILE_ALIGN = 65536;
+    S.many = true;
+    S.file_base.assign(1, 0); S.ref_base.assign(1, 0);
+    for (int f = 0; f < n; f++) {
+        uz_bamsrc one;
+        open_source(one, paths[f], bai_paths ? bai_paths[f] : nullptr, 0);
+        if (f == 0) S.path = one.path;
+        S.parts.push_back(uz_bamsrc::Part{one.size});
+        const int64_t base = S.file_base.back();
+        const int64_t next = base + ((int64_t)one.size + FILE_ALIGN - 1) / FILE_ALIGN * FILE_ALIGN;
+        if (next >= ((int64_t)1 << 48)) fail(UZ_IO_E_RANGE, "the files of the set hold more than 2^48 bytes together: their virtual offsets do not fit");
+        const int64_t nr = (int64_t)S.ref_base.back() + (int64_t)one.contigs.size();
+        if (nr > INT32_MAX) fail(UZ_IO_E_RANGE, "the files of the set name more than 2^31 - 1 references together");
+        const uint64_t vb = (uint64_t)base << 16, vsize = (uint64_t)one.size << 16;
+        for (BaiRef &r : one.refs) {
+            for (auto &bin : r.bins)
+                for (Chunk &c : bin.second) {
+                    if (c.beg > vsize || c.end > vsize + 0xFFFF) fail(UZ_IO_E_FORMAT, "the index of %s points past the end of the file (a stale or truncated index?)", paths[f]);
+                    c.beg += vb; c.end += vb;
+                }
+            for (uint64_t &v : r.linear) {
+                if (v > vsize) fail(UZ_IO_E_FORMAT, "the index of %s points past the end of the file (a stale or truncated index?)", paths[f]);
+                v += vb;
+            }
+            S.refs.push_back(std::move(r));
+        }
+        for (size_t c = 0; c < one.contigs.size(); c++) { S.contigs.push_back(one.contigs[c]); S.contig_len.push_back(one.contig_len[c]); S.ref_file.push_back(f); }
+        S.file_base.push_back(next); S.ref_base.push_back((int32_t)nr);
+        S.salt1.push_back(f ? mix64((uint64_t)f) : 0);
+        S.salt2.push_back(f ? (uint32_t)(mix64(~(uint64_t)f) >> 32) : 0u);
+    }
+    const size_t total = (size_t)S.file_base.back();
+    if (!total) return;
+    void *m = mmap(nullptr, total, PROT_NONE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
+    if (m == MAP_FAILED) fail(UZ_IO_E_OPEN, "cannot reserve %zu bytes of address space for %d files", total, n);
+    S.map = (const uint8_t *)m; S.size = total;
+    for (int f = 0; f < n; f++) {
+        if (!S.parts[(size_t)f].size) continue;
+        void *at = (uint8_t *)m + S.file_base[(size_t)f];
+        const int fd = open(paths[f], O_RDONLY);
+        struct stat st;
+        const bool same = fd >= 0 && fstat(fd, &st) == 0 && (size_t)st.st_size == S.parts[(size_t)f].size;
+        const bool ok = same && mmap(at, S.parts[(size_t)f].size, PROT_READ, MAP_SHARED | MAP_FIXED, fd, 0) == at;
+        if (fd >= 0) close(fd);
+        if (!same) fail(UZ_IO_E_OPEN, "%s changed while the set was opened", paths[f]);
+        if (!ok) fail(UZ_IO_E_OPEN, "cannot map %s", paths[f]);
     }
 }
 
@@ -606,10 +703,10 @@ void mates_in_task(const uz_stage &P, Task &T, Scratch &W, size_t ti);
 
 // descriptor route: a record the host walked itself keeps its bytes (the device packs it from there: uz_stage_kept hands them over as the
 // batch's aux bytes) instead of the link-form extract
-void keep_raw(Task &T, WRec &r, const uint8_t *p, uint32_t bs) {
+void keep_raw(Task &T, WRec &r, const uint8_t *p, uint32_t bs, const FileKey &fk) {
     const uint32_t l_name = p[8];
     r.l_name = (uint8_t)(l_name - 1);
-    r.nhash2 = uz_name_hash2(p + 32, l_name - 1);
+    r.nhash2 = uz_name_hash2(p + 32, l_name - 1) ^ fk.s2;
     r.pay_at = (uint32_t)T.raw.size();
     r.cigar_at = 4 + bs;
     T.raw.insert(T.raw.end(), p - 4, p + bs);
@@ -622,6 +719,7 @@ void walk_task(const uz_stage &P, Task &T, Scratch &W, size_t ti, bool finish = 
     const Opt &o = P.opt;
     const std::vector<Fx> &fx = P.fx[(size_t)T.tid];
     const int32_t max_len = P.fx_max_len[(size_t)T.tid];
+    const FileKey fk = file_key(S, T.tid);
     Stream s(S, W.inf, W.buf);
     if (P.inflated && !T.pre.empty()) { s.pre.blks = &T.pre; s.pre.base = P.inflated; }
     std::vector<WRec> &all = W.all;
@@ -639,7 +737,7 @@ void walk_task(const uz_stage &P, Task &T, Scratch &W, size_t ti, bool finish = 
             uint32_t bs;
             if (!s.next(voff, p, bs)) { stop = true; break; } // end of the file
             if (voff >= T.spans[ci].end) break;
-            const int32_t tid = rdi32(p), pos = rdi32(p + 4);
+            const int32_t tid = shift_ref(rdi32(p), fk), pos = rdi32(p + 4);
             if (tid != T.tid) {
                 if (tid < 0 || tid > T.tid) { stop = true; break; }
                 s.advance(bs);
@@ -660,9 +758,9 @@ void walk_task(const uz_stage &P, Task &T, Scratch &W, size_t ti, bool finish = 
             memset(&r, 0, sizeof(r));
             r.voff = voff; r.pos = pos; r.end = end; r.flag = fl; r.mapq = p[9];
             r.n_cigar = (uint16_t)ncig; r.l_seq = (uint16_t)lseq;
-            r.mtid = rdi32(p + 20); r.mpos = rdi32(p + 24); r.tlen = rdi32(p + 28);
+            r.mtid = shift_ref(rdi32(p + 20), fk); r.mpos = rdi32(p + 24); r.tlen = rdi32(p + 28);
             r.mate_ref = -2;
-            r.nhash = hash_name(p + 32, (size_t)l_name - 1);
+            r.nhash = hash_name(p + 32, (size_t)l_name - 1) ^ fk.s1;
             // does a fetch return it?  (start < hi and end > lo: read_collector.py:385, :167)
             bool direct = false, listable = o.bl;
             uint16_t um = 0;
@@ -700,7 +798,7 @@ void walk_task(const uz_stage &P, Task &T, Scratch &W, size_t ti, bool finish = 
                     use_list = ok;
                 }
             }
-            if (P.desc) keep_raw(tmp, r, p, bs);
+            if (P.desc) keep_raw(tmp, r, p, bs, fk);
             else extract(tmp, r, p, bs, o, bases, use_list ? &blv : nullptr);
             all.push_back(r);
             s.advance(bs);
@@ -797,6 +895,7 @@ void lookup_walk(const uz_stage &P, Task &T, int32_t mtid, int32_t mpos, Inflate
     T.tid = mtid; T.a = mpos; T.b = mpos + 1; T.f0 = T.f1 = 0;
     T.by_hash = P.desc;
     spans_for(S.refs[(size_t)mtid], T.a, T.b, T.spans);
+    const FileKey fk = file_key(S, mtid);
     Stream s(S, inf);
     bool stop = false;
     for (size_t ci = 0; ci < T.spans.size() && !stop; ci++) {
@@ -807,7 +906,7 @@ void lookup_walk(const uz_stage &P, Task &T, int32_t mtid, int32_t mpos, Inflate
             uint32_t bs;
             if (!s.next(voff, p, bs)) { stop = true; break; }
             if (voff >= T.spans[ci].end) break;
-            const int32_t tid2 = rdi32(p), pos = rdi32(p + 4);
+            const int32_t tid2 = shift_ref(rdi32(p), fk), pos = rdi32(p + 4);
             if (tid2 != T.tid) { if (tid2 < 0 || tid2 > T.tid) { stop = true; break; } s.advance(bs); continue; }
             if (pos > mpos) { stop = true; break; }
             const uint32_t l_name = p[8], ncig = rd16(p + 12);
@@ -818,17 +917,17 @@ void lookup_walk(const uz_stage &P, Task &T, int32_t mtid, int32_t mpos, Inflate
             const int32_t end = endpos_of(p, pos, fl, ncig, l_name);
             T.n_walked++;
             if (end > mpos) {
-                const uint64_t h = hash_name(p + 32, (size_t)l_name - 1);
-                const uint32_t h2 = P.desc ? uz_name_hash2(p + 32, l_name - 1) : 0u;
+                const uint64_t h = hash_name(p + 32, (size_t)l_name - 1) ^ fk.s1;
+                const uint32_t h2 = P.desc ? uz_name_hash2(p + 32, l_name - 1) ^ fk.s2 : 0u;
                 if (asked(h, h2, l_name - 1, p + 32)) {
                     WRec r;
                     memset(&r, 0, sizeof(r));
                     r.voff = voff; r.pos = pos; r.end = end; r.flag = fl; r.mapq = p[9];
                     r.n_cigar = (uint16_t)ncig; r.l_seq = (uint16_t)lseq;
-                    r.mtid = rdi32(p + 20); r.mpos = rdi32(p + 24); r.tlen = rdi32(p + 28);
+                    r.mtid = shift_ref(rdi32(p + 20), fk); r.mpos = rdi32(p + 24); r.tlen = rdi32(p + 28);
                     r.mate_ref = -2; r.nhash = h; r.keep = 0;
                     r.umask = P.opt.masks ? (uint16_t)0 : (uint16_t)UZ_UMASK_ALL;
-                    if (P.desc) keep_raw(T, r, p, bs);
+                    if (P.desc) keep_raw(T, r, p, bs, fk);
                     else extract(T, r, p, bs, P.opt, P.opt.all_bases);
                     T.recs.push_back(r);
                 }
@@ -1457,6 +1556,30 @@ int uz_bamsrc_open(const char *path, const char *bai_path, int64_t head_records,
     *out = s;
     return UZ_IO_OK;
 }
+int uz_bamsrc_open_many(const char *const *paths, const char *const *bai_paths, int32_t n, int64_t head_records, uz_bamsrc **out) {
+    if (!paths || !out || n < 1) { last_error = "uz_bamsrc_open_many: at least one path"; return UZ_IO_E_ARG; }
+    for (int32_t f = 0; f < n; f++) if (!paths[f]) { last_error = "null argument"; return UZ_IO_E_ARG; }
+    *out = nullptr;
+    uz_bamsrc *s = new uz_bamsrc();
+    const int rc = guarded([&] {
+        if (n == 1) open_source(*s, paths[0], bai_paths ? bai_paths[0] : nullptr, head_records); // one path: uz_bamsrc_open's source
+        else open_many(*s, n, paths, bai_paths);
+    });
+    if (rc != UZ_IO_OK) { delete s; return rc; }
+    *out = s;
+    return UZ_IO_OK;
+}
+int32_t uz_bamsrc_n_files(const uz_bamsrc *s) { return s ? (int32_t)s->salt1.size() : 0; }
+int uz_bamsrc_files(const uz_bamsrc *s, int64_t *file_base, int32_t *ref_base, uint64_t *salt1, uint32_t *salt2) {
+    if (!s) { last_error = "null argument"; return UZ_IO_E_ARG; }
+    const size_t n = s->salt1.size();
+    if (file_base) memcpy(file_base, s->file_base.data(), (n + 1) * sizeof(int64_t));
+    if (ref_base) memcpy(ref_base, s->ref_base.data(), (n + 1) * sizeof(int32_t));
+    if (salt1) memcpy(salt1, s->salt1.data(), n * sizeof(uint64_t));
+    if (salt2) memcpy(salt2, s->salt2.data(), n * sizeof(uint32_t));
+    return UZ_IO_OK;
+}
+int32_t uz_bamsrc_ref_file(const uz_bamsrc *s, int32_t ref) { return (s && ref >= 0 && (size_t)ref < s->ref_file.size()) ? s->ref_file[(size_t)ref] : -1; }
 void uz_bamsrc_close(uz_bamsrc *s) { delete s; }
 int32_t uz_bamsrc_n_contigs(const uz_bamsrc *s) { return s ? (int32_t)s->contigs.size() : 0; }
 const char *uz_bamsrc_contig_name(const uz_bamsrc *s, int32_t i) { return (s && i >= 0 && (size_t)i < s->contigs.size()) ? s->contigs[(size_t)i].c_str() : nullptr; }
@@ -1529,10 +1652,11 @@ int uz_stage_gather_blocks(uz_stage *P, uint8_t *comp, int64_t cap, int64_t *in_
                         // ended "incomplete" on the device and was walked again by the host, two of 2 059 per feed pass -- with the joins on the device
                         // the one thing left that makes the host inflate and walk).
                         int extra = (int64_t)(c.end >> 16) > stop ? 1 : 0;
+                        const size_t lim = chain_end(S, coff); // (the extra block is never the next file's header)
                         while (coff <= stop || extra > 0) {
                             if (coff > stop) extra--;
                             BlockHdr h;
-                            if (!block_at(S, coff, h)) break;
+                            if (!block_at(S, coff, lim, h)) break;
                             if (coff > last) { T.pre.push_back(PreBlk{coff, 0, h.isize, h.crc, (uint32_t)h.blen, (uint32_t)(h.cdata - (size_t)coff)}); last = coff; }
                             T.span_stop[ci] = coff;
                             coff += (int64_t)h.blen;

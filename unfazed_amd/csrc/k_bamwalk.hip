@@ -14,6 +14,7 @@
 //                      ONE pass: every task writes its 64-byte descriptors in file order into a slice of the output sized for the most records
 //                      its bytes can hold (a record is at least 36 bytes) and counts them; every inflated byte is read once through the windows
 //                      (the lanes' own reads hit the same lines in L2).  Then the mate-candidate filter: k_tab_insert, k_desc_filter.
+//   k_bam_walk_many    the same body (bamwalk_body.hpp) over the blocks of many files presented as one: references shifted, names salted per file.
 //   k_bam_extract      one lane per KEPT record (the host's answer: uz_kept_rec): the plain columns of uz_reads_packed_view from the record's
 //                      bytes -- start, tlen, flag, l_seq, n_cigar, mapq, the aux bits (mate on the same reference, an SA tag, no CIGAR / SEQ /
 //                      QUAL), every CIGAR word, the bases as BAM packs them (four bits: the device's own row format), the one-bit plane
@@ -80,165 +81,16 @@ struct WalkArgs {
 __device__ __forceinline__ unsigned long long tab_key(uint64_t h1) { return (unsigned long long)h1 | 1ULL; } // (never 0 = empty; merging two hashes keeps a record too many, never one too few)
 __device__ __forceinline__ size_t tab_slot(unsigned long long key, int64_t size) { return (size_t)((key * 0x9E3779B97F4A7C15ULL) >> 20) & (size_t)(size - 1); }
 
-__global__ __launch_bounds__(64) void k_bam_walk(WalkArgs a) {
-    constexpr bool FILL = true;
-    __shared__ uint4 win[WIN / 16];
-    __shared__ uint16_t offs[WIN_RECS];
-    __shared__ int s_n, s_state;
-    __shared__ long long s_next;
-    // the task's fetches and reach intervals, searched once per record: in LDS when they fit (they do unless a task holds thousands of fetches)
-    constexpr int FCAP = 1024, RCAP = 256;
-    __shared__ int32_t f_lo[FCAP], f_hi[FCAP], r_a[RCAP], r_b[RCAP];
-    const int t = blockIdx.x, lane = threadIdx.x;
-    const int32_t *tc = a.task + UZ_WALK_TASK_COLS * (size_t)t;
-    const int32_t tid = tc[0], tb = tc[1], sp0 = tc[2], sp1 = tc[3], r0 = tc[4], r1 = tc[5], f0 = tc[6], f1 = tc[7], max_len = tc[8];
-    const uint8_t *win8 = reinterpret_cast<const uint8_t *>(win);
-    const bool f_lds = f1 - f0 <= FCAP, r_lds = r1 - r0 <= RCAP;
-    if (f_lds) for (int i = lane; i < f1 - f0; i += 64) { f_lo[i] = a.fetch[3 * (f0 + i)]; f_hi[i] = a.fetch[3 * (f0 + i) + 1]; }
-    if (r_lds) for (int i = lane; i < r1 - r0; i += 64) { r_a[i] = a.reach[2 * (r0 + i)]; r_b[i] = a.reach[2 * (r0 + i) + 1]; }
-    __syncthreads();
-    int64_t n_out = 0, walked = 0, n_dir = 0;
-    int flag = 0;
-    bool stop = false;
-    for (int sp = sp0; sp < sp1 && !stop && !flag; sp++) {
-        const int64_t *sc = a.span + UZ_WALK_SPAN_COLS * (size_t)sp;
-        const uint64_t span_end = (uint64_t)sc[1];
-        int64_t cur = sc[2];
-        const int64_t bend = sc[3], blk0 = sc[4], blk1 = sc[5];
-        if (blk0 >= blk1) { stop = true; break; } // no block at the span's start: the end of the file (the host's walk stops there too)
-        bool span_done = false;
-        int64_t bi_cur = blk0; // the block that holds `cur` (the cursor only moves forward: a step or none per window)
-        while (!span_done) {
-            while (bi_cur + 1 < blk1 && a.blk_at[bi_cur + 1] <= cur) bi_cur++;
-            const int64_t w0 = cur & ~(int64_t)15;
-#pragma unroll
-            for (int it = 0; it < WIN / 16 / 64; it++) {
-                const int idx = it * 64 + lane;
-                win[idx] = *reinterpret_cast<const uint4 *>(a.buf + w0 + 16 * (int64_t)idx);
-            }
-            __syncthreads();
-            if (lane == 0) { // the chain of block_size fields inside the window
-                int k = 0, state = 0; // 0: the window is used up; 1: the gathered bytes end here; 2: ... in the middle of a record; 3: not a record
-                int64_t c = cur;
-                const int64_t wend = w0 + WIN;
-                while (k < WIN_RECS) {
-                    if (c + 4 > bend) { state = c >= bend ? 1 : 2; break; }
-                    if (c + 4 > wend) break;
-                    const int32_t bs = (int32_t)ld32(win8 + (c - w0));
-                    if (bs < 32) { state = 3; break; }
-                    if (c + 4 + (int64_t)bs > bend) { state = 2; break; }
-                    offs[k++] = (uint16_t)(c - w0);
-                    c += 4 + (int64_t)bs;
-                }
-                s_n = k; s_state = state; s_next = c;
-            }
-            __syncthreads();
-            const int n = s_n, state = s_state;
-            const int64_t next = s_next;
-            int ended = 0; // the kind of the record that ended the walk of this span, 0: none did
-            for (int b0 = 0; b0 < n && !ended; b0 += 64) {
-                const int j = b0 + lane;
-                const bool valid = j < n;
-                int kind = K_SKIP;
-                bool counted = false;
-                int64_t c = 0;
-                uint64_t voff = 0;
-                int32_t pos = 0, end = 0;
-                uint32_t l_name = 0, ncig = 0, fl = 0, lseq = 0, bs = 0;
-                const uint8_t *p = a.buf;
-                if (valid) {
-                    c = w0 + offs[j];
-                    bs = ld32(win8 + offs[j]);
-                    // the record's own bytes: from the window in LDS when it lies inside it whole (all but the last record or two of a window),
-                    // else from where it lies -- every field below is read byte by byte (BAM fields are unaligned)
-                    p = (uint32_t)offs[j] + 4u + bs <= (uint32_t)WIN ? win8 + offs[j] + 4 : a.buf + c + 4;
-                    // the block that holds the record's first byte: the first whose end lies behind it (an empty block holds nothing)
-                    int64_t lo = bi_cur; // (a window reaches into the next block or two at most)
-                    while (lo + 1 < blk1 && a.blk_at[lo + 1] <= c) lo++;
-                    voff = ((uint64_t)a.blk_coff[lo] << 16) | (uint64_t)(c - a.blk_at[lo]);
-                    if (voff >= span_end) kind = K_BREAK;
-                    else {
-                        const int32_t rt = (int32_t)ld32(p);
-                        pos = (int32_t)ld32(p + 4);
-                        if (rt != tid) kind = (rt < 0 || rt > tid) ? K_STOP : K_SKIP;
-                        else if (pos >= tb) kind = K_STOP;
-                        else {
-                            l_name = p[8]; ncig = ld16(p + 12); fl = ld16(p + 14);
-                            const int32_t ls = (int32_t)ld32(p + 16);
-                            lseq = (uint32_t)ls;
-                            if (ls < 0 || ls > 0xFFFF || l_name < 1 || 32 + (uint64_t)l_name + 4 * (uint64_t)ncig > (uint64_t)bs) kind = K_BAD;
-                            else {
-                                end = endpos_of(p, pos, fl, ncig, l_name);
-                                counted = true;
-                                // between two reach intervals nothing can be fetched (and a mate position there goes through the index)
-                                bool gap;
-                                if (r_lds) {
-                                    int ri = 0;
-                                    while (ri < r1 - r0 && pos >= r_b[ri]) ri++;
-                                    gap = ri < r1 - r0 && end <= r_a[ri];
-                                } else {
-                                    int ri = r0;
-                                    while (ri < r1 && pos >= a.reach[2 * ri + 1]) ri++;
-                                    gap = ri < r1 && end <= a.reach[2 * ri];
-                                }
-                                if (gap) kind = K_SKIP;
-                                else if (32 + (uint64_t)l_name + 4 * (uint64_t)ncig + ((uint64_t)lseq + 1) / 2 + (uint64_t)lseq > (uint64_t)bs) kind = K_BAD; // (the host's extract)
-                                else kind = K_EMIT;
-                            }
-                        }
-                    }
-                }
-                const unsigned long long term = __ballot(valid && kind >= K_BREAK);
-                const int first = term ? __ffsll((long long)term) - 1 : 64;
-                const bool live = valid && lane < first;
-                walked += __popcll(__ballot(live && counted));
-                const bool emit = live && kind == K_EMIT;
-                const unsigned long long m = __ballot(emit);
-                // does a fetch return it?  (start < hi and end > lo: read_collector.py:385, :167)
-                bool direct = false;
-                if (emit) {
-                    const int64_t key = (int64_t)pos - max_len;
-                    if (f_lds) {
-                        int lo = 0, hi = f1 - f0;
-                        while (lo < hi) { const int mid = (lo + hi) >> 1; if ((int64_t)f_lo[mid] < key) lo = mid + 1; else hi = mid; }
-                        for (; lo < f1 - f0 && f_lo[lo] < end; lo++)
-                            if (f_hi[lo] > pos) { direct = true; break; }
-                    } else {
-                        int lo = f0, hi = f1;
-                        while (lo < hi) { const int mid = (lo + hi) >> 1; if ((int64_t)a.fetch[3 * mid] < key) lo = mid + 1; else hi = mid; }
-                        for (; lo < f1 && a.fetch[3 * lo] < end; lo++)
-                            if (a.fetch[3 * lo + 1] > pos) { direct = true; break; }
-                    }
-                }
-                n_dir += __popcll(__ballot(direct));
-                if (FILL && emit) {
-                    const int rank = __popcll(m & ((1ULL << lane) - 1ULL));
-                    uz_walk_desc d;
-                    d.voff = voff; d.src = (uint64_t)(c + 4);
-                    d.h1 = name_hash1(p + 32, l_name - 1);
-
-                    d.pos = pos; d.end = end; d.tlen = (int32_t)ld32(p + 28); d.mpos = (int32_t)ld32(p + 24); d.mtid = (int32_t)ld32(p + 20);
-                    d.h2 = uz_name_hash2(p + 32, l_name - 1);
-                    d.task = (uint32_t)t;
-                    d.flag = (uint16_t)fl; d.l_seq = (uint16_t)lseq; d.n_cigar = (uint16_t)ncig;
-                    d.mapq = p[9]; d.l_name = (uint8_t)(l_name - 1); d.direct = direct ? 1 : 0; d.pad8 = 0; d.pad16 = 0;
-                    a.out[a.first[t] + n_out + rank] = d;
-                }
-                n_out += __popcll(m);
-                if (first < 64) ended = __shfl(kind, first, 64);
-            }
-            if (ended == K_BREAK) span_done = true;
-            else if (ended == K_STOP) { stop = true; span_done = true; }
-            else if (ended == K_BAD || state == 3) { flag |= UZ_WALK_TASK_BAD; span_done = true; }
-            else if (state == 1 || state == 2) { flag |= UZ_WALK_TASK_INCOMPLETE; span_done = true; }
-            cur = next;
-            __syncthreads(); // the window is read to the end before the next one lands
-        }
-    }
-    if (lane == 0) { // (a flagged task goes back to the host: what it wrote into its slice is never looked at)
-        a.count[t] = flag ? 0 : n_out; a.n_direct[t] = flag ? 0 : n_dir; a.walked[t] = walked; a.flags[t] = flag;
-    }
+__device__ __forceinline__ int32_t walk_set_ref(int32_t r, int32_t ref_base, int32_t n_ref) {
+    return r < 0 ? r : ((uint32_t)r < (uint32_t)n_ref ? r + ref_base : INT32_MAX);
 }
+// the walk kernel, built twice from one body (bamwalk_body.hpp): for one file's blocks, and for the blocks of many files presented as one
+#define UZ_WALK_KERNEL k_bam_walk
+#define UZ_WALK_MANY 0
+#include "bamwalk_body.hpp"
+#define UZ_WALK_KERNEL k_bam_walk_many
+#define UZ_WALK_MANY 1
+#include "bamwalk_body.hpp"
 
 // The hash set of mate candidates belongs to the HOST task (the stage's own task: finish_task in io_stage.cpp keeps the records that share a
 // name with a direct record of the task), and a host task is walked as several sub-tasks here (column 9 of a walk task names its host task;
@@ -481,10 +333,11 @@ __global__ __launch_bounds__(256) void k_bam_extract(ExtractArgs a) {
 // the caller for the most records the task's bytes can hold), count / n_direct / walked / flags per task; tab_first: the hash sets' slices
 void uz_launch_bam_walk(uz_ctx *c, hipStream_t st, int n_tasks, const uint8_t *buf, const int64_t *blk_at, const int64_t *blk_coff, const int32_t *task,
                         const int64_t *span, const int32_t *reach, const int32_t *fetch, int64_t *count, const int64_t *first, int64_t *walked, int32_t *flags,
-                        uz_walk_desc *out, int64_t *n_direct, int64_t *tab_first) {
+                        uz_walk_desc *out, int64_t *n_direct, int64_t *tab_first, const uz_walk_file *tfile) {
     if (n_tasks <= 0) return;
     WalkArgs a{buf, blk_at, blk_coff, task, span, reach, fetch, count, first, walked, flags, out, n_direct, nullptr, nullptr};
-    hipLaunchKernelGGL(k_bam_walk, dim3((unsigned)n_tasks), dim3(64), 0, st, a);
+    if (tfile) hipLaunchKernelGGL(k_bam_walk_many, dim3((unsigned)n_tasks), dim3(64), 0, st, a, tfile); // (a batch over many files: the tasks' files)
+    else hipLaunchKernelGGL(k_bam_walk, dim3((unsigned)n_tasks), dim3(64), 0, st, a);
     hipLaunchKernelGGL((k_walk_scan<true>), dim3(1), dim3(256), 0, st, n_tasks, (const int64_t *)n_direct, tab_first, task);
     UZ_HIP(hipGetLastError());
 }
@@ -503,6 +356,33 @@ void uz_launch_desc_filter(uz_ctx *c, hipStream_t st, bool fill, int n_tasks, co
     UZ_HIP(hipGetLastError());
 }
 size_t uz_bam_walk_pad() { return (size_t)WIN + 64; }
+
+// ---- a table over many files (abi.hip: uz_reads_files): per file the smallest and the largest name id of its records, one workgroup per file
+// (rec_b: the table's RecB headers, 16 bytes each, the name id their second word; rec_first [n_files + 1] checked by the caller)
+namespace {
+__global__ __launch_bounds__(256) void k_reads_files(const uint32_t *__restrict__ rec_b, const int64_t *__restrict__ rec_first, uint32_t *__restrict__ mn, uint32_t *__restrict__ mx) {
+    __shared__ uint32_t s_lo[4], s_hi[4];
+    const int f = blockIdx.x;
+    const int64_t a = rec_first[f], b = rec_first[f + 1];
+    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
+    for (int64_t i = a + threadIdx.x; i < b; i += 256) {
+        const uint32_t q = rec_b[4 * i + 1];
+        lo = min(lo, q); hi = max(hi, q);
+    }
+    for (int off = 32; off; off >>= 1) { lo = min(lo, (uint32_t)__shfl_xor((int)lo, off, 64)); hi = max(hi, (uint32_t)__shfl_xor((int)hi, off, 64)); }
+    if ((threadIdx.x & 63) == 0) { s_lo[threadIdx.x >> 6] = lo; s_hi[threadIdx.x >> 6] = hi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        mn[f] = min(min(s_lo[0], s_lo[1]), min(s_lo[2], s_lo[3]));
+        mx[f] = max(max(s_hi[0], s_hi[1]), max(s_hi[2], s_hi[3]));
+    }
+}
+} // namespace
+void uz_launch_reads_files(uz_ctx *c, hipStream_t st, int32_t n_files, const void *rec_b, const int64_t *rec_first, uint32_t *mn, uint32_t *mx) {
+    if (n_files <= 0) return;
+    hipLaunchKernelGGL(k_reads_files, dim3((unsigned)n_files), dim3(256), 0, st, (const uint32_t *)rec_b, rec_first, mn, mx);
+    UZ_HIP(hipGetLastError());
+}
 
 void uz_launch_bam_extract(uz_ctx *c, hipStream_t st, int64_t n, const uint8_t *buf, int64_t buf_bytes, const uint8_t *aux, int64_t aux_bytes, const uz_kept_rec *kept,
                            int thr, int32_t *start, int32_t *tlen, int32_t *mate, uint32_t *qname, uint16_t *flag, uint16_t *l_seq, uint16_t *n_cigar, uint8_t *mapq,

@@ -409,6 +409,8 @@ struct uz_ctx {
 
     // uz_reads_names: ids / lengths / offsets / bytes on the device and one page-locked staging block, kept from call to call
     DevBuf<uint32_t> nm_ids, nm_len, nm_off;
+    DevBuf<int64_t> rf_first; // uz_reads_files: the files' first records, and ...
+    DevBuf<uint32_t> rf_mm;   // ... their smallest and largest name ids
     DevBuf<uint8_t> nm_out;
     uint8_t *nm_pin = nullptr;
     size_t nm_pin_cap = 0;
@@ -505,7 +507,7 @@ void uz_launch_inflate(uz_ctx *c, hipStream_t st, int64_t n_blocks, const uint8_
 // the record walk on the device (k_bamwalk.hip): every pointer device memory; fill = false: counts + offsets (count, first, walked, flags), fill = true: the descriptors
 void uz_launch_bam_walk(uz_ctx *c, hipStream_t st, int n_tasks, const uint8_t *buf, const int64_t *blk_at, const int64_t *blk_coff, const int32_t *task,
                         const int64_t *span, const int32_t *reach, const int32_t *fetch, int64_t *count, const int64_t *first, int64_t *walked, int32_t *flags,
-                        uz_walk_desc *out, int64_t *n_direct, int64_t *tab_first);
+                        uz_walk_desc *out, int64_t *n_direct, int64_t *tab_first, const uz_walk_file *tfile = nullptr);
 void uz_launch_desc_filter(uz_ctx *c, hipStream_t st, bool fill, int n_tasks, const uz_walk_desc *in, const int64_t *first, const int64_t *count,
                            const int32_t *task, const int64_t *tab_first, unsigned long long *tab, int64_t *kcount, int64_t *kfirst, uz_walk_desc *out);
 size_t uz_bam_walk_pad(); // bytes the inflated buffer must be padded by (the walk's LDS windows read past the last record)
@@ -525,6 +527,7 @@ void uz_join_needs(uz_ctx *c, uz_ctx::WalkSlot &w, uz_need_rec *out);
 // debug / parity: the kept records of a finished join in output order
 void uz_join_fetch(uz_ctx *c, uz_ctx::WalkSlot &w, uint64_t *voff, uint32_t *qname, int32_t *mate, uint8_t *bases, uz_kept_rec *kept);
 // the read names of name ids (a table built by uz_reads_from_walk with names): lengths, then bytes
+void uz_launch_reads_files(uz_ctx *c, hipStream_t st, int32_t n_files, const void *rec_b, const int64_t *rec_first, uint32_t *mn, uint32_t *mx);
 void uz_launch_name_lens(uz_ctx *c, hipStream_t st, int64_t n_ids, const uint32_t *ids, const uint32_t *name_rec, const uz_kept_rec *kept, int64_t n_recs, int64_t names_bytes,
                          uint32_t *len);
 void uz_launch_name_gather(uz_ctx *c, hipStream_t st, int64_t n_ids, const uint32_t *ids, const uint32_t *name_rec, const uz_kept_rec *kept, const uint8_t *names,

@@ -15,7 +15,7 @@
     X(uint8_t, comp) X(uint8_t, out) X(int64_t, in_off) X(int64_t, out_off) X(int64_t, blk_coff) X(int32_t, task) X(int64_t, span) X(int32_t, reach)  \
     X(int32_t, fetch) X(int64_t, count) X(int64_t, first) X(int64_t, walked) X(int32_t, flags) X(int64_t, n_direct) X(int64_t, tab_first)            \
     X(int64_t, kcount) X(int64_t, kfirst) X(int32_t, iflags) X(uint32_t, blk_crc) X(uz_walk_desc, desc) X(unsigned long long, tab)                   \
-    X(uz_walk_desc, desc_kept)
+    X(uz_walk_desc, desc_kept) X(uz_walk_file, tfile)
 // ... and of uz_ctx::WalkSlot::Join (k_bamjoin.hip: uz_join_run; look_tid is its scratch for the host's answers)
 #define UZ_JOIN_BUFS(X)                                                                                                                               \
     X(uint8_t, tmp) X(int32_t, jtask) X(int32_t, keep) X(int32_t, mate) X(int32_t, target) X(unsigned long long, hkey_in) X(uint32_t, hval_in)       \

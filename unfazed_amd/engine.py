@@ -21,13 +21,13 @@ K_BCF_CELLS, K_BCF_COPY = 11, 12  # uz_samples_from_bcf: its kernel and (not a k
 
 EXPORTS = [
     "uz_create", "uz_destroy", "uz_last_error", "uz_sync", "uz_set_params",
-    "uz_sites_upload", "uz_family_upload", "uz_sites_family_upload_async", "uz_samples_upload", "uz_samples_from_text", "uz_samples_from_bcf", "uz_samples_unsettled", "uz_samples_settle", "uz_families_from_samples", "uz_family_fetch", "uz_samples_free", "uz_reads_upload", "uz_reads_upload_packed", "uz_reads_wait", "uz_reads_headers", "uz_bgzf_inflate", "uz_bgzf_inflate_to_host", "uz_bam_walk", "uz_crc32_blocks", "uz_bam_walk_fetch", "uz_bam_walk_release", "uz_reads_from_bam",
+    "uz_sites_upload", "uz_family_upload", "uz_sites_family_upload_async", "uz_samples_upload", "uz_samples_from_text", "uz_samples_from_bcf", "uz_samples_unsettled", "uz_samples_settle", "uz_families_from_samples", "uz_family_fetch", "uz_samples_free", "uz_reads_upload", "uz_reads_upload_packed", "uz_reads_wait", "uz_reads_headers", "uz_bgzf_inflate", "uz_bgzf_inflate_to_host", "uz_bam_walk", "uz_bam_walk_many", "uz_reads_files", "uz_crc32_blocks", "uz_bam_walk_fetch", "uz_bam_walk_release", "uz_reads_from_bam",
     "uz_bam_walk_flags", "uz_bam_join", "uz_bam_join_needs", "uz_bam_join_fetch", "uz_reads_from_walk", "uz_reads_names", "uz_walk_slot_stats", "uz_walk_reserve",
     "uz_pinned_alloc", "uz_pinned_free",
     "uz_sites_adopt_device", "uz_family_adopt_device", "uz_reads_adopt_device",
     "uz_sites_free", "uz_reads_free", "uz_drop_derived",
     "uz_site_scan", "uz_site_scan_many", "uz_site_classes", "uz_find", "uz_find_fetch", "uz_find_cohort",
-    "uz_phase", "uz_phase_begin", "uz_phase_end", "uz_phase_cohort", "uz_phase_votes", "uz_phase_groups", "uz_phase_sizing_fetch", "uz_phase_cnv", "uz_phase_cnv_cohort", "uz_phase_cnv_sites",
+    "uz_phase", "uz_phase_begin", "uz_phase_end", "uz_phase_cohort", "uz_phase_cohort_joined", "uz_phase_votes", "uz_phase_groups", "uz_phase_sizing_fetch", "uz_phase_cnv", "uz_phase_cnv_cohort", "uz_phase_cnv_sites",
     "uz_prof_enable", "uz_prof_reset", "uz_prof_get", "uz_prof_units",
 ]
 
@@ -64,6 +64,8 @@ def load_library(path: Optional[str] = None):
     L.uz_bgzf_inflate_to_host.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp, vp]
     L.uz_crc32_blocks.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
     L.uz_bam_walk.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, C.c_int32, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp, vp]
+    L.uz_bam_walk_many.argtypes = L.uz_bam_walk.argtypes[:-2] + [C.c_int32, vp, vp, vp, vp, vp, vp]
+    L.uz_reads_files.argtypes = [vp, C.c_int, C.c_int32, vp, vp, vp]
     L.uz_bam_walk_fetch.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.uz_bam_walk_release.argtypes = [vp, C.c_int]
     L.uz_reads_from_bam.argtypes = [vp, C.c_int, vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_uint32, C.c_int32, vp, C.c_int64, vp]
@@ -104,6 +106,7 @@ def load_library(path: Optional[str] = None):
     L.uz_phase_begin.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int]
     L.uz_phase_end.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]
     L.uz_phase_cohort.argtypes = [vp, vp, C.c_int32, vp, C.c_int, vp, vp, vp, vp]
+    L.uz_phase_cohort_joined.argtypes = [vp, C.c_int, vp, C.c_int32, vp, vp, C.c_int, vp, vp, vp, vp]
     L.uz_phase_cnv.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
     L.uz_phase_cnv_cohort.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp]
     L.uz_phase_cnv_sites.argtypes = [vp, vp, vp]
@@ -337,11 +340,13 @@ class HipEngine:
         self._ck(self.L.uz_reads_upload(self.h, v.ref(), C.byref(rid)), "uz_reads_upload")
         return rid.value
 
-    def upload_reads_staged(self, src, fc, flo, fhi, fex, min_base_qual: int, all_bases: bool = False, wide_no_units: bool = False):
+    def upload_reads_staged(self, src, fc, flo, fhi, fex, min_base_qual: int, all_bases: bool = False, wide_no_units: bool = False, walk_only: bool = False):
         """One batch straight from an indexed BAM (io_native.BamSource) uploaded as one table: stage_reads on a slot of its own, then
         upload_reads_packed.  -> (reads id, the staged view: `.qnames` maps the name ids of the result lists back to strings -- names of the
         caller's own, valid after the table is freed and after later batches are staged on any route)"""
-        staged = self.stage_reads(src, fc, flo, fhi, fex, min_base_qual, all_bases=all_bases, wide_no_units=wide_no_units, slot="single")
+        staged = self.stage_reads(src, fc, flo, fhi, fex, min_base_qual, all_bases=all_bases, wide_no_units=wide_no_units, slot="single", walk_only=walk_only)
+        if staged is None:  # walk_only: the batch is not one for the device's walk (stage_reads) -- nothing was staged
+            return None, None
         rid = None
         try:
             rid = self.upload_reads_packed(staged)
@@ -360,7 +365,7 @@ class HipEngine:
             staged.qnames = staged.qnames.frozen()
         return rid, staged
 
-    def stage_reads(self, src, fc, flo, fhi, fex, min_base_qual: int, all_bases: bool = False, wide_no_units: bool = False, slot=0):
+    def stage_reads(self, src, fc, flo, fhi, fex, min_base_qual: int, all_bases: bool = False, wide_no_units: bool = False, slot=0, walk_only: bool = False):
         """One batch of an indexed BAM (io_native.BamSource) -- the records its fetches return + their mates -- made ready for
         upload_reads_packed, by the route the switches choose (read here, on every call):
           default          the blocks go up and are inflated, checked and walked in HBM (include/uz_bamwalk.h), the joins run there too
@@ -376,6 +381,8 @@ class HipEngine:
         second: round 3's product route spent 1.2 s of its 2.4 s per 20 k DNMs there).  The next stage_reads on a slot re-uses them: the table
         staged there must have landed on the device by then, and names that lie there (host joins) answer for the later batch.  May be called
         from a worker thread (hostpath._chunked_batch stages chunk k + 1 beside the device work of chunk k).
+        walk_only: a batch that does not take the device's walk (the switches, or its blocks exceed UZ_WALK_MAX_BYTES) is not staged at all -> None
+        (hostpath's cohort route over many files then stages its kids one by one).
         `.qnames`, `.io_stats`, `.timing` ride on the result."""
         if slot not in self._slots:
             pool = PinnedPool()
@@ -392,6 +399,8 @@ class HipEngine:
             if kb is not None:
                 kb._alloc = pair.alloc  # (host joins: the names of its records come back into the slot's page-locked memory: reads_from_bam)
                 return kb
+        if walk_only:
+            return None
         pair.start()
         packed = src.select(fc, flo, fhi, int(min_base_qual), pool=pool, all_bases=bool(all_bases), extra=fex, wide_no_units=bool(wide_no_units),
                             inflate=self.inflate_blocks if inflate else None, inflate_alloc=pair.alloc if inflate else None)
@@ -461,13 +470,19 @@ class HipEngine:
         """uz_bam_walk (the caller holds _walk_sem: UZ_WALKS_AT_ONCE batches at a time): the plan's blocks up, inflated, checked against their
         CRC-32 and walked in HBM -> (walk id, descriptors)"""
         wid, nd = C.c_int(-1), C.c_int64(0)
-        rc = self.L.uz_bam_walk(self.h, plan["comp"].ctypes.data, int(plan["comp_bytes"]), int(plan["n_blocks"]), plan["in_off"].ctypes.data,
-                                plan["out_off"].ctypes.data, plan["blk_coff"].ctypes.data, plan["blk_crc"].ctypes.data if plan.get("blk_crc") is not None else None,
-                                int(plan["task"].shape[0]), plan["task"].ctypes.data, int(plan["span"].shape[0]), plan["span"].ctypes.data,
-                                int(plan["reach"].shape[0]), plan["reach"].ctypes.data, int(plan["fetch"].shape[0]), plan["fetch"].ctypes.data,
-                                C.byref(wid), C.byref(nd))
+        args = [self.h, plan["comp"].ctypes.data, int(plan["comp_bytes"]), int(plan["n_blocks"]), plan["in_off"].ctypes.data,
+                plan["out_off"].ctypes.data, plan["blk_coff"].ctypes.data, plan["blk_crc"].ctypes.data if plan.get("blk_crc") is not None else None,
+                int(plan["task"].shape[0]), plan["task"].ctypes.data, int(plan["span"].shape[0]), plan["span"].ctypes.data,
+                int(plan["reach"].shape[0]), plan["reach"].ctypes.data, int(plan["fetch"].shape[0]), plan["fetch"].ctypes.data]
+        files = plan.get("files")  # a source over many files (io_native.BamSource.open_many): the walk shifts references and salts names per file
+        if files is not None:
+            name = "uz_bam_walk_many"
+            args += [int(files["salt1"].size), files["file_base"].ctypes.data, files["ref_base"].ctypes.data, files["salt1"].ctypes.data, files["salt2"].ctypes.data]
+        else:
+            name = "uz_bam_walk"
+        rc = getattr(self.L, name)(*args, C.byref(wid), C.byref(nd))
         if rc != 0:
-            raise UnfazedHipError("uz_bam_walk: %s" % (self.L.uz_last_error(self.h) or b"").decode(errors="replace"))
+            raise UnfazedHipError("%s: %s" % (name, (self.L.uz_last_error(self.h) or b"").decode(errors="replace")))
         return wid.value, int(nd.value)
 
     def bam_walk(self, plan: dict, alloc=None):
@@ -537,6 +552,15 @@ class HipEngine:
     def reads_names(self, rid: int, ids) -> list:
         from .io_native import names_of_buffer
         return names_of_buffer(*self.reads_names_raw(rid, ids))
+
+    def reads_files(self, rid: int, ref_base):
+        """a table over many files (io_native.BamSource.open_many): per file its first record and its first name id (uz_reads_files)
+        -> (rec_first [n + 1], name_first [n + 1]); refused when a file's name ids are not one range"""
+        ref_base = np.ascontiguousarray(ref_base, np.int32)
+        n = int(ref_base.size) - 1
+        rec_first, name_first = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
+        self._ck(self.L.uz_reads_files(self.h, int(rid), n, ref_base.ctypes.data, rec_first.ctypes.data, name_first.ctypes.data), "uz_reads_files")
+        return rec_first, name_first
 
     def walk_slot_stats(self) -> dict:
         z = np.zeros(8, np.int64)
@@ -723,7 +747,7 @@ class HipEngine:
         return dict(status=status[:n], counts=counts[: 4 * n].reshape(n, 4), origin=origin[:n], evidence=evidence[:n])
 
     def phase_cohort(self, groups, dv: abi.Held, params: abi.Params, found_list=None, want_lists: bool = True,
-                     find_mode: int = abi.FIND_SECOND_WINDOW):
+                     find_mode: int = abi.FIND_SECOND_WINDOW, joined=None):
         """Cohort form of phase(): groups = [(fam, reads_h, first, count, cutoff)] over the DNMs of `dv` (several kids, each
         with its own family columns / alignment records / insert cutoff), one launch sequence.  Same result layout as
         phase(); the query-name ids of the lists are those of each group's own table."""
@@ -736,13 +760,27 @@ class HipEngine:
         counts = np.zeros(max(1, 4 * n), dtype=np.int32)
         origin = np.zeros(max(1, n), dtype=np.int32)
         evidence = np.zeros(max(1, n), dtype=np.int32)
-        self._ck(self.L.uz_phase_cohort(self.h, arr, len(groups), dv.ref(), int(find_mode), status.ctypes.data, counts.ctypes.data,
-                                        origin.ctypes.data, evidence.ctypes.data), "uz_phase_cohort")
+        if joined is None:
+            self._ck(self.L.uz_phase_cohort(self.h, arr, len(groups), dv.ref(), int(find_mode), status.ctypes.data, counts.ctypes.data,
+                                            origin.ctypes.data, evidence.ctypes.data), "uz_phase_cohort")
+        else:  # ONE table over the groups' files (uz_phase_cohort_joined): the lists carry that table's name ids
+            rid, base = joined
+            base = np.ascontiguousarray(base, np.int32)
+            assert base.size == len(groups)
+            self._ck(self.L.uz_phase_cohort_joined(self.h, int(rid), arr, len(groups), base.ctypes.data, dv.ref(), int(find_mode), status.ctypes.data,
+                                                   counts.ctypes.data, origin.ctypes.data, evidence.ctypes.data), "uz_phase_cohort_joined")
         r = dict(status=status[:n], counts=counts[: 4 * n].reshape(n, 4), origin=origin[:n], evidence=evidence[:n], lists=None)
         if want_lists:
             vo, vv = self.votes(n)
             r["lists"] = [tuple(vv[vo[4 * k + j]: vo[4 * k + j + 1]] for j in range(4)) for k in range(n)]
         return r
+
+    def phase_cohort_joined(self, rid: int, groups, group_ref_base, dv: abi.Held, params: abi.Params, found_list=None, want_lists: bool = True,
+                            find_mode: int = abi.FIND_SECOND_WINDOW):
+        """phase_cohort on ONE reads table built over the groups' alignment files presented as one (io_native.BamSource.open_many): no table is
+        concatenated.  groups as phase_cohort's (their reads handle is not looked at); group_ref_base[g]: the first contig of group g's file in the
+        table.  The query-name ids of the lists are the table's own."""
+        return self.phase_cohort(groups, dv, params, found_list, want_lists, find_mode, joined=(rid, group_ref_base))
 
     def votes(self, n: int):
         vo = np.zeros(4 * n + 1, dtype=np.int64)

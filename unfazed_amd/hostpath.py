@@ -196,10 +196,12 @@ def samples_route(is_bcf: bool = False) -> str:
 
 class _Stats(dict):
     """PhasingHost.stats: the counters of calls a host has not made yet (find_cohort_calls, find_kid_calls, cnv_cohort_calls,
-    cnv_kid_calls, and samples_parsed_device / sites_unsettled of the sample tables the device parsed from the text) read as 0 and are
+    cnv_kid_calls, samples_parsed_device / sites_unsettled of the sample tables the device parsed from the text, and bam_walks / read_tables /
+    phase_cohort_calls of the read side: batches staged from indexed BAMs, reads tables made for a batch, cohort read stages) read as 0 and are
     entered by their first increment"""
 
-    ROUTE_KEYS = ("find_cohort_calls", "find_kid_calls", "cnv_cohort_calls", "cnv_kid_calls", "samples_parsed_device", "sites_unsettled")
+    ROUTE_KEYS = ("find_cohort_calls", "find_kid_calls", "cnv_cohort_calls", "cnv_kid_calls", "samples_parsed_device", "sites_unsettled",
+                  "bam_walks", "read_tables", "phase_cohort_calls")
 
     def __missing__(self, key):
         if key in self.ROUTE_KEYS:
@@ -767,6 +769,117 @@ class PhasingHost:
                 print("[uz] chunked batch, ms per step:", trace[0], file=sys.stderr)
         return True
 
+    # ------------------------------------------------------- the read side of a batch that is not chunked
+    COHORT_RUN_DNMS = CHUNK_DNMS  # DNMs per run of the cohort route (UZ_COHORT_RUN_DNMS): CHUNK_DNMS was measured for one kid's chunks; no sweep over runs of
+    #                               kids has been measured yet (scripts/reads_route_ab.py makes it)
+    READS_ROUTE_DEFAULT = "kid"   # UZ_READS_ROUTE: "cohort" has not been measured against "kid" yet (scripts/reads_route_ab.py) and stays behind the switch
+
+    def _reads_route(self, batch) -> str:
+        """How the alignment side of a cohort call is done.  "kid": every (kid, BAM) group is staged by itself -- fetch list, walk, joins, table --
+        and uz_phase_cohort lays the tables end to end.  "cohort": the groups' files are presented to the BAM stage as ONE file
+        (io_native.BamSource.open_many), walked and joined in one batch per run of kids, and uz_phase_cohort_joined runs on the table that comes out.
+        The cohort route needs two or more groups, every group's file a .bam with a BAI taking the staged route, a backend that has it, and UZ_WALK /
+        UZ_JOINS / UZ_INFLATE at their device defaults; UZ_READS_ROUTE=kid / cohort chooses, default READS_ROUTE_DEFAULT."""
+        if len(batch) < 2 or os.environ.get("UZ_READS_ROUTE", self.READS_ROUTE_DEFAULT).lower() != "cohort":
+            return "kid"
+        many, stager = getattr(self.reads_by_bam, "stager_many", None), getattr(self.reads_by_bam, "stager", None)
+        if many is None or stager is None or not hasattr(self.backend, "phase_cohort_joined") or not hasattr(self.backend, "upload_reads_staged"):
+            return "kid"
+        if any(os.environ.get(k, "device") != "device" for k in ("UZ_WALK", "UZ_JOINS", "UZ_INFLATE")):
+            return "kid"
+        return "cohort" if all(bam.endswith(".bam") and self._indexed(bam) and stager(bam) is not None for (_, bam) in batch) else "kid"
+
+    def _cohort_runs(self, items):
+        """the groups, in order, cut into runs of at most UZ_COHORT_RUN_DNMS DNMs; a kid is never split (one larger than the limit is a run of its own)"""
+        limit = int(os.environ.get("UZ_COHORT_RUN_DNMS", self.COHORT_RUN_DNMS))
+        runs, n = [[]], 0
+        for item in items:
+            if runs[-1] and n + len(item[1]) > limit:
+                runs.append([])
+                n = 0
+            runs[-1].append(item)
+            n += len(item[1])
+        return [r for r in runs if r]
+
+    def _joined_run(self, items, dnms, pedigrees, prep, found, params, readlen, stdevs, insert_size_max_sample, want_lists, mode, results) -> bool:
+        """One run of the cohort route: ONE source over the kids' files, the kids' fetch lists end to end (contigs moved to each file's place among
+        the source's), ONE staged batch and table, ONE uz_phase_cohort_joined; one name map serves all kids.  False: the device's walk does not take
+        the batch (its blocks exceed UZ_WALK_MAX_BYTES) -- nothing was done."""
+        src = self.reads_by_bam.stager_many([bam for (_, bam), _ in items])
+        groups, order, parts, has_sv = [], [], [], False
+        for g, ((kid, bam), idxs) in enumerate(items):
+            fam = self.family(kid, pedigrees[kid]["dad"], pedigrees[kid]["mom"])
+            cutoff = self.kid_cutoff(kid, bam, readlen, stdevs, insert_size_max_sample)
+            fc, flo, fhi, fex, sv_g = self._fetches_of(idxs, dnms, prep, found, params, cutoff)
+            parts.append((np.asarray(fc, np.int64) + int(src.ref_base[g]), flo, fhi, fex))
+            has_sv = has_sv or sv_g
+            groups.append((fam, -1, len(order), len(idxs), cutoff))
+            order.extend(idxs)
+        fc, flo, fhi = (np.concatenate([p[j] for p in parts]).astype(np.int32) for j in range(3))
+        fex = np.concatenate([p[3] for p in parts]).astype(np.uint16)
+        rh, table = self.backend.upload_reads_staged(src, fc, flo, fhi, fex, int(params.min_gt_qual), all_bases=bool(params.no_extended), wide_no_units=has_sv,
+                                                     walk_only=True)
+        if rh is None:
+            return False
+        self.stats["bam_walks"] += 1
+        self.stats["read_tables"] += 1
+        try:
+            dv = self._dnms_view_of(order, dnms, prep, found, groups[0][4])
+            res = self.backend.phase_cohort_joined(rh, groups, src.ref_base[:-1], dv, params, [found[i] for i in order], want_lists, find_mode=mode)
+            self.stats["phase_cohort_calls"] += 1
+        finally:
+            self.backend.free_reads(rh)
+        for k, i in enumerate(order):
+            results[i] = (res, k, table)
+        return True
+
+    def _kid_run(self, items, dnms, pedigrees, prep, found, params, readlen, stdevs, insert_size_max_sample, want_lists, mode, results) -> None:
+        """The groups staged one by one -- its own family columns, alignment file and insert cutoff each -- and sent to the device as ONE batch:
+        uz_phase for one group, uz_phase_cohort (which lays the tables end to end) for several."""
+        groups, order_all, tables, handles = [], [], [], []
+        for (kid, bam), idxs in items:
+            dad_id, mom_id = pedigrees[kid]["dad"], pedigrees[kid]["mom"]
+            fam = self.family(kid, dad_id, mom_id)
+            cutoff = self.kid_cutoff(kid, bam, readlen, stdevs, insert_size_max_sample)
+            region_table = None
+            if self._indexed(bam):
+                # decode only what the batch's fetches can return (+ mates) through the index: the read stage looks at
+                # nothing else (read_collector.py:385, :167, :400), so nothing else is inflated, staged or uploaded
+                fc, flo, fhi, fex, has_sv = self._fetches_of(idxs, dnms, prep, found, params, cutoff)
+                stager = getattr(self.reads_by_bam, "stager", None)
+                src = stager(bam) if (stager and hasattr(self.backend, "upload_reads_staged")) else None
+                if src is not None:
+                    # BAM + BAI -> the link form in one pass (uz_bam_stage_*): no table in between
+                    rh, region_table = self.backend.upload_reads_staged(src, fc, flo, fhi, fex, int(params.min_gt_qual),
+                                                                        all_bases=bool(params.no_extended), wide_no_units=has_sv)
+                    self.stats["bam_walks"] += 1
+                else:
+                    region_table = self.reads_by_bam.regions(bam, fc, flo, fhi)
+                    rh = self.backend.upload_reads(region_table, min_base_qual=int(params.min_gt_qual), point_only=True,
+                                                   fetches=(fc, flo, fhi, fex), all_bases=bool(params.no_extended), wide_no_units=has_sv)
+                self.stats["read_tables"] += 1
+                handles.append(rh)
+            else:
+                rh = self.reads(bam, params.min_gt_qual)
+            groups.append((fam, rh, len(order_all), len(idxs), cutoff))
+            tables.append(region_table if region_table is not None else self.reads_by_bam[bam])
+            order_all.extend(idxs)
+        if order_all:
+            dv = self._dnms_view_of(order_all, dnms, prep, found, groups[0][4])
+            fl = [found[i] for i in order_all]
+            if len(groups) == 1:
+                res = self.backend.phase(groups[0][0], groups[0][1], dv, params, fl, want_lists, find_mode=mode)
+            else:
+                res = self.backend.phase_cohort(groups, dv, params, fl, want_lists, find_mode=mode)
+                self.stats["phase_cohort_calls"] += 1
+            free = getattr(self.backend, "free_reads", None)
+            for rh in handles:  # region tables live for one batch
+                if free:
+                    free(rh)
+            for g, (fam, rh, first, count, cutoff) in enumerate(groups):
+                for k in range(first, first + count):
+                    results[order_all[k]] = (res, k, tables[g])
+
     def run_read_phasing(self, dnms, pedigrees, *args, **kwargs):
         """run_read_phasing_impl, and whatever it raises behind find() -- a reference KeyError mimicked in pass 1, an I/O error of a BAM stage --
         the caller's DNMs carry their `candidate_sites` / `het_sites`: the reference annotates in find(), before any phasing work starts
@@ -863,51 +976,22 @@ class PhasingHost:
         # pass 2: device.  One batch per kid (its own family columns, alignment file and insert cutoff); several kids go
         # to the device as ONE cohort batch (uz_phase_cohort), not as one launch sequence per kid
         results: Dict[int, dict] = {}
-        groups, order_all, tables, handles = [], [], [], []
         sec_pass1.__exit__()
         with _Sec("chunked"):
           chunked = self._chunked_batch(batch, dnms, pedigrees, prep, found, params, readlen, stdevs, insert_size_max_sample, want_lists, info["mode"], results,
                                         while_first_stages=attach_sites)
         attach_sites()  # (a batch that did not take the chunked route: here; otherwise done already, and this is a no-op)
-        for (kid, bam), idxs in ([] if chunked else batch.items()):
-            dad_id, mom_id = pedigrees[kid]["dad"], pedigrees[kid]["mom"]
-            fam = self.family(kid, dad_id, mom_id)
-            cutoff = self.kid_cutoff(kid, bam, readlen, stdevs, insert_size_max_sample)
-            region_table = None
-            if self._indexed(bam):
-                # decode only what the batch's fetches can return (+ mates) through the index: the read stage looks at
-                # nothing else (read_collector.py:385, :167, :400), so nothing else is inflated, staged or uploaded
-                fc, flo, fhi, fex, has_sv = self._fetches_of(idxs, dnms, prep, found, params, cutoff)
-                stager = getattr(self.reads_by_bam, "stager", None)
-                src = stager(bam) if (stager and hasattr(self.backend, "upload_reads_staged")) else None
-                if src is not None:
-                    # BAM + BAI -> the link form in one pass (uz_bam_stage_*): no table in between
-                    rh, region_table = self.backend.upload_reads_staged(src, fc, flo, fhi, fex, int(params.min_gt_qual),
-                                                                        all_bases=bool(params.no_extended), wide_no_units=has_sv)
+        if not chunked:
+            ctx = (dnms, pedigrees, prep, found, params, readlen, stdevs, insert_size_max_sample, want_lists, info["mode"], results)
+            with _Sec("reads"):  # (the read side of the call: what scripts/reads_route_ab.py times by route)
+                if self._reads_route(batch) == "cohort":
+                    # the kids' files walked and joined as ONE batch per run of kids, the read stage on the table that comes out (_joined_run); a
+                    # run the device's walk does not take goes kid by kid
+                    for run in self._cohort_runs(list(batch.items())):
+                        if not self._joined_run(run, *ctx):
+                            self._kid_run(run, *ctx)
                 else:
-                    region_table = self.reads_by_bam.regions(bam, fc, flo, fhi)
-                    rh = self.backend.upload_reads(region_table, min_base_qual=int(params.min_gt_qual), point_only=True,
-                                                   fetches=(fc, flo, fhi, fex), all_bases=bool(params.no_extended), wide_no_units=has_sv)
-                handles.append(rh)
-            else:
-                rh = self.reads(bam, params.min_gt_qual)
-            groups.append((fam, rh, len(order_all), len(idxs), cutoff))
-            tables.append(region_table if region_table is not None else self.reads_by_bam[bam])
-            order_all.extend(idxs)
-        if order_all:
-            dv = self._dnms_view_of(order_all, dnms, prep, found, groups[0][4])
-            fl = [found[i] for i in order_all]
-            if len(groups) == 1:
-                res = self.backend.phase(groups[0][0], groups[0][1], dv, params, fl, want_lists, find_mode=info["mode"])
-            else:
-                res = self.backend.phase_cohort(groups, dv, params, fl, want_lists, find_mode=info["mode"])
-            free = getattr(self.backend, "free_reads", None)
-            for rh in handles:  # region tables live for one batch
-                if free:
-                    free(rh)
-            for g, (fam, rh, first, count, cutoff) in enumerate(groups):
-                for k in range(first, first + count):
-                    results[order_all[k]] = (res, k, tables[g])
+                    self._kid_run(list(batch.items()), *ctx)
         self._indexed_memo = None
         # pass 3: records, in the reference's order.  The names of the reads in the result lists: one look-up per table for the whole batch
         # (a staged table answers ids through the C ABI: hundreds of thousands of single calls were a third of round 3's host time); the chunks

@@ -32,6 +32,7 @@ IO_EXPORTS = [
     "uz_reads_select_fill", "uz_select_free", "uz_vcf_decode_regions", "uz_vcf_index_names", "uz_vcf_io_stats",
     "uz_bam_decode_memory",
     "uz_bamsrc_open", "uz_bamsrc_close", "uz_bamsrc_n_contigs", "uz_bamsrc_contig_name", "uz_bamsrc_contig_length", "uz_bamsrc_tlen_head",
+    "uz_bamsrc_open_many", "uz_bamsrc_n_files", "uz_bamsrc_files", "uz_bamsrc_ref_file",
     "uz_index_summary", "uz_inflate_backend", "uz_io_default_threads", "uz_io_cpu_quota", "uz_bam_stage_plan", "uz_bam_stage_begin", "uz_bam_stage_finish", "uz_stage_gather_blocks", "uz_stage_set_inflated", "uz_stage_sizes", "uz_stage_io_stats", "uz_stage_timing", "uz_stage_fill", "uz_stage_qname", "uz_stage_qnames",
     "uz_stage_free", "uz_stage_walk_plan_sizes", "uz_stage_walk_plan", "uz_bam_stage_finish_desc", "uz_stage_kept_sizes", "uz_stage_kept", "uz_stage_walk_host", "uz_stage_kept_debug", "uz_stage_name_records", "uz_packed_block_sums", "uz_stage_merge_subtasks", "uz_bam_stage_finish_sub",
     "uz_stage_walk_flagged", "uz_stage_lookup", "uz_stage_extra", "uz_stage_n_lookup_tasks", "uz_sites_pack", "uz_sites_unpack", "uz_samples_pack",
@@ -143,6 +144,12 @@ def load():
     lib.uz_index_summary.argtypes = [C.c_char_p, C.c_int, C.c_void_p, C.c_int64]
     lib.uz_index_summary.restype = C.c_int64
     lib.uz_bamsrc_open.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.POINTER(C.c_void_p)]
+    lib.uz_bamsrc_open_many.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]
+    lib.uz_bamsrc_n_files.argtypes = [C.c_void_p]
+    lib.uz_bamsrc_n_files.restype = C.c_int32
+    lib.uz_bamsrc_files.argtypes = [C.c_void_p] * 5
+    lib.uz_bamsrc_ref_file.argtypes = [C.c_void_p, C.c_int32]
+    lib.uz_bamsrc_ref_file.restype = C.c_int32
     lib.uz_bamsrc_close.argtypes = [C.c_void_p]
     lib.uz_bamsrc_close.restype = None
     lib.uz_bamsrc_n_contigs.argtypes = [C.c_void_p]
@@ -931,14 +938,47 @@ class BamSource:
         self.lib = load()
         h = C.c_void_p()
         _check(self.lib, self.lib.uz_bamsrc_open(os.fsencode(path), os.fsencode(bai) if bai else None, int(insert_size_max_sample) + 1, C.byref(h)))
+        self._adopt(h, path, threads, int(insert_size_max_sample) + 1)
+
+    def _adopt(self, h, path, threads: int, head_records: int):
         self._h = _Handle(h.value, self.lib.uz_bamsrc_close)
         self.path, self.threads = path, threads
         nc = self.lib.uz_bamsrc_n_contigs(h)
         self.contigs = [self.lib.uz_bamsrc_contig_name(h, i).decode() for i in range(nc)]
         self.contig_len = [self.lib.uz_bamsrc_contig_length(h, i) for i in range(nc)]
-        head = np.zeros(int(insert_size_max_sample) + 1, np.int32)
+        head = np.zeros(max(1, head_records), np.int32)
         k = self.lib.uz_bamsrc_tlen_head(h, head.ctypes.data, head.size)
         self.tlen_head = head[: int(k)].copy()
+        # the files of the source (one, or uz_bamsrc_open_many's): where each starts in the virtual file and among the references, and its name salts
+        nf = self.n_files = int(self.lib.uz_bamsrc_n_files(h))
+        self.file_base, self.ref_base = np.zeros(nf + 1, np.int64), np.zeros(nf + 1, np.int32)
+        self.salt1, self.salt2 = np.zeros(nf, np.uint64), np.zeros(nf, np.uint32)
+        _check(self.lib, self.lib.uz_bamsrc_files(h, self.file_base.ctypes.data, self.ref_base.ctypes.data, self.salt1.ctypes.data, self.salt2.ctypes.data))
+
+    @classmethod
+    def open_many(cls, paths, bais=None, threads: int = 0, insert_size_max_sample: int = -1) -> "BamSource":
+        """Many indexed BAMs as ONE source (uz_bamsrc_open_many): its contigs are file 0's, then file 1's, ... (`ref_base`), a fetch names a
+        contig of that list.  `paths` is kept as `.paths`; `.tlen_head` is empty for a set (the insert cutoff is per file).  One path: the source
+        uz_bamsrc_open gives (insert_size_max_sample as there, default: no head)."""
+        self = cls.__new__(cls)
+        self.lib = load()
+        paths = [os.fspath(p) for p in paths]
+        n = len(paths)
+        pa = (C.c_char_p * max(1, n))(*[os.fsencode(p) for p in paths])
+        ba = (C.c_char_p * max(1, n))(*[os.fsencode(b) if b else None for b in bais]) if bais is not None else None
+        h = C.c_void_p()
+        _check(self.lib, self.lib.uz_bamsrc_open_many(pa, ba, n, int(insert_size_max_sample) + 1, C.byref(h)))
+        self._adopt(h, paths[0], threads, int(insert_size_max_sample) + 1)
+        self.paths = tuple(paths)
+        return self
+
+    def ref_file(self, ref: int) -> int:
+        return int(self.lib.uz_bamsrc_ref_file(self._h.ptr, int(ref)))
+
+    def _plan_files(self, plan: dict) -> None:
+        """a source over many files: the per-file table the device's walk needs (uz_bam_walk_many) rides on the plan"""
+        if self.n_files > 1:
+            plan["files"] = dict(file_base=self.file_base, ref_base=self.ref_base, salt1=self.salt1, salt2=self.salt2)
 
     def select(self, contig, lo, hi, min_base_qual: int, alloc=None, all_bases=False, lists=True, extra=None, pool=None, wide_no_units=False,
                inflate=None, inflate_alloc=None, inflate_max_bytes=16 << 30, base_lists=None, tup8=None):
@@ -1096,6 +1136,7 @@ class BamSource:
         _check(self.lib, self.lib.uz_stage_walk_plan(sh.ptr, task.ctypes.data, span.ctypes.data, reach.ctypes.data, fetch.ctypes.data, blk_coff.ctypes.data,
                                                      blk_crc.ctypes.data))
         plan.update(task=task[:nt], span=span[:nsp], reach=reach[:nr], fetch=fetch[:nf], blk_coff=blk_coff[:nblk], blk_crc=blk_crc[:nblk], n_ref=len(self.contigs))
+        self._plan_files(plan)
         t1 = time.perf_counter()
         if join is not None:
             return self._joined_on_the_device(join, sh, plan, n_host, nt, int(min_base_qual), bool(all_bases), release, t0, t1)

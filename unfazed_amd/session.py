@@ -213,6 +213,15 @@ class _LazyReads(dict):
             self._stagers[bam] = _STAGERS[key]
         return self._stagers[bam]
 
+    def stager_many(self, bams):
+        """the files of one run of a cohort call opened as ONE source (io_native.BamSource.open_many: hostpath.PhasingHost._joined_run), kept for the
+        process per tuple of files like the per-file sources.  A set keeps no file descriptor open, only address space."""
+        from .io_native import BamSource
+        key = ("many",) + tuple((os.path.abspath(b), os.stat(b).st_size, os.stat(b).st_mtime_ns) for b in bams)
+        if key not in _STAGERS:
+            _STAGERS[key] = BamSource.open_many(list(bams), threads=_io_threads())
+        return _STAGERS[key]
+
     def regions(self, bam: str, tid, lo, hi) -> ReadsTable:
         if bam.endswith(".cram"):
             raise CramNotSupported(bam)
