@@ -163,6 +163,15 @@ int uz_sites_pack(const uz_sites_view *in, uint8_t *out, int64_t cap, uz_sites_v
 /* its inverse on the host (what the device's expansion computes): the plain columns of a compact view */
 int uz_sites_unpack(const uz_sites_view *v, int32_t *pos, uint8_t *sflags, uint8_t *ref_base, uint8_t *alt_base);
 
+/* The het form of a trio's genotype columns (uz_types.h: uz_family_view.het9 ...): gt and the nine eight-bit columns of `in`, n_sites
+ * sites -> one block at `out` (256-byte aligned, the caller's -- pinned -- memory: written straight into it) holding het9 and
+ * het_span_off, and `view` pointing into it (gt and the wide list are taken over from `in`, the nine plain columns are NULL).  *bytes:
+ * the block's size -- call with out NULL first. */
+int uz_family_pack_het(const uz_family_view *in, int64_t n_sites, uint8_t *out, int64_t cap, uz_family_view *view, int64_t *bytes);
+/* its inverse on the host (what the device's expansion writes): cols u16 [9][n_sites] -- rd kid, dad, mom, ad, gq -- widened for the
+ * kid-het sites, zeros for all others.  UZ_IO_E_ARG: a span whose kid-het sites are not the number het_span_off names. */
+int uz_family_unpack_het(const uz_family_view *v, int64_t n_sites, uint16_t *cols);
+
 /* The device-facing columns of samples pick[0 .. n_pick) of a decoded table (uz_types.h: uz_samples_view), made ONCE per sample instead of
  * once per trio: gt copied, depths in 16 bits (negative = missing -> UZ_U16_MISSING, clamped at 32767), floor(GQ) (NaN or negative =
  * missing, clamped at 32767) -- rows [n_pick][n_sites] in the caller's memory (pinned for the upload) -- and the table-level wide

@@ -156,6 +156,17 @@ typedef struct uz_family_view {
     const uint8_t *ref_depth8[3];
     const uint8_t *alt_depth8[3];
     const uint8_t *gq8[3];
+    /* The het form (uz_family_pack_het writes it; all nine plain columns, 16- and 8-bit, are then NULL): the nine bytes travel for the
+     * kid-het sites only -- (gt & 3) == UZ_HET on this view's own gt -- since the SNV / breakpoint classes of every other site follow from
+     * gt alone (HET and CAND need a het kid, ALT_DAD is the parental pattern).  Sites in spans of UZ_SITE_SPAN, as the compact site form.
+     *   het9[9 * e + q]   het site e in site order, q = rd kid, dad, mom, ad kid, dad, mom, gq kid, dad, mom, in the eight-bit encoding above
+     *   het_span_off[s]   kid-het sites before span s (n_spans + 1 entries, the last n_het)
+     * Only uz_sites_family_upload_async takes it, together with the compact site form; the device writes the 16-bit columns of the het
+     * sites and zeros for all others.  What needs the other sites' columns refuses such a family (UZ_E_STATE): the DEL / DUP classes
+     * (uz_phase_cnv, uz_phase_cnv_cohort, a whole-region find) and uz_family_fetch. */
+    const uint8_t *het9;
+    const int32_t *het_span_off;
+    int64_t n_het;
 } uz_family_view;
 #define UZ_U8_MISSING 254u
 #define UZ_U8_SEE_WIDE 255u

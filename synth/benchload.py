@@ -108,9 +108,13 @@ class BenchLoad:
             np.add.at(kk, hi_i, -1)
         return np.nonzero(np.cumsum(kk[:-1]) > 0)[0]
 
-    def pinned_sites(self, pool, sel, eight_bit=True, compact=False):
+    def pinned_sites(self, pool, sel, eight_bit=True, compact=False, het=False):
         """the site + genotype columns of `sel` in pinned memory, as one slab -> (held view, site columns, genotype columns, wide list, n);
-        compact: the site columns in the compact link form (io_native.pack_sites; hs_k["link_bytes"]: the packer's count)"""
+        compact: the site columns in the compact link form (io_native.pack_sites; hs_k["link_bytes"]: the packer's count)
+        het (with compact and eight_bit): the genotype columns in the het form (io_native.pack_family_het: nine bytes per kid-het site;
+        hg_k = {"rd": None, "ad": None, "gq": None, "het": (het9, het_span_off), "link_bytes": the packer's count})"""
+        if het and not (compact and eight_bit):
+            raise ValueError("the het form travels with the compact site form and the eight-bit columns")
         from unfazed_amd import abi, io_native
         sc = self.sc
         co_s = np.asarray(sc.contig_off, np.int64)
@@ -131,7 +135,11 @@ class BenchLoad:
         if eight_bit:  # the nine genotype columns in eight bits (uz_types.h: depths of 255 and more, or missing, through the wide list)
             r8, a8, g8, wide_k = abi.family_columns8(hg_k["rd"], hg_k["ad"], hg_k["gq"])
             hg_k = dict(rd=list(r8), ad=list(a8), gq=list(g8))
-        hg_k = {k: [pinned_copy(pool, x) for x in v] for k, v in hg_k.items()}
+        if het:  # (the packer writes straight into the pinned slab: the nine columns themselves never get there)
+            h9, hoff, nb = io_native.pack_family_het(hs_k["gt"], hg_k["rd"], hg_k["ad"], hg_k["gq"], alloc=pool.alloc)
+            hg_k = dict(rd=None, ad=None, gq=None, het=(h9, hoff), link_bytes=nb)
+        else:
+            hg_k = {k: [pinned_copy(pool, x) for x in v] for k, v in hg_k.items()}
         if svc is not None:
             svk = svc
             for k in plain:
@@ -145,10 +153,14 @@ class BenchLoad:
         return abi.Held(svk, hs_k), hs_k, hg_k, wide_k, int(sel.size)
 
     def stage(self, eng, P, mode, fid, pool, chunks=None, last_chunk=0.7, first_chunk=None, sites16=False, per_chunk_sites=True, log_first=False,
-              compact_sites=True):
+              compact_sites=True, het_sites=None):
         """What the decoders would leave in pinned memory for a staged pass: per chunk of DNMs (whole clusters) the records the chunk's fetches
         return + their mates, in the link form (selected on the host out of the generator's table), and the site windows.
+        het_sites: the genotype columns of the site windows in the het form (None: whenever the site form is compact and eight-bit and the
+        workload is not "cnv", whose allele-balance stage reads every site's columns)
         -> (chunks for pipeline.run_pipelined, stats)"""
+        if het_sites is None:
+            het_sites = bool(compact_sites) and not sites16 and not self.cnv
         from unfazed_amd import io_native, shard
         from unfazed_amd.staging import fetch_points
         ev, sc, cl, wl, n = self.ev, self.sc, self.cl, self.wl, self.n
@@ -190,11 +202,12 @@ class BenchLoad:
             # the site columns cut per chunk (the windows of the chunk's DNMs): the site stage of chunk k + 1 then runs while the records of
             # chunk k are still on the link (config 5 the same way: the allele-balance stage of a chunk runs on the chunk's own windows)
             for c in out:
-                held, hs_k, hg_k, wide_k, ns = self.pinned_sites(pool, self.window_sites(c["a"], c["b"], P), eight_bit=not sites16, compact=compact_sites)
+                held, hs_k, hg_k, wide_k, ns = self.pinned_sites(pool, self.window_sites(c["a"], c["b"], P), eight_bit=not sites16, compact=compact_sites, het=het_sites)
                 c["sites"] = (held, hs_k, hg_k, wide_k)
                 n_sites_staged += ns
                 # (the site columns: the packer's count, or 4 + 1 + 1 + 1 B per site; gt; the nine genotype columns; the wide list)
-                site_bytes += (hs_k["link_bytes"] if compact_sites else ns * 7) + ns * (1 + (18 if sites16 else 9)) + (0 if wide_k is None else len(wide_k[0]) * 32)
+                site_bytes += ((hs_k["link_bytes"] if compact_sites else ns * 7) + ns + (hg_k["link_bytes"] if het_sites else ns * (18 if sites16 else 9))
+                               + (0 if wide_k is None else len(wide_k[0]) * 32))
         return out, dict(read_bytes=staged_bytes, records=staged_records, sites=n_sites_staged, site_bytes=site_bytes)
 
     def free(self):

@@ -110,6 +110,10 @@ class FamilyView(C.Structure):
         ("ref_depth8", _p * 3),  # the nine columns in eight bits for the host link (then ref_depth / alt_depth / gq are NULL)
         ("alt_depth8", _p * 3),
         ("gq8", _p * 3),
+        # the het form (uz_types.h; io_native.pack_family_het): nine bytes per kid-het site, then all nine plain columns are NULL
+        ("het9", _p),
+        ("het_span_off", _p),
+        ("n_het", C.c_int64),
     ]
 
 
@@ -581,23 +585,31 @@ def sites_view(t: SitesTable) -> Held:
     return Held(v, arrs)
 
 
-def family_view(gt: np.ndarray, rd: np.ndarray, ad: np.ndarray, gq: np.ndarray, wide=None) -> Held:
+def family_view(gt: np.ndarray, rd: np.ndarray, ad: np.ndarray, gq: np.ndarray, wide=None, het=None) -> Held:
     """gt u8[S]; rd/ad/gq u16[3][S] in kid, dad, mom order.  wide = (site int64[W], ref_depth int32[3][W], alt_depth int32[3][W]): the
-    sites whose depths do not fit the 16-bit columns (model.SitesTable.family_columns lists them), or None."""
+    sites whose depths do not fit the 16-bit columns (model.SitesTable.family_columns lists them), or None.
+    het = (het9 u8[9 * n_het], het_span_off i32[n_spans + 1]) of io_native.pack_family_het: the het form, rd / ad / gq are then None."""
     gt = _c(gt, np.uint8)
-    eight = all(np.asarray(x[m]).dtype == np.uint8 for x in (rd, ad, gq) for m in range(3))  # the link form of family_columns8
-    dt = np.uint8 if eight else np.uint16
-    rd = [_c(rd[m], dt) for m in range(3)]
-    ad = [_c(ad[m], dt) for m in range(3)]
-    gq = [_c(gq[m], dt) for m in range(3)]
     v = FamilyView()
     v.gt = _ptr(gt)
-    for m in range(3):
-        if eight:
-            v.ref_depth8[m], v.alt_depth8[m], v.gq8[m] = _ptr(rd[m]), _ptr(ad[m]), _ptr(gq[m])
-        else:
-            v.ref_depth[m], v.alt_depth[m], v.gq[m] = _ptr(rd[m]), _ptr(ad[m]), _ptr(gq[m])
-    keep = dict(gt=gt, rd=rd, ad=ad, gq=gq)
+    if het is not None:
+        if rd is not None or ad is not None or gq is not None:
+            raise ValueError("the het form travels without the nine plain columns")
+        h9, hoff = _c(het[0], np.uint8), _c(het[1], np.int32)
+        v.het9, v.het_span_off, v.n_het = _ptr(h9), _ptr(hoff), int(h9.size // 9)
+        keep = dict(gt=gt, het9=h9, het_span_off=hoff)
+    else:
+        eight = all(np.asarray(x[m]).dtype == np.uint8 for x in (rd, ad, gq) for m in range(3))  # the link form of family_columns8
+        dt = np.uint8 if eight else np.uint16
+        rd = [_c(rd[m], dt) for m in range(3)]
+        ad = [_c(ad[m], dt) for m in range(3)]
+        gq = [_c(gq[m], dt) for m in range(3)]
+        for m in range(3):
+            if eight:
+                v.ref_depth8[m], v.alt_depth8[m], v.gq8[m] = _ptr(rd[m]), _ptr(ad[m]), _ptr(gq[m])
+            else:
+                v.ref_depth[m], v.alt_depth[m], v.gq[m] = _ptr(rd[m]), _ptr(ad[m]), _ptr(gq[m])
+        keep = dict(gt=gt, rd=rd, ad=ad, gq=gq)
     if wide is not None and len(wide[0]):
         ws = _c(wide[0], np.int64)
         wr = [_c(wide[1][m], np.int32) for m in range(3)]

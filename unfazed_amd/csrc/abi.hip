@@ -150,6 +150,7 @@ FamilyDev &fam_of(uz_ctx *c, int id) {
         f.pending = false;
         UZ_HIP(hipStreamWaitEvent(c->stream, f.ready, 0));
         SitesDev &s0 = c->sites[f.sites_id];
+        if (f.het_only && s0.n) s0.expand_pending = true; // (sites used before their family: expanded again, now with the het columns)
         if (s0.expand_pending) { // compact site form: ONE launch expands the sites and readies the family
             if (s0.pending) { s0.pending = false; UZ_HIP(hipStreamWaitEvent(c->stream, s0.ready, 0)); }
             uz_sites_expand(c, s0, &f);
@@ -610,6 +611,24 @@ static bool family_view_eight(const uz_family_view *v) {
     return n8 == 9;
 }
 
+// which form ...: true = the het form (uz_family_view.het9 ...: nine bytes per kid-het site), its offsets checked here -- that they ascend
+// from 0 to n_het; the expansion kernel holds every span's count against them (no host pass over gt)
+static bool family_view_het(const uz_family_view *v, int64_t n_sites) {
+    if (!v->het9 && !v->het_span_off) return false;
+    const int64_t n_spans = (n_sites + UZ_SITE_SPAN - 1) / UZ_SITE_SPAN;
+    UZ_REQUIRE(v->het_span_off && v->n_het >= 0 && v->n_het <= n_sites && (v->n_het == 0 || v->het9), UZ_E_ARG,
+               "a het-form family view sets het_span_off, n_het and -- for any het site -- het9");
+    UZ_REQUIRE(v->het_span_off[0] == 0 && v->het_span_off[n_spans] == v->n_het, UZ_E_ARG, "het_span_off does not cover het9");
+    for (int64_t sp = 0; sp < n_spans; sp++) UZ_REQUIRE(v->het_span_off[sp] <= v->het_span_off[sp + 1], UZ_E_ARG, "het_span_off must ascend");
+    return true;
+}
+
+// What needs the genotype columns of sites where the kid is not het -- the DEL / DUP classes, the columns themselves -- refuses a family
+// that was staged in the het form
+static void refuse_het_only(const FamilyDev &f, const char *what) {
+    if (f.het_only) throw UzError{UZ_E_STATE, std::string(what) + ": this family was staged in the het form (genotype columns of the kid-het sites only)"};
+}
+
 // the too-deep sites of a family view (host pointers) -> the family's side table on the device
 static void family_wide(uz_ctx *c, hipStream_t st, const uz_family_view *v, FamilyDev &f, int64_t n_sites) {
     f.n_wide = 0;
@@ -701,8 +720,13 @@ int uz_sites_family_upload_async(uz_ctx *c, const uz_sites_view *v, const uz_fam
         f.owned = true;
         const bool eight = family_view_eight(fv);
         const bool compact = sites_view_compact(v);
-        const size_t n_spans = (n + UZ_SITE_SPAN - 1) / UZ_SITE_SPAN, n_esc = compact ? (size_t)v->n_pos_esc : 0;
+        const bool het = family_view_het(fv, s.n);
+        UZ_REQUIRE(!het || (compact && !eight && !fv->ref_depth[0]), UZ_E_ARG,
+                   "the het form of a family travels with the compact site form and without the nine plain columns");
+        const size_t n_spans = (n + UZ_SITE_SPAN - 1) / UZ_SITE_SPAN, n_esc = compact ? (size_t)v->n_pos_esc : 0, n_het = het ? (size_t)fv->n_het : 0;
         uint8_t *st8[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        uint8_t *st_het9 = nullptr;
+        int32_t *st_hoff = nullptr;
         uint16_t *c_d16 = nullptr;
         uint8_t *c_b8 = nullptr;
         int32_t *c_span = nullptr, *c_eidx = nullptr, *c_eval = nullptr, *c_eoff = nullptr;
@@ -722,6 +746,7 @@ int uz_sites_family_upload_async(uz_ctx *c, const uz_sites_view *v, const uz_fam
             f.gt = cv.take<uint8_t>(n);
             for (int m = 0; m < 3; m++) { f.rd[m] = cv.take<uint16_t>(n); f.ad[m] = cv.take<uint16_t>(n); f.gq[m] = cv.take<uint16_t>(n); }
             if (eight) for (int k = 0; k < 9; k++) st8[k] = cv.take<uint8_t>(n);
+            if (het) { st_het9 = cv.take<uint8_t>(9 * n_het); st_hoff = cv.take<int32_t>(n_spans + 1); }
             if (!pass) f.block = uz_block_get(c, cv.off + 256);
         }
         try {
@@ -745,6 +770,8 @@ int uz_sites_family_upload_async(uz_ctx *c, const uz_sites_view *v, const uz_fam
                         f.stage8[m] = h2d(st, st8[m], fv->ref_depth8[m], n); f.stage8[3 + m] = h2d(st, st8[3 + m], fv->alt_depth8[m], n);
                         f.stage8[6 + m] = h2d(st, st8[6 + m], fv->gq8[m], n);
                     }
+                } else if (het) { // (the same: the expansion writes the family's own 16-bit columns from them)
+                    f.het9 = h2d(st, st_het9, fv->het9, 9 * n_het); f.het_off = h2d(st, st_hoff, fv->het_span_off, n_spans + 1);
                 } else
                     for (int m = 0; m < 3; m++) {
                         f.rd[m] = const_cast<uint16_t *>(h2d(st, f.rd[m], fv->ref_depth[m], n));
@@ -753,6 +780,7 @@ int uz_sites_family_upload_async(uz_ctx *c, const uz_sites_view *v, const uz_fam
                     }
             }
             if (eight) { f.widen_pending = true; f.gq_clamped = true; }
+            if (het) { f.het_only = true; f.n_het = (int64_t)n_het; f.gq_clamped = true; }
             s.expand_pending = compact && n;
             family_wide(c, st, fv, f, s.n);
             UZ_HIP(hipEventCreateWithFlags(&f.ready, hipEventDisableTiming));
@@ -1015,6 +1043,7 @@ int uz_families_from_samples(uz_ctx *c, int samples_id, int32_t n, const int32_t
 int uz_family_fetch(uz_ctx *c, int fam_id, uint8_t *gt, uint16_t *cols) {
     return guarded(c, [&] {
         FamilyDev &f = fam_of(c, fam_id);
+        refuse_het_only(f, "uz_family_fetch");
         SitesDev &s = sites_of(c, f.sites_id);
         const size_t n = (size_t)s.n;
         if (!n) return;
@@ -1887,7 +1916,7 @@ int uz_reads_free(uz_ctx *c, int reads_id) {
 int uz_site_scan(uz_ctx *c, int fam_id) {
     return guarded(c, [&] {
         FamilyDev &f = fam_of(c, fam_id);
-        uz_launch_site_scan(c, f, sites_of(c, f.sites_id), true);
+        uz_launch_site_scan(c, f, sites_of(c, f.sites_id), !f.het_only); // (a het-form family has the SNV / breakpoint classes only)
     });
 }
 
@@ -1898,6 +1927,7 @@ int uz_site_scan_many(uz_ctx *c, const int32_t *fam_ids, int32_t n_fam) {
         std::vector<FamilyDev *> fams;
         for (int32_t k = 0; k < n_fam; k++) {
             FamilyDev &f = fam_of(c, fam_ids[k]);
+            refuse_het_only(f, "uz_site_scan_many");
             UZ_REQUIRE(f.sites_id == fam_of(c, fam_ids[0]).sites_id, UZ_E_ARG, "the families of one cohort scan must share a sites table");
             for (int32_t j = 0; j < k; j++) UZ_REQUIRE(fam_ids[j] != fam_ids[k], UZ_E_ARG, "family listed twice");
             fams.push_back(&f);
@@ -1911,9 +1941,11 @@ int uz_site_classes(uz_ctx *c, int fam_id, uint8_t *out) {
         FamilyDev &f = fam_of(c, fam_id);
         SitesDev &s = sites_of(c, f.sites_id);
         UZ_REQUIRE(out != nullptr, UZ_E_ARG, "null output");
-        if (!uz_site_scan_fresh(c, f, true)) uz_launch_site_scan(c, f, s, true);
+        const bool cnv = !f.het_only; // (a het-form family has the SNV / breakpoint classes only: bits 3-6 stay 0)
+        if (!uz_site_scan_fresh(c, f, cnv)) uz_launch_site_scan(c, f, s, cnv);
         if (s.n) UZ_HIP(hipMemcpyAsync(out, f.cls, (size_t)s.n, hipMemcpyDeviceToHost, c->stream));
         UZ_HIP(hipStreamSynchronize(c->stream));
+        if (f.het_only) uz_check_upload_flag(c); // (the expansion held every span's het count against het_span_off)
     });
 }
 
@@ -1925,11 +1957,13 @@ int uz_find(uz_ctx *c, int fam_id, const uz_dnms_view *d, int mode, int64_t *can
         c->cohort_on = false;
         c->phase_valid = false;
         const bool cnv = (mode & UZ_FIND_WHOLE_REGION) != 0;
+        if (cnv) refuse_het_only(f, "a whole-region find");
         if (!uz_site_scan_fresh(c, f, cnv)) uz_launch_site_scan(c, f, s, cnv); // (reads nothing of the batch: queued before the batch is staged)
         uz_stage_dnms(c, d);
         const FindKey key = find_key_of(c, fam_id, mode, d); // (behind the site scan's launch: host work beside the device's)
         find_target(c);
         uz_launch_find(c, f, s, mode);
+        if (f.het_only) uz_check_upload_flag(c); // (the expansion held every span's het count against het_span_off; the find has waited for it)
         find_done(c, key);
         c->find_fam = fam_id;
         if (cand_off) memcpy(cand_off, c->cand_off_h.data(), ((size_t)d->n + 1) * sizeof(int64_t));
@@ -2211,6 +2245,7 @@ static void cohort_find_stage(uz_ctx *c, const uz_cohort_group *groups, int32_t 
         UZ_REQUIRE(groups[g].dnm_first >= 0 && groups[g].dnm_count >= 0 && (int64_t)groups[g].dnm_first + groups[g].dnm_count <= n, UZ_E_ARG,
                    "cohort group outside the DNM batch");
         UZ_REQUIRE(fam_of(c, groups[g].fam_id).sites_id == f0->sites_id, UZ_E_ARG, "the families of a cohort batch must share a sites table");
+        if (cnv) refuse_het_only(fam_of(c, groups[g].fam_id), "a whole-region find / the allele-balance stage");
         if (groups[g].dnm_count) spans.push_back({groups[g].dnm_first, groups[g].dnm_count});
     }
     std::sort(spans.begin(), spans.end());
@@ -2288,6 +2323,7 @@ int uz_phase_cnv(uz_ctx *c, int fam_id, const uz_dnms_view *d, const int32_t *rb
                  int32_t *evidence, int32_t *etype) {
     return guarded(c, [&] {
         FamilyDev &f = fam_of(c, fam_id);
+        refuse_het_only(f, "uz_phase_cnv");
         SitesDev &s = sites_of(c, f.sites_id);
         UZ_REQUIRE(d != nullptr, UZ_E_ARG, "null DNM view");
         find_target(c); c->phase_valid = false; c->cnv_valid = false;

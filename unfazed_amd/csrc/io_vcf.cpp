@@ -1316,6 +1316,70 @@ int uz_sites_unpack(const uz_sites_view *v, int32_t *pos, uint8_t *sflags, uint8
     });
 }
 
+// ---------------------------------------------------------------- het form of a trio's columns (uz_types.h: uz_family_view.het9 ...)
+
+int uz_family_pack_het(const uz_family_view *in, int64_t n_sites, uint8_t *out, int64_t cap, uz_family_view *view, int64_t *bytes) {
+    if (!in || !bytes || (out && !view)) { last_error = "null argument"; return UZ_IO_E_ARG; }
+    return guarded([&] {
+        const int64_t n = n_sites;
+        if (n < 0 || n >= ((int64_t)1 << 31)) fail(UZ_IO_E_ARG, "bad site count");
+        const uint8_t *col[9];
+        for (int m = 0; m < 3; m++) { col[m] = in->ref_depth8[m]; col[3 + m] = in->alt_depth8[m]; col[6 + m] = in->gq8[m]; }
+        if (n && !in->gt) fail(UZ_IO_E_ARG, "null gt");
+        for (int q = 0; q < 9; q++)
+            if (n && !col[q]) fail(UZ_IO_E_ARG, "uz_family_pack_het takes the nine eight-bit columns");
+        const int64_t n_spans = (n + UZ_SITE_SPAN - 1) / UZ_SITE_SPAN;
+        int64_t n_het = 0;
+        for (int64_t i = 0; i < n; i++) n_het += (in->gt[i] & 3) == UZ_HET;
+        auto al = [](int64_t x) { return (x + 255) & ~(int64_t)255; };
+        const int64_t o_het = 0, o_off = al(o_het + 9 * n_het), end = al(o_off + 4 * (n_spans + 1));
+        *bytes = end;
+        if (!out) return;
+        if (cap < end) fail(UZ_IO_E_ARG, "uz_family_pack_het: %lld bytes of room for %lld", (long long)cap, (long long)end);
+        if ((uintptr_t)out % 256) fail(UZ_IO_E_ARG, "uz_family_pack_het: the block must be 256-byte aligned");
+        uint8_t *h9 = out + o_het;
+        int32_t *hoff = (int32_t *)(out + o_off);
+        int64_t e = 0;
+        for (int64_t i = 0; i < n; i++) {
+            if (i % UZ_SITE_SPAN == 0) hoff[i / UZ_SITE_SPAN] = (int32_t)e;
+            if ((in->gt[i] & 3) != UZ_HET) continue;
+            for (int q = 0; q < 9; q++) h9[9 * e + q] = col[q][i];
+            e++;
+        }
+        hoff[n_spans] = (int32_t)e;
+        *view = *in; // (gt and the wide list are taken over from `in`)
+        for (int m = 0; m < 3; m++) {
+            view->ref_depth[m] = view->alt_depth[m] = view->gq[m] = nullptr;
+            view->ref_depth8[m] = view->alt_depth8[m] = view->gq8[m] = nullptr;
+        }
+        view->het9 = h9; view->het_span_off = hoff; view->n_het = n_het;
+    });
+}
+
+int uz_family_unpack_het(const uz_family_view *v, int64_t n_sites, uint16_t *cols) {
+    if (!v || (n_sites > 0 && !cols)) { last_error = "null argument"; return UZ_IO_E_ARG; }
+    return guarded([&] {
+        const int64_t n = n_sites, n_spans = (n + UZ_SITE_SPAN - 1) / UZ_SITE_SPAN;
+        if (n < 0) fail(UZ_IO_E_ARG, "bad site count");
+        if (n && (!v->gt || !v->het_span_off || v->n_het < 0 || (v->n_het && !v->het9))) fail(UZ_IO_E_ARG, "not a het-form family view");
+        if (n && (v->het_span_off[0] != 0 || v->het_span_off[n_spans] != v->n_het)) fail(UZ_IO_E_ARG, "het_span_off does not cover het9");
+        for (int64_t s = 0; s < n_spans; s++) {
+            const int64_t lo = s * UZ_SITE_SPAN, hi = std::min(n, lo + UZ_SITE_SPAN);
+            int64_t e = v->het_span_off[s];
+            for (int64_t i = lo; i < hi; i++) {
+                const bool het = (v->gt[i] & 3) == UZ_HET;
+                if (het && e >= v->n_het) fail(UZ_IO_E_ARG, "span %lld: more kid-het sites than het_span_off names", (long long)s);
+                for (int q = 0; q < 9; q++) {
+                    const uint32_t b = het ? v->het9[9 * e + q] : 0u;
+                    cols[(size_t)q * (size_t)n + (size_t)i] = (uint16_t)(het && b == (q < 6 ? (uint32_t)UZ_U8_MISSING : 255u) ? UZ_U16_MISSING : b);
+                }
+                e += het;
+            }
+            if (e != v->het_span_off[s + 1]) fail(UZ_IO_E_ARG, "span %lld: its kid-het sites are not the number het_span_off names", (long long)s);
+        }
+    });
+}
+
 // ---------------------------------------------------------------- per-sample device columns (uz_types.h: uz_samples_view)
 
 int uz_samples_pack(const uz_vcf_view *in, int32_t n_pick, const int32_t *pick, int threads, uint8_t *gt, uint16_t *ref_depth, uint16_t *alt_depth,

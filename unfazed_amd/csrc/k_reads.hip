@@ -1551,6 +1551,7 @@ void uz_check_upload_flag(uz_ctx *c) {
                                   : f == 6 ? "aux of the reads view: a simple-CIGAR code on a record whose n_cigar is not 1"
                                   : f == 7 ? "mate_d / esc16_* of the reads view: a mate index outside the table"
                                   : f == 8 ? "pair_d8 of the reads view: a SECOND record that no FIRST record names, or one that two of them name"
+                                  : f == 10 ? "het_span_off of the family view: a span whose kid-het sites (by gt) are not the number its offsets name"
                                   : f == 9 ? "bl_* of the reads view: a listed base outside the record's unit mask or its length, positions not ascending, a unit of the mask without a listed base, or a list on a record without a mask / without bases"
                                            : "n_cigar_total / n_row_units of the reads view do not match its columns"};
     }

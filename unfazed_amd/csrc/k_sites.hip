@@ -827,6 +827,9 @@ void uz_fold_complex(uz_ctx *c, uint8_t *gt, const uint8_t *sflags, int64_t n) {
 // table's family that k_widen8 and k_fold_complex do apart: the eight-bit genotype columns widened, the complex bit folded into gt.  pos: one
 // segmented sum scan over the span -- an anchor (the span's first site, an escape) starts a segment with its absolute pos, every other site
 // adds its difference.  2 KB of LDS: the workgroups fit beside the header build's (k_pack_link holds most of a CU's LDS).
+// The het form of the family (uz_family_view.het9 ...): the span's kid-het sites are ranked by a scan over the gt bytes -- in front of the
+// barrier the pos scan already has -- het site number r of the span reads its nine bytes at het_span_off[span] + r, every other site gets
+// zeros; a span whose count is not what het_span_off names raises the upload flag (code 10), and no byte beyond n_het is read.
 struct SitesExpand {
     const uint16_t *d16;
     const uint8_t *b8;
@@ -835,15 +838,21 @@ struct SitesExpand {
     uint8_t *sflags, *ref, *alt;
     uint8_t *gt; // null: no family
     int widen;   // the family's nine columns came in eight bits: widen them (w)
+    int het;     // ... in the het form: w.d from het9 (w.s unused)
     Widen8 w;
+    const uint8_t *het9;
+    const int32_t *hoff;
+    int64_t n_het;
+    int32_t *flag;
 };
+__device__ __forceinline__ uint16_t widen8_one(uint32_t u, int q) { return (uint16_t)(u == (q < 6 ? (uint32_t)UZ_U8_MISSING : 255u) ? 0xFFFFu : u); }
 __device__ __forceinline__ void seg_add(uint32_t &f, uint32_t &v, uint32_t fp, uint32_t vp) { // (fp, vp) before (f, v)
     v = f ? v : vp + v;
     f |= fp;
 }
 __global__ __launch_bounds__(256) void k_sites_expand(int64_t n, SitesExpand x) {
     __shared__ uint16_t mark[UZ_SITE_SPAN]; // escape number within the span + 1 at an escaped site, else 0
-    __shared__ uint32_t wf[4], wv_[4];
+    __shared__ uint32_t wf[4], wv_[4], hc[4];
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     const int64_t base = (int64_t)blockIdx.x * UZ_SITE_SPAN, i0 = base + 4 * t;
     for (int j = t; j < UZ_SITE_SPAN; j += 256) mark[j] = 0;
@@ -864,6 +873,24 @@ __global__ __launch_bounds__(256) void k_sites_expand(int64_t n, SitesExpand x) 
     } else
         for (int k = 0; k < 4; k++)
             if (i0 + k < n) { d[k] = x.d16[i0 + k]; b[k] = x.b8[i0 + k]; }
+    uint32_t hm = 0, hcnt = 0, hincl = 0; // het form: which of the lane's four sites are kid-het, how many, and up to this lane within the wave
+    if (x.het) {
+        uint32_t g4 = 0; // (a site beyond n reads as 0 = UZ_HOM_REF)
+        if (full) g4 = *reinterpret_cast<const uint32_t *>(x.gt + i0);
+        else
+            for (int k = 0; k < 4; k++)
+                if (i0 + k < n) g4 |= (uint32_t)x.gt[i0 + k] << (8 * k);
+#pragma unroll
+        for (int k = 0; k < 4; k++) hm |= ((g4 >> (8 * k) & 3u) == (uint32_t)UZ_HET ? 1u : 0u) << k;
+        hcnt = __popc(hm);
+        hincl = hcnt;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t up = __shfl_up(hincl, o, 64);
+            if (lane >= o) hincl += up;
+        }
+        if (lane == 63) hc[wv] = hincl;
+    }
     uint32_t loc[4], locf[4], f = 0, acc = 0;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -887,6 +914,13 @@ __global__ __launch_bounds__(256) void k_sites_expand(int64_t n, SitesExpand x) 
     uint32_t fp = 0, vp = 0; // the waves before this one
     for (int w = 0; w < wv; w++) { uint32_t fw = wf[w], vw = wv_[w]; seg_add(fw, vw, fp, vp); fp = fw; vp = vw; }
     seg_add(fx, vx, fp, vp);
+    uint32_t hrank = hincl - hcnt; // kid-het sites of the span before this lane's
+    int64_t he0 = 0;
+    if (x.het) {
+        for (int w = 0; w < wv; w++) hrank += hc[w];
+        he0 = x.hoff[blockIdx.x];
+        if (t == 255 && (int64_t)(hrank + hcnt) != (int64_t)x.hoff[blockIdx.x + 1] - he0) x.flag[0] = 10;
+    }
     int32_t p[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) p[k] = (int32_t)(locf[k] ? loc[k] : vx + loc[k]);
@@ -917,6 +951,19 @@ __global__ __launch_bounds__(256) void k_sites_expand(int64_t n, SitesExpand x) 
                 *reinterpret_cast<ushort4 *>(x.w.d[q] + i0) = make_ushort4(wd(v.x), wd(v.y), wd(v.z), wd(v.w));
             }
         }
+        if (x.het) {
+            uint16_t v[9][4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int64_t e = he0 + hrank;
+                const bool h = (hm >> k & 1u) && e < x.n_het; // (a broken het_span_off: flagged above, nothing read beyond the list)
+#pragma unroll
+                for (int q = 0; q < 9; q++) v[q][k] = h ? widen8_one(x.het9[9 * e + q], q) : (uint16_t)0;
+                hrank += hm >> k & 1u;
+            }
+#pragma unroll
+            for (int q = 0; q < 9; q++) *reinterpret_cast<ushort4 *>(x.w.d[q] + i0) = make_ushort4(v[q][0], v[q][1], v[q][2], v[q][3]);
+        }
         return;
     }
     for (int k = 0; k < 4; k++) {
@@ -929,6 +976,12 @@ __global__ __launch_bounds__(256) void k_sites_expand(int64_t n, SitesExpand x) 
                 const uint32_t v = x.w.s[q][i];
                 x.w.d[q][i] = (uint16_t)(v == (q < 6 ? (uint32_t)UZ_U8_MISSING : 255u) ? 0xFFFFu : v);
             }
+        if (x.het) {
+            const int64_t e = he0 + hrank;
+            const bool h = (hm >> k & 1u) && e < x.n_het;
+            for (int q = 0; q < 9; q++) x.w.d[q][i] = h ? widen8_one(x.het9[9 * e + q], q) : (uint16_t)0;
+            hrank += hm >> k & 1u;
+        }
     }
 }
 void uz_sites_expand(uz_ctx *c, SitesDev &s, FamilyDev *f) {
@@ -941,6 +994,7 @@ void uz_sites_expand(uz_ctx *c, SitesDev &s, FamilyDev *f) {
         x.gt = f->gt;
         x.widen = f->widen_pending;
         f->widen_pending = false;
+        x.het = f->het_only; x.het9 = f->het9; x.hoff = f->het_off; x.n_het = f->n_het; x.flag = c->hflags;
         for (int m = 0; m < 3; m++) {
             x.w.s[m] = f->stage8[m]; x.w.s[3 + m] = f->stage8[3 + m]; x.w.s[6 + m] = f->stage8[6 + m];
             x.w.d[m] = f->rd[m]; x.w.d[3 + m] = f->ad[m]; x.w.d[6 + m] = f->gq[m];
@@ -1095,8 +1149,13 @@ static void check_gq_clamp(const uz_ctx *c, const FamilyDev &f) {
     UZ_REQUIRE(!f.gq_clamped || c->P.min_gt_qual <= 254, UZ_E_STATE,
                "this family was staged with eight-bit genotype qualities (clamped at 254): --min-gt-qual above 254 needs the 16-bit columns");
 }
+static void check_het_only(const FamilyDev &f, bool with_cnv) {
+    UZ_REQUIRE(!(with_cnv && f.het_only), UZ_E_STATE,
+               "this family was staged in the het form (genotype columns of the kid-het sites only): the DEL / DUP classes need every site's columns");
+}
 void uz_launch_site_scan(uz_ctx *c, FamilyDev &f, const SitesDev &s, bool with_cnv) {
     check_gq_clamp(c, f);
+    check_het_only(f, with_cnv);
     if (s.n > 0) { launch_site_scan(c, fam_ptrs(f), f.cls, s.n, with_cnv, nullptr, 1); launch_site_scan_wide(c, f, with_cnv); }
     f.cls_has_cnv = with_cnv;
     f.cls_valid = true;
@@ -1105,7 +1164,7 @@ void uz_launch_site_scan(uz_ctx *c, FamilyDev &f, const SitesDev &s, bool with_c
 
 void uz_launch_site_scan_many(uz_ctx *c, FamilyDev *const *fams, int n_fam, const SitesDev &s, bool with_cnv) {
     if (n_fam <= 0) return;
-    for (int k = 0; k < n_fam; k++) check_gq_clamp(c, *fams[k]);
+    for (int k = 0; k < n_fam; k++) { check_gq_clamp(c, *fams[k]); check_het_only(*fams[k], with_cnv); }
     if (s.n > 0) {
         std::vector<FamBatchItem> items((size_t)n_fam);
         for (int k = 0; k < n_fam; k++) { items[(size_t)k].f = fam_ptrs(*fams[k]); items[(size_t)k].cls = fams[k]->cls; }

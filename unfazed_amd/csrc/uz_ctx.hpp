@@ -138,6 +138,12 @@ struct FamilyDev {
     // eight-bit link form (uz_family_view.ref_depth8 ...): the staged bytes, widened into rd / ad / gq at first use; gq was clamped at 254
     const uint8_t *stage8[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool widen_pending = false, gq_clamped = false;
+    // het form (uz_family_view.het9 ...): the staged bytes of the kid-het sites; uz_sites_expand writes rd / ad / gq from them (zeros at every
+    // other site).  het_only stays set for the family's life: the DEL / DUP classes and uz_family_fetch refuse it (uz_refuse_het_only)
+    bool het_only = false;
+    const uint8_t *het9 = nullptr;
+    const int32_t *het_off = nullptr;
+    int64_t n_het = 0;
     // made by uz_families_from_samples: rd / ad / gq are rows of that sample table, wide_site is the table's, and gt / cls / wide_depth
     // lie in a block the TABLE owns (one per call, SamplesDev::fam_blocks) -- `block` and `wide_block` stay empty
     int samples_id = -1;

@@ -277,11 +277,13 @@ class HipEngine:
         self._ck(self.L.uz_samples_free(self.h, int(samples_h)), "uz_samples_free")
         getattr(self, "_samples", {}).pop(int(samples_h), None)
 
-    def upload_sites_family_async(self, held: abi.Held, gt, rd, ad, gq, wide=None):
+    def upload_sites_family_async(self, held: abi.Held, gt, rd, ad, gq, wide=None, het=None):
         """sites + one trio's genotype columns queued on the copy stream (uz_sites_family_upload_async) -> (sites id, family id);
         the arrays (pinned) must stay alive until a call using the family has returned: the engine keeps them.
-        rd / ad / gq as uint8 arrays = the eight-bit link form (abi.family_columns8, which also extends `wide`)."""
-        v = abi.family_view(gt, rd, ad, gq, wide)
+        rd / ad / gq as uint8 arrays = the eight-bit link form (abi.family_columns8, which also extends `wide`).
+        het = (het9, het_span_off) of io_native.pack_family_het = the het form (rd / ad / gq None; with compact sites only): such a family
+        serves the SNV / breakpoint classes, finds and read stages -- CNV classes, whole-region finds and family_fetch raise UZ_E_STATE."""
+        v = abi.family_view(gt, rd, ad, gq, wide, het=het)
         sid, fid = C.c_int(-1), C.c_int(-1)
         self._ck(self.L.uz_sites_family_upload_async(self.h, held.ref(), v.ref(), C.byref(sid), C.byref(fid)), "uz_sites_family_upload_async")
         self._staged_sites[sid.value] = (held, v)

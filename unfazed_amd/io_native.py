@@ -35,7 +35,7 @@ IO_EXPORTS = [
     "uz_bamsrc_open_many", "uz_bamsrc_n_files", "uz_bamsrc_files", "uz_bamsrc_ref_file",
     "uz_index_summary", "uz_inflate_backend", "uz_io_default_threads", "uz_io_cpu_quota", "uz_bam_stage_plan", "uz_bam_stage_begin", "uz_bam_stage_finish", "uz_stage_gather_blocks", "uz_stage_set_inflated", "uz_stage_sizes", "uz_stage_io_stats", "uz_stage_timing", "uz_stage_fill", "uz_stage_qname", "uz_stage_qnames",
     "uz_stage_free", "uz_stage_walk_plan_sizes", "uz_stage_walk_plan", "uz_bam_stage_finish_desc", "uz_stage_kept_sizes", "uz_stage_kept", "uz_stage_walk_host", "uz_stage_kept_debug", "uz_stage_name_records", "uz_packed_block_sums", "uz_stage_merge_subtasks", "uz_bam_stage_finish_sub",
-    "uz_stage_walk_flagged", "uz_stage_lookup", "uz_stage_extra", "uz_stage_n_lookup_tasks", "uz_sites_pack", "uz_sites_unpack", "uz_samples_pack",
+    "uz_stage_walk_flagged", "uz_stage_lookup", "uz_stage_extra", "uz_stage_n_lookup_tasks", "uz_sites_pack", "uz_sites_unpack", "uz_family_pack_het", "uz_family_unpack_het", "uz_samples_pack",
     "uz_vcf_decode_regions_lazy", "uz_vcf_is_lazy", "uz_vcf_fill_samples", "uz_vcf_samples_text", "uz_vcf_samples_bcf", "uz_vcf_record_samples",
 ]
 
@@ -104,6 +104,8 @@ def load():
     lib.uz_vcf_view_get.argtypes = [C.c_void_p, C.POINTER(VcfView)]
     lib.uz_sites_pack.argtypes = [C.POINTER(abi.SitesView), C.c_void_p, C.c_int64, C.POINTER(abi.SitesView), C.POINTER(C.c_int64)]
     lib.uz_sites_unpack.argtypes = [C.POINTER(abi.SitesView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.uz_family_pack_het.argtypes = [C.POINTER(abi.FamilyView), C.c_int64, C.c_void_p, C.c_int64, C.POINTER(abi.FamilyView), C.POINTER(C.c_int64)]
+    lib.uz_family_unpack_het.argtypes = [C.POINTER(abi.FamilyView), C.c_int64, C.c_void_p]
     lib.uz_samples_pack.argtypes = [C.POINTER(VcfView), C.c_int32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int64,
                                     C.c_void_p, C.c_void_p, C.c_void_p]
     lib.uz_vcf_sample.argtypes = [C.c_void_p, C.c_int32]
@@ -229,6 +231,41 @@ def pack_sites(plain: "abi.SitesView", alloc=None):
     v = abi.SitesView()
     _check(lib, lib.uz_sites_pack(C.byref(plain), block.ctypes.data, int(block.nbytes), C.byref(v), C.byref(nb)))
     return v, block, int(nb.value)
+
+
+def pack_family_het(gt, rd8, ad8, gq8, alloc=None):
+    """A trio's gt and nine eight-bit columns (abi.family_columns8) in the het form (uz_family_pack_het: the nine bytes of the kid-het sites
+    only) -> (het9 u8 [9 * n_het], het_span_off i32 [n_spans + 1], the block's bytes): views of one block.  alloc(nbytes) -> a 256-byte
+    aligned uint8 array (pinned: PinnedPool.alloc -- the packer writes straight into it); None: numpy memory."""
+    lib = load()
+    fv = abi.family_view(gt, rd8, ad8, gq8)
+    if not fv.view.ref_depth8[0] and len(gt):
+        raise ValueError("pack_family_het takes the eight-bit columns")
+    n = int(np.asarray(gt).size)
+    nb = C.c_int64(0)
+    _check(lib, lib.uz_family_pack_het(fv.ref(), n, None, 0, None, C.byref(nb)))
+    size = max(256, int(nb.value))
+    if alloc is None:
+        raw = np.zeros(size + 256, np.uint8)
+        k = (-raw.ctypes.data) % 256
+        block = raw[k: k + size]
+    else:
+        block = alloc(size)
+    v = abi.FamilyView()
+    _check(lib, lib.uz_family_pack_het(fv.ref(), n, block.ctypes.data, int(block.nbytes), C.byref(v), C.byref(nb)))
+    n_het, n_spans = int(v.n_het), (n + 1023) // 1024
+    o_off = int(v.het_span_off) - block.ctypes.data
+    return block[: 9 * n_het], block[o_off: o_off + 4 * (n_spans + 1)].view(np.int32), int(nb.value)
+
+
+def unpack_family_het(gt, het9, het_span_off):
+    """the host twin of the device's expansion: the het form -> cols u16 [9][S] (rd k d m, ad k d m, gq k d m), zeros off the kid-het sites"""
+    lib = load()
+    fv = abi.family_view(gt, None, None, None, het=(het9, het_span_off))
+    n = int(np.asarray(gt).size)
+    cols = np.zeros((9, max(1, n)), np.uint16)
+    _check(lib, lib.uz_family_unpack_het(fv.ref(), n, cols.ctypes.data))
+    return cols[:, :n] if n else cols[:, :0]
 
 
 def pack_samples(table: SitesTable, pick, threads: int = 0, alloc=None):

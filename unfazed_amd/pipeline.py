@@ -16,7 +16,9 @@ A chunk is a dict:
     a, b        its DNMs are [a, b) of the batch (results are written there)
     dnms        abi.dnms_view of them
     sites       (held sites view, host site columns incl. "gt", genotype columns {"rd", "ad", "gq"} (8- or 16-bit), wide list or None), all in
-                pinned memory -- or None when the caller's family handle `fid` covers the chunk (one site table for the whole batch)
+                pinned memory -- or None when the caller's family handle `fid` covers the chunk (one site table for the whole batch).
+                The het form (uz_types.h: uz_family_view.het9): the genotype columns are {"rd": None, "ad": None, "gq": None,
+                "het": (het9, het_span_off)} (not for cnv: the allele-balance stage needs every site's columns)
     records     the chunk's records in the link form (abi.Held of uz_reads_packed_view, pinned) -- or a callable returning it, called
                 when the chunk's het lists are known: records(k, het_off, het_idx) -> abi.Held   (a decoder working from files)
 """
@@ -49,7 +51,10 @@ def run_pipelined(eng, P, mode, n: int, chunks: Sequence[dict], cnv: bool = Fals
         if not own_sites[k]:
             return
         held, hs_k, hg_k, wide_k = chunks[k]["sites"]
-        sids[k], fids[k] = eng.upload_sites_family_async(held, hs_k["gt"], hg_k["rd"], hg_k["ad"], hg_k["gq"], wide_k)
+        if hg_k.get("het") is not None:
+            sids[k], fids[k] = eng.upload_sites_family_async(held, hs_k["gt"], None, None, None, wide_k, het=hg_k["het"])
+        else:
+            sids[k], fids[k] = eng.upload_sites_family_async(held, hs_k["gt"], hg_k["rd"], hg_k["ad"], hg_k["gq"], wide_k)
 
     try:
         import inspect
