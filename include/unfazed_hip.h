@@ -290,7 +290,10 @@ int uz_phase_end(uz_ctx *ctx, int fam_id, int reads_id, const uz_dnms_view *dnms
 /* Cohort form (603 samples in one run, README.md:208; one alignment file per kid, unfazed.py:574-575): the
  * DNMs of many kids -- each with its own trio columns, its own alignment records and its own insert cutoff -- in ONE
  * launch sequence instead of one per kid.  `dnms` holds all groups' DNMs back to back; `rcontig` refers to the group's
- * own reads table and dnms->cutoff is ignored.  All families must belong to one sites table.  The kids' tables are laid
+ * own reads table and dnms->cutoff is ignored.  The groups must cover [0, dnms->n) exactly once, in any order; empty groups
+ * are allowed and one family (with its reads table) may serve several groups.  UZ_E_ARG, as from uz_find_cohort and before
+ * anything of the context is touched: a gap, an overlap, a group outside the batch, families of different sites tables.
+ * Families whose classes are stale are classified in one launch first.  The kids' tables are laid
  * end to end in HBM as one table (virtual contigs = kid x contig; rebuilt only when the list of reads_ids changes), the
  * window emit reads every DNM's own family column, the read stage every DNM's own cutoff.  Results as uz_phase, in DNM
  * order; uz_phase_votes / uz_phase_groups afterwards give query-name ids of the group's own table. */
@@ -299,7 +302,8 @@ int uz_phase_cohort(uz_ctx *ctx, const uz_cohort_group *groups, int32_t n_groups
 /* The same run on a table that already IS the groups' tables end to end: one built over the groups' alignment files presented as one file
  * (uz_bam_walk_many ... uz_reads_from_walk).  group_ref_base [n_groups]: where each group's file starts among the table's contigs (its contigs
  * reach to the next larger base of any group, or to the table's end); `rcontig` of a DNM is the file's own number and becomes -1 outside the
- * file.  groups[g].reads_id is not looked at.  Nothing is concatenated and nothing copied per group; uz_phase_votes / uz_phase_groups give the
+ * file.  groups[g].reads_id is not looked at; the groups are held to uz_phase_cohort's rules (exact cover of [0, dnms->n), one sites table:
+ * UZ_E_ARG otherwise) and their stale families classified in one launch.  Nothing is concatenated and nothing copied per group; uz_phase_votes / uz_phase_groups give the
  * TABLE's name ids (uz_reads_files: where each file's begin). */
 int uz_phase_cohort_joined(uz_ctx *ctx, int reads_id, const uz_cohort_group *groups, int32_t n_groups, const int32_t *group_ref_base, const uz_dnms_view *dnms,
                            int find_mode, int32_t *status, int32_t *counts, int32_t *origin, int32_t *evidence);

@@ -50,3 +50,19 @@ def test_cnv_phasing_of_three_kids_by_both_routes_on_the_oracle(monkeypatch):
     assert cohort[3]["cnv_cohort_calls"] == 1 and cohort[3]["cnv_kid_calls"] == 0 and cohort[3]["find_cohort_calls"] == 1
     assert kid[3]["cnv_cohort_calls"] == 0 and kid[3]["cnv_kid_calls"] == 3 and kid[3]["find_kid_calls"] == 3
     assert sum(1 for r in cohort[0].values() if r["cnv_evidence_type"] == "ALLELE-BALANCE") >= 3
+
+
+def test_group_tuples_of_both_forms():
+    """HipEngine._groups: the find side's (fam, first, count) and the read stage's (fam, reads, first, count, cutoff) give the same array type;
+    the short form carries reads_id -1 and cutoff 0.0, which the find-side calls do not read."""
+    from unfazed_amd.engine import HipEngine
+    fields = lambda arr, n: [(g.fam_id, g.reads_id, g.dnm_first, g.dnm_count, g.cutoff) for g in arr[:n]]  # noqa: E731
+    short = HipEngine._groups([(7, 0, 3), (9, 3, 0), (7, 3, 5)])
+    assert isinstance(short[0], abi.CohortGroup)
+    assert fields(short, 3) == [(7, -1, 0, 3, 0.0), (9, -1, 3, 0, 0.0), (7, -1, 3, 5, 0.0)]
+    long = HipEngine._groups([(7, 2, 0, 3, 412.5), (9, 4, 3, 5, 388.25)])
+    assert isinstance(long[0], abi.CohortGroup)
+    assert fields(long, 2) == [(7, 2, 0, 3, 412.5), (9, 4, 3, 5, 388.25)]
+    mixed = HipEngine._groups([(1, 0, 2), (2, 5, 2, 1, 100.0)])
+    assert fields(mixed, 2) == [(1, -1, 0, 2, 0.0), (2, 5, 2, 1, 100.0)]
+    assert len(HipEngine._groups([])) == 1  # (never a zero-length array: the call refuses n_groups = 0 itself)

@@ -13,7 +13,15 @@ from unfazed_amd.hostpath import concordant_cutoff
 pytestmark = pytest.mark.gpu
 
 
-def test_cohort_batch_equals_per_kid_batches(engine):
+E_ARG = -1
+RESULTS = ("status", "counts", "origin", "evidence")
+
+
+@pytest.fixture(scope="module")
+def three(engine):
+    """three kids of one synth.small set staged on the context, and what one uz_phase per kid gives for each: made once, before any cohort call
+    on these tables"""
+    from types import SimpleNamespace
     kids = ["kidA", "kidB", "kidC"]
     ds = make_small(SmallConfig(seed=909, n_dnms=21, kids=kids, cluster_prob=0.6, odd_read_prob=0.05))
     sites, reads = tables(ds)
@@ -54,30 +62,97 @@ def test_cohort_batch_equals_per_kid_batches(engine):
             cols[k] += c[k]
         first += len(dn)
     dv_all = abi.dnms_view(cutoff=0.0, **cols)
-    for attempt in range(2):  # the second call reuses the merged table
-        got = engine.phase_cohort(groups, dv_all, P, want_lists=False)
-        vo, vv = engine.votes(first)
-        go, gq = engine.groups(first)
-        for (fam, rh, f0, cnt, cutoff), kid in zip(groups, kids):
-            r, wvo, wvv, wgo, wgq = want[kid]
-            for k in ("status", "counts", "origin", "evidence"):
-                assert np.array_equal(got[k][f0: f0 + cnt], r[k]), (kid, k)
-            for d in range(cnt):
-                for j in range(4):
-                    assert np.array_equal(vv[vo[4 * (f0 + d) + j]: vo[4 * (f0 + d) + j + 1]], wvv[wvo[4 * d + j]: wvo[4 * d + j + 1]]), (kid, d, j)
-                for j in range(2):
-                    assert np.array_equal(gq[go[2 * (f0 + d) + j]: go[2 * (f0 + d) + j + 1]], wgq[wgo[2 * d + j]: wgo[2 * d + j + 1]]), (kid, d, j)
-    assert sum(int((want[k][0]["status"] == abi.ST_OK).sum()) for k in kids) >= 3
-    # a plain uz_phase afterwards is unaffected by the cohort state
-    kid = kids[0]
-    dn = [d for d in ds.dnms if d["kid"] == kid]
-    c, cutoff = view(dn, kid, cuts[kid])
-    again = engine.phase_raw(fams[kid], rhs[kid], abi.dnms_view(cutoff=cutoff, **c), P, abi.FIND_SECOND_WINDOW)
-    for k in ("status", "counts", "origin", "evidence"):
-        assert np.array_equal(again[k], want[kid][0][k])
+    yield SimpleNamespace(kids=kids, ds=ds, sites=sites, P=P, sid=sid, fams=fams, rhs=rhs, cuts=cuts, view=view, groups=groups, want=want,
+                          dv_all=dv_all, n=first)
     for kid in kids:
         engine.free_reads(rhs[kid])
     engine.free_sites(sid)
+
+
+def _equals_per_kid(engine, t, got):
+    """the results of a cohort batch over t.groups, and the lists the context holds behind them, against one uz_phase per kid"""
+    vo, vv = engine.votes(t.n)
+    go, gq = engine.groups(t.n)
+    for (fam, rh, f0, cnt, cutoff), kid in zip(t.groups, t.kids):
+        r, wvo, wvv, wgo, wgq = t.want[kid]
+        for k in RESULTS:
+            assert np.array_equal(got[k][f0: f0 + cnt], r[k]), (kid, k)
+        for d in range(cnt):
+            for j in range(4):
+                assert np.array_equal(vv[vo[4 * (f0 + d) + j]: vo[4 * (f0 + d) + j + 1]], wvv[wvo[4 * d + j]: wvo[4 * d + j + 1]]), (kid, d, j)
+            for j in range(2):
+                assert np.array_equal(gq[go[2 * (f0 + d) + j]: go[2 * (f0 + d) + j + 1]], wgq[wgo[2 * d + j]: wgo[2 * d + j + 1]]), (kid, d, j)
+
+
+def _plain_again(engine, t, what):
+    """a plain uz_phase of kid 0 is what it was before any cohort call"""
+    kid = t.kids[0]
+    dn = [d for d in t.ds.dnms if d["kid"] == kid]
+    c, cutoff = t.view(dn, kid, t.cuts[kid])
+    again = engine.phase_raw(t.fams[kid], t.rhs[kid], abi.dnms_view(cutoff=cutoff, **c), t.P, abi.FIND_SECOND_WINDOW)
+    for k in RESULTS:
+        assert np.array_equal(again[k], t.want[kid][0][k]), (what, k)
+
+
+def test_cohort_batch_equals_per_kid_batches(engine, three):
+    t = three
+    for attempt in range(2):  # the second call reuses the merged table
+        got = engine.phase_cohort(t.groups, t.dv_all, t.P, want_lists=False)
+        _equals_per_kid(engine, t, got)
+    assert sum(int((t.want[k][0]["status"] == abi.ST_OK).sum()) for k in t.kids) >= 3
+    # a plain uz_phase afterwards is unaffected by the cohort state
+    _plain_again(engine, t, "after a cohort batch")
+
+
+def bad_covers(groups, other_fam):
+    """four batches over three groups (fam, reads, first, count, cutoff) that a cohort call must refuse: the middle group moved or resized so
+    that a DNM is in no group or in two, the last group reaching past the batch, the middle group's family on another sites table"""
+    A, B, C = groups
+    assert B[3] >= 2
+    return {
+        "gap": [A, (B[0], B[1], B[2] + 1, B[3] - 1, B[4]), C],
+        "overlap": [A, (B[0], B[1], B[2] - 1, B[3] + 1, B[4]), C],
+        "past n": [A, B, (C[0], C[1], C[2], C[3] + 1, C[4])],
+        "two sites tables": [A, (other_fam, B[1], B[2], B[3], B[4]), C],
+    }
+
+
+def test_refusals_leave_the_context_usable(engine, three):
+    """uz_phase_cohort refuses groups that do not cover the batch exactly once, reach past it or mix sites tables (UZ_E_ARG, a message), and the
+    context is as usable afterwards as one that never saw the call (tests/test_find_cohort_gpu.py holds uz_find_cohort to the same)"""
+    t = three
+    ped = t.ds.pedigrees[t.kids[1]]
+    sid2 = engine.upload_sites(t.sites)
+    other = engine.add_family(sid2, *t.sites.family_columns(t.kids[1], ped["dad"], ped["mom"]))
+    engine.set_params(t.P)
+    out = [np.zeros(4 * t.n, np.int32) for _ in range(4)]
+    for what, g in bad_covers(t.groups, other).items():
+        rc = engine.L.uz_phase_cohort(engine.h, engine._groups(g), len(g), t.dv_all.ref(), abi.FIND_SECOND_WINDOW, *[x.ctypes.data for x in out])
+        assert rc == E_ARG, what
+        assert engine.L.uz_last_error(engine.h), what
+        _plain_again(engine, t, what)
+    _equals_per_kid(engine, t, engine.phase_cohort(t.groups, t.dv_all, t.P, want_lists=False))
+    engine.free_sites(sid2)
+
+
+def test_one_family_serving_two_groups(engine, three):
+    """kid 0's DNMs as two groups over the same family and reads table, next to the other kids' groups, give what the unsplit batch gives, DNM for
+    DNM -- with every family's classes stale when the split batch arrives (another min_depth), so that the one scan launch meets kid 0's family
+    in two groups and classifies it once"""
+    t = three
+    P2 = abi.make_params(min_depth=9)
+    fam, rh, first, count, cutoff = t.groups[0]
+    assert first == 0 and count >= 2
+    half = count // 2
+    split = [(fam, rh, 0, half, cutoff), (fam, rh, half, count - half, cutoff)] + t.groups[1:]
+    got = engine.phase_cohort(split, t.dv_all, P2)
+    want = engine.phase_cohort(t.groups, t.dv_all, P2)
+    for k in RESULTS:
+        assert np.array_equal(got[k], want[k]), k
+    assert int((want["status"] == abi.ST_OK).sum()) >= 3
+    for d in range(t.n):
+        for j in range(4):
+            assert np.array_equal(got["lists"][d][j], want["lists"][d][j]), (d, j)
 
 
 def test_cohort_of_two_hundred_kids_equals_the_oracle_kid_by_kid(engine):

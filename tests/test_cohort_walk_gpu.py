@@ -117,7 +117,11 @@ def test_interleaved_name_ranges_are_refused(engine):
         engine.free_reads(rid)
 
 
-def test_joined_cohort_phase_equals_the_cohort_of_tables_and_the_oracle(engine, tmp_path):
+@pytest.fixture(scope="module")
+def four(engine, tmp_path_factory):
+    """four kids from files: each kid's table staged from its own BAM, the joined table staged from the four files as one, the groups over
+    both, and the batch's results by uz_phase_cohort on the per-file tables and by the CPU oracle; made once"""
+    from types import SimpleNamespace
     from filesio import dump_dataset, write_bai
     from helpers import tables
     from oracle_backend import OracleBackend
@@ -126,7 +130,7 @@ def test_joined_cohort_phase_equals_the_cohort_of_tables_and_the_oracle(engine, 
     from unfazed_amd.staging import fetch_points
     kids = ["kidA", "kidB", "kidC", "kidD"]
     ds = make_small(SmallConfig(seed=911, n_dnms=20, kids=kids, cluster_prob=0.6, odd_read_prob=0.05))
-    paths = dump_dataset(ds, str(tmp_path))
+    paths = dump_dataset(ds, str(tmp_path_factory.mktemp("four")))
     for b in paths["bams"].values():
         write_bai(b)
     sites, reads = tables(ds)
@@ -136,7 +140,7 @@ def test_joined_cohort_phase_equals_the_cohort_of_tables_and_the_oracle(engine, 
     sid, osid = engine.upload_sites(sites), orc.upload_sites(sites)
     many = io_native.BamSource.open_many([paths["bams"][k] for k in kids], threads=2)
     groups, ogroups, cols, first, found_all = [], [], dict(contig=[], rcontig=[], start=[], end=[], vartype=[], refs=[], alts=[]), 0, []
-    per_f, per_rid, per_names = [], [], []
+    per_f, per_rid, per_names, per_cols = [], [], [], []
     for g, kid in enumerate(kids):
         ped = ds.pedigrees[kid]
         fam_cols = sites.family_columns(kid, ped["dad"], ped["mom"])
@@ -157,7 +161,7 @@ def test_joined_cohort_phase_equals_the_cohort_of_tables_and_the_oracle(engine, 
         f = fetch_points(c["rcontig"], c["start"], [0] * len(dn), sites.pos, ho, hi, P, allele_len=[max(len(r), len(a)) for r, a in zip(refs, alts)])
         f = (np.ascontiguousarray(f[0], np.int32), np.ascontiguousarray(f[1], np.int32), np.ascontiguousarray(f[2], np.int32), np.ascontiguousarray(f[3], np.uint16))
         rid, _, names, _ = _table(engine, src, f)
-        per_f.append(f); per_rid.append(rid); per_names.append(names)
+        per_f.append(f); per_rid.append(rid); per_names.append(names); per_cols.append(c)
         groups.append((engine.add_family(sid, *fam_cols), rid, first, len(dn), cutoff))
         ogroups.append((ofam, orc.upload_reads(rt), first, len(dn), cutoff))
         found_all += found
@@ -165,35 +169,74 @@ def test_joined_cohort_phase_equals_the_cohort_of_tables_and_the_oracle(engine, 
             cols[k] += c[k]
         first += len(dn)
     dv = abi.dnms_view(cutoff=0.0, **cols)
+    kid0 = engine.phase_raw(groups[0][0], per_rid[0], abi.dnms_view(cutoff=groups[0][4], **per_cols[0]), P, abi.FIND_SECOND_WINDOW)  # (before any cohort call)
     want = engine.phase_cohort(groups, dv, P)
     oracle = orc.phase_cohort(ogroups, dv, P, found_all)
     case = manycases.Case([paths["bams"][k] for k in kids], per_f, {}, None)
     jrid, _, jnames, jkb = _table(engine, many, manycases.joined_fetches(many, case))
     try:
-        rec_first, name_first = engine.reads_files(jrid, many.ref_base)
-        assert np.array_equal(name_first, manycases.ends([len(x) for x in per_names])) and jnames == [x for p in per_names for x in p]
-        got = engine.phase_cohort_joined(jrid, groups, many.ref_base[:-1], dv, P)
-        for k in ("status", "counts", "origin", "evidence"):
-            assert np.array_equal(got[k], want[k]), k
-            assert np.array_equal(got[k], oracle[k]), k
-        assert int((got["status"] == abi.ST_OK).sum()) >= 3
-        for g, (fam, rid, f0, cnt, cutoff) in enumerate(groups):
-            rt = reads["mem://%s.bam" % kids[g]]
-            for d in range(f0, f0 + cnt):
-                for j in (0, 1):  # read names: the table's ids = the file's + the file's first name id
-                    assert np.array_equal(got["lists"][d][j], want["lists"][d][j].astype(np.int64) + name_first[g]), (g, d, j)
-                    assert sorted(jnames[q] for q in got["lists"][d][j]) == sorted(rt.qnames[q] for q in oracle["lists"][d][j]), (g, d, j)
-                for j in (2, 3):  # site positions
-                    assert np.array_equal(got["lists"][d][j], want["lists"][d][j]) and np.array_equal(got["lists"][d][j], oracle["lists"][d][j]), (g, d, j)
-        # a DNM whose file-local contig is not one of its group's file is on no contig of the table, as in uz_phase_cohort
-        bad = dict(cols)
-        bad["rcontig"] = [len(many.contigs) // len(kids)] + cols["rcontig"][1:]
-        dvb = abi.dnms_view(cutoff=0.0, **bad)
-        a, b = engine.phase_cohort_joined(jrid, groups, many.ref_base[:-1], dvb, P, want_lists=False), engine.phase_cohort(groups, dvb, P, want_lists=False)
-        for k in ("status", "counts", "origin", "evidence"):
-            assert np.array_equal(a[k], b[k]), k
+        yield SimpleNamespace(kids=kids, ds=ds, sites=sites, reads=reads, P=P, many=many, groups=groups, cols=cols, per_cols=per_cols, per_rid=per_rid,
+                              per_names=per_names, dv=dv, kid0=kid0, want=want, oracle=oracle, jrid=jrid, jnames=jnames)
     finally:
         engine.free_reads(jrid)
         for r in per_rid:
             engine.free_reads(r)
         engine.free_sites(sid)
+
+
+def test_joined_cohort_phase_equals_the_cohort_of_tables_and_the_oracle(engine, four):
+    t = four
+    kids, reads, P, many, groups, cols, dv = t.kids, t.reads, t.P, t.many, t.groups, t.cols, t.dv
+    per_names, want, oracle, jrid, jnames = t.per_names, t.want, t.oracle, t.jrid, t.jnames
+    engine.set_params(P)
+    rec_first, name_first = engine.reads_files(jrid, many.ref_base)
+    assert np.array_equal(name_first, manycases.ends([len(x) for x in per_names])) and jnames == [x for p in per_names for x in p]
+    got = engine.phase_cohort_joined(jrid, groups, many.ref_base[:-1], dv, P)
+    for k in ("status", "counts", "origin", "evidence"):
+        assert np.array_equal(got[k], want[k]), k
+        assert np.array_equal(got[k], oracle[k]), k
+    assert int((got["status"] == abi.ST_OK).sum()) >= 3
+    for g, (fam, rid, f0, cnt, cutoff) in enumerate(groups):
+        rt = reads["mem://%s.bam" % kids[g]]
+        for d in range(f0, f0 + cnt):
+            for j in (0, 1):  # read names: the table's ids = the file's + the file's first name id
+                assert np.array_equal(got["lists"][d][j], want["lists"][d][j].astype(np.int64) + name_first[g]), (g, d, j)
+                assert sorted(jnames[q] for q in got["lists"][d][j]) == sorted(rt.qnames[q] for q in oracle["lists"][d][j]), (g, d, j)
+            for j in (2, 3):  # site positions
+                assert np.array_equal(got["lists"][d][j], want["lists"][d][j]) and np.array_equal(got["lists"][d][j], oracle["lists"][d][j]), (g, d, j)
+    # a DNM whose file-local contig is not one of its group's file is on no contig of the table, as in uz_phase_cohort
+    bad = dict(cols)
+    bad["rcontig"] = [len(many.contigs) // len(kids)] + cols["rcontig"][1:]
+    dvb = abi.dnms_view(cutoff=0.0, **bad)
+    a, b = engine.phase_cohort_joined(jrid, groups, many.ref_base[:-1], dvb, P, want_lists=False), engine.phase_cohort(groups, dvb, P, want_lists=False)
+    for k in ("status", "counts", "origin", "evidence"):
+        assert np.array_equal(a[k], b[k]), k
+
+
+def test_refusals_on_the_joined_table_leave_the_context_usable(engine, four):
+    """uz_phase_cohort_joined refuses what uz_phase_cohort refuses of a batch's groups (tests/test_cohort_gpu.py: a gap, an overlap, a group past
+    the batch, two sites tables): UZ_E_ARG and a message, a plain uz_phase of kid 0 afterwards as before any cohort call, and the good batch on
+    the joined table still what the per-file tables give"""
+    from test_cohort_gpu import E_ARG, bad_covers
+    t = four
+    ped = t.ds.pedigrees[t.kids[2]]
+    sid2 = engine.upload_sites(t.sites)
+    other = engine.add_family(sid2, *t.sites.family_columns(t.kids[2], ped["dad"], ped["mom"]))
+    engine.set_params(t.P)
+    n = t.dv.view.n
+    out = [np.zeros(4 * n, np.int32) for _ in range(4)]
+    base = np.ascontiguousarray(t.many.ref_base[:-1], np.int32)
+    dv0 = abi.dnms_view(cutoff=t.groups[0][4], **t.per_cols[0])
+    for what, g3 in bad_covers(t.groups[1:], other).items():  # (the last three kids' groups, so that "past n" is past the batch's end)
+        g = [t.groups[0]] + g3
+        rc = engine.L.uz_phase_cohort_joined(engine.h, int(t.jrid), engine._groups(g), len(g), base.ctypes.data, t.dv.ref(), abi.FIND_SECOND_WINDOW,
+                                             *[x.ctypes.data for x in out])
+        assert rc == E_ARG, what
+        assert engine.L.uz_last_error(engine.h), what
+        again = engine.phase_raw(t.groups[0][0], t.per_rid[0], dv0, t.P, abi.FIND_SECOND_WINDOW)
+        for k in ("status", "counts", "origin", "evidence"):
+            assert np.array_equal(again[k], t.kid0[k]), (what, k)
+    got = engine.phase_cohort_joined(t.jrid, t.groups, t.many.ref_base[:-1], t.dv, t.P, want_lists=False)
+    for k in ("status", "counts", "origin", "evidence"):
+        assert np.array_equal(got[k], t.want[k]), k
+    engine.free_sites(sid2)

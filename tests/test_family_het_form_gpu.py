@@ -120,7 +120,7 @@ def test_what_needs_every_sites_columns_is_refused(engine):
     assert engine.L.uz_find(engine.h, fid, dv.ref(), abi.FIND_WHOLE_REGION, co.ctypes.data, ho.ctypes.data) == E_STATE
     cnt, a, b, c = np.zeros(2 * n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
     assert engine.L.uz_phase_cnv(engine.h, fid, dv.ref(), None, cnt.ctypes.data, a.ctypes.data, b.ctypes.data, c.ctypes.data) == E_STATE
-    groups = engine._find_groups([(fid, 0, n)])
+    groups = engine._groups([(fid, 0, n)])
     assert engine.L.uz_phase_cnv_cohort(engine.h, groups, 1, dv.ref(), None, cnt.ctypes.data, a.ctypes.data, b.ctypes.data, c.ctypes.data) == E_STATE
     gt, cols = np.zeros(t.n_sites, np.uint8), np.zeros((9, t.n_sites), np.uint16)
     assert engine.L.uz_family_fetch(engine.h, fid, gt.ctypes.data, cols.ctypes.data) == E_STATE

@@ -142,7 +142,7 @@ def test_refusals_leave_the_context_usable(engine, second, want, P):
     sub = cc.view(rows[:5], abi.FIND_SECOND_WINDOW)
     plain = [np.array(x) for x in second.find(want["fams"][0], sub, P, abi.FIND_SECOND_WINDOW)]
     for what, g in bad.items():
-        rc = engine.L.uz_find_cohort(engine.h, engine._find_groups(g), len(g), dv.ref(), abi.FIND_SECOND_WINDOW, co.ctypes.data, ho.ctypes.data)
+        rc = engine.L.uz_find_cohort(engine.h, engine._groups(g), len(g), dv.ref(), abi.FIND_SECOND_WINDOW, co.ctypes.data, ho.ctypes.data)
         assert rc == E_ARG, what
         assert engine.L.uz_last_error(engine.h)
         # a plain find afterwards is what it is on a context that never saw a cohort call: no family-per-DNM state is left behind

@@ -1296,6 +1296,15 @@ void uz_reads_make_ready(uz_ctx *c, ReadsDev &r) {
     r.pending = false;
 }
 
+void uz_reads_ready_for_threshold(uz_ctx *c, ReadsDev &r, const char *what) {
+    uz_reads_make_ready(c, r);
+    if (r.qlow_valid && r.qlow_thr == c->P.min_gt_qual) return;
+    UZ_REQUIRE(r.qual8 != nullptr, UZ_E_STATE,
+               std::string(what) + " was packed for --min-gt-qual " + std::to_string(r.qlow_thr) + ", the parameters say " +
+                   std::to_string(c->P.min_gt_qual) + ": decode it again for this threshold");
+    uz_build_qlow(c, c->stream, r, c->P.min_gt_qual);
+}
+
 int uz_reads_upload_impl(uz_ctx *c, const uz_reads_view *v, ReadsDev &r) {
     // the ASCII form (uz_reads_view): the fixed-width columns are staged as they are, the CIGAR words and
     // the bases are re-laid in the packed geometry on the device, the qualities are kept for the plane
@@ -1954,7 +1963,6 @@ int uz_find(uz_ctx *c, int fam_id, const uz_dnms_view *d, int mode, int64_t *can
         FamilyDev &f = fam_of(c, fam_id);
         SitesDev &s = sites_of(c, f.sites_id);
         UZ_REQUIRE(d != nullptr && d->n >= 0, UZ_E_ARG, "bad DNM view");
-        c->cohort_on = false;
         c->phase_valid = false;
         const bool cnv = (mode & UZ_FIND_WHOLE_REGION) != 0;
         if (cnv) refuse_het_only(f, "a whole-region find");
@@ -2003,7 +2011,6 @@ static void phase_whole(uz_ctx *c, int fam_id, int reads_id, const uz_dnms_view 
     ReadsDev &r = reads_of(c, reads_id);
     UZ_REQUIRE(d != nullptr, UZ_E_ARG, "null DNM view");
     UZ_REQUIRE(!(find_mode & UZ_FIND_WHOLE_REGION), UZ_E_ARG, "the read stage runs on SNV / breakpoint windows");
-    c->cohort_on = false;
     c->phase_valid = false;
     c->phase_qbase.clear();
     static const bool trace = getenv("UZ_PHASE_HOST_TRACE") != nullptr; // development aid: where the HOST's time of a read-stage call goes (us)
@@ -2058,195 +2065,54 @@ int uz_phase_end(uz_ctx *c, int fam_id, int reads_id, const uz_dnms_view *d, int
     });
 }
 
-// The run of a cohort batch over ONE table whose contigs are "group x contig" -- the merged table of uz_phase_cohort, or a table built over the
-// groups' files at once (uz_phase_cohort_joined): reads contigs renumbered into that table (contig_base[g] + the file's own number, -1 outside the
-// nc_g[g] contigs of the group's file), family / cutoff / name base per DNM, then find and the read stage.
-static void cohort_run(uz_ctx *c, const uz_cohort_group *groups, int32_t n_groups, const uz_dnms_view *d, int find_mode, FamilyDev &f0, SitesDev &s, ReadsDev &R,
-                   const int64_t *contig_base, const int32_t *nc_g, const uint32_t *q_base, int32_t *status, int32_t *counts, int32_t *origin, int32_t *evidence) {
-    const int32_t n = d->n;
-    // ---- the batch: reads contigs renumbered into the merged table, family / cutoff / name base per DNM
-    std::vector<int32_t> rc((size_t)n), fam_h((size_t)n, 0);
-    std::vector<double> cut_h((size_t)n, 0.0);
-    c->phase_qbase.assign((size_t)n, 0);
-    for (int32_t k = 0; k < n; k++) rc[(size_t)k] = -1;
-    std::vector<uint8_t *> cls_h((size_t)n_groups);
-    for (int32_t g = 0; g < n_groups; g++) {
-        FamilyDev &f = fam_of(c, groups[g].fam_id);
-        if (!uz_site_scan_fresh(c, f, false)) uz_launch_site_scan(c, f, s, false);
-        cls_h[(size_t)g] = f.cls;
-        for (int32_t k = groups[g].dnm_first; k < groups[g].dnm_first + groups[g].dnm_count; k++) {
-            const int32_t t = d->rcontig[k];
-            rc[(size_t)k] = (t >= 0 && t < nc_g[g]) ? (int32_t)(contig_base[g] + t) : -1;
-            fam_h[(size_t)k] = g; cut_h[(size_t)k] = groups[g].cutoff; c->phase_qbase[(size_t)k] = q_base ? q_base[g] : 0u;
-        }
-    }
-    uz_dnms_view dv = *d;
-    dv.rcontig = rc.data();
-    find_target(c); c->phase_valid = false; // (the cohort's lists take the place of the older set, under no key)
-    uz_stage_dnms(c, &dv);
-    c->dn_fam.ensure((size_t)n + 1); c->dn_cutoff.ensure((size_t)n + 1); c->fam_cls.ensure((size_t)n_groups + 1);
-    if (n) {
-        UZ_HIP(hipMemcpyAsync(c->dn_fam.p, fam_h.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        UZ_HIP(hipMemcpyAsync(c->dn_cutoff.p, cut_h.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    }
-    UZ_HIP(hipMemcpyAsync(c->fam_cls.p, cls_h.data(), (size_t)n_groups * sizeof(uint8_t *), hipMemcpyHostToDevice, c->stream));
-    UZ_HIP(hipStreamSynchronize(c->stream)); // the staging vectors above are locals
-    c->cohort_on = true;
-    try {
-        uz_launch_find(c, f0, s, find_mode, false);
-        c->find_fam = groups[0].fam_id;
-        uz_launch_phase(c, f0, s, R, status, counts, origin, evidence);
-    } catch (...) { c->cohort_on = false; throw; }
-    c->cohort_on = false;
-}
+// ---------------------------------------------------------------- cohort batches: description (cohort_batch), staging (cohort_stage), run
+// cohort mode (a family per DNM: k_sites.hip uz_launch_find; a cutoff per DNM: k_reads.hip uz_launch_phase) for the launches of one scope.
+// The only writer of cohort_on: outside such a scope it is false, whatever a launch threw.
+struct CohortMode {
+    uz_ctx *c;
+    explicit CohortMode(uz_ctx *c_) : c(c_) { c->cohort_on = true; }
+    ~CohortMode() { c->cohort_on = false; }
+};
+// search_dist = 0 for the find of an allele-balance stage: run_cnv_phasing calls find(..., search_dist=0, whole_region=True), sv_phaser.py:375-389
+struct ZeroSearchDist {
+    uz_ctx *c;
+    const int32_t sd;
+    explicit ZeroSearchDist(uz_ctx *c_) : c(c_), sd(c_->P.search_dist) { c->P.search_dist = 0; }
+    ~ZeroSearchDist() { c->P.search_dist = sd; }
+};
 
-int uz_phase_cohort(uz_ctx *c, const uz_cohort_group *groups, int32_t n_groups, const uz_dnms_view *d, int find_mode, int32_t *status,
-                    int32_t *counts, int32_t *origin, int32_t *evidence) {
-    return guarded(c, [&] {
-        UZ_REQUIRE(groups && n_groups > 0 && d, UZ_E_ARG, "bad cohort batch");
-        UZ_REQUIRE(!(find_mode & UZ_FIND_WHOLE_REGION), UZ_E_ARG, "the read stage runs on SNV / breakpoint windows");
-        const int32_t n = d->n;
-        FamilyDev &f0 = fam_of(c, groups[0].fam_id);
-        SitesDev &s = sites_of(c, f0.sites_id);
-        // ---- the kids' tables end to end as one table
-        std::vector<int> ids;
-        int64_t tot_n = 0, tot_c = 0, tot_u = 0, tot_s = 0, tot_p = 0, tot_contigs = 0;
-        uint64_t tot_q = 0;
-        for (int32_t g = 0; g < n_groups; g++) {
-            UZ_REQUIRE(groups[g].dnm_first >= 0 && groups[g].dnm_count >= 0 && groups[g].dnm_first + groups[g].dnm_count <= n, UZ_E_ARG,
-                       "cohort group outside the DNM batch");
-            UZ_REQUIRE(fam_of(c, groups[g].fam_id).sites_id == f0.sites_id, UZ_E_ARG, "the families of a cohort batch must share a sites table");
-            ReadsDev &r = reads_of(c, groups[g].reads_id);
-            UZ_REQUIRE(groups[g].reads_id != c->cohort_reads, UZ_E_ARG, "the merged cohort table cannot be a member of a cohort");
-            uz_reads_make_ready(c, r);
-            if (!r.qlow_valid || r.qlow_thr != c->P.min_gt_qual) {
-                UZ_REQUIRE(r.qual8 != nullptr, UZ_E_STATE, "a reads table of the cohort was packed for another --min-gt-qual");
-                uz_build_qlow(c, c->stream, r, c->P.min_gt_qual);
-            }
-            ids.push_back(groups[g].reads_id);
-            tot_n += r.n; tot_c += r.n_cigar_total; tot_u += r.n_row_units; tot_s += r.n_seq_units; tot_p += r.n_plane_units;
-            tot_contigs += r.n_contigs; tot_q += r.n_qnames;
-        }
-        UZ_REQUIRE(tot_n < (int64_t)0x7FFFFFF0 && tot_c < ((int64_t)1 << 32) && tot_u < ((int64_t)1 << 32) && tot_q < ((uint64_t)1 << 32), UZ_E_RANGE,
-                   "the cohort's alignment records exceed one table's index ranges");
-        std::vector<int64_t> rec_base((size_t)n_groups), contig_base((size_t)n_groups);
-        std::vector<uint32_t> q_base((size_t)n_groups);
-        {
-            int64_t rb = 0, cb = 0;
-            uint32_t qb = 0;
-            for (int32_t g = 0; g < n_groups; g++) {
-                const ReadsDev &r = reads_of(c, groups[g].reads_id);
-                rec_base[(size_t)g] = rb; contig_base[(size_t)g] = cb; q_base[(size_t)g] = qb;
-                rb += r.n; cb += r.n_contigs; qb += r.n_qnames;
-            }
-        }
-        if (c->cohort_reads < 0 || !c->reads[(size_t)c->cohort_reads].live || c->cohort_ids != ids) {
-            if (c->cohort_reads >= 0 && c->reads[(size_t)c->cohort_reads].live) {
-                UZ_HIP(hipStreamSynchronize(c->stream));
-                free_reads(c, c->reads[(size_t)c->cohort_reads]);
-            }
-            ReadsDev m;
-            m.live = true;
-            m.n = tot_n; m.n_contigs = (int32_t)tot_contigs; m.n_qnames = (uint32_t)tot_q; m.n_cigar_total = tot_c; m.n_row_units = tot_u;
-            m.n_seq_units = tot_s; m.n_plane_units = tot_p;
-            uint32_t *cigar = nullptr; uint8_t *seq4 = nullptr, *qlow = nullptr;
-            for (int pass = 0; pass < 2; pass++) {
-                Carver cv(pass ? m.block.p : nullptr);
-                carve_common(cv, m);
-                cigar = cv.take<uint32_t>((size_t)tot_c);
-                seq4 = cv.take<uint8_t>((size_t)tot_s * UZ_SEQ4_UNIT_BYTES);
-                qlow = cv.take<uint8_t>((size_t)tot_p * UZ_QLOW_UNIT_BYTES);
-                if (!pass) m.block = uz_block_get(c, cv.off + 256);
-            }
-            m.cigar = cigar; m.seq4 = seq4; m.qlow = qlow;
-            m.qlow_thr = c->P.min_gt_qual; m.qlow_valid = true;
-            try {
-                std::vector<int64_t> co((size_t)tot_contigs + 1, 0);
-                std::vector<int32_t> ms((size_t)tot_contigs + 1, 0);
-                int64_t cg = 0, un = 0, sn = 0;
-                for (int32_t g = 0; g < n_groups; g++) {
-                    const ReadsDev &r = reads_of(c, groups[g].reads_id);
-                    std::vector<int64_t> rco((size_t)r.n_contigs + 1);
-                    std::vector<int32_t> rms((size_t)r.n_contigs + 1);
-                    UZ_HIP(hipMemcpyAsync(rco.data(), r.contig_off, rco.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-                    if (r.n_contigs) UZ_HIP(hipMemcpyAsync(rms.data(), r.max_span, (size_t)r.n_contigs * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-                    UZ_HIP(hipStreamSynchronize(c->stream));
-                    for (int32_t k = 0; k < r.n_contigs; k++) {
-                        co[(size_t)contig_base[(size_t)g] + k] = rec_base[(size_t)g] + rco[(size_t)k];
-                        ms[(size_t)contig_base[(size_t)g] + k] = rms[(size_t)k];
-                    }
-                    uz_concat_table(c, c->stream, m, r, rec_base[(size_t)g], cg, un, sn, q_base[(size_t)g]);
-                    cg += r.n_cigar_total; un += r.n_plane_units; sn += r.n_seq_units;
-                }
-                co[(size_t)tot_contigs] = tot_n;
-                UZ_HIP(hipMemcpyAsync(m.contig_off, co.data(), co.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-                UZ_HIP(hipMemcpyAsync(m.max_span, ms.data(), ms.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-                uz_finish_table(c, c->stream, m);
-                UZ_HIP(hipStreamSynchronize(c->stream)); // co / ms are stack-local
-            } catch (...) { uz_block_put(c, m.block); throw; }
-            const int k = new_slot(c->reads);
-            c->reads[(size_t)k] = m;
-            c->cohort_reads = k;
-            c->cohort_ids = ids;
-        }
-        ReadsDev &R = c->reads[(size_t)c->cohort_reads];
-        std::vector<int32_t> nc_g((size_t)n_groups);
-        for (int32_t g = 0; g < n_groups; g++) nc_g[(size_t)g] = reads_of(c, groups[g].reads_id).n_contigs;
-        cohort_run(c, groups, n_groups, d, find_mode, f0, s, R, contig_base.data(), nc_g.data(), q_base.data(), status, counts, origin, evidence);
-    });
-}
+struct CohortBatch {
+    const uz_cohort_group *groups = nullptr; int32_t n_groups = 0; // as the caller gave them
+    const uz_dnms_view *d = nullptr; bool cnv = false;
+    FamilyDev *f0 = nullptr; SitesDev *s = nullptr; // the family of group 0, and the sites table all families share
+    std::vector<int32_t> fam;       // per DNM: its group
+    std::vector<uint8_t *> cls;     // per group: the class column of its family
+    std::vector<FamilyDev *> stale; // the families whose classes are not those of the parameters, each once (a family may serve several groups)
+};
 
-// uz_phase_cohort's run on a table that already IS the groups' tables end to end: one built over the groups' files presented as one
-// (uz_bam_walk_many -> uz_reads_from_walk).  group_ref_base [n_groups]: where each group's file starts among the table's contigs; the file's contigs
-// reach to the next larger base of any group, or to the table's last.  No concatenation, no copy per group; the vote lists carry the table's own
-// name ids (uz_reads_files says where each file's start).  groups[g].reads_id is not looked at.
-int uz_phase_cohort_joined(uz_ctx *c, int reads_id, const uz_cohort_group *groups, int32_t n_groups, const int32_t *group_ref_base, const uz_dnms_view *d,
-                           int find_mode, int32_t *status, int32_t *counts, int32_t *origin, int32_t *evidence) {
-    return guarded(c, [&] {
-        UZ_REQUIRE(groups && n_groups > 0 && d && group_ref_base, UZ_E_ARG, "bad cohort batch");
-        UZ_REQUIRE(!(find_mode & UZ_FIND_WHOLE_REGION), UZ_E_ARG, "the read stage runs on SNV / breakpoint windows");
-        const int32_t n = d->n;
-        FamilyDev &f0 = fam_of(c, groups[0].fam_id);
-        SitesDev &s = sites_of(c, f0.sites_id);
-        ReadsDev &R = reads_of(c, reads_id);
-        UZ_REQUIRE(reads_id != c->cohort_reads, UZ_E_ARG, "the merged cohort table of uz_phase_cohort is not a joined table");
-        std::vector<int32_t> bases(group_ref_base, group_ref_base + n_groups);
-        std::sort(bases.begin(), bases.end());
-        std::vector<int64_t> contig_base((size_t)n_groups);
-        std::vector<int32_t> nc_g((size_t)n_groups);
-        for (int32_t g = 0; g < n_groups; g++) {
-            UZ_REQUIRE(groups[g].dnm_first >= 0 && groups[g].dnm_count >= 0 && groups[g].dnm_first + groups[g].dnm_count <= n, UZ_E_ARG,
-                       "cohort group outside the DNM batch");
-            UZ_REQUIRE(fam_of(c, groups[g].fam_id).sites_id == f0.sites_id, UZ_E_ARG, "the families of a cohort batch must share a sites table");
-            UZ_REQUIRE(group_ref_base[g] >= 0 && group_ref_base[g] <= R.n_contigs, UZ_E_ARG, "a group's file starts outside the table's contigs");
-            const auto nx = std::upper_bound(bases.begin(), bases.end(), group_ref_base[g]);
-            contig_base[(size_t)g] = group_ref_base[g];
-            nc_g[(size_t)g] = (nx == bases.end() ? R.n_contigs : *nx) - group_ref_base[g];
-        }
-        uz_reads_make_ready(c, R);
-        if (!R.qlow_valid || R.qlow_thr != c->P.min_gt_qual) {
-            UZ_REQUIRE(R.qual8 != nullptr, UZ_E_STATE, "the joined reads table was packed for another --min-gt-qual");
-            uz_build_qlow(c, c->stream, R, c->P.min_gt_qual);
-        }
-        cohort_run(c, groups, n_groups, d, find_mode, f0, s, R, contig_base.data(), nc_g.data(), nullptr, status, counts, origin, evidence);
-    });
-}
-
-// What a cohort find and a cohort allele-balance stage share (unfazed_hip.h: uz_find_cohort): the groups checked, the stale families
-// classified in one launch, the batch staged with a family per DNM (dn_fam = the DNM's group, fam_cls = the class column of every group,
-// as uz_phase_cohort stages them).  Nothing of the context is touched before every check has passed.
-static void cohort_find_stage(uz_ctx *c, const uz_cohort_group *groups, int32_t n_groups, const uz_dnms_view *d, bool cnv, FamilyDev *&f0, SitesDev *&s0) {
+// The groups of a cohort call, checked: every group inside the batch, one sites table, the DNMs covered exactly once (empty groups are
+// allowed), no het-form family when the whole-region classes are needed (cnv).  Everything that can refuse a batch for its groups is here,
+// and nothing of the context is touched.
+static CohortBatch cohort_batch(uz_ctx *c, const uz_cohort_group *groups, int32_t n_groups, const uz_dnms_view *d, bool cnv) {
     UZ_REQUIRE(groups && n_groups > 0 && d && d->n >= 0, UZ_E_ARG, "bad cohort batch");
+    CohortBatch b;
+    b.groups = groups; b.n_groups = n_groups; b.d = d; b.cnv = cnv;
+    b.f0 = &fam_of(c, groups[0].fam_id);
+    b.s = &sites_of(c, b.f0->sites_id);
     const int32_t n = d->n;
-    f0 = &fam_of(c, groups[0].fam_id);
-    s0 = &sites_of(c, f0->sites_id);
+    b.fam.resize((size_t)n);
+    b.cls.resize((size_t)n_groups);
     std::vector<std::pair<int32_t, int32_t>> spans;
     for (int32_t g = 0; g < n_groups; g++) {
+        FamilyDev *f = &fam_of(c, groups[g].fam_id);
         UZ_REQUIRE(groups[g].dnm_first >= 0 && groups[g].dnm_count >= 0 && (int64_t)groups[g].dnm_first + groups[g].dnm_count <= n, UZ_E_ARG,
                    "cohort group outside the DNM batch");
-        UZ_REQUIRE(fam_of(c, groups[g].fam_id).sites_id == f0->sites_id, UZ_E_ARG, "the families of a cohort batch must share a sites table");
-        if (cnv) refuse_het_only(fam_of(c, groups[g].fam_id), "a whole-region find / the allele-balance stage");
+        UZ_REQUIRE(f->sites_id == b.f0->sites_id, UZ_E_ARG, "the families of a cohort batch must share a sites table");
+        if (cnv) refuse_het_only(*f, "a whole-region find / the allele-balance stage");
         if (groups[g].dnm_count) spans.push_back({groups[g].dnm_first, groups[g].dnm_count});
+        b.cls[(size_t)g] = f->cls;
+        for (int32_t k = 0; k < groups[g].dnm_count; k++) b.fam[(size_t)groups[g].dnm_first + (size_t)k] = g;
+        if (!uz_site_scan_fresh(c, *f, cnv) && std::find(b.stale.begin(), b.stale.end(), f) == b.stale.end()) b.stale.push_back(f);
     }
     std::sort(spans.begin(), spans.end());
     int64_t next = 0;
@@ -2255,34 +2121,176 @@ static void cohort_find_stage(uz_ctx *c, const uz_cohort_group *groups, int32_t 
         next += sp.second;
     }
     UZ_REQUIRE(next == n, UZ_E_ARG, "the groups of a cohort batch must cover its DNMs exactly once");
-    std::vector<FamilyDev *> stale; // (each family once: a family may serve several groups)
-    for (int32_t g = 0; g < n_groups; g++) {
-        FamilyDev *f = &fam_of(c, groups[g].fam_id);
-        if (!uz_site_scan_fresh(c, *f, cnv) && std::find(stale.begin(), stale.end(), f) == stale.end()) stale.push_back(f);
-    }
-    if (!stale.empty()) uz_launch_site_scan_many(c, stale.data(), (int)stale.size(), *s0, cnv);
-    std::vector<int32_t> fam_h((size_t)n, 0);
-    std::vector<uint8_t *> cls_h((size_t)n_groups);
-    for (int32_t g = 0; g < n_groups; g++) {
-        cls_h[(size_t)g] = fam_of(c, groups[g].fam_id).cls;
-        for (int32_t k = groups[g].dnm_first; k < groups[g].dnm_first + groups[g].dnm_count; k++) fam_h[(size_t)k] = g;
-    }
+    return b;
+}
+
+// A checked batch into the context: the stale families classified in ONE launch, the DNM columns `dv` (the batch's own, or a copy with the
+// reads contigs renumbered), dn_fam = the DNM's group, fam_cls = the class column of every group, dn_cutoff when the read stage follows.
+static void cohort_stage(uz_ctx *c, CohortBatch &b, const uz_dnms_view *dv, const double *cutoff_per_dnm /* may be null */) {
+    const size_t n = (size_t)dv->n, ng = (size_t)b.n_groups;
+    if (!b.stale.empty()) uz_launch_site_scan_many(c, b.stale.data(), (int)b.stale.size(), *b.s, b.cnv);
     find_target(c); c->phase_valid = false; // (the cohort's lists take the place of the oldest set, under no key)
-    uz_stage_dnms(c, d);
-    c->dn_fam.ensure((size_t)n + 1); c->fam_cls.ensure((size_t)n_groups + 1);
-    if (n) UZ_HIP(hipMemcpyAsync(c->dn_fam.p, fam_h.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    UZ_HIP(hipMemcpyAsync(c->fam_cls.p, cls_h.data(), (size_t)n_groups * sizeof(uint8_t *), hipMemcpyHostToDevice, c->stream));
-    UZ_HIP(hipStreamSynchronize(c->stream)); // the staging vectors above are locals
+    uz_stage_dnms(c, dv);
+    c->dn_fam.ensure(n + 1); c->fam_cls.ensure(ng + 1);
+    if (cutoff_per_dnm) c->dn_cutoff.ensure(n + 1);
+    if (n) UZ_HIP(hipMemcpyAsync(c->dn_fam.p, b.fam.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if (n && cutoff_per_dnm) UZ_HIP(hipMemcpyAsync(c->dn_cutoff.p, cutoff_per_dnm, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    UZ_HIP(hipMemcpyAsync(c->fam_cls.p, b.cls.data(), ng * sizeof(uint8_t *), hipMemcpyHostToDevice, c->stream));
+    UZ_HIP(hipStreamSynchronize(c->stream)); // the host sides of these copies are the callers' locals
+}
+
+// The table a read-stage cohort batch runs on, its contigs "group x contig": contig_base[g] + the number of a contig in group g's file, for
+// the nc[g] contigs of that file; q_base[g]: the first query-name id of group g (empty: the vote lists keep the table's own ids).
+struct CohortTable {
+    ReadsDev *R = nullptr;
+    std::vector<int64_t> contig_base;
+    std::vector<int32_t> nc;
+    std::vector<uint32_t> q_base;
+};
+
+// The read stage of a cohort batch over its table: reads contigs renumbered into the table (-1 outside the contigs of the group's file),
+// cutoff / name base per DNM, then find and the read stage.
+static void cohort_run(uz_ctx *c, CohortBatch &b, const CohortTable &t, int find_mode, int32_t *status, int32_t *counts, int32_t *origin, int32_t *evidence) {
+    const size_t n = (size_t)b.d->n;
+    std::vector<int32_t> rc(n);
+    std::vector<double> cut(n);
+    std::vector<uint32_t> qb(n);
+    for (size_t k = 0; k < n; k++) {
+        const size_t g = (size_t)b.fam[k];
+        const int32_t r = b.d->rcontig[k];
+        rc[k] = (r >= 0 && r < t.nc[g]) ? (int32_t)(t.contig_base[g] + r) : -1;
+        cut[k] = b.groups[g].cutoff;
+        qb[k] = t.q_base.empty() ? 0u : t.q_base[g];
+    }
+    uz_dnms_view dv = *b.d;
+    dv.rcontig = rc.data();
+    cohort_stage(c, b, &dv, cut.data());
+    c->phase_qbase = std::move(qb);
+    CohortMode on(c);
+    uz_launch_find(c, *b.f0, *b.s, find_mode, false);
+    c->find_fam = b.groups[0].fam_id;
+    uz_launch_phase(c, *b.f0, *b.s, *t.R, status, counts, origin, evidence);
+}
+
+// The members' tables end to end as ONE table: the merged table of the context when it was built from these members, else built here (the
+// one before it is freed).  Every member is held to the threshold of the parameters before anything is built.
+static CohortTable cohort_merged_table(uz_ctx *c, const uz_cohort_group *groups, int32_t n_groups) {
+    const size_t ng = (size_t)n_groups;
+    CohortTable t;
+    t.contig_base.resize(ng); t.nc.resize(ng); t.q_base.resize(ng);
+    std::vector<int64_t> rec_base(ng);
+    std::vector<int> ids;
+    int64_t tot_n = 0, tot_c = 0, tot_u = 0, tot_s = 0, tot_p = 0, tot_contigs = 0;
+    uint64_t tot_q = 0;
+    for (size_t g = 0; g < ng; g++) {
+        ReadsDev &r = reads_of(c, groups[g].reads_id);
+        UZ_REQUIRE(groups[g].reads_id != c->cohort_reads, UZ_E_ARG, "the merged cohort table cannot be a member of a cohort");
+        uz_reads_ready_for_threshold(c, r, "a reads table of the cohort");
+        ids.push_back(groups[g].reads_id);
+        rec_base[g] = tot_n; t.contig_base[g] = tot_contigs; t.q_base[g] = (uint32_t)tot_q; t.nc[g] = r.n_contigs;
+        tot_n += r.n; tot_c += r.n_cigar_total; tot_u += r.n_row_units; tot_s += r.n_seq_units; tot_p += r.n_plane_units;
+        tot_contigs += r.n_contigs; tot_q += r.n_qnames;
+    }
+    UZ_REQUIRE(tot_n < (int64_t)0x7FFFFFF0 && tot_c < ((int64_t)1 << 32) && tot_u < ((int64_t)1 << 32) && tot_q < ((uint64_t)1 << 32), UZ_E_RANGE,
+               "the cohort's alignment records exceed one table's index ranges");
+    if (c->cohort_reads < 0 || !c->reads[(size_t)c->cohort_reads].live || c->cohort_ids != ids) {
+        if (c->cohort_reads >= 0 && c->reads[(size_t)c->cohort_reads].live) {
+            UZ_HIP(hipStreamSynchronize(c->stream));
+            free_reads(c, c->reads[(size_t)c->cohort_reads]);
+        }
+        ReadsDev m;
+        m.live = true;
+        m.n = tot_n; m.n_contigs = (int32_t)tot_contigs; m.n_qnames = (uint32_t)tot_q; m.n_cigar_total = tot_c; m.n_row_units = tot_u;
+        m.n_seq_units = tot_s; m.n_plane_units = tot_p;
+        for (int pass = 0; pass < 2; pass++) {
+            Carver cv(pass ? m.block.p : nullptr);
+            carve_common(cv, m);
+            m.cigar = cv.take<uint32_t>((size_t)tot_c);
+            m.seq4 = cv.take<uint8_t>((size_t)tot_s * UZ_SEQ4_UNIT_BYTES);
+            m.qlow = cv.take<uint8_t>((size_t)tot_p * UZ_QLOW_UNIT_BYTES);
+            if (!pass) m.block = uz_block_get(c, cv.off + 256);
+        }
+        m.qlow_thr = c->P.min_gt_qual; m.qlow_valid = true;
+        try {
+            std::vector<int64_t> co((size_t)tot_contigs + 1, 0);
+            std::vector<int32_t> ms((size_t)tot_contigs + 1, 0);
+            int64_t cg = 0, un = 0, sn = 0;
+            for (size_t g = 0; g < ng; g++) {
+                const ReadsDev &r = reads_of(c, groups[g].reads_id);
+                std::vector<int64_t> rco((size_t)r.n_contigs + 1);
+                std::vector<int32_t> rms((size_t)r.n_contigs + 1);
+                UZ_HIP(hipMemcpyAsync(rco.data(), r.contig_off, rco.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+                if (r.n_contigs) UZ_HIP(hipMemcpyAsync(rms.data(), r.max_span, (size_t)r.n_contigs * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+                UZ_HIP(hipStreamSynchronize(c->stream));
+                for (int32_t k = 0; k < r.n_contigs; k++) {
+                    co[(size_t)t.contig_base[g] + k] = rec_base[g] + rco[(size_t)k];
+                    ms[(size_t)t.contig_base[g] + k] = rms[(size_t)k];
+                }
+                uz_concat_table(c, c->stream, m, r, rec_base[g], cg, un, sn, t.q_base[g]);
+                cg += r.n_cigar_total; un += r.n_plane_units; sn += r.n_seq_units;
+            }
+            co[(size_t)tot_contigs] = tot_n;
+            UZ_HIP(hipMemcpyAsync(m.contig_off, co.data(), co.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+            UZ_HIP(hipMemcpyAsync(m.max_span, ms.data(), ms.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+            uz_finish_table(c, c->stream, m);
+            UZ_HIP(hipStreamSynchronize(c->stream)); // co / ms are stack-local
+        } catch (...) { uz_block_put(c, m.block); throw; }
+        const int k = new_slot(c->reads);
+        c->reads[(size_t)k] = m;
+        c->cohort_reads = k;
+        c->cohort_ids = ids;
+    }
+    t.R = &c->reads[(size_t)c->cohort_reads];
+    return t;
+}
+
+int uz_phase_cohort(uz_ctx *c, const uz_cohort_group *groups, int32_t n_groups, const uz_dnms_view *d, int find_mode, int32_t *status,
+                    int32_t *counts, int32_t *origin, int32_t *evidence) {
+    return guarded(c, [&] {
+        UZ_REQUIRE(!(find_mode & UZ_FIND_WHOLE_REGION), UZ_E_ARG, "the read stage runs on SNV / breakpoint windows");
+        CohortBatch b = cohort_batch(c, groups, n_groups, d, false);
+        const CohortTable t = cohort_merged_table(c, groups, n_groups);
+        cohort_run(c, b, t, find_mode, status, counts, origin, evidence);
+    });
+}
+
+// A table that already IS the groups' tables end to end: one built over the groups' files presented as one (uz_bam_walk_many ->
+// uz_reads_from_walk).  group_ref_base [n_groups]: where each group's file starts among the table's contigs; the file's contigs reach to the
+// next larger base of any group, or to the table's last.  No concatenation, no copy per group; the vote lists carry the table's own name ids
+// (uz_reads_files says where each file's start).  groups[g].reads_id is not looked at.
+static CohortTable cohort_joined_table(uz_ctx *c, int reads_id, const int32_t *group_ref_base, int32_t n_groups) {
+    UZ_REQUIRE(group_ref_base != nullptr, UZ_E_ARG, "bad cohort batch");
+    CohortTable t;
+    t.R = &reads_of(c, reads_id);
+    UZ_REQUIRE(reads_id != c->cohort_reads, UZ_E_ARG, "the merged cohort table of uz_phase_cohort is not a joined table");
+    std::vector<int32_t> bases(group_ref_base, group_ref_base + n_groups);
+    std::sort(bases.begin(), bases.end());
+    t.contig_base.resize((size_t)n_groups); t.nc.resize((size_t)n_groups);
+    for (int32_t g = 0; g < n_groups; g++) {
+        UZ_REQUIRE(group_ref_base[g] >= 0 && group_ref_base[g] <= t.R->n_contigs, UZ_E_ARG, "a group's file starts outside the table's contigs");
+        const auto nx = std::upper_bound(bases.begin(), bases.end(), group_ref_base[g]);
+        t.contig_base[(size_t)g] = group_ref_base[g];
+        t.nc[(size_t)g] = (nx == bases.end() ? t.R->n_contigs : *nx) - group_ref_base[g];
+    }
+    uz_reads_ready_for_threshold(c, *t.R, "the joined reads table");
+    return t;
+}
+
+int uz_phase_cohort_joined(uz_ctx *c, int reads_id, const uz_cohort_group *groups, int32_t n_groups, const int32_t *group_ref_base, const uz_dnms_view *d,
+                           int find_mode, int32_t *status, int32_t *counts, int32_t *origin, int32_t *evidence) {
+    return guarded(c, [&] {
+        UZ_REQUIRE(!(find_mode & UZ_FIND_WHOLE_REGION), UZ_E_ARG, "the read stage runs on SNV / breakpoint windows");
+        CohortBatch b = cohort_batch(c, groups, n_groups, d, false);
+        const CohortTable t = cohort_joined_table(c, reads_id, group_ref_base, n_groups);
+        cohort_run(c, b, t, find_mode, status, counts, origin, evidence);
+    });
 }
 
 int uz_find_cohort(uz_ctx *c, const uz_cohort_group *groups, int32_t n_groups, const uz_dnms_view *d, int mode, int64_t *cand_off, int64_t *het_off) {
     return guarded(c, [&] {
-        FamilyDev *f0 = nullptr;
-        SitesDev *s = nullptr;
-        cohort_find_stage(c, groups, n_groups, d, (mode & UZ_FIND_WHOLE_REGION) != 0, f0, s);
-        c->cohort_on = true;
-        try { uz_launch_find(c, *f0, *s, mode); } catch (...) { c->cohort_on = false; throw; }
-        c->cohort_on = false;
+        CohortBatch b = cohort_batch(c, groups, n_groups, d, (mode & UZ_FIND_WHOLE_REGION) != 0);
+        cohort_stage(c, b, d, nullptr);
+        { CohortMode on(c); uz_launch_find(c, *b.f0, *b.s, mode); }
         c->find_fam = groups[0].fam_id;
         if (cand_off) memcpy(cand_off, c->cand_off_h.data(), ((size_t)d->n + 1) * sizeof(int64_t));
         if (het_off) memcpy(het_off, c->het_off_h.data(), ((size_t)d->n + 1) * sizeof(int64_t));
@@ -2329,10 +2337,7 @@ int uz_phase_cnv(uz_ctx *c, int fam_id, const uz_dnms_view *d, const int32_t *rb
         find_target(c); c->phase_valid = false; c->cnv_valid = false;
         uz_stage_dnms(c, d);
         if (!uz_site_scan_fresh(c, f, true)) uz_launch_site_scan(c, f, s, true);
-        const int32_t sd = c->P.search_dist;
-        c->P.search_dist = 0; // run_cnv_phasing calls find(..., search_dist=0, whole_region=True), sv_phaser.py:375-389
-        try { uz_launch_find(c, f, s, UZ_FIND_WHOLE_REGION, false); } catch (...) { c->P.search_dist = sd; throw; }
-        c->P.search_dist = sd;
+        { ZeroSearchDist zero(c); uz_launch_find(c, f, s, UZ_FIND_WHOLE_REGION, false); }
         c->find_fam = fam_id;
         cnv_after_find(c, s, (size_t)d->n, rb_counts, cnv_counts, origin, evidence, etype);
     });
@@ -2341,18 +2346,12 @@ int uz_phase_cnv(uz_ctx *c, int fam_id, const uz_dnms_view *d, const int32_t *rb
 int uz_phase_cnv_cohort(uz_ctx *c, const uz_cohort_group *groups, int32_t n_groups, const uz_dnms_view *d, const int32_t *rb_counts, int32_t *cnv_counts,
                         int32_t *origin, int32_t *evidence, int32_t *etype) {
     return guarded(c, [&] {
-        FamilyDev *f0 = nullptr;
-        SitesDev *s = nullptr;
-        cohort_find_stage(c, groups, n_groups, d, true, f0, s);
+        CohortBatch b = cohort_batch(c, groups, n_groups, d, true);
+        cohort_stage(c, b, d, nullptr);
         c->cnv_valid = false;
-        const int32_t sd = c->P.search_dist;
-        c->P.search_dist = 0; // as uz_phase_cnv
-        c->cohort_on = true;
-        try { uz_launch_find(c, *f0, *s, UZ_FIND_WHOLE_REGION, false); } catch (...) { c->cohort_on = false; c->P.search_dist = sd; throw; }
-        c->cohort_on = false;
-        c->P.search_dist = sd;
+        { ZeroSearchDist zero(c); CohortMode on(c); uz_launch_find(c, *b.f0, *b.s, UZ_FIND_WHOLE_REGION, false); }
         c->find_fam = groups[0].fam_id;
-        cnv_after_find(c, *s, (size_t)d->n, rb_counts, cnv_counts, origin, evidence, etype);
+        cnv_after_find(c, *b.s, (size_t)d->n, rb_counts, cnv_counts, origin, evidence, etype);
     });
 }
 

@@ -1670,16 +1670,7 @@ void uz_launch_phase(uz_ctx *c, FamilyDev &f, const SitesDev &s, ReadsDev &r, in
     const auto host_t0 = std::chrono::steady_clock::now();
     auto host_us = [&] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - host_t0).count(); };
     double t_queued = 0, t_synced = 0, t_sized = 0;
-    // an asynchronous upload of this table must have landed before the first kernel reads it
-    uz_reads_make_ready(c, r);
-    // the quality plane holds ONE threshold: tables that kept their full qualities are re-thresholded, the others
-    // were decoded for a threshold and refuse another
-    if (!r.qlow_valid || r.qlow_thr != c->P.min_gt_qual) {
-        UZ_REQUIRE(r.qual8 != nullptr, UZ_E_STATE,
-                   "the reads table was packed for --min-gt-qual " + std::to_string(r.qlow_thr) + ", the parameters say " +
-                       std::to_string(c->P.min_gt_qual) + ": decode it again for this threshold");
-        uz_build_qlow(c, c->stream, r, c->P.min_gt_qual);
-    }
+    uz_reads_ready_for_threshold(c, r, "the reads table");
 
     PhaseArgs a;
     memset(&a, 0, sizeof(a));

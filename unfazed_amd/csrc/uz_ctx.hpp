@@ -469,6 +469,9 @@ void uz_block_put(uz_ctx *c, DevBlock b);
 void uz_kcopy(uz_ctx *c, void *dst, const void *src, size_t bytes);
 // waits for an asynchronous upload and builds its headers, on the compute stream (no-op for a table that is ready)
 void uz_reads_make_ready(uz_ctx *c, ReadsDev &r);
+// uz_reads_make_ready, and the table's quality plane brought to the threshold of the parameters.  The plane holds ONE threshold: a table that
+// kept its full qualities is re-thresholded, one decoded for a threshold refuses another (UZ_E_STATE; `what` names the table in the message)
+void uz_reads_ready_for_threshold(uz_ctx *c, ReadsDev &r, const char *what);
 // hflags[0], the consistency flag of the header builds whose commands have run: read and cleared; set -> UzError (UZ_E_RANGE, what the code says)
 void uz_check_upload_flag(uz_ctx *c);
 // stage launchers

@@ -660,36 +660,37 @@ class HipEngine:
         """transient: the index lists come back as views of page-locked buffers this engine re-uses (valid until the find after next) -- what a
         pipeline that reads them at once wants (pipeline.run_pipelined)"""
         self.set_params(params)
-        n = dv.view.n
+        return self._find_out(dv.view.n, fetch, transient,
+                              lambda co, ho: self._ck(self.L.uz_find(self.h, int(fam), dv.ref(), int(mode), co, ho), "uz_find"))
+
+    def _find_out(self, n, fetch, transient, run):
+        """The outputs of a find over n DNMs: run(cand_off, het_off) makes the call on the two offset arrays' addresses; the index lists behind
+        them are fetched when asked for."""
         co = np.zeros(n + 1, dtype=np.int64)
         ho = np.zeros(n + 1, dtype=np.int64)
-        self._ck(self.L.uz_find(self.h, int(fam), dv.ref(), int(mode), co.ctypes.data, ho.ctypes.data), "uz_find")
+        run(co.ctypes.data, ho.ctypes.data)
         if not fetch:
             return co, None, None, ho, None
         ci, cf, hi = self._fetch(int(co[n]), int(ho[n]), transient=transient)
         return co, ci, cf, ho, hi
 
     @staticmethod
-    def _find_groups(groups):
-        """[(fam, first, count)] -> uz_cohort_group array (reads_id and cutoff are not read by the find-side cohort calls)"""
+    def _groups(groups):
+        """[(fam, first, count)] or [(fam, reads_h, first, count, cutoff)] -> uz_cohort_group array.  The short form is the find side's, whose
+        calls read neither the reads handle nor the cutoff: -1 and 0.0."""
         arr = (abi.CohortGroup * max(1, len(groups)))()
-        for k, (fam, first, count) in enumerate(groups):
-            arr[k].fam_id, arr[k].reads_id, arr[k].dnm_first, arr[k].dnm_count, arr[k].cutoff = int(fam), -1, int(first), int(count), 0.0
+        for k, g in enumerate(groups):
+            fam, rh, first, count, cutoff = g if len(g) == 5 else (g[0], -1, g[1], g[2], 0.0)
+            arr[k].fam_id, arr[k].reads_id, arr[k].dnm_first, arr[k].dnm_count, arr[k].cutoff = int(fam), int(rh), int(first), int(count), float(cutoff)
         return arr
 
     def find_cohort(self, groups, dv: abi.Held, params: abi.Params, mode: int, fetch: bool = True):
         """Cohort form of find(): groups = [(fam, first, count)] covering the DNMs of `dv` exactly once (several kids, each with its own
         family columns), one launch sequence (uz_find_cohort).  Same result layout as find(), in DNM order."""
         self.set_params(params)
-        n = dv.view.n
-        co = np.zeros(n + 1, dtype=np.int64)
-        ho = np.zeros(n + 1, dtype=np.int64)
-        self._ck(self.L.uz_find_cohort(self.h, self._find_groups(groups), len(groups), dv.ref(), int(mode), co.ctypes.data, ho.ctypes.data),
-                 "uz_find_cohort")
-        if not fetch:
-            return co, None, None, ho, None
-        ci, cf, hi = self._fetch(int(co[n]), int(ho[n]))
-        return co, ci, cf, ho, hi
+        arr = self._groups(groups)
+        return self._find_out(dv.view.n, fetch, False,
+                              lambda co, ho: self._ck(self.L.uz_find_cohort(self.h, arr, len(groups), dv.ref(), int(mode), co, ho), "uz_find_cohort"))
 
     def _fetch(self, nc: int, nh: int, transient: bool = False):
         if transient:
@@ -718,19 +719,26 @@ class HipEngine:
         return ci[:nc], cf[:nc], hi[:nh]
 
     # ----------------------------------------------------------- read stage
-    def phase_raw(self, fam: int, reads_h: int, dv: abi.Held, params: abi.Params, find_mode: int):
-        self.set_params(params)
-        n = dv.view.n
+    def _phase_out(self, n, run):
+        """The results of a read stage over n DNMs: run(status, counts, origin, evidence) makes the call on the four arrays' addresses."""
         status = np.empty(max(1, n), dtype=np.int32)  # (the call writes all n entries of each, or raises)
         counts = np.empty(max(1, 4 * n), dtype=np.int32)
         origin = np.empty(max(1, n), dtype=np.int32)
         evidence = np.empty(max(1, n), dtype=np.int32)
-        self._ck(
-            self.L.uz_phase(self.h, int(fam), int(reads_h), dv.ref(), int(find_mode), status.ctypes.data,
-                            counts.ctypes.data, origin.ctypes.data, evidence.ctypes.data),
-            "uz_phase",
-        )
+        run(status.ctypes.data, counts.ctypes.data, origin.ctypes.data, evidence.ctypes.data)
         return dict(status=status[:n], counts=counts[: 4 * n].reshape(n, 4), origin=origin[:n], evidence=evidence[:n])
+
+    def _with_lists(self, r, n, want_lists):
+        """the vote lists of the read stage that made `r`, four per DNM -- or None -- as r["lists"]"""
+        r["lists"] = None
+        if want_lists:
+            vo, vv = self.votes(n)
+            r["lists"] = [tuple(vv[vo[4 * k + j]: vo[4 * k + j + 1]] for j in range(4)) for k in range(n)]
+        return r
+
+    def phase_raw(self, fam: int, reads_h: int, dv: abi.Held, params: abi.Params, find_mode: int):
+        self.set_params(params)
+        return self._phase_out(dv.view.n, lambda *out: self._ck(self.L.uz_phase(self.h, int(fam), int(reads_h), dv.ref(), int(find_mode), *out), "uz_phase"))
 
     def phase_begin(self, fam: int, reads_h: int, dv: abi.Held, params: abi.Params, find_mode: int):
         """first half of phase_raw (uz_phase_begin): queues the batch and returns; phase_end -- same arguments -- hands out the results.
@@ -739,14 +747,7 @@ class HipEngine:
         self._ck(self.L.uz_phase_begin(self.h, int(fam), int(reads_h), dv.ref(), int(find_mode)), "uz_phase_begin")
 
     def phase_end(self, fam: int, reads_h: int, dv: abi.Held, params: abi.Params, find_mode: int):
-        n = dv.view.n
-        status = np.empty(max(1, n), dtype=np.int32)
-        counts = np.empty(max(1, 4 * n), dtype=np.int32)
-        origin = np.empty(max(1, n), dtype=np.int32)
-        evidence = np.empty(max(1, n), dtype=np.int32)
-        self._ck(self.L.uz_phase_end(self.h, int(fam), int(reads_h), dv.ref(), int(find_mode), status.ctypes.data, counts.ctypes.data,
-                                     origin.ctypes.data, evidence.ctypes.data), "uz_phase_end")
-        return dict(status=status[:n], counts=counts[: 4 * n].reshape(n, 4), origin=origin[:n], evidence=evidence[:n])
+        return self._phase_out(dv.view.n, lambda *out: self._ck(self.L.uz_phase_end(self.h, int(fam), int(reads_h), dv.ref(), int(find_mode), *out), "uz_phase_end"))
 
     def phase_cohort(self, groups, dv: abi.Held, params: abi.Params, found_list=None, want_lists: bool = True,
                      find_mode: int = abi.FIND_SECOND_WINDOW, joined=None):
@@ -755,27 +756,16 @@ class HipEngine:
         phase(); the query-name ids of the lists are those of each group's own table."""
         self.set_params(params)
         n = dv.view.n
-        arr = (abi.CohortGroup * len(groups))()
-        for k, (fam, rh, first, count, cutoff) in enumerate(groups):
-            arr[k].fam_id, arr[k].reads_id, arr[k].dnm_first, arr[k].dnm_count, arr[k].cutoff = int(fam), int(rh), int(first), int(count), float(cutoff)
-        status = np.zeros(max(1, n), dtype=np.int32)
-        counts = np.zeros(max(1, 4 * n), dtype=np.int32)
-        origin = np.zeros(max(1, n), dtype=np.int32)
-        evidence = np.zeros(max(1, n), dtype=np.int32)
+        arr = self._groups(groups)
         if joined is None:
-            self._ck(self.L.uz_phase_cohort(self.h, arr, len(groups), dv.ref(), int(find_mode), status.ctypes.data, counts.ctypes.data,
-                                            origin.ctypes.data, evidence.ctypes.data), "uz_phase_cohort")
+            r = self._phase_out(n, lambda *out: self._ck(self.L.uz_phase_cohort(self.h, arr, len(groups), dv.ref(), int(find_mode), *out), "uz_phase_cohort"))
         else:  # ONE table over the groups' files (uz_phase_cohort_joined): the lists carry that table's name ids
             rid, base = joined
             base = np.ascontiguousarray(base, np.int32)
             assert base.size == len(groups)
-            self._ck(self.L.uz_phase_cohort_joined(self.h, int(rid), arr, len(groups), base.ctypes.data, dv.ref(), int(find_mode), status.ctypes.data,
-                                                   counts.ctypes.data, origin.ctypes.data, evidence.ctypes.data), "uz_phase_cohort_joined")
-        r = dict(status=status[:n], counts=counts[: 4 * n].reshape(n, 4), origin=origin[:n], evidence=evidence[:n], lists=None)
-        if want_lists:
-            vo, vv = self.votes(n)
-            r["lists"] = [tuple(vv[vo[4 * k + j]: vo[4 * k + j + 1]] for j in range(4)) for k in range(n)]
-        return r
+            r = self._phase_out(n, lambda *out: self._ck(self.L.uz_phase_cohort_joined(self.h, int(rid), arr, len(groups), base.ctypes.data, dv.ref(),
+                                                                                       int(find_mode), *out), "uz_phase_cohort_joined"))
+        return self._with_lists(r, n, want_lists)
 
     def phase_cohort_joined(self, rid: int, groups, group_ref_base, dv: abi.Held, params: abi.Params, found_list=None, want_lists: bool = True,
                             find_mode: int = abi.FIND_SECOND_WINDOW):
@@ -819,38 +809,26 @@ class HipEngine:
               find_mode: int = abi.FIND_SECOND_WINDOW):
         """Backend entry used by PhasingHost.run_read_phasing (found_list is ignored:
         the window lists are recomputed on the device for the batch)."""
-        r = self.phase_raw(fam, reads_h, dv, params, find_mode)
-        n = dv.view.n
-        if want_lists:
-            vo, vv = self.votes(n)
-            r["lists"] = [tuple(vv[vo[4 * k + j]: vo[4 * k + j + 1]] for j in range(4)) for k in range(n)]
-        else:
-            r["lists"] = None
-        return r
+        return self._with_lists(self.phase_raw(fam, reads_h, dv, params, find_mode), dv.view.n, want_lists)
 
     # ------------------------------------------------------------ CNV stage
     def phase_cnv(self, fam: int, dv: abi.Held, params: abi.Params, rb_counts=None, want_lists: bool = True):
         """K6: allele-balance phasing of the DEL / DUP of the batch + summarize_record's decision (merged with the
         read-backed counts when given).  -> dict(cnv_counts [n,2], origin, evidence, etype[, lists: (dad, mom) positions])"""
         self.set_params(params)
-        n = dv.view.n
-        cnt = np.zeros(max(1, 2 * n), np.int32)
-        origin = np.zeros(max(1, n), np.int32)
-        evidence = np.zeros(max(1, n), np.int32)
-        etype = np.zeros(max(1, n), np.int32)
-        rb = None
-        if rb_counts is not None:
-            rb = np.ascontiguousarray(rb_counts, np.int32).reshape(-1)
-            assert rb.size == 4 * n
-        self._ck(self.L.uz_phase_cnv(self.h, int(fam), dv.ref(), rb.ctypes.data if rb is not None else None, cnt.ctypes.data,
-                                     origin.ctypes.data, evidence.ctypes.data, etype.ctypes.data), "uz_phase_cnv")
-        return self._cnv_result(n, cnt, origin, evidence, etype, want_lists)
+        return self._cnv_out(dv.view.n, rb_counts, want_lists, lambda *io: self._ck(self.L.uz_phase_cnv(self.h, int(fam), dv.ref(), *io), "uz_phase_cnv"))
 
     def phase_cnv_cohort(self, groups, dv: abi.Held, params: abi.Params, rb_counts=None, want_lists: bool = True):
         """Cohort form of phase_cnv(): groups = [(fam, first, count)] covering the DNMs of `dv` exactly once, one whole-region find with a
         family per DNM and one K6 launch (uz_phase_cnv_cohort).  Same result layout as phase_cnv(), in DNM order."""
         self.set_params(params)
-        n = dv.view.n
+        arr = self._groups(groups)
+        return self._cnv_out(dv.view.n, rb_counts, want_lists,
+                             lambda *io: self._ck(self.L.uz_phase_cnv_cohort(self.h, arr, len(groups), dv.ref(), *io), "uz_phase_cnv_cohort"))
+
+    def _cnv_out(self, n, rb_counts, want_lists, run):
+        """The outputs of an allele-balance stage over n DNMs: run(rb_counts or None, cnv_counts, origin, evidence, etype) makes the call on the
+        arrays' addresses; the site lists behind the counts are fetched when asked for."""
         cnt = np.zeros(max(1, 2 * n), np.int32)
         origin = np.zeros(max(1, n), np.int32)
         evidence = np.zeros(max(1, n), np.int32)
@@ -859,11 +837,7 @@ class HipEngine:
         if rb_counts is not None:
             rb = np.ascontiguousarray(rb_counts, np.int32).reshape(-1)
             assert rb.size == 4 * n
-        self._ck(self.L.uz_phase_cnv_cohort(self.h, self._find_groups(groups), len(groups), dv.ref(), rb.ctypes.data if rb is not None else None,
-                                            cnt.ctypes.data, origin.ctypes.data, evidence.ctypes.data, etype.ctypes.data), "uz_phase_cnv_cohort")
-        return self._cnv_result(n, cnt, origin, evidence, etype, want_lists)
-
-    def _cnv_result(self, n, cnt, origin, evidence, etype, want_lists):
+        run(rb.ctypes.data if rb is not None else None, cnt.ctypes.data, origin.ctypes.data, evidence.ctypes.data, etype.ctypes.data)
         r = dict(cnv_counts=cnt[: 2 * n].reshape(n, 2), origin=origin[:n], evidence=evidence[:n], etype=etype[:n], lists=None)
         if want_lists:
             off = np.zeros(2 * n + 1, np.int64)

@@ -15,6 +15,7 @@ from __future__ import annotations
 import os
 import sys
 import types
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -207,6 +208,73 @@ class _Stats(dict):
         if key in self.ROUTE_KEYS:
             return 0
         raise KeyError(key)
+
+
+@dataclass
+class _ReadCall:
+    """What the read-side routes of ONE run_read_phasing call share: the call's DNMs and pedigrees, pass 1's `prep` (REF / ALT, reads contig, flags
+    per DNM) and the window lists `found`, the parameters, the three values behind a kid's insert cutoff, whether lists are wanted, the find
+    mode -- and `results`, which the routes fill: DNM index -> (device result, index in it, reads table)."""
+    host: "PhasingHost"
+    dnms: Sequence[dict]
+    pedigrees: dict
+    prep: Dict[int, dict]
+    found: Dict[int, dict]
+    params: abi.Params
+    readlen: int
+    stdevs: int
+    insert_size_max_sample: int
+    want_lists: bool
+    mode: int
+    results: Dict[int, tuple]
+
+    def kid(self, kid: str, bam: str):
+        """-> (family handle, insert cutoff) of one kid's group"""
+        ped = self.pedigrees[kid]
+        return self.host.family(kid, ped["dad"], ped["mom"]), self.host.kid_cutoff(kid, bam, self.readlen, self.stdevs, self.insert_size_max_sample)
+
+    def fetches(self, idxs, cutoff):
+        """the fetches the read stage will make for these DNMs (staging.fetch_points): the DNM position and every het site of its window
+        (read_collector.py:385, :167) -> (contig, lo, hi, extra, the batch holds SVs)"""
+        from .staging import fetch_points
+        dnms, prep, found = self.dnms, self.prep, self.found
+        het_off = np.zeros(len(idxs) + 1, np.int64)
+        for k, i in enumerate(idxs):
+            het_off[k + 1] = het_off[k] + len(found[i]["het_idx"])
+        het_idx = np.concatenate([found[i]["het_idx"] for i in idxs] + [np.zeros(0, np.int32)]).astype(np.int64)
+        vts = [vartype_code(dnms[i]["vartype"]) for i in idxs]
+        fc, flo, fhi, fex = fetch_points(
+            [prep[i]["tid"] for i in idxs], [int(dnms[i]["start"]) for i in idxs], [prep[i]["dflags"] for i in idxs],
+            self.host.sites.pos, het_off, het_idx, self.params, vartype=vts,
+            end=[int(dnms[i]["end"]) for i in idxs], cutoff=cutoff,
+            allele_len=[max(len(prep[i]["ref"]), len(prep[i]["alt"])) for i in idxs])
+        # (the read stage asks for the quality bits of "good" records only -- the DNM reads of a point variant and the records
+        # registered at het sites, both under goodread, read_collector.py:43-46; SV evidence is collected under
+        # goodread(read, True) from flags, CIGARs and mates alone, :476-596 -- so every batch travels with the qualities as
+        # counts + short lists and, of the rows, the 32-base units that hold a one-base fetch; the +-cutoff fetches around an
+        # SV's breakpoints stage no unit)
+        return fc, flo, fhi, fex, any(v != abi.VT_POINT for v in vts)
+
+    def dnms_view(self, idxs, cutoff):
+        dnms, prep, found = self.dnms, self.prep, self.found
+        prefix, contig_index = self.host.prefix, self.host.sites.contig_index
+        return abi.dnms_view(
+            contig=[contig_index.get(prefix + dnms[i]["chrom"].strip("chr"), -1) for i in idxs],
+            rcontig=[prep[i]["tid"] for i in idxs],
+            start=[int(dnms[i]["start"]) for i in idxs],
+            end=[int(dnms[i]["end"]) for i in idxs],
+            vartype=[vartype_code(dnms[i]["vartype"]) for i in idxs],
+            refs=[prep[i]["ref"] for i in idxs],
+            alts=[prep[i]["alt"] for i in idxs],
+            cutoff=cutoff,
+            dflags=[prep[i]["dflags"] for i in idxs],
+            mult=[found[i]["mult"] for i in idxs],
+        )
+
+    def stage_kwargs(self, has_sv: bool) -> dict:
+        """how a backend stages or uploads the records of a batch of this call: the threshold of the quality bits, every base or the listed
+        ones, no row units for a batch that holds SVs"""
+        return dict(min_base_qual=int(self.params.min_gt_qual), all_bases=bool(self.params.no_extended), wide_no_units=has_sv)
 
 
 class PhasingHost:
@@ -628,49 +696,9 @@ class PhasingHost:
             return rt.contig_index[alt], abi.DF_FETCH_FALLBACK
         return -1, 0
 
-    def _fetches_of(self, idxs, dnms, prep, found, params, cutoff):
-        """the fetches the read stage will make for these DNMs (staging.fetch_points): the DNM position and every het site of its window
-        (read_collector.py:385, :167) -> (contig, lo, hi, extra, the batch holds SVs)"""
-        from .staging import fetch_points
-        het_off = np.zeros(len(idxs) + 1, np.int64)
-        for k, i in enumerate(idxs):
-            het_off[k + 1] = het_off[k] + len(found[i]["het_idx"])
-        het_idx = np.concatenate([found[i]["het_idx"] for i in idxs] + [np.zeros(0, np.int32)]).astype(np.int64)
-        vts = [vartype_code(dnms[i]["vartype"]) for i in idxs]
-        fc, flo, fhi, fex = fetch_points(
-            [prep[i]["tid"] for i in idxs], [int(dnms[i]["start"]) for i in idxs], [prep[i]["dflags"] for i in idxs],
-            self.sites.pos, het_off, het_idx, params, vartype=vts,
-            end=[int(dnms[i]["end"]) for i in idxs], cutoff=cutoff,
-            allele_len=[max(len(prep[i]["ref"]), len(prep[i]["alt"])) for i in idxs])
-        # (the read stage asks for the quality bits of "good" records only -- the DNM reads of a point variant and the records
-        # registered at het sites, both under goodread, read_collector.py:43-46; SV evidence is collected under
-        # goodread(read, True) from flags, CIGARs and mates alone, :476-596 -- so every batch travels with the qualities as
-        # counts + short lists and, of the rows, the 32-base units that hold a one-base fetch; the +-cutoff fetches around an
-        # SV's breakpoints stage no unit)
-        return fc, flo, fhi, fex, any(v != abi.VT_POINT for v in vts)
-
-    def _dnms_view_of(self, idxs, dnms, prep, found, cutoff):
-        name_of = {}
-        for i in idxs:
-            nm = self.prefix + dnms[i]["chrom"].strip("chr")
-            name_of[i] = self.sites.contig_index.get(nm, -1)
-        return abi.dnms_view(
-            contig=[name_of[i] for i in idxs],
-            rcontig=[prep[i]["tid"] for i in idxs],
-            start=[int(dnms[i]["start"]) for i in idxs],
-            end=[int(dnms[i]["end"]) for i in idxs],
-            vartype=[vartype_code(dnms[i]["vartype"]) for i in idxs],
-            refs=[prep[i]["ref"] for i in idxs],
-            alts=[prep[i]["alt"] for i in idxs],
-            cutoff=cutoff,
-            dflags=[prep[i]["dflags"] for i in idxs],
-            mult=[found[i]["mult"] for i in idxs],
-        )
-
     CHUNK_DNMS = 3400  # DNMs per chunk of a large batch (bench.py's files -> results pass: 1500 / 2500 / 3400 / 4000 / 5000 = 23.7 / 24.6 / 25.9 / 24.3 / 22.5 k DNMs/s)
 
-    def _chunked_batch(self, batch, dnms, pedigrees, prep, found, params, readlen, stdevs, insert_size_max_sample, want_lists, mode, results,
-                       while_first_stages=None) -> bool:
+    def _chunked_batch(self, call: _ReadCall, batch, while_first_stages=None) -> bool:
         """A large batch of ONE kid from an indexed BAM through the staged pipeline (pipeline.run_pipelined: what bench.py measures) -- the
         reference runs one task per DNM on a thread pool, each opening the alignment file for its own window (snv_phaser.py:244-298); here chunk
         k + 1 is decoded on a worker thread (BAM blocks through the index straight into the link form, the blocks inflated on the device) while
@@ -686,8 +714,8 @@ class PhasingHost:
             return False
         from concurrent.futures import ThreadPoolExecutor
         src = stager(bam)
-        fam = self.family(kid, pedigrees[kid]["dad"], pedigrees[kid]["mom"])
-        cutoff = self.kid_cutoff(kid, bam, readlen, stdevs, insert_size_max_sample)
+        fam, cutoff = call.kid(kid, bam)
+        results = call.results
         # The first chunk half-size (nothing hides its decode), the rest in equal chunks of at most `chunk` DNMs (a short tail is spread over them,
         # not joined to the last one: the read stage of a larger last chunk is what nothing hides).  (Round 5 needed equal chunks for another reason --
         # a device slot that met a larger batch grew through hipFree + hipMalloc with every stream waiting; the slots are chosen best-fit and grow
@@ -714,12 +742,12 @@ class PhasingHost:
         # (0.08 s of waiting per call for 0.016 s of work, `UZ_HOST_TRACE=1`); the workers are left with native code that needs no lock.
         def fetches(k):
             with _Sec("fetches_of"):
-                return self._fetches_of(parts[k], dnms, prep, found, params, cutoff)
+                return call.fetches(parts[k], cutoff)
 
         def stage(k, f):
             fc, flo, fhi, fex, has_sv = f
             with _Sec("stage_reads"):
-                return self.backend.stage_reads(src, fc, flo, fhi, fex, int(params.min_gt_qual), all_bases=bool(params.no_extended), wide_no_units=has_sv, slot=k % n_slots)
+                return self.backend.stage_reads(src, fc, flo, fhi, fex, slot=k % n_slots, **call.stage_kwargs(has_sv))
 
         with ThreadPoolExecutor(ahead) as ex:
             futs = {}
@@ -738,7 +766,7 @@ class PhasingHost:
               with _Sec("done"):
                 part = parts[k]
                 lists = None
-                if want_lists:
+                if call.want_lists:
                     with _Sec("votes"):
                         vo, vv = self.backend.votes(len(part))
                     lists = _VoteLists(vo, vv)
@@ -761,10 +789,10 @@ class PhasingHost:
                     while_first_stages()  # host work that nothing below waits for, beside the native decode of the first chunks
                     # (on a thread of its own it gains nothing: the chunk pipeline is bound by the device's chain since the joins run there, and the
                     # interpreter lock only moves the waiting around -- measured, round 6)
-            chunks = [dict(a=cuts[k], b=cuts[k + 1], dnms=self._dnms_view_of(parts[k], dnms, prep, found, cutoff), records=records, sites=None)
+            chunks = [dict(a=cuts[k], b=cuts[k + 1], dnms=call.dnms_view(parts[k], cutoff), records=records, sites=None)
                       for k in range(len(parts))]
             trace = [] if os.environ.get("UZ_HOST_TRACE") else None  # development aid: ms per pipeline step (find, collect, queue, records + upload)
-            pipeline.run_pipelined(self.backend, params, mode, len(idxs), chunks, fid=fam, lag=lag, on_done=done, trace=trace, env_lag=False)
+            pipeline.run_pipelined(self.backend, call.params, call.mode, len(idxs), chunks, fid=fam, lag=lag, on_done=done, trace=trace, env_lag=False)
             if trace:
                 print("[uz] chunked batch, ms per step:", trace[0], file=sys.stderr)
         return True
@@ -801,76 +829,71 @@ class PhasingHost:
             n += len(item[1])
         return [r for r in runs if r]
 
-    def _joined_run(self, items, dnms, pedigrees, prep, found, params, readlen, stdevs, insert_size_max_sample, want_lists, mode, results) -> bool:
+    def _joined_run(self, call: _ReadCall, items) -> bool:
         """One run of the cohort route: ONE source over the kids' files, the kids' fetch lists end to end (contigs moved to each file's place among
         the source's), ONE staged batch and table, ONE uz_phase_cohort_joined; one name map serves all kids.  False: the device's walk does not take
         the batch (its blocks exceed UZ_WALK_MAX_BYTES) -- nothing was done."""
         src = self.reads_by_bam.stager_many([bam for (_, bam), _ in items])
         groups, order, parts, has_sv = [], [], [], False
         for g, ((kid, bam), idxs) in enumerate(items):
-            fam = self.family(kid, pedigrees[kid]["dad"], pedigrees[kid]["mom"])
-            cutoff = self.kid_cutoff(kid, bam, readlen, stdevs, insert_size_max_sample)
-            fc, flo, fhi, fex, sv_g = self._fetches_of(idxs, dnms, prep, found, params, cutoff)
+            fam, cutoff = call.kid(kid, bam)
+            fc, flo, fhi, fex, sv_g = call.fetches(idxs, cutoff)
             parts.append((np.asarray(fc, np.int64) + int(src.ref_base[g]), flo, fhi, fex))
             has_sv = has_sv or sv_g
             groups.append((fam, -1, len(order), len(idxs), cutoff))
             order.extend(idxs)
         fc, flo, fhi = (np.concatenate([p[j] for p in parts]).astype(np.int32) for j in range(3))
         fex = np.concatenate([p[3] for p in parts]).astype(np.uint16)
-        rh, table = self.backend.upload_reads_staged(src, fc, flo, fhi, fex, int(params.min_gt_qual), all_bases=bool(params.no_extended), wide_no_units=has_sv,
-                                                     walk_only=True)
+        rh, table = self.backend.upload_reads_staged(src, fc, flo, fhi, fex, walk_only=True, **call.stage_kwargs(has_sv))
         if rh is None:
             return False
         self.stats["bam_walks"] += 1
         self.stats["read_tables"] += 1
         try:
-            dv = self._dnms_view_of(order, dnms, prep, found, groups[0][4])
-            res = self.backend.phase_cohort_joined(rh, groups, src.ref_base[:-1], dv, params, [found[i] for i in order], want_lists, find_mode=mode)
+            dv = call.dnms_view(order, groups[0][4])
+            res = self.backend.phase_cohort_joined(rh, groups, src.ref_base[:-1], dv, call.params, [call.found[i] for i in order], call.want_lists,
+                                                   find_mode=call.mode)
             self.stats["phase_cohort_calls"] += 1
         finally:
             self.backend.free_reads(rh)
         for k, i in enumerate(order):
-            results[i] = (res, k, table)
+            call.results[i] = (res, k, table)
         return True
 
-    def _kid_run(self, items, dnms, pedigrees, prep, found, params, readlen, stdevs, insert_size_max_sample, want_lists, mode, results) -> None:
+    def _kid_run(self, call: _ReadCall, items) -> None:
         """The groups staged one by one -- its own family columns, alignment file and insert cutoff each -- and sent to the device as ONE batch:
         uz_phase for one group, uz_phase_cohort (which lays the tables end to end) for several."""
         groups, order_all, tables, handles = [], [], [], []
         for (kid, bam), idxs in items:
-            dad_id, mom_id = pedigrees[kid]["dad"], pedigrees[kid]["mom"]
-            fam = self.family(kid, dad_id, mom_id)
-            cutoff = self.kid_cutoff(kid, bam, readlen, stdevs, insert_size_max_sample)
+            fam, cutoff = call.kid(kid, bam)
             region_table = None
             if self._indexed(bam):
                 # decode only what the batch's fetches can return (+ mates) through the index: the read stage looks at
                 # nothing else (read_collector.py:385, :167, :400), so nothing else is inflated, staged or uploaded
-                fc, flo, fhi, fex, has_sv = self._fetches_of(idxs, dnms, prep, found, params, cutoff)
+                fc, flo, fhi, fex, has_sv = call.fetches(idxs, cutoff)
                 stager = getattr(self.reads_by_bam, "stager", None)
                 src = stager(bam) if (stager and hasattr(self.backend, "upload_reads_staged")) else None
                 if src is not None:
                     # BAM + BAI -> the link form in one pass (uz_bam_stage_*): no table in between
-                    rh, region_table = self.backend.upload_reads_staged(src, fc, flo, fhi, fex, int(params.min_gt_qual),
-                                                                        all_bases=bool(params.no_extended), wide_no_units=has_sv)
+                    rh, region_table = self.backend.upload_reads_staged(src, fc, flo, fhi, fex, **call.stage_kwargs(has_sv))
                     self.stats["bam_walks"] += 1
                 else:
                     region_table = self.reads_by_bam.regions(bam, fc, flo, fhi)
-                    rh = self.backend.upload_reads(region_table, min_base_qual=int(params.min_gt_qual), point_only=True,
-                                                   fetches=(fc, flo, fhi, fex), all_bases=bool(params.no_extended), wide_no_units=has_sv)
+                    rh = self.backend.upload_reads(region_table, point_only=True, fetches=(fc, flo, fhi, fex), **call.stage_kwargs(has_sv))
                 self.stats["read_tables"] += 1
                 handles.append(rh)
             else:
-                rh = self.reads(bam, params.min_gt_qual)
+                rh = self.reads(bam, call.params.min_gt_qual)
             groups.append((fam, rh, len(order_all), len(idxs), cutoff))
             tables.append(region_table if region_table is not None else self.reads_by_bam[bam])
             order_all.extend(idxs)
         if order_all:
-            dv = self._dnms_view_of(order_all, dnms, prep, found, groups[0][4])
-            fl = [found[i] for i in order_all]
+            dv = call.dnms_view(order_all, groups[0][4])
+            fl = [call.found[i] for i in order_all]
             if len(groups) == 1:
-                res = self.backend.phase(groups[0][0], groups[0][1], dv, params, fl, want_lists, find_mode=mode)
+                res = self.backend.phase(groups[0][0], groups[0][1], dv, call.params, fl, call.want_lists, find_mode=call.mode)
             else:
-                res = self.backend.phase_cohort(groups, dv, params, fl, want_lists, find_mode=mode)
+                res = self.backend.phase_cohort(groups, dv, call.params, fl, call.want_lists, find_mode=call.mode)
                 self.stats["phase_cohort_calls"] += 1
             free = getattr(self.backend, "free_reads", None)
             for rh in handles:  # region tables live for one batch
@@ -878,7 +901,7 @@ class PhasingHost:
                     free(rh)
             for g, (fam, rh, first, count, cutoff) in enumerate(groups):
                 for k in range(first, first + count):
-                    results[order_all[k]] = (res, k, tables[g])
+                    call.results[order_all[k]] = (res, k, tables[g])
 
     def run_read_phasing(self, dnms, pedigrees, *args, **kwargs):
         """run_read_phasing_impl, and whatever it raises behind find() -- a reference KeyError mimicked in pass 1, an I/O error of a BAM stage --
@@ -977,21 +1000,21 @@ class PhasingHost:
         # to the device as ONE cohort batch (uz_phase_cohort), not as one launch sequence per kid
         results: Dict[int, dict] = {}
         sec_pass1.__exit__()
+        call = _ReadCall(host=self, dnms=dnms, pedigrees=pedigrees, prep=prep, found=found, params=params, readlen=readlen, stdevs=stdevs,
+                         insert_size_max_sample=insert_size_max_sample, want_lists=want_lists, mode=info["mode"], results=results)
         with _Sec("chunked"):
-          chunked = self._chunked_batch(batch, dnms, pedigrees, prep, found, params, readlen, stdevs, insert_size_max_sample, want_lists, info["mode"], results,
-                                        while_first_stages=attach_sites)
+          chunked = self._chunked_batch(call, batch, while_first_stages=attach_sites)
         attach_sites()  # (a batch that did not take the chunked route: here; otherwise done already, and this is a no-op)
         if not chunked:
-            ctx = (dnms, pedigrees, prep, found, params, readlen, stdevs, insert_size_max_sample, want_lists, info["mode"], results)
             with _Sec("reads"):  # (the read side of the call: what scripts/reads_route_ab.py times by route)
                 if self._reads_route(batch) == "cohort":
                     # the kids' files walked and joined as ONE batch per run of kids, the read stage on the table that comes out (_joined_run); a
                     # run the device's walk does not take goes kid by kid
                     for run in self._cohort_runs(list(batch.items())):
-                        if not self._joined_run(run, *ctx):
-                            self._kid_run(run, *ctx)
+                        if not self._joined_run(call, run):
+                            self._kid_run(call, run)
                 else:
-                    self._kid_run(list(batch.items()), *ctx)
+                    self._kid_run(call, list(batch.items()))
         self._indexed_memo = None
         # pass 3: records, in the reference's order.  The names of the reads in the result lists: one look-up per table for the whole batch
         # (a staged table answers ids through the C ABI: hundreds of thousands of single calls were a third of round 3's host time); the chunks
