@@ -136,7 +136,10 @@ int uz_reads_upload(uz_ctx *ctx, const uz_reads_view *reads, int *reads_id);
  * nor the kernels of the table before wait for it), and the call returns; the host buffers (pinned memory for
  * full link speed, uz_pinned_alloc) must stay untouched until uz_reads_wait or a uz_phase on the table has
  * returned.  uz_phase on the table waits for the build on the device, so the upload and the build of the next
- * table overlap the kernels of the current one. */
+ * table overlap the kernels of the current one.
+ * The quality bits of listed bases (uz_reads_packed_view.bl_qlow, (n_bl + 7) / 8 bytes) travel with the other link columns; the column is
+ * taken only with bl_pos / bl_code and the counts through the dictionary (tup_n_bl) -- UZ_E_ARG without them, with bl_n, or beside the quality
+ * plane -- and a record whose set bits are not the number its count names fails the table (UZ_E_RANGE when the build has run). */
 int uz_reads_upload_packed(uz_ctx *ctx, const uz_reads_packed_view *reads, int *reads_id);
 int uz_reads_wait(uz_ctx *ctx, int reads_id);
 /* what the device made of a table's fixed-width columns, whatever form they travelled in (plain, 16- / 8-bit differences, the pair

@@ -226,7 +226,10 @@ void uz_reads_source_close(uz_psrc *src);
  * unit_masks = 3 (SV batches): as 1, and a fetch wider than two bases stages NO unit of the records it returns: collect_reads_sv
  * (read_collector.py:476-596) looks at flags, CIGARs and mates only; the bases of its records are read at the het sites they overlap
  * -- one-base fetches of the same batch -- and the only quality bits the read stage ever asks for are those of records that pass
- * goodread (:43-46) at such sites, so the list form serves SV batches too. */
+ * goodread (:43-46) at such sites, so the list form serves SV batches too.
+ * unit_masks & 4: the bases of such a record as a list where that is fewer bytes (uz_types.h: bl_*; two-bit sources).
+ * unit_masks & 8 (valid only together with 4): the quality bits of the listed bases ride with them (uz_types.h: bl_qlow) -- a record with a
+ * base list then owns no entries in qlow_pos, and its count is the number of its set bits (uz_select_base_quals: 1 when the plan did so). */
 /* tuples: 0, or 1 (build the dictionary of the small columns, uz_reads_packed_view.tup) | 2 (the output will set cigar_compact) | 4 (the
  * output will take the qualities as lists: n_low joins the combination); uz_select_n_tuples then gives the table length, or -1
  * when the selection holds more than 65536 combinations (the output keeps the plain columns) */
@@ -250,6 +253,7 @@ int64_t uz_select_n_seq_units(const uz_select *s);
 int64_t uz_select_n_bl(const uz_select *s);
 int64_t uz_select_n_bl_units(const uz_select *s);
 int uz_select_bl_wide(const uz_select *s);
+int uz_select_base_quals(const uz_select *s); /* 1: planned with the quality bits of the listed bases (the output view needs bl_qlow) */
 int64_t uz_select_n_exc(const uz_select *s); /* entries of the exc_* columns (0 for a source with four-bit rows) */
 int64_t uz_select_n_qlow_pos(const uz_select *s); /* entries of qlow_pos when the output takes the quality plane as lists */
 int uz_select_qlow_pos_wide(const uz_select *s);  /* 1 when a kept read is longer than 256 bases */

@@ -401,13 +401,22 @@ typedef struct uz_reads_packed_view {
     const uint8_t *tup_n_bl;   /* [n_tup] */
     const uint8_t *bl_pos;     /* [n_bl] (* 2 bytes when bl_wide) */
     const uint8_t *bl_code;    /* [(n_bl + 3) / 4] */
+    /* The quality bits of the listed bases -- optional (NULL: the form above).  The read stage asks for a quality bit only where it asks for
+     * a base, so a record with a base list needs its bits at the listed positions and nowhere else: entry e of the bl_* table is bit e & 7
+     * of byte e >> 3, set iff that base's quality lies below min_base_qual.  With the column set, a record with listed bases (k > 0) owns NO
+     * entries in qlow_pos (quantity 3 of its pk_sums share is 0), and the count that travels for it (n_low / tup_n_low) is the number of its
+     * set bits when the whole read has at most UZ_QLOW_LIST_MAX low-quality bases -- a subset keeps "at most UZ_QLOW_LIST_MAX" true -- or the
+     * read's own (saturated) count when it has more: all its bits are then 0 and it gets no quality row, as before.  The device writes the
+     * quality words of such a record's units from the bits as it writes their base rows, and holds the bits against the count (UZ_E_RANGE).
+     * Records without a base list keep their entries in qlow_pos.  Needs bl_pos / bl_code. */
+    const uint8_t *bl_qlow;    /* [(n_bl + 7) / 8] */
     int64_t n_bl;
     int64_t n_bl_units;
     int32_t bl_wide;
     int32_t reserved2;
     /* Span sums -- optional (NULL: the device computes them itself, one more pass over the small columns and a scan).  The header build lays the
      * records' variable-length parts out by the running sums of UZ_PK_SUMS per-record quantities: 0 CIGAR words, 1 row units, 2 base-row units
-     * that travelled as rows, 3 listed low-quality positions, 4 CIGAR words that travelled (cigar_compact), 5 start differences and 6 name-id
+     * that travelled as rows, 3 listed low-quality positions (none for a record with a base list when bl_qlow is set), 4 CIGAR words that travelled (cigar_compact), 5 start differences and 6 name-id
      * differences / new names (difference forms; modulo 2^32 where a column is), 7 row units and 8 listed bases of the records whose bases came as a
      * list, 9 FIRST and 10 SECOND records of the pair form.  A packer knows them as it packs: pk_sums[UZ_PK_SUMS * b + k] = quantity k summed over
      * the records in front of span b, spans of 1 << UZ_PK_SHIFT(n_segs) records, b = 0 .. n_pk_spans (the last row: the totals).

@@ -153,16 +153,20 @@ class BenchLoad:
         return abi.Held(svk, hs_k), hs_k, hg_k, wide_k, int(sel.size)
 
     def stage(self, eng, P, mode, fid, pool, chunks=None, last_chunk=0.7, first_chunk=None, sites16=False, per_chunk_sites=True, log_first=False,
-              compact_sites=True, het_sites=None):
+              compact_sites=True, het_sites=None, base_quals=None):
         """What the decoders would leave in pinned memory for a staged pass: per chunk of DNMs (whole clusters) the records the chunk's fetches
         return + their mates, in the link form (selected on the host out of the generator's table), and the site windows.
         het_sites: the genotype columns of the site windows in the het form (None: whenever the site form is compact and eight-bit and the
         workload is not "cnv", whose allele-balance stage reads every site's columns)
+        base_quals: the quality bits of the listed bases ride with them (uz_types.h bl_qlow; None: wherever base lists are on and the
+        workload is not "cnv"; False: the listed records send their low-quality positions, the form of the rounds before)
         -> (chunks for pipeline.run_pipelined, stats)"""
         if het_sites is None:
             het_sites = bool(compact_sites) and not sites16 and not self.cnv
         from unfazed_amd import io_native, shard
         from unfazed_amd.staging import fetch_points
+        if base_quals is None:
+            base_quals = not self.cnv
         ev, sc, cl, wl, n = self.ev, self.sc, self.cl, self.wl, self.n
         dv = self.view_of(0, n)
         co, ci, cf, ho, hi = eng.find(fid, dv, P, mode)
@@ -186,7 +190,7 @@ class BenchLoad:
             # bits of records that pass goodread only, which the lists hold (uz_types.h).  The chunk's columns back to back in one pinned
             # block: they cross the link as one copy.
             pool.new_slab(slab_hint)
-            part = src.select(fc, flo, fhi, alloc=pool.alloc, all_bases=bool(P.no_extended), lists=True, extra=fex, wide_no_units=self.cnv)
+            part = src.select(fc, flo, fhi, alloc=pool.alloc, all_bases=bool(P.no_extended), lists=True, extra=fex, wide_no_units=self.cnv, base_quals=bool(base_quals))
             slab_hint = max(64 << 20, int(pool.end_slab() * 1.3))
             if log_first and not out:  # development aid: the first chunk, column by column
                 import sys
@@ -223,5 +227,6 @@ def link_bytes(pv) -> int:
     return (int(pv.n_segs) * fixed + t8 + int(pv.n_tup) * 11 + int(pv.n_esc16) * 12 + int(pv.n_cigar_total) * 4
             + ((0 if dic else int(pv.n_segs)) + int(pv.n_qlow_pos) * (2 if pv.qlow_pos_wide else 1) if lists_f else int(pv.n_row_units) * 4)
             + (int(pv.n_seq_units) * 8 + int(pv.n_exc) * 7 if pv.seq2 else int(pv.n_seq_units) * 16)
+            + ((int(pv.n_bl) + 7) // 8 if pv.bl_qlow else 0)  # the quality bits of the listed bases
             + (int(pv.n_bl) * (2 if pv.bl_wide else 1) + (int(pv.n_bl) + 3) // 4 + (int(pv.n_tup) if pv.tup_n_bl else int(pv.n_segs) if pv.bl_n else 0))
             + ((int(pv.n_pk_spans) + 1) * 88 if pv.pk_sums else 0))  # (the packer's span sums: uz_types.h pk_sums)

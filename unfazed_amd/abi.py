@@ -222,7 +222,7 @@ class ReadsPackedView(C.Structure):
         ("pair_d8", _p),  # the pair form: tlen, mate and name id in one byte (with start_d8; the other difference columns then NULL)
         # the bases of a record as a list (uz_types.h bl_*): per record the number of listed bases (0: its units travel as rows), their query
         # indices and two-bit codes
-        ("bl_n", _p), ("tup_n_bl", _p), ("bl_pos", _p), ("bl_code", _p), ("n_bl", C.c_int64), ("n_bl_units", C.c_int64), ("bl_wide", C.c_int32),
+        ("bl_n", _p), ("tup_n_bl", _p), ("bl_pos", _p), ("bl_code", _p), ("bl_qlow", _p), ("n_bl", C.c_int64), ("n_bl_units", C.c_int64), ("bl_wide", C.c_int32),
         ("reserved2", C.c_int32),
         # span sums (uz_types.h pk_sums): the running sums the device's header build lays the records out by, from the packer
         ("pk_sums", _p), ("n_pk_spans", C.c_int64),
@@ -259,7 +259,7 @@ TUP8_SPAN = 1024  # uz_types.h UZ_TUP8_SPAN
 
 def packed_view_alloc(n, n_contigs, n_cigar_total, n_row_units, alloc=None, n_seq_units=None, n_exc=None, n_qlow_pos=None,
                       qlow_pos_wide=False, with_end=True, with_umask=False, cigar_omitted=None, n_tup=None, n_esc16=None, start8=False,
-                      narrow8=False, pair8=False, n_bl=None, n_bl_units=0, bl_wide=False, pk_sums=False, tup_off_link=False) -> "Held":
+                      narrow8=False, pair8=False, n_bl=None, n_bl_units=0, bl_wide=False, pk_sums=False, tup_off_link=False, base_quals=False) -> "Held":
     """A packed view over freshly allocated, writable arrays (alloc(nbytes) -> uint8 array; default numpy).
     n_seq_units: row units of the records that carry bases (default: all of them).
     n_exc: None = four-bit base rows (seq4); a number = two-bit rows (seq2) with that many listed bases (exc_*).
@@ -273,6 +273,7 @@ def packed_view_alloc(n, n_contigs, n_cigar_total, n_row_units, alloc=None, n_se
     pair8 (with start8): tlen, mate and name id in the pair form's one byte (pair_d8) instead of tlen_s / mate_d* / qname_d*.
     n_bl: None = every record's staged units travel as rows; a number = the list form of the bases for some records (bl_* columns with that many
     listed bases; the count per record in the dictionary, tup_n_bl, or the plain bl_n column), n_bl_units their row units.
+    base_quals (with n_bl): the quality bits of the listed bases ride with them (uz_types.h bl_qlow: one bit per listed base).
     cigar_omitted: None = every CIGAR word; a number = cigar_compact with that many simple records (n_cigar_total is the plain total:
     the words that stay home are taken off here)."""
     if n_seq_units is None:
@@ -330,6 +331,8 @@ def packed_view_alloc(n, n_contigs, n_cigar_total, n_row_units, alloc=None, n_se
         wb = 2 if bl_wide else 1
         arrs["bl_pos"] = alloc(wb * max(1, n_bl))[: wb * max(1, n_bl)]
         arrs["bl_code"] = alloc((max(1, n_bl) + 3) // 4 + 4)[: (max(1, n_bl) + 3) // 4]
+        if base_quals:
+            arrs["bl_qlow"] = alloc((max(1, n_bl) + 7) // 8 + 8)[: (max(1, n_bl) + 7) // 8]
         v.n_bl, v.n_bl_units, v.bl_wide = n_bl, n_bl_units, 1 if bl_wide else 0
     if n_esc16 is not None:
         if start8:
@@ -525,6 +528,15 @@ def base_lists(held: "Held"):
     e = np.arange(m)
     code = (a["bl_code"][e >> 2] >> (2 * (e & 3))) & 3 if m else np.zeros(0, np.uint8)
     return off, pos.astype(np.uint16), code.astype(np.uint8)
+
+
+def base_qual_bits(held: "Held"):
+    """the quality bits of the listed bases of a packed view (uz_types.h bl_qlow), one 0 / 1 per entry of the list, or None without the column"""
+    a = held.arrays
+    if "bl_qlow" not in a:
+        return None
+    m = int(held.view.n_bl)
+    return np.unpackbits(a["bl_qlow"][: (m + 7) // 8], bitorder="little")[:m]
 
 
 class CohortGroup(C.Structure):

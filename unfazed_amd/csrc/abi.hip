@@ -1132,8 +1132,13 @@ static void check_packed_view(const uz_reads_packed_view *v) {
                    "the list form of the bases (bl_*) needs unit masks, the list form of the qualities and two-bit rows");
         UZ_REQUIRE(v->n_bl >= 0 && v->n_bl_units >= 0 && v->n_bl_units <= v->n_bl && (v->n_bl == 0 || (v->bl_pos && v->bl_code)), UZ_E_ARG, "bad bl_* columns");
         UZ_REQUIRE(v->n_seq_units + v->n_bl_units <= v->n_row_units, UZ_E_ARG, "n_seq_units + n_bl_units must not exceed n_row_units");
-    } else
+        // the quality bits of the listed bases: with the lists themselves, the counts through the dictionary (never beside the plane: the list
+        // form of the bases has been held to the list form of the qualities above)
+        UZ_REQUIRE(!v->bl_qlow || (v->bl_pos && v->bl_code && !v->bl_n), UZ_E_ARG, "bl_qlow needs bl_pos / bl_code and tup_n_bl, not bl_n");
+    } else {
         UZ_REQUIRE(v->n_bl == 0 && v->n_bl_units == 0, UZ_E_ARG, "n_bl / n_bl_units without bl_n / tup_n_bl");
+        UZ_REQUIRE(!v->bl_qlow, UZ_E_ARG, "bl_qlow without the list form of the bases (tup_n_bl, bl_pos, bl_code)");
+    }
     UZ_REQUIRE(v->cigar_compact ? v->n_cigar_omitted >= 0 && v->n_cigar_omitted <= v->n_segs : v->n_cigar_omitted == 0, UZ_E_ARG, "bad n_cigar_omitted");
     UZ_REQUIRE(v->n_cigar_total + v->n_cigar_omitted < ((int64_t)1 << 32), UZ_E_RANGE, "more than 2^32 CIGAR operations");
     if (v->pk_sums) { // the packer's span sums: rows that ascend from zero to the totals the view declares (the device holds every span against its row)
@@ -1183,7 +1188,7 @@ static void reads_from_packed_host(uz_ctx *c, hipStream_t st, const uz_reads_pac
     const bool ccompact = v->cigar_compact != 0;
     const size_t n = (size_t)r.n, nc = (size_t)r.n_cigar_total, nu = (size_t)r.n_row_units, ns = (size_t)r.n_seq_units, ncs = (size_t)v->n_cigar_total;
     const size_t nsl = (size_t)v->n_seq_units; // units on the link
-    const size_t nbl = (size_t)r.n_bl, nblp = nbl * (v->bl_wide ? 2 : 1), nblc = (nbl + 3) / 4;
+    const size_t nbl = (size_t)r.n_bl, nblp = nbl * (v->bl_wide ? 2 : 1), nblc = (nbl + 3) / 4, nblq = (nbl + 7) / 8;
     const bool two_bit = v->seq2 != nullptr;
     const size_t ne = two_bit ? (size_t)v->n_exc : 0;
     const bool t8 = v->tup8 != nullptr; // the dictionary index in one byte: rebuilt into the 16-bit column's place by the header build's first kernel
@@ -1264,6 +1269,7 @@ static void reads_from_packed_host(uz_ctx *c, hipStream_t st, const uz_reads_pac
         if (blf) {
             if (v->bl_n) col.bl_n = S.col(v->bl_n, n);
             col.bl_pos = S.col(v->bl_pos, nblp); col.bl_code = S.col(v->bl_code, nblc, 4);
+            if (v->bl_qlow) col.bl_qlow = S.col(v->bl_qlow, nblq, 8);
             col.bl_wide = v->bl_wide;
             col.n_seq_link = (int64_t)nsl;
             col.seq4_out = reinterpret_cast<uint32_t *>(const_cast<uint8_t *>(r.seq4));

@@ -136,6 +136,11 @@ struct uz_select {
     std::vector<uint8_t> tup_nb;        // (list count of the combination)
     int64_t n_bl_units = 0;             // row units of the listed records (not in n_seq)
     int bl_wide = 0;
+    // the quality bits of the listed bases (uz_types.h bl_qlow; planned with unit_masks & 8): one byte (0 / 1) per entry of bl_pos here.  A record
+    // with a base list then owns no entries in qlow_pos, and its n_low is the number of its set bits (more than UZ_QLOW_LIST_MAX low-quality
+    // bases in the whole read: the read's own count, all bits 0)
+    int base_quals = 0;
+    std::vector<uint8_t> bl_q;
 };
 
 // start / tlen / mate / qname of kept record k as 16-bit differences (uz_reads_packed_view.start_d ...): v[c] the column values,
@@ -443,6 +448,7 @@ int uz_reads_select_plan(const uz_psrc *src, int64_t n_fetch, const int32_t *con
         // it returns -- collect_reads_sv looks at flags, CIGARs and mates only (read_collector.py:476-596); the bases of such a record
         // are read at the het sites it overlaps, which have one-base fetches of their own
         const bool wide_none = (unit_masks & 2) != 0;
+        if ((unit_masks & 8) && !(unit_masks & 4)) fail(UZ_IO_E_ARG, "unit_masks & 8 (quality bits with the listed bases) is valid only together with 4 (the list form of the bases)");
         std::vector<uint16_t> um;
         if (masks) um.assign((size_t)n + 1, 0);
         uint16_t *ump = um.data();
@@ -630,6 +636,34 @@ int uz_reads_select_plan(const uz_psrc *src, int64_t n_fetch, const int32_t *con
             sel->bl_off[(size_t)sel->n_sel] = (int64_t)sel->bl_pos.size();
             for (int64_t k = 0; k < sel->n_sel && !sel->bl_wide; k++) // (two-byte positions as soon as the table holds a read longer than 256 bases: the rule of qlow_pos_wide)
                 if (full->l_seq[sel->index[(size_t)k]] > 256) sel->bl_wide = 1;
+            if (unit_masks & 8) {
+                // The quality bits ride with the listed bases: the read stage asks for a quality bit only where it asks for a base, and of such a
+                // record it can ask for the listed bases only.  Its low-quality positions leave qlow_pos (they were counted above), and the count
+                // that travels becomes the number of LISTED low-quality bases -- unless the whole read has more than UZ_QLOW_LIST_MAX of them:
+                // then the read's own count travels, as before, and every bit stays 0 (the record is never "good": no bit is asked for).
+                sel->base_quals = 1;
+                sel->bl_q.assign(sel->bl_pos.size(), 0);
+                const int wk = workers_for(sel->n_sel, threads, 4096);
+                std::vector<int64_t> gone((size_t)wk + 1, 0);
+                parallel_slices(sel->n_sel, wk, [&](int64_t a, int64_t b, int slice) {
+                    int64_t c = 0;
+                    for (int64_t k = a; k < b; k++) {
+                        const int nbk = sel->bl_n[(size_t)k];
+                        if (!nbk || src_low_count(src, sel->index[(size_t)k]) > UZ_QLOW_LIST_MAX) continue;
+                        c += sel->n_low[(size_t)k];
+                        const uint16_t *lp = sel->bl_pos.data() + sel->bl_off[(size_t)k];
+                        uint8_t *lq = sel->bl_q.data() + sel->bl_off[(size_t)k];
+                        int set = 0;
+                        src_low_positions(src, sel->index[(size_t)k], [&](int bq) {
+                            const uint16_t *it = std::lower_bound(lp, lp + nbk, (uint16_t)bq);
+                            if (it != lp + nbk && *it == (uint16_t)bq) { lq[it - lp] = 1; set++; }
+                        });
+                        sel->n_low[(size_t)k] = (uint8_t)set;
+                    }
+                    gone[(size_t)slice] = c;
+                });
+                for (int k = 0; k < wk; k++) sel->n_qpos -= gone[(size_t)k];
+            }
         }
         if (tuples & 1) { // the small columns as a dictionary: combinations numbered in order of first appearance
             struct KeyHash { size_t operator()(const std::pair<uint64_t, uint32_t> &k) const { return std::hash<uint64_t>()(k.first * 0x9E3779B97F4A7C15ULL + k.second * 0xC2B2AE3D27D4EB4FULL); } };
@@ -731,6 +765,7 @@ int64_t uz_select_n_exc(const uz_select *s) { return s ? s->n_exc : 0; }
 int64_t uz_select_n_bl(const uz_select *s) { return (s && !s->bl_n.empty()) ? (int64_t)s->bl_pos.size() : -1; } /* -1: planned without the list form of the bases */
 int64_t uz_select_n_bl_units(const uz_select *s) { return s ? s->n_bl_units : 0; }
 int uz_select_bl_wide(const uz_select *s) { return s ? s->bl_wide : 0; }
+int uz_select_base_quals(const uz_select *s) { return s ? s->base_quals : 0; }
 int64_t uz_select_n_qlow_pos(const uz_select *s) { return s ? s->n_qpos : 0; }
 int uz_select_end_derivable(const uz_select *s) { return s ? s->end_derivable : 0; }
 int64_t uz_select_n_esc16(const uz_select *s) { return s ? s->n_esc16 : 0; }
@@ -829,6 +864,10 @@ int uz_reads_select_fill(const uz_select *s, int threads, uz_reads_packed_view *
             fail(UZ_IO_E_ARG, "the list form of the bases: the output view needs bl_n (or tup_n_bl with the dictionary), bl_pos and bl_code exactly when the selection was planned with it (uz_select_n_bl)");
         out->n_bl = blf ? (int64_t)s->bl_pos.size() : 0; out->n_bl_units = blf ? s->n_bl_units : 0;
         if (blf && out->n_bl) memset(w(out->bl_code), 0, (size_t)(out->n_bl + 3) / 4);
+        const bool blq = s->base_quals != 0;
+        if (blq != (out->bl_qlow != nullptr))
+            fail(UZ_IO_E_ARG, "the quality bits of the listed bases: the output view needs bl_qlow exactly when the selection was planned with them (uz_select_base_quals)");
+        if (blq && out->n_bl) memset(w(out->bl_qlow), 0, (size_t)(out->n_bl + 7) / 8);
         const bool lists = out->n_low != nullptr || (tup && out->tup_n_low != nullptr);
         if (masks && !lists) fail(UZ_IO_E_ARG, "unit masks need the list form of the qualities in the output (n_low / qlow_pos)");
         if (!lists && !full->qlow) fail(UZ_IO_E_ARG, "the source table has the quality plane as lists: the output view needs n_low / qlow_pos");
@@ -838,7 +877,7 @@ int uz_reads_select_fill(const uz_select *s, int threads, uz_reads_packed_view *
         if (lists) {
             ol.assign((size_t)m + 1, 0);
             for (int64_t k = 0; k < m; k++)
-                ol[(size_t)k + 1] = ol[(size_t)k] + ((s->bases[(size_t)k] && s->n_low[(size_t)k] <= UZ_QLOW_LIST_MAX) ? s->n_low[(size_t)k] : 0);
+                ol[(size_t)k + 1] = ol[(size_t)k] + ((s->bases[(size_t)k] && s->n_low[(size_t)k] <= UZ_QLOW_LIST_MAX && !(blq && s->bl_n[(size_t)k])) ? s->n_low[(size_t)k] : 0);
         }
         std::vector<int64_t> oe;
         if (two_bit) {
@@ -932,6 +971,7 @@ int uz_reads_select_fill(const uz_select *s, int threads, uz_reads_packed_view *
                         else w(out->bl_pos)[at] = (uint8_t)q;
                         const uint8_t c2 = (uint8_t)((row[q >> 2] >> (6 - 2 * (q & 3))) & 3u);
                         if (c2) __atomic_fetch_or(w(out->bl_code) + (at >> 2), (uint8_t)(c2 << (2 * (at & 3))), __ATOMIC_RELAXED);
+                        if (blq && s->bl_q[(size_t)at]) __atomic_fetch_or(w(out->bl_qlow) + (at >> 3), (uint8_t)(1u << (at & 7)), __ATOMIC_RELAXED);
                     }
                     for (int64_t e = 0; e < s->exc_n[(size_t)k]; e++) {
                         const int64_t fr = s->exc_lo[(size_t)k] + e, t2 = oe[(size_t)k] + e;
@@ -962,7 +1002,7 @@ int uz_reads_select_fill(const uz_select *s, int threads, uz_reads_packed_view *
                     memcpy(w(out->qlow) + ou[k] * UZ_QLOW_UNIT_BYTES, full->qlow + (size_t)src->uoff[i] * UZ_QLOW_UNIT_BYTES, units * UZ_QLOW_UNIT_BYTES);
                 else {
                     if (!tup) w(out->n_low)[k] = s->n_low[(size_t)k];
-                    if (s->bases[(size_t)k] && s->n_low[(size_t)k] <= UZ_QLOW_LIST_MAX) {
+                    if (s->bases[(size_t)k] && s->n_low[(size_t)k] <= UZ_QLOW_LIST_MAX && !(blq && s->bl_n[(size_t)k])) { // (a base list with its quality bits: none here)
                         int64_t at = ol[(size_t)k];
                         auto put = [&](int b) {
                             if (out->qlow_pos_wide) { w(out->qlow_pos)[2 * at] = (uint8_t)(b & 255); w(out->qlow_pos)[2 * at + 1] = (uint8_t)(b >> 8); }
@@ -1016,7 +1056,7 @@ struct SumsView {
         q[2] = nb ? 0u : staged;
         q[7] = nb ? staged : 0u;
         q[8] = nb;
-        q[3] = (nl >= 0 && !(ax & UZ_AUX_NO_SEQ) && nl <= UZ_QLOW_LIST_MAX) ? (uint32_t)nl : 0u;
+        q[3] = (nl >= 0 && !(ax & UZ_AUX_NO_SEQ) && nl <= UZ_QLOW_LIST_MAX && !(nb && v->bl_qlow)) ? (uint32_t)nl : 0u; // (bl_qlow: the bits ride with the listed bases)
         const bool diff_form = v->tlen_s != nullptr || v->pair_d8 != nullptr;
         if (diff_form) {
             if (v->start_d8) { const uint32_t x = v->start_d8[i]; q[5] = x == UZ_D8_ESC ? (uint32_t)esc_find(i, 0) : x; }

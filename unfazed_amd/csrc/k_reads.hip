@@ -282,7 +282,8 @@ static inline int uz_pk_shift(int64_t n) { return UZ_PK_SHIFT(n); } // (uz_types
 // ones that travelled as rows); tenth and eleventh, the FIRST and SECOND records of the pair form (their totals must agree)
 #define UZ_PK_SCANNED 9 // the running sums the header build needs per record (the last two are totals only)
 // um: which units of the record's rows were staged (UZ_UMASK_ALL: all of them)
-__device__ __forceinline__ void pk_vals(uint32_t nc, uint32_t ls, uint32_t aux, int nl, uint32_t um, uint32_t nb, uint32_t (&v)[UZ_PK_SUMS]) {
+// blq: the quality bits of listed bases ride with them (uz_types.h bl_qlow): a record with a base list owns no listed positions
+__device__ __forceinline__ void pk_vals(uint32_t nc, uint32_t ls, uint32_t aux, int nl, uint32_t um, uint32_t nb, bool blq, uint32_t (&v)[UZ_PK_SUMS]) {
     v[4] = (aux & UZ_AUX_SIMPLE_MASK) ? 0u : nc;
     v[5] = 0u; v[6] = 0u; v[9] = 0u; v[10] = 0u; // (set by the callers from the difference columns)
     const uint32_t staged = (aux & UZ_AUX_NO_SEQ) ? 0u : (um == UZ_UMASK_ALL ? UZ_ROW_UNITS(ls) : (uint32_t)__popc(um));
@@ -290,7 +291,7 @@ __device__ __forceinline__ void pk_vals(uint32_t nc, uint32_t ls, uint32_t aux, 
     v[2] = nb ? 0u : staged; // units that travelled as rows
     v[7] = nb ? staged : 0u; // units of a record whose bases came as a list
     v[8] = nb;
-    v[3] = (nl >= 0 && !(aux & UZ_AUX_NO_SEQ) && nl <= UZ_QLOW_LIST_MAX) ? (uint32_t)nl : 0u;
+    v[3] = (nl >= 0 && !(aux & UZ_AUX_NO_SEQ) && nl <= UZ_QLOW_LIST_MAX && !(blq && nb)) ? (uint32_t)nl : 0u;
 }
 // the small columns of record i, plain or through the dictionary (uz_reads_packed_view.tup)
 struct RecSmall { uint32_t flag, ls, nc, mapq, aux, um; int nl; uint32_t nb; };
@@ -463,7 +464,7 @@ __global__ __launch_bounds__(256) void k_off_block_sums(int64_t n, RecColumns c_
             if (!in[u]) continue;
             const int64_t i = idx[u];
             uint32_t v[UZ_PK_SUMS];
-            pk_vals(r[u].nc, r[u].ls, r[u].aux, r[u].nl, r[u].um, r[u].nb, v);
+            pk_vals(r[u].nc, r[u].ls, r[u].aux, r[u].nl, r[u].um, r[u].nb, c.bl_qlow != nullptr, v);
             if (c.diff_form()) {
                 v[5] = c.start_d8 ? (sd[u] == UZ_D8_ESC ? (uint32_t)esc16_of(c, i, 0) : sd[u]) : start_diff(c, i);
                 v[6] = c.pair_d8 ? ((pd[u] != UZ_P8_SECOND && pd[u] != UZ_P8_SECOND_TLEN && pd[u] != UZ_P8_OLD) ? 1u : 0u) : qname_diff(c, i);
@@ -591,7 +592,7 @@ __global__ __launch_bounds__(256) void k_pack_rec(int64_t n, RecColumns c_in, co
         const int nl = rs.nl;
         const uint32_t um = rs.um, nb = rs.nb;
         uint32_t v[UZ_PK_SUMS], inc[UZ_PK_SCANNED];
-        pk_vals(nc, ls, ax, nl, um, nb, v);
+        pk_vals(nc, ls, ax, nl, um, nb, c.bl_qlow != nullptr, v);
         if (c.diff_form() && in) { v[5] = start_diff(c, i); v[6] = qname_diff(c, i); }
         PK_TICK(1); // small columns + dictionary + differences
 #pragma unroll
@@ -713,10 +714,16 @@ __global__ __launch_bounds__(256) void k_pack_rec(int64_t n, RecColumns c_in, co
                     int cur = -1, last = -1;
                     uint32_t row = sq, seen = 0u;
                     bool bad = false;
+                    // (bl_qlow: the quality word of a unit is gathered beside its base row and stored with it -- for a record whose count allows
+                    // a quality row at all)
+                    const bool qrow = c.bl_qlow != nullptr && nl >= 0 && nl <= UZ_QLOW_LIST_MAX;
+                    uint32_t qw = 0u;
+                    int bl_low = 0; // set quality bits of the record's listed bases
                     for (uint32_t e = 0; e < nb; e++) {
                         const unsigned long long g = at + e;
                         const int pos = c.bl_wide ? ((int)c.bl_pos[2 * g] | ((int)c.bl_pos[2 * g + 1] << 8)) : (int)c.bl_pos[g];
                         const uint32_t code = ((uint32_t)c.bl_code[g >> 2] >> (2u * (uint32_t)(g & 3ULL))) & 3u;
+                        const uint32_t qbit = c.bl_qlow ? ((uint32_t)c.bl_qlow[g >> 3] >> (uint32_t)(g & 7ULL)) & 1u : 0u;
                         const int u = pos >> 5;
                         bad |= pos <= last || pos >= (int)ls || u > 14 || !((um >> u) & 1u);
                         last = pos;
@@ -724,6 +731,8 @@ __global__ __launch_bounds__(256) void k_pack_rec(int64_t n, RecColumns c_in, co
                             if (cur >= 0) {
 #pragma unroll
                                 for (int q = 0; q < 4; q++) { c.seq4_out[4 * (size_t)row + q] = w4r[q]; w4r[q] = 0u; }
+                                if (qrow) plane_out[(size_t)row] = qw;
+                                qw = 0u;
                                 row++;
                             }
                             cur = u;
@@ -731,12 +740,17 @@ __global__ __launch_bounds__(256) void k_pack_rec(int64_t n, RecColumns c_in, co
                         }
                         const int k32 = pos & 31; // byte k32 >> 1 of the row, high nibble when k32 is even
                         w4r[k32 >> 3] |= (1u << code) << (8 * ((k32 >> 1) & 3) + ((k32 & 1) ? 0 : 4));
+                        qw |= qbit << k32;
+                        bl_low += (int)qbit;
                     }
                     if (cur >= 0) {
 #pragma unroll
                         for (int q = 0; q < 4; q++) c.seq4_out[4 * (size_t)row + q] = w4r[q];
+                        if (qrow) plane_out[(size_t)row] = qw;
                     }
                     if (bad || seen != um) hflags[0] = 9; // a position outside the mask / not ascending, or a unit of the mask without a listed base
+                    // (the guard of the bit form, where k_pack_link has it: as many set bits as the count says; none for a record without a quality row)
+                    if (c.bl_qlow != nullptr && nl >= 0 && bl_low != (qrow ? nl : 0)) hflags[0] = 4;
                 }
             }
             PK_TICK(6); // listed bases
@@ -745,9 +759,10 @@ __global__ __launch_bounds__(256) void k_pack_rec(int64_t n, RecColumns c_in, co
                 // record whose bits can be asked for, written here from its listed positions
                 nlow[i] = (uint8_t)nl;
                 low_for_qc = nl;
-                const bool listed = v[3] == (uint32_t)nl && !(ax & UZ_AUX_NO_SEQ) && nl <= UZ_QLOW_LIST_MAX;
+                const bool with_bits = nb && c.bl_qlow != nullptr; // its quality words were written with its base rows, from the bits of its listed bases
+                const bool listed = (with_bits || v[3] == (uint32_t)nl) && !(ax & UZ_AUX_NO_SEQ) && nl <= UZ_QLOW_LIST_MAX;
                 qoff[i] = listed ? sq : UZ_NO_QLOW_OFF;
-                if (listed) {
+                if (listed && !with_bits) { // (with bits: held against the count above, beside the rows)
                     const unsigned long long at = run[3] + pre[3] + inc[3] - v[3];
                     int pos[UZ_QLOW_LIST_MAX];
                     bool bad = false;
@@ -867,7 +882,7 @@ __global__ __launch_bounds__(256, 5) void k_pack_link(int64_t n, RecColumns c_in
     RecColumns c = uz_columns_of<true>(c_in);
     __shared__ uint16_t s_tup[UZ_PL_SPAN];
     __shared__ uint8_t s_sd[UZ_PL_SPAN], s_pd[UZ_PL_SPAN];
-    __shared__ uint8_t s_qp[UZ_PL_QP], s_blp[UZ_PL_BL], s_blc[UZ_PL_BL / 4 + 8];
+    __shared__ uint8_t s_qp[UZ_PL_QP], s_blp[UZ_PL_BL], s_blc[UZ_PL_BL / 4 + 8], s_blq[UZ_PL_BL / 8 + 8]; // (the span's slices of bl_code and bl_qlow, byte for byte)
     __shared__ uint32_t s_cig[UZ_PL_CIG];
     __shared__ unsigned long long s_esck[UZ_PL_ESC];
     __shared__ int32_t s_escv[UZ_PL_ESC];
@@ -965,12 +980,18 @@ __global__ __launch_bounds__(256, 5) void k_pack_link(int64_t n, RecColumns c_in
     const bool q_in = qn_ <= UZ_PL_QP, b_in = bn_ <= UZ_PL_BL, g_in = gn_ <= UZ_PL_CIG;
     const int64_t e0 = c.n_esc16 > 0 ? (int64_t)uni64((unsigned long long)esc_span[0]) : 0, e1 = c.n_esc16 > 0 ? (int64_t)uni64((unsigned long long)esc_span[1]) : 0;
     const bool e_in = e1 - e0 <= UZ_PL_ESC;
-    const uint32_t b0lo = (uint32_t)(b0 & 3ULL); // (four two-bit codes per byte: the span's first code sits b0lo codes into its first byte)
+    // (four two-bit codes per byte of bl_code, eight quality bits per byte of bl_qlow: the span's first entry sits b0 & 3 codes / b0 & 7 bits
+    // into the first byte of its slice; both slices are copied as they lie)
+    const uint32_t b0lo = (uint32_t)(b0 & 7ULL);
     if (q_in) for (int k = t; k < (int)qn_; k += 256) s_qp[k] = c.qlow_pos[q0 + k];
     if (b_in) {
         for (int k = t; k < (int)bn_; k += 256) s_blp[k] = c.bl_pos[b0 + k];
-        const int ncb = (int)((b0lo + bn_ + 3u) >> 2);
+        const int ncb = (int)(((b0lo & 3u) + bn_ + 3u) >> 2);
         for (int k = t; k < ncb; k += 256) s_blc[k] = c.bl_code[(b0 >> 2) + k];
+        if (c.bl_qlow) {
+            const int nqb = (int)((b0lo + bn_ + 7u) >> 3);
+            for (int k = t; k < nqb; k += 256) s_blq[k] = c.bl_qlow[(b0 >> 3) + k];
+        }
     }
     if (g_in) for (int k = t; k < (int)gn_; k += 256) s_cig[k] = c.cigar_staged[g0 + k];
     if (e_in) for (int k = t; k < (int)(e1 - e0); k += 256) { s_esck[k] = c.esc16_key[e0 + k]; s_escv[k] = c.esc16_val[e0 + k]; }
@@ -991,10 +1012,16 @@ __global__ __launch_bounds__(256, 5) void k_pack_link(int64_t n, RecColumns c_in
     auto qpos_at = [&](uint32_t r) -> int { return q_in ? (int)s_qp[r] : (int)c.qlow_pos[q0 + r]; };
     auto blpos_at = [&](uint32_t r) -> int { return b_in ? (int)s_blp[r] : (int)c.bl_pos[b0 + r]; };
     auto blcode_at = [&](uint32_t r) -> uint32_t {
-        const uint32_t g = b0lo + r;
+        const uint32_t g = (b0lo & 3u) + r;
         const uint32_t byte = b_in ? (uint32_t)s_blc[g >> 2] : (uint32_t)c.bl_code[(b0 >> 2) + (g >> 2)];
         return (byte >> (2u * (g & 3u))) & 3u;
     };
+    auto blq_at = [&](uint32_t r) -> uint32_t { // (only asked with the column)
+        const uint32_t g = b0lo + r;
+        const uint32_t byte = b_in ? (uint32_t)s_blq[g >> 3] : (uint32_t)c.bl_qlow[(b0 >> 3) + (g >> 3)];
+        return (byte >> (g & 7u)) & 1u;
+    };
+    const bool blq = c.bl_qlow != nullptr;
     auto cig_at = [&](uint32_t r) -> uint32_t { return g_in ? s_cig[r] : c.cigar_staged[g0 + r]; };
     for (int it = 0; it < UZ_PL_SPAN / 256; it++) {
         const int k = it * 256 + t; // the record's place in the span
@@ -1007,7 +1034,7 @@ __global__ __launch_bounds__(256, 5) void k_pack_link(int64_t n, RecColumns c_in
         const uint32_t mapq = de.z & 0xFFu, ax = (de.z >> 8) & 0xFFu, nb = de.z >> 24;
         const int nl = (int)((de.z >> 16) & 0xFFu);
         uint32_t v[UZ_PK_SUMS], inc[UZ_PK_SCANNED];
-        pk_vals(nc, ls, ax, nl, um, nb, v);
+        pk_vals(nc, ls, ax, nl, um, nb, c.bl_qlow != nullptr, v);
         if (!in) {
 #pragma unroll
             for (int q = 0; q < UZ_PK_SUMS; q++) v[q] = 0u;
@@ -1129,6 +1156,14 @@ __global__ __launch_bounds__(256, 5) void k_pack_link(int64_t n, RecColumns c_in
             umask_out[i] = (uint16_t)(nb ? (um | UZ_UMASK_LISTED) : um);
             if (um != UZ_UMASK_ALL && (units > 15 || (um >> units) != 0u)) hflags[0] = 5; // a unit beyond the read, or a read too long for a mask
             PK_TICK(5); // pair + header stores
+            // The count and the QC word first: nothing below changes them, and their inputs need not live through the two list loops.
+            // list form of the staged plane: the count as it is; a quality row (at the record's base-row position) only for a record whose
+            // bits can be asked for -- written from its listed positions, or, with bl_qlow, from the bits of its listed bases beside their rows
+            nlow[i] = (uint8_t)nl;
+            qs[i] = uz_qs_word(flag, ax, mapq, nl, (int)nc, cig_nonmatch, cig_none);
+            const bool with_bits = blq && nb != 0u;
+            const bool listed = (with_bits || v3 == (uint32_t)nl) && !(ax & UZ_AUX_NO_SEQ) && nl <= UZ_QLOW_LIST_MAX;
+            qoff[i] = listed ? sq : UZ_NO_QLOW_OFF;
             if (nb) {
                 // The listed bases -> the record's rows (one 16-byte row per unit of its mask; bases that were not listed stay code 0, which
                 // the readers of a listed record refuse: phase_body.hpp uz_base).  Positions ascend, so the units come in row order.
@@ -1139,9 +1174,12 @@ __global__ __launch_bounds__(256, 5) void k_pack_link(int64_t n, RecColumns c_in
                     int cur = -1, last = -1;
                     uint32_t row = sq, seen = 0u;
                     bool bad = false;
+                    uint32_t qw = 0u; // the unit's quality word, gathered beside its base row (bl_qlow)
+                    int bl_low = 0;   // ... and the set bits of the record
+                    const bool qrow = with_bits && listed;
                     for (uint32_t e = 0; e < nb; e++) {
                         const int pos = blpos_at(at + e);
-                        const uint32_t code = blcode_at(at + e);
+                        const uint32_t code = blcode_at(at + e), qbit = blq ? blq_at(at + e) : 0u;
                         const int u = pos >> 5;
                         bad |= pos <= last || pos >= (int)ls || u > 14 || !((um >> u) & 1u);
                         last = pos;
@@ -1149,6 +1187,8 @@ __global__ __launch_bounds__(256, 5) void k_pack_link(int64_t n, RecColumns c_in
                             if (cur >= 0) {
                                 reinterpret_cast<uint4 *>(c.seq4_out)[row] = make_uint4(w4r[0], w4r[1], w4r[2], w4r[3]);
                                 w4r[0] = w4r[1] = w4r[2] = w4r[3] = 0u;
+                                if (qrow) plane_out[(size_t)row] = qw;
+                                qw = 0u;
                                 row++;
                             }
                             cur = u;
@@ -1156,18 +1196,20 @@ __global__ __launch_bounds__(256, 5) void k_pack_link(int64_t n, RecColumns c_in
                         }
                         const int k32 = pos & 31; // byte k32 >> 1 of the row, high nibble when k32 is even
                         w4r[k32 >> 3] |= (1u << code) << (8 * ((k32 >> 1) & 3) + ((k32 & 1) ? 0 : 4));
+                        qw |= qbit << k32;
+                        bl_low += (int)qbit;
                     }
-                    if (cur >= 0) reinterpret_cast<uint4 *>(c.seq4_out)[row] = make_uint4(w4r[0], w4r[1], w4r[2], w4r[3]);
+                    if (cur >= 0) {
+                        reinterpret_cast<uint4 *>(c.seq4_out)[row] = make_uint4(w4r[0], w4r[1], w4r[2], w4r[3]);
+                        if (qrow) plane_out[(size_t)row] = qw;
+                    }
                     if (bad || seen != um) hflags[0] = 9; // a position outside the mask / not ascending, or a unit of the mask without a listed base
+                    // (the guard of the bit form: as many set bits as the count says; none for a record without a quality row)
+                    if (with_bits && bl_low != (listed ? nl : 0)) hflags[0] = 4;
                 }
             }
             PK_TICK(6); // listed bases
-            // list form of the staged plane: the count as it is; a quality row (at the record's base-row position) only for a record whose
-            // bits can be asked for, written here from its listed positions
-            nlow[i] = (uint8_t)nl;
-            const bool listed = v3 == (uint32_t)nl && !(ax & UZ_AUX_NO_SEQ) && nl <= UZ_QLOW_LIST_MAX;
-            qoff[i] = listed ? sq : UZ_NO_QLOW_OFF;
-            if (listed) {
+            if (listed && !with_bits) {
                 const uint32_t at = r_qp;
                 bool bad = false;
                 int prev = -1;
@@ -1185,7 +1227,6 @@ __global__ __launch_bounds__(256, 5) void k_pack_link(int64_t n, RecColumns c_in
                 } else
                     for (int u = 0; u < units; u++) plane_out[(size_t)at_row++] = row_word(u);
             }
-            qs[i] = uz_qs_word(flag, ax, mapq, nl, (int)nc, cig_nonmatch, cig_none);
             PK_TICK(7); // quality list
         }
     }
@@ -1342,8 +1383,14 @@ __global__ __launch_bounds__(256) void k_patch_exc(int64_t n_exc, const uint32_t
 }
 } // namespace
 
-// (sized for the short spans whatever the table gets: 80 bytes per 1024 records)
-size_t uz_rec_scratch_bytes(int64_t n) { return (size_t)(((n + (1 << UZ_PK_SHIFT_SMALL) - 1) >> UZ_PK_SHIFT_SMALL) + 2) * (UZ_PK_SUMS + 1) * sizeof(unsigned long long); }
+// (sized for the short spans whatever the table gets: 96 bytes per 1024 records; never less than the packed dictionary of UZ_PL_DICT_MIN
+// combinations, so that a table of a few hundred records -- a chunk of a small batch: a combination of its own for every few records -- is
+// built by k_pack_link as the large ones are)
+#define UZ_PL_DICT_MIN 256
+size_t uz_rec_scratch_bytes(int64_t n) {
+    const size_t spans = (size_t)(((n + (1 << UZ_PK_SHIFT_SMALL) - 1) >> UZ_PK_SHIFT_SMALL) + 2) * (UZ_PK_SUMS + 1) * sizeof(unsigned long long);
+    return std::max(spans, (size_t)UZ_PL_DICT_MIN * sizeof(uint4));
+}
 
 // The dictionary index in one byte (uz_types.h tup8) back to the 16-bit column the header build reads: a workgroup per span of UZ_TUP8_SPAN
 // records, four records per lane (one 4-byte load, one 8-byte store); an escaped record's place in the escape list is the span's offset + the
@@ -1546,7 +1593,7 @@ void uz_check_upload_flag(uz_ctx *c) {
         c->hflags[0] = 0;
         throw UzError{UZ_E_RANGE, f == 2 ? "SEQ holds a character outside BAM's 16-code alphabet"
                                   : f == 3 ? "exc_* columns of the reads view: an entry names a record without bases, a base beyond l_seq or a code above 15"
-                                  : f == 4 ? "qlow_pos of the reads view: positions of a record are not ascending or lie beyond l_seq"
+                                  : f == 4 ? "qlow_pos / bl_qlow of the reads view: positions of a record are not ascending or lie beyond l_seq, or the set quality bits of its listed bases are not the number its count names"
                                   : f == 5 ? "umask of the reads view: a unit beyond the read's length, or a mask on a read longer than 480 bases"
                                   : f == 6 ? "aux of the reads view: a simple-CIGAR code on a record whose n_cigar is not 1"
                                   : f == 7 ? "mate_d / esc16_* of the reads view: a mate index outside the table"

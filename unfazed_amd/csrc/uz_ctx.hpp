@@ -205,6 +205,7 @@ struct RecColumns {
     // two-bit codes; seq4_out: the device's base rows (the header build writes the units of the listed records, behind the n_seq_link units that
     // travelled as rows)
     const uint8_t *bl_n = nullptr, *tup_n_bl = nullptr, *bl_pos = nullptr, *bl_code = nullptr;
+    const uint8_t *bl_qlow = nullptr; // the quality bits of the listed bases (uz_types.h bl_qlow; null: such a record's positions stand in qlow_pos)
     int32_t bl_wide = 0;
     int64_t n_seq_link = 0;
     uint32_t *seq4_out = nullptr;

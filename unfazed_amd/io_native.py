@@ -28,7 +28,7 @@ IO_EXPORTS = [
     "uz_bam_tlen_head", "uz_bam_timing", "uz_bam_decode_regions", "uz_bam_io_stats", "uz_vcf_decode", "uz_vcf_free", "uz_vcf_view_get", "uz_vcf_sample",
     "uz_vcf_contig", "uz_vcf_ref", "uz_vcf_alt", "uz_vcf_header", "uz_vcf_line", "uz_vcf_info", "uz_vcf_is_bcf",
     "uz_reads_pack_sizes", "uz_reads_pack_exceptions", "uz_reads_pack_lists", "uz_reads_pack_end_derivable", "uz_reads_pack_cigar_omitted", "uz_reads_pack", "uz_reads_source_open", "uz_reads_source_close", "uz_reads_select_plan",
-    "uz_select_n_records", "uz_select_n_cigar_total", "uz_select_n_row_units", "uz_select_n_seq_units", "uz_select_n_bl", "uz_select_n_bl_units", "uz_select_bl_wide", "uz_select_n_exc", "uz_select_n_qlow_pos", "uz_select_qlow_pos_wide", "uz_select_end_derivable", "uz_select_n_cigar_omitted", "uz_select_n_tuples", "uz_select_n_esc16", "uz_select_n_esc16_start8", "uz_select_n_esc16_narrow8", "uz_select_pair8_ok", "uz_select_n_esc16_pair8", "uz_select_n_new_names", "uz_select_qname_map",
+    "uz_select_n_records", "uz_select_n_cigar_total", "uz_select_n_row_units", "uz_select_n_seq_units", "uz_select_n_bl", "uz_select_n_bl_units", "uz_select_bl_wide", "uz_select_base_quals", "uz_select_n_exc", "uz_select_n_qlow_pos", "uz_select_qlow_pos_wide", "uz_select_end_derivable", "uz_select_n_cigar_omitted", "uz_select_n_tuples", "uz_select_n_esc16", "uz_select_n_esc16_start8", "uz_select_n_esc16_narrow8", "uz_select_pair8_ok", "uz_select_n_esc16_pair8", "uz_select_n_new_names", "uz_select_qname_map",
     "uz_reads_select_fill", "uz_select_free", "uz_vcf_decode_regions", "uz_vcf_index_names", "uz_vcf_io_stats",
     "uz_bam_decode_memory",
     "uz_bamsrc_open", "uz_bamsrc_close", "uz_bamsrc_n_contigs", "uz_bamsrc_contig_name", "uz_bamsrc_contig_length", "uz_bamsrc_tlen_head",
@@ -134,6 +134,7 @@ def load():
     lib.uz_reads_select_plan.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                          C.POINTER(C.c_void_p)]
     lib.uz_select_bl_wide.argtypes = [C.c_void_p]
+    lib.uz_select_base_quals.argtypes = [C.c_void_p]
     for fn in (lib.uz_select_n_records, lib.uz_select_n_cigar_total, lib.uz_select_n_row_units, lib.uz_select_n_seq_units, lib.uz_select_n_bl, lib.uz_select_n_bl_units,
                lib.uz_select_n_exc, lib.uz_select_n_qlow_pos, lib.uz_select_n_cigar_omitted, lib.uz_select_n_tuples, lib.uz_select_n_esc16, lib.uz_select_n_esc16_start8, lib.uz_select_n_esc16_narrow8, lib.uz_select_n_esc16_pair8, lib.uz_select_n_new_names):
         fn.argtypes = [C.c_void_p]
@@ -654,7 +655,7 @@ class ReadsSource:
         self.threads = threads
 
     def select(self, contig, lo, hi, alloc=None, want_index=False, all_bases=False, lists=True, with_end=None, extra=None, cigar_compact=True,
-               tuples=True, d16=True, start8=True, wide_no_units=False, narrow8=True, pair8=True, base_lists=None, tup8=None):
+               tuples=True, d16=True, start8=True, wide_no_units=False, narrow8=True, pair8=True, base_lists=None, tup8=None, base_quals=False):
         """The records the fetches (contig[k], lo[k], hi[k]) return plus their mates, as a packed table.
         tup8 (default: on, not for SV batches: _link_defaults): the dictionary index in one byte (uz_types.h tup8; abi.compact_tup) -- what crosses the link.  Records that
         are reachable only as mates are staged without their bases unless all_bases (--no-extended batches need them).
@@ -670,14 +671,16 @@ class ReadsSource:
         within +-75 kept records).
         pair8 (with start8): tlen, mate and name id in the pair form's ONE byte (uz_types.h, pair_d8) when the source's name ids ascend
         by first appearance (any decoder's table; else the narrow8 form).  The output then numbers the names of the selection by first
-        appearance: `.qname_map[output id]` = the source's id."""
+        appearance: `.qname_map[output id]` = the source's id.
+        base_quals (with base_lists; default off): the quality bits of the listed bases ride with them (uz_types.h bl_qlow) -- a record with a
+        base list then sends no low-quality positions."""
         contig, lo, hi, extra = _fetch_lists(contig, lo, hi, extra)
         tup8, base_lists = _link_defaults(tup8, base_lists, wide_no_units)
         sel = C.c_void_p()
         masks = extra is not None and lists and not all_bases
         _check(self.lib, self.lib.uz_reads_select_plan(self._h.ptr, int(contig.size), contig.ctypes.data, lo.ctypes.data,
                                                        hi.ctypes.data, 1 if all_bases else 0,
-                                                       ((3 if wide_no_units else 1) | (4 if base_lists else 0)) if masks else 0,
+                                                       ((3 if wide_no_units else 1) | (4 if base_lists else 0) | (8 if base_lists and base_quals else 0)) if masks else 0,
                                                        extra.ctypes.data if masks else None,
                                                        (1 | (2 if cigar_compact else 0) | (4 if lists else 0)) if tuples else 0,
                                                        int(self.threads), C.byref(sel)))
@@ -700,7 +703,7 @@ class ReadsSource:
                                                      else self.lib.uz_select_n_esc16_start8 if start8 else self.lib.uz_select_n_esc16)(sel)) if d16 else None,
                                         start8=bool(d16 and start8), narrow8=bool(d16 and start8 and narrow8), pair8=pair8,
                                         n_bl=n_bl if n_bl >= 0 else None, n_bl_units=int(self.lib.uz_select_n_bl_units(sel)), bl_wide=bool(self.lib.uz_select_bl_wide(sel)),
-                                        pk_sums=True, tup_off_link=bool(tup8 and n_tup >= 0))
+                                        pk_sums=True, tup_off_link=bool(tup8 and n_tup >= 0), base_quals=bool(n_bl >= 0 and self.lib.uz_select_base_quals(sel)))
             idx = np.zeros(max(1, n), np.int32) if want_index else None
             _check(self.lib, self.lib.uz_reads_select_fill(sel, int(self.threads), out.ref(),
                                                            idx.ctypes.data if want_index else None))
