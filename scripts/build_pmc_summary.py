@@ -18,7 +18,7 @@ try:
 except Exception:
     pass
 out = {
-    "kernel": "k_pack_link (header build of the link form, csrc/k_reads.hip)",
+    "kernel": "k_pack_link (header build of the link form, csrc/k_records.hip)",
     "kernel_source_sha": j.get("bench", {}).get("kernel_source_sha"),
     "how": "scripts/build_pmc.sh: rocprofv3 --kernel-trace --pmc in six passes over `bench.py --full --no-cpu --feed-dnms 0 --no-config5 --steps 1 --warmup 1` (the staged pass of "
            "100 k DNMs: %s chunks; under --pmc kernels run one at a time: solo durations); per launch, mean over the launches; scripts/build_pmc_summary.py" % j.get("bench", {}).get("chunks"),

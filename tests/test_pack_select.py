@@ -463,7 +463,7 @@ def test_pair_form_codes_and_its_fallback():
 
 def test_span_sums_of_a_packed_view_are_the_running_sums_of_its_columns():
     """uz_packed_block_sums (uz_types.h pk_sums) against numpy on a link-form selection: per span of 1024 records the running sums of the eleven
-    quantities the device's header build lays the records out by (csrc/k_reads.hip pk_vals)."""
+    quantities the device's header build lays the records out by (csrc/k_records.hip pk_vals)."""
     from synth.small import SmallConfig, make_small
     from helpers import tables
     ds = make_small(SmallConfig(seed=4242, n_dnms=40, cluster_prob=0.7, indel_prob=0.05, softclip_prob=0.05))

@@ -25,6 +25,36 @@ def _odd_table(n_dnms=40):
     return rh, arrs, N
 
 
+def _tup8_table(src, fetches, hot_keep=None, **select_kw):
+    """A selection with the dictionary index in one byte (uz_types.h tup8).  hot_keep: the hot table cut to that many entries -- few enough
+    that the escape list is exercised on a small table."""
+    part, idx = src.select(*fetches, want_index=True, tup8=False, **select_kw)
+    n = idx.size
+    if hot_keep is None:
+        assert abi.compact_tup(part)
+        return part
+    t = part.arrays["tup"][:n]
+    keep = np.argsort(-np.bincount(t, minlength=int(part.view.n_tup)), kind="stable")[:hot_keep]
+    assert abi.compact_tup(part)
+    a = part.arrays
+    full = abi.tup_column(part)
+    # rebuild the form with only `hot_keep` hot entries
+    lut = np.full(int(part.view.n_tup), 255, np.uint8)
+    lut[keep] = np.arange(keep.size, dtype=np.uint8)
+    a["tup8"][:n] = lut[full]
+    esc = a["tup8"][:n] == 255
+    ne = int(esc.sum())
+    e16 = np.zeros(max(1, ne), np.uint16)
+    e16[:ne] = full[esc]
+    off = np.zeros((n + abi.TUP8_SPAN - 1) // abi.TUP8_SPAN + 1, np.uint32)
+    off[1:] = np.cumsum(np.add.reduceat(esc.astype(np.int64), np.arange(0, n, abi.TUP8_SPAN)))
+    a["tup_hot"][:] = 0
+    a["tup_hot"][: keep.size] = keep
+    a["tup_esc"], a["tup_esc_off"] = e16, off
+    part.view.tup_esc, part.view.tup_esc_off, part.view.n_tup_esc = e16.ctypes.data, off.ctypes.data, ne
+    return part
+
+
 def test_every_form_decodes_to_the_source_columns(engine):
     rh, arrs, N = _odd_table()
     pk = io_native.pack_reads(rh, 20, with_end=True)
@@ -259,31 +289,8 @@ def test_the_dictionary_index_in_one_byte(engine):
     engine.free_reads(rid)
 
     def fresh(hot_keep=None):
-        part, _ = src.select(*fetches, want_index=True, tup8=False)
-        if hot_keep is not None:  # (few enough hot entries that the escape list is exercised on this small table)
-            t = part.arrays["tup"][:n]
-            keep = np.argsort(-np.bincount(t, minlength=int(part.view.n_tup)), kind="stable")[:hot_keep]
-            part.arrays["tup"][:n] = t  # unchanged; the cut happens below
-            assert abi.compact_tup(part)
-            a = part.arrays
-            full = abi.tup_column(part)
-            # rebuild the form with only `hot_keep` hot entries
-            lut = np.full(int(part.view.n_tup), 255, np.uint8)
-            lut[keep] = np.arange(keep.size, dtype=np.uint8)
-            a["tup8"][:n] = lut[full]
-            esc = a["tup8"][:n] == 255
-            ne = int(esc.sum())
-            e16 = np.zeros(max(1, ne), np.uint16)
-            e16[:ne] = full[esc]
-            off = np.zeros((n + abi.TUP8_SPAN - 1) // abi.TUP8_SPAN + 1, np.uint32)
-            off[1:] = np.cumsum(np.add.reduceat(esc.astype(np.int64), np.arange(0, n, abi.TUP8_SPAN)))
-            a["tup_hot"][:] = 0
-            a["tup_hot"][: keep.size] = keep
-            a["tup_esc"], a["tup_esc_off"] = e16, off
-            part.view.tup_esc, part.view.tup_esc_off, part.view.n_tup_esc = e16.ctypes.data, off.ctypes.data, ne
-        else:
-            assert abi.compact_tup(part)
-        return part
+        return _tup8_table(src, fetches, hot_keep)
+
     for hot_keep in (None, 3):
         part = fresh(hot_keep)
         assert "tup8" in part.arrays and "tup" not in part.arrays and (hot_keep is None or int(part.view.n_tup_esc) > 100)

@@ -1023,7 +1023,7 @@ int uz_reads_select_fill(const uz_select *s, int threads, uz_reads_packed_view *
 
 } // extern "C"
 
-// ---- span sums of a packed view (uz_types.h: pk_sums): the host's statement of csrc/k_reads.hip k_off_block_sums + the scan behind it
+// ---- span sums of a packed view (uz_types.h: pk_sums): the host's statement of csrc/k_records.hip k_off_block_sums + the scan behind it
 namespace {
 struct SumsView {
     const uz_reads_packed_view *v;

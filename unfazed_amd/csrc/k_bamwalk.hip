@@ -18,7 +18,7 @@
 //   k_bam_extract      one lane per KEPT record (the host's answer: uz_kept_rec): the plain columns of uz_reads_packed_view from the record's
 //                      bytes -- start, tlen, flag, l_seq, n_cigar, mapq, the aux bits (mate on the same reference, an SA tag, no CIGAR / SEQ /
 //                      QUAL), every CIGAR word, the bases as BAM packs them (four bits: the device's own row format), the one-bit plane
-//                      "quality below the threshold" -- at the offsets the header build (k_reads.hip: k_pack_rec) will derive for itself.
+//                      "quality below the threshold" -- at the offsets the header build (k_records.hip: k_pack_rec) will derive for itself.
 //
 // Parity: tests/test_bamwalk_gpu.py holds the descriptors against the host's twin (uz_stage_walk_host) and the table against the one the host
 // route stages for the same fetches (uz_reads_headers, then the read stage's results).
