@@ -52,7 +52,10 @@ extern "C" {
 #define UZ_K_VCF_COPY 10   /* not a kernel: the chunks' host-to-device copies on the copy stream, timed beside the two kernels */
 #define UZ_K_BCF_CELLS 11  /* k_bcf_cells: the values of a BCF's five FORMAT fields read into the sample table's rows (uz_samples_from_bcf), one launch per chunk */
 #define UZ_K_BCF_COPY 12   /* not a kernel: the copies of that route's chunks on the copy stream */
-#define UZ_K_COUNT 13
+#define UZ_K_HEAD_INFLATE 13 /* k_bgzf_inflate + k_bgzf_crc32 over the heads of a group of files (uz_head_walk) */
+#define UZ_K_HEAD_WALK 14    /* k_head_walk */
+#define UZ_K_HEAD_RANK 15    /* k_head_rank */
+#define UZ_K_COUNT 16
 
 typedef struct uz_ctx uz_ctx;
 
@@ -176,6 +179,35 @@ int uz_bam_walk(uz_ctx *ctx, const uint8_t *comp, int64_t comp_bytes, int64_t n_
                 const uint32_t *blk_crc /* [n_blocks] the CRC-32 of every block's footer: held against the inflated bytes (k_bgzf_crc32); NULL: not checked */,
                 int32_t n_tasks, const int32_t *task, int64_t n_spans, const int64_t *span, int64_t n_reach, const int32_t *reach, int64_t n_fetch,
                 const int32_t *fetch, int *walk_id, int64_t *n_desc);
+/* ---- The insert cutoff's input on the device: the template lengths of a file's first records and two order statistics of |tlen - 2 readlen|
+ * (read_collector.py:11-25: estimate_concordant_insert_len reads the first insert_size_max_sample + 1 records of the alignment file and takes the
+ * 99.5th percentile; the percentile's float arithmetic stays on the host, hostpath.cutoff_from_ranks).  Owner's thread only.
+ * uz_head_walk (read_collector.py:11-25: the loop over the file's first records): the heads of n_files files, in rounds.  *head_id = -1 opens a
+ *   head -- tlen columns of want[f] records per file -- and names it; a later call with that id appends to the same columns (its n_files and
+ *   want are the first call's, have[f] what the calls so far have taken).  comp (page-locked host memory is fastest): the compressed bytes of
+ *   this call's blocks; in_off[k]: where block k's DEFLATE stream starts in comp; isize[k]: its inflated size (<= 64 KiB); crc[k]: its footer's
+ *   CRC-32; blk_first [n_files + 1]: file f's blocks are [blk_first[f], blk_first[f + 1]) -- consecutive blocks of the file, none for a file
+ *   this call does not walk; start[f]: the first record's offset in the file's inflated bytes of this call.  The blocks are inflated in HBM,
+ *   every block is held against its CRC-32, and k_head_walk (one wavefront per file) writes the records' tlen behind the have[f] it holds.
+ *   -> per file: taken (records of this call), cursor (offset, in this call's inflated bytes of the file, of the first record not taken),
+ *   state: UZ_HEAD_DONE (have + taken = want), UZ_HEAD_END (the bytes ended at a record boundary or inside a record: a record is taken only
+ *   when its 4 + block_size bytes lie wholly inside the bytes given), UZ_HEAD_BAD (a block_size below 32, a block that does not inflate to its
+ *   size, a CRC-32 mismatch: the FILE is bad, not the call), UZ_HEAD_NONE (no block of the file in this call).
+ * uz_head_rank (read_collector.py:11-25: `np.percentile(insert_sizes, 99.5)` over abs(tlen - 2 readlen)): per file the keys |tlen - 2 readlen| at
+ *   ranks k[f] and min(k[f] + 1, n - 1) of their ascending order, n = the records the file's column holds (k_head_rank: an exact radix select;
+ *   64-bit arithmetic, 0 <= readlen < 2^30).  k[f] < 0: the file is skipped (a / b = 0).  k[f] >= n: UZ_E_ARG.
+ * uz_head_fetch (read_collector.py:11-25, for the parity tests): file f's column, out [cap] -> *n records.
+ * uz_head_free: gives the head's columns up. */
+#define UZ_HEAD_NONE 0
+#define UZ_HEAD_DONE 1
+#define UZ_HEAD_END 2
+#define UZ_HEAD_BAD 3
+int uz_head_walk(uz_ctx *ctx, int *head_id, int32_t n_files, const uint8_t *comp, int64_t comp_bytes, int64_t n_blocks, const int64_t *in_off,
+                 const int32_t *isize, const uint32_t *crc, const int64_t *blk_first, const int64_t *start, const int64_t *want, const int64_t *have,
+                 int64_t *taken, int64_t *cursor, int32_t *state);
+int uz_head_rank(uz_ctx *ctx, int head_id, int32_t readlen, const int64_t *k, uint32_t *a, uint32_t *b);
+int uz_head_fetch(uz_ctx *ctx, int head_id, int32_t file, int32_t *out, int64_t cap, int64_t *n);
+int uz_head_free(uz_ctx *ctx, int head_id);
 /* k_bgzf_crc32 alone (the parity tests hold it against zlib): blocks data[off[k] .. off[k + 1]) of at most 64 KiB (host memory), want[k] their CRC-32;
  * *first_bad = -1, or a block whose checksum differs */
 int uz_crc32_blocks(uz_ctx *ctx, const uint8_t *data, int64_t n_blocks, const int64_t *off, const uint32_t *want, int64_t *first_bad);

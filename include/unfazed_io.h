@@ -293,6 +293,24 @@ int32_t uz_bamsrc_n_contigs(const uz_bamsrc *s);
 const char *uz_bamsrc_contig_name(const uz_bamsrc *s, int32_t i);
 int32_t uz_bamsrc_contig_length(const uz_bamsrc *s, int32_t i);
 int64_t uz_bamsrc_tlen_head(const uz_bamsrc *s, int32_t *out, int64_t cap); /* as uz_bam_tlen_head */
+/* ---- Where a file's head lies (the insert-size estimate reads the first records of the file, read_collector.py:11-25; the device route walks
+ * them itself: unfazed_hip.h uz_head_walk).  A source opened with head_records = 0 reads no record, but its header parse knows where the first
+ * alignment record starts:
+ * uz_bamsrc_first_voff  out [n_files]: that record's virtual offset in the source's numbering (compressed offset of its block << 16 | offset in
+ *                       the block's inflated bytes; a header that ends with its block names the start of the next block).
+ * uz_bamsrc_list_blocks the BGZF blocks of one file from compressed offset `coff` (the source's numbering) on.  Stops when the blocks' ISIZE sum
+ *                       has reached want_bytes (at least one block is listed), at the end of the file (*at_end = 1), or after `cap` blocks.  Per
+ *                       block: its offset, its size in the file, ISIZE, the footer's CRC-32, where its DEFLATE stream starts.  It hops from header
+ *                       to header through the map (BSIZE, then ISIZE and CRC at the block's end): nothing is inflated.  A header that is not a BGZF
+ *                       header, a block that runs beyond the file or declares more than 64 KiB: UZ_IO_E_FORMAT, as the block reader.  The empty
+ *                       EOF block is listed like any other (ISIZE 0).
+ * uz_bamsrc_gather_ranges  n byte ranges, range i from source srcs[i] at src_off[i], copied to dst + dst_off[i] on the library's threads: the
+ *                       compressed bytes of a head are ONE contiguous range of its file, so the gather of a group of files is one copy each. */
+int uz_bamsrc_first_voff(const uz_bamsrc *s, uint64_t *out);
+int uz_bamsrc_list_blocks(const uz_bamsrc *s, int64_t coff, int64_t want_bytes, int64_t cap, int64_t *blk_off, int32_t *blk_csize, int32_t *blk_isize,
+                          uint32_t *blk_crc, int64_t *blk_data, int64_t *n_out, int *at_end);
+int uz_bamsrc_gather_ranges(const uz_bamsrc *const *srcs, int32_t n, const int64_t *src_off, const int64_t *bytes, const int64_t *dst_off, uint8_t *dst,
+                            int64_t dst_cap, int threads);
 const char *uz_inflate_backend(void); /* "libdeflate" (found at run time) or "zlib" */
 int uz_io_default_threads(void);      /* what `threads <= 0` means: CPUs of the affinity mask, held to twice the cgroup CPU quota */
 int uz_io_cpu_quota(void);            /* CPUs the container's cgroup grants (cpu.max), 0 = unlimited */

@@ -494,6 +494,8 @@ void uz_destroy(uz_ctx *c) {
 #undef UZ_X
     }
     for (void *b : c->book.take_parked()) (void)hipFree(b);
+    for (auto &h : c->heads) { h.tlen.release(); h.first_d.release(); }
+    c->hd_comp.release(); c->hd_out.release(); c->hd_i64.release(); c->hd_i32.release(); c->hd_u32.release();
     for (FindSlot &a : c->find_alt) {
         a.cnt_c.release(); a.cnt_h.release(); a.win_range.release(); a.cand_off.release(); a.het_off.release();
         a.cand_idx.release(); a.het_idx.release(); a.cand_flags.release();
@@ -2735,6 +2737,166 @@ int uz_crc32_blocks(uz_ctx *c, const uint8_t *data, int64_t n_blocks, const int6
         UZ_HIP(hipStreamSynchronize(c->stream));
         (void)hipFree(d); (void)hipFree(d_off); (void)hipFree(d_want); (void)hipFree(d_err);
         if (e) *first_bad = e - 1;
+    });
+}
+
+// ---- the heads of a cohort's alignment files (read_collector.py:11-25; csrc/k_bamhead.hip, csrc/headwalk.hpp)
+static uz_ctx::HeadDev &head_of(uz_ctx *c, int id) {
+    UZ_REQUIRE(id >= 0 && id < (int)c->heads.size() && c->heads[(size_t)id].live, UZ_E_ARG, "unknown head id");
+    return c->heads[(size_t)id];
+}
+
+int uz_head_walk(uz_ctx *c, int *head_id, int32_t n_files, const uint8_t *comp, int64_t comp_bytes, int64_t n_blocks, const int64_t *in_off,
+                 const int32_t *isize, const uint32_t *crc, const int64_t *blk_first, const int64_t *start, const int64_t *want, const int64_t *have,
+                 int64_t *taken, int64_t *cursor, int32_t *state) {
+    return guarded(c, [&] {
+        UZ_REQUIRE(head_id && n_files >= 1 && n_files < (1 << 24) && n_blocks >= 0 && n_blocks < ((int64_t)1 << 31) && comp_bytes >= 0 && blk_first && start && want && have &&
+                       taken && cursor && state && (n_blocks == 0 || (comp && in_off && isize && crc)),
+                   UZ_E_ARG, "bad arguments");
+        const size_t nf = (size_t)n_files, nb = (size_t)n_blocks;
+        UZ_REQUIRE(blk_first[0] == 0 && blk_first[nf] == n_blocks, UZ_E_ARG, "bad block table (blk_first)");
+        for (size_t f = 0; f < nf; f++) UZ_REQUIRE(blk_first[f] <= blk_first[f + 1], UZ_E_ARG, "bad block table (blk_first)");
+        std::vector<int64_t> out_off(nb + 1, 0);
+        for (size_t k = 0; k < nb; k++) {
+            UZ_REQUIRE(in_off[k] >= 0 && in_off[k] < comp_bytes && isize[k] >= 0 && isize[k] <= 65536, UZ_E_ARG, "bad block table (a BGZF block inflates to at most 64 KiB)");
+            out_off[k + 1] = out_off[k] + isize[k];
+        }
+        // the head: a new one is entered only when the whole call has gone through
+        const bool fresh = *head_id < 0;
+        uz_ctx::HeadDev made;
+        uz_ctx::HeadDev *H = fresh ? &made : &head_of(c, *head_id);
+        if (fresh) {
+            made.n_files = n_files; made.want.assign(want, want + nf); made.have.assign(nf, 0); made.first.assign(nf + 1, 0);
+            for (size_t f = 0; f < nf; f++) {
+                UZ_REQUIRE(want[f] >= 0 && want[f] <= INT32_MAX, UZ_E_ARG, "bad record count wanted");
+                made.first[f + 1] = made.first[f] + want[f];
+            }
+        } else {
+            UZ_REQUIRE(H->n_files == n_files, UZ_E_ARG, "the head holds another number of files");
+            for (size_t f = 0; f < nf; f++) UZ_REQUIRE(H->want[f] == want[f], UZ_E_ARG, "the head was opened with other record counts");
+        }
+        std::vector<int32_t> ok(nf, 0);
+        for (size_t f = 0; f < nf; f++) {
+            UZ_REQUIRE(have[f] == H->have[f], UZ_E_ARG, "have[] is not what the head's walks have taken so far");
+            const int64_t len = out_off[(size_t)blk_first[f + 1]] - out_off[(size_t)blk_first[f]];
+            ok[f] = blk_first[f + 1] > blk_first[f] ? 1 : 0;
+            UZ_REQUIRE(!ok[f] || (start[f] >= 0 && start[f] <= len), UZ_E_ARG, "a file's start offset lies outside its bytes");
+        }
+        try {
+            if (fresh) {
+                made.tlen.ensure((size_t)made.first[nf] + 1);
+                made.first_d.ensure(nf + 1);
+                UZ_HIP(hipMemcpyAsync(made.first_d.p, made.first.data(), (nf + 1) * 8, hipMemcpyHostToDevice, c->stream));
+            }
+            // one table of 64-bit columns, one of 32-bit ones
+            enum { I_IN = 0 };
+            const size_t o_out = nb, o_base = o_out + nb + 1, o_start = o_base + nf + 1, o_want = o_start + nf, o_have = o_want + nf, o_taken = o_have + nf,
+                         o_cursor = o_taken + nf, n64 = o_cursor + nf;
+            std::vector<int64_t> t64(n64, 0);
+            for (size_t k = 0; k < nb; k++) t64[I_IN + k] = in_off[k];
+            std::copy(out_off.begin(), out_off.end(), t64.begin() + (ptrdiff_t)o_out);
+            for (size_t f = 0; f <= nf; f++) t64[o_base + f] = out_off[(size_t)blk_first[f]];
+            for (size_t f = 0; f < nf; f++) { t64[o_start + f] = ok[f] ? start[f] : 0; t64[o_want + f] = want[f]; t64[o_have + f] = have[f]; }
+            const size_t o_ok = 0, o_state = nf, o_flags = 2 * nf, n32 = o_flags + 4 * (nf + 1); // flags: [cursor, err, crc err, -] for the group, then per file
+            c->hd_comp.ensure((size_t)comp_bytes + 1024); c->hd_out.ensure((size_t)out_off[nb] + 64);
+            c->hd_i64.ensure(n64); c->hd_i32.ensure(n32); c->hd_u32.ensure(nb + 1);
+            hipStream_t st = c->stream;
+            int64_t *d64 = c->hd_i64.p;
+            int32_t *d32 = c->hd_i32.p;
+            UZ_HIP(hipMemcpyAsync(d64, t64.data(), n64 * 8, hipMemcpyHostToDevice, st));
+            std::vector<int32_t> flags(4 * (nf + 1), 0);
+            if (nb) {
+                UZ_HIP(hipMemsetAsync(c->hd_comp.p + comp_bytes, 0, 1024, st));
+                UZ_HIP(hipMemcpyAsync(c->hd_comp.p, comp, (size_t)comp_bytes, hipMemcpyHostToDevice, st));
+                UZ_HIP(hipMemcpyAsync(c->hd_u32.p, crc, nb * 4, hipMemcpyHostToDevice, st));
+                const int64_t padded = (comp_bytes + 1024) & ~(int64_t)3;
+                auto inflate_and_check = [&](size_t b0, size_t b1, size_t slot) {
+                    uz_launch_inflate(c, st, (int64_t)(b1 - b0), c->hd_comp.p, padded, d64 + I_IN + b0, d64 + o_out + b0, c->hd_out.p, d32 + o_flags + 4 * slot);
+                    uz_launch_crc32(c, st, (int64_t)(b1 - b0), c->hd_out.p, d64 + o_out + b0, c->hd_u32.p + b0, d32 + o_flags + 4 * slot + 2);
+                };
+                {
+                    ProfScope ps(c, UZ_K_HEAD_INFLATE);
+                    inflate_and_check(0, nb, 0);
+                }
+                UZ_HIP(hipMemcpyAsync(flags.data(), d32 + o_flags, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+                UZ_HIP(hipStreamSynchronize(st));
+                if (flags[1] || flags[2]) { // some block is bad: file by file, to know whose -- the FILE is marked, the call goes on
+                    for (size_t f = 0; f < nf; f++)
+                        if (ok[f]) inflate_and_check((size_t)blk_first[f], (size_t)blk_first[f + 1], f + 1);
+                    UZ_HIP(hipMemcpyAsync(flags.data(), d32 + o_flags, flags.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+                    UZ_HIP(hipStreamSynchronize(st));
+                    for (size_t f = 0; f < nf; f++)
+                        if (ok[f] && (flags[4 * (f + 1) + 1] || flags[4 * (f + 1) + 2])) ok[f] = -1;
+                }
+            }
+            UZ_HIP(hipMemcpyAsync(d32 + o_ok, ok.data(), nf * 4, hipMemcpyHostToDevice, st));
+            {
+                ProfScope ps(c, UZ_K_HEAD_WALK);
+                uz_launch_head_walk(c, st, n_files, c->hd_out.p, d64 + o_base, d32 + o_ok, d64 + o_start, d64 + o_want, d64 + o_have, fresh ? made.first_d.p : H->first_d.p,
+                                    fresh ? made.tlen.p : H->tlen.p, d64 + o_taken, d64 + o_cursor, d32 + o_state);
+            }
+            UZ_HIP(hipMemcpyAsync(taken, d64 + o_taken, nf * 8, hipMemcpyDeviceToHost, st));
+            UZ_HIP(hipMemcpyAsync(cursor, d64 + o_cursor, nf * 8, hipMemcpyDeviceToHost, st));
+            UZ_HIP(hipMemcpyAsync(state, d32 + o_state, nf * 4, hipMemcpyDeviceToHost, st));
+            UZ_HIP(hipStreamSynchronize(st));
+        } catch (...) {
+            (void)hipStreamSynchronize(c->stream);
+            if (fresh) { made.tlen.release(); made.first_d.release(); }
+            throw;
+        }
+        for (size_t f = 0; f < nf; f++) {
+            UZ_REQUIRE(taken[f] >= 0 && H->have[f] + taken[f] <= H->want[f], UZ_E_STATE, "the head walk took more records than wanted");
+            H->have[f] += taken[f];
+        }
+        if (fresh) {
+            made.live = true;
+            const int k = new_slot(c->heads);
+            c->heads[(size_t)k] = made;
+            *head_id = k;
+        }
+    });
+}
+
+int uz_head_rank(uz_ctx *c, int head_id, int32_t readlen, const int64_t *k, uint32_t *a, uint32_t *b) {
+    return guarded(c, [&] {
+        uz_ctx::HeadDev &H = head_of(c, head_id);
+        UZ_REQUIRE(k && a && b && readlen >= 0 && readlen < (1 << 30), UZ_E_ARG, "bad arguments (0 <= readlen < 2^30)");
+        const size_t nf = (size_t)H.n_files;
+        std::vector<int64_t> t64(2 * nf);
+        for (size_t f = 0; f < nf; f++) {
+            UZ_REQUIRE(k[f] < H.have[f] || k[f] < 0, UZ_E_ARG, "a rank beyond the records the file's column holds");
+            t64[f] = k[f] < 0 ? 0 : H.have[f]; // (a skipped file: no records as far as the kernel is concerned)
+            t64[nf + f] = k[f];
+        }
+        c->hd_i64.ensure(2 * nf); c->hd_u32.ensure(2 * nf);
+        hipStream_t st = c->stream;
+        UZ_HIP(hipMemcpyAsync(c->hd_i64.p, t64.data(), 2 * nf * 8, hipMemcpyHostToDevice, st));
+        {
+            ProfScope ps(c, UZ_K_HEAD_RANK);
+            uz_launch_head_rank(c, st, H.n_files, H.tlen.p, H.first_d.p, c->hd_i64.p, c->hd_i64.p + nf, readlen, c->hd_u32.p, c->hd_u32.p + nf);
+        }
+        UZ_HIP(hipMemcpyAsync(a, c->hd_u32.p, nf * 4, hipMemcpyDeviceToHost, st));
+        UZ_HIP(hipMemcpyAsync(b, c->hd_u32.p + nf, nf * 4, hipMemcpyDeviceToHost, st));
+        UZ_HIP(hipStreamSynchronize(st));
+    });
+}
+
+int uz_head_fetch(uz_ctx *c, int head_id, int32_t file, int32_t *out, int64_t cap, int64_t *n) {
+    return guarded(c, [&] {
+        uz_ctx::HeadDev &H = head_of(c, head_id);
+        UZ_REQUIRE(file >= 0 && file < H.n_files && n && cap >= 0 && (cap == 0 || out), UZ_E_ARG, "bad arguments");
+        *n = std::min<int64_t>(cap, H.have[(size_t)file]);
+        if (*n) UZ_HIP(hipMemcpyAsync(out, H.tlen.p + H.first[(size_t)file], (size_t)*n * 4, hipMemcpyDeviceToHost, c->stream));
+        UZ_HIP(hipStreamSynchronize(c->stream));
+    });
+}
+
+int uz_head_free(uz_ctx *c, int head_id) {
+    return guarded(c, [&] {
+        uz_ctx::HeadDev &H = head_of(c, head_id);
+        UZ_HIP(hipStreamSynchronize(c->stream));
+        H.tlen.release(); H.first_d.release();
+        H = uz_ctx::HeadDev();
     });
 }
 

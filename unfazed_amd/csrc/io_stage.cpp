@@ -86,6 +86,7 @@ struct uz_bamsrc {
     std::vector<std::string> contigs;
     std::vector<int32_t> contig_len;
     std::vector<int32_t> tlen_head;
+    std::vector<uint64_t> first_voff; // [n_files]: the virtual offset (the source's) of every file's first alignment record, where its header ends
     // A source over many files (uz_bamsrc_open_many) is ONE virtual file: `map` is a reserved address range in which file f is mapped at
     // file_base[f] (the running sum of the sizes rounded up to 64 KiB), `size` the whole range; contigs / contig_len / refs are those of file 0, then
     // file 1, ... (ref_base: the running sum of their counts), every offset of a file's index shifted by its base.  A record's refID and next_refID
@@ -306,6 +307,12 @@ void open_source(uz_bamsrc &S, const char *path, const char *bai_path, int64_t h
     }
     if (S.contigs.size() != S.refs.size()) fail(UZ_IO_E_FORMAT, "the index %s holds %zu references, the BAM header %zu", bai.c_str(), S.refs.size(), S.contigs.size());
     s.blk = 0;
+    { // where the first alignment record starts: inside the block that holds the cursor, or -- the header ends with its block -- at the next one's start
+        uint64_t v = (uint64_t)s.next_coff << 16;
+        for (const auto &b : s.blks)
+            if (s.cur < b.at + b.isize) { v = ((uint64_t)b.coff << 16) | (uint64_t)(s.cur - b.at); break; }
+        S.first_voff = {v};
+    }
     while ((int64_t)S.tlen_head.size() < head_records) {
         uint64_t voff;
         const uint8_t *p;
@@ -358,6 +365,7 @@ void open_many(uz_bamsrc &S, int n, const char *const *paths, const char *const 
             S.refs.push_back(std::move(r));
         }
         for (size_t c = 0; c < one.contigs.size(); c++) { S.contigs.push_back(one.contigs[c]); S.contig_len.push_back(one.contig_len[c]); S.ref_file.push_back(f); }
+        S.first_voff.push_back(one.first_voff[0] + vb);
         S.file_base.push_back(next); S.ref_base.push_back((int32_t)nr);
         S.salt1.push_back(f ? mix64((uint64_t)f) : 0);
         S.salt2.push_back(f ? (uint32_t)(mix64(~(uint64_t)f) >> 32) : 0u);
@@ -1589,6 +1597,50 @@ int64_t uz_bamsrc_tlen_head(const uz_bamsrc *s, int32_t *out, int64_t cap) {
     const int64_t k = std::min<int64_t>(cap, (int64_t)s->tlen_head.size());
     memcpy(out, s->tlen_head.data(), (size_t)k * sizeof(int32_t));
     return k;
+}
+int uz_bamsrc_first_voff(const uz_bamsrc *s, uint64_t *out) {
+    if (!s || !out) { last_error = "null argument"; return UZ_IO_E_ARG; }
+    memcpy(out, s->first_voff.data(), s->first_voff.size() * sizeof(uint64_t));
+    return UZ_IO_OK;
+}
+// the BGZF blocks of a file from `coff` on, hopping from header to header through the map: nothing is inflated (block_at makes every check)
+int uz_bamsrc_list_blocks(const uz_bamsrc *s, int64_t coff, int64_t want_bytes, int64_t cap, int64_t *blk_off, int32_t *blk_csize, int32_t *blk_isize,
+                          uint32_t *blk_crc, int64_t *blk_data, int64_t *n_out, int *at_end) {
+    if (!s || !n_out || !at_end || cap < 0 || (cap > 0 && (!blk_off || !blk_csize || !blk_isize || !blk_crc || !blk_data))) { last_error = "null argument"; return UZ_IO_E_ARG; }
+    *n_out = 0; *at_end = 0;
+    return guarded([&] {
+        const size_t lim = chain_end(*s, coff);
+        int64_t n = 0, sum = 0;
+        for (;;) {
+            if (n > 0 && sum >= want_bytes) break;
+            BlockHdr h;
+            if (!block_at(*s, coff, lim, h)) {
+                if ((size_t)coff != lim) fail(UZ_IO_E_FORMAT, "truncated BGZF block at byte %lld", (long long)coff); // (fewer than 18 bytes left: no header fits)
+                *at_end = 1;
+                break;
+            }
+            if (h.isize > 65536u) fail(UZ_IO_E_FORMAT, "BGZF block at byte %lld declares %u inflated bytes (a block holds at most 65536)", (long long)coff, h.isize);
+            if (n >= cap) break;
+            blk_off[n] = coff; blk_csize[n] = (int32_t)h.blen; blk_isize[n] = (int32_t)h.isize; blk_crc[n] = h.crc; blk_data[n] = (int64_t)h.cdata;
+            n++; sum += (int64_t)h.isize; coff += (int64_t)h.blen;
+            *n_out = n;
+        }
+    });
+}
+// the compressed bytes of several files' heads, each ONE contiguous range of its file, copied into one buffer on the pool's threads
+int uz_bamsrc_gather_ranges(const uz_bamsrc *const *srcs, int32_t n, const int64_t *src_off, const int64_t *bytes, const int64_t *dst_off, uint8_t *dst,
+                            int64_t dst_cap, int threads) {
+    if (n < 0 || (n > 0 && (!srcs || !src_off || !bytes || !dst_off || !dst))) { last_error = "null argument"; return UZ_IO_E_ARG; }
+    return guarded([&] {
+        for (int32_t i = 0; i < n; i++)
+            if (!srcs[i] || src_off[i] < 0 || bytes[i] < 0 || (uint64_t)src_off[i] + (uint64_t)bytes[i] > (uint64_t)srcs[i]->size || dst_off[i] < 0 ||
+                (uint64_t)dst_off[i] + (uint64_t)bytes[i] > (uint64_t)dst_cap)
+                fail(UZ_IO_E_ARG, "range %d lies outside its file or the buffer", (int)i);
+        parallel_slices(n, resolve_threads(threads), [&](int64_t lo, int64_t hi, int) {
+            for (int64_t i = lo; i < hi; i++)
+                if (bytes[i]) memcpy(dst + dst_off[i], srcs[i]->map + src_off[i], (size_t)bytes[i]);
+        });
+    });
 }
 const char *uz_inflate_backend(void) { return libdeflate().ok ? "libdeflate" : "zlib"; }
 int uz_io_default_threads(void) { return resolve_threads(0); }

@@ -414,6 +414,21 @@ struct uz_ctx {
     WalkSlot walk[WALK_SLOTS];
     WalkBook book; // which slots are held, the largest request every kind of buffer has seen, the blocks that were outgrown (its own lock)
 
+    // the heads of a cohort's alignment files (k_bamhead.hip, uz_head_walk): a head holds the tlen columns of its files, file f's at first[f] with
+    // room for want[f] records, have[f] of them written by the walks so far; the walk's own buffers (hd_*) are the context's and grow like the others
+    struct HeadDev {
+        bool live = false;
+        int32_t n_files = 0;
+        std::vector<int64_t> want, have, first; // first: [n_files + 1]
+        DevBuf<int32_t> tlen;
+        DevBuf<int64_t> first_d;
+    };
+    std::vector<HeadDev> heads;
+    DevBuf<uint8_t> hd_comp, hd_out;
+    DevBuf<int64_t> hd_i64;
+    DevBuf<int32_t> hd_i32;
+    DevBuf<uint32_t> hd_u32;
+
     // uz_reads_names: ids / lengths / offsets / bytes on the device and one page-locked staging block, kept from call to call
     DevBuf<uint32_t> nm_ids, nm_len, nm_off;
     DevBuf<int64_t> rf_first; // uz_reads_files: the files' first records, and ...
@@ -547,6 +562,11 @@ void uz_launch_bam_extract(uz_ctx *c, hipStream_t st, int64_t n, const uint8_t *
                            int thr, int32_t *start, int32_t *tlen, int32_t *mate, uint32_t *qname, uint16_t *flag, uint16_t *l_seq, uint16_t *n_cigar, uint8_t *mapq,
                            uint8_t *aux_col, uint32_t *cigar, uint8_t *seq4, uint32_t *plane, int32_t *err, uint8_t *names, int64_t n_cigar_total, int64_t n_row_units,
                            int64_t n_seq_units, int64_t names_bytes);
+// the head walk and the rank selection (k_bamhead.hip): device pointers
+void uz_launch_head_walk(uz_ctx *c, hipStream_t st, int32_t n_files, const uint8_t *buf, const int64_t *base, const int32_t *ok, const int64_t *start,
+                         const int64_t *want, const int64_t *have, const int64_t *first, int32_t *tlen, int64_t *taken, int64_t *cursor, int32_t *state);
+void uz_launch_head_rank(uz_ctx *c, hipStream_t st, int32_t n_files, const int32_t *tlen, const int64_t *first, const int64_t *n_of, const int64_t *k_of,
+                         int32_t readlen, uint32_t *out_a, uint32_t *out_b);
 // CRC-32 of inflated blocks against their BGZF footers (k_inflate.hip): device pointers; *err: 0, or 1 + a block whose checksum differs
 void uz_launch_crc32(uz_ctx *c, hipStream_t st, int64_t n_blocks, const uint8_t *out, const int64_t *out_off, const uint32_t *want, int32_t *err);
 int uz_phase_votes_impl(uz_ctx *c, int64_t *vote_off, int32_t *vote_val);

@@ -18,6 +18,10 @@ SIZING_REDUCED_WORDS = 263  # unfazed_hip.h UZ_SIZING_REDUCED_WORDS
 K_SITE_SCAN, K_WINDOW_COUNT, K_WINDOW_FILL, K_PHASE, K_SIZING, K_CNV, K_FAMILY_PACK, K_CNV_DENSE = 0, 1, 2, 3, 4, 5, 6, 7
 K_VCF_TABS, K_VCF_CELLS, K_VCF_COPY = 8, 9, 10  # uz_samples_from_text: the two kernels and (not a kernel) the chunks' copies
 K_BCF_CELLS, K_BCF_COPY = 11, 12  # uz_samples_from_bcf: its kernel and (not a kernel) its chunks' copies
+K_HEAD_INFLATE, K_HEAD_WALK, K_HEAD_RANK = 13, 14, 15  # uz_head_walk: inflate + CRC-32 of a group's heads, k_head_walk; uz_head_rank: k_head_rank
+HEAD_NONE, HEAD_DONE, HEAD_END, HEAD_BAD = 0, 1, 2, 3  # unfazed_hip.h UZ_HEAD_*
+HEAD_MAX_BYTES = 8 << 30  # inflated bytes of one uz_head_walk launch unless UZ_HEAD_MAX_BYTES says otherwise: a choice, not a measurement
+HEAD_MAX_ROUNDS = 8       # walks of one file before it is handed back to the host route
 
 EXPORTS = [
     "uz_create", "uz_destroy", "uz_last_error", "uz_sync", "uz_set_params",
@@ -29,6 +33,7 @@ EXPORTS = [
     "uz_site_scan", "uz_site_scan_many", "uz_site_classes", "uz_find", "uz_find_fetch", "uz_find_cohort",
     "uz_phase", "uz_phase_begin", "uz_phase_end", "uz_phase_cohort", "uz_phase_cohort_joined", "uz_phase_votes", "uz_phase_groups", "uz_phase_sizing_fetch", "uz_phase_cnv", "uz_phase_cnv_cohort", "uz_phase_cnv_sites",
     "uz_prof_enable", "uz_prof_reset", "uz_prof_get", "uz_prof_units",
+    "uz_head_walk", "uz_head_rank", "uz_head_fetch", "uz_head_free",
 ]
 
 _lib = None
@@ -113,6 +118,10 @@ def load_library(path: Optional[str] = None):
     L.uz_phase_votes.argtypes = [vp, vp, vp]
     L.uz_phase_groups.argtypes = [vp, vp, vp]
     L.uz_phase_sizing_fetch.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.uz_head_walk.argtypes = [vp, C.POINTER(C.c_int), C.c_int32, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.uz_head_rank.argtypes = [vp, C.c_int, C.c_int32, vp, vp, vp]
+    L.uz_head_fetch.argtypes = [vp, C.c_int, C.c_int32, vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.uz_head_free.argtypes = [vp, C.c_int]
     L.uz_prof_enable.argtypes = [vp, C.c_int]
     L.uz_prof_reset.argtypes = [vp]
     L.uz_prof_get.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
@@ -159,6 +168,9 @@ class HipEngine:
             pool.free_all()
             pair.free_all()
         self._slots = {}
+        if getattr(self, "_head_pin", None) is not None:
+            self._head_pin[0].free_all()
+            self._head_pin = None
         if getattr(self, "h", None):
             self.L.uz_destroy(self.h)
             self.h = None
@@ -846,6 +858,177 @@ class HipEngine:
             self._ck(self.L.uz_phase_cnv_sites(self.h, off.ctypes.data, pos.ctypes.data), "uz_phase_cnv_sites")
             r["lists"] = [(pos[off[2 * k]: off[2 * k + 1]], pos[off[2 * k + 1]: off[2 * k + 2]]) for k in range(n)]
         return r
+
+    # ---------------------------------------------------------- the heads of a cohort's alignment files (read_collector.py:11-25)
+    def head_walk(self, head: int, comp: np.ndarray, comp_bytes: int, in_off, isize, crc, blk_first, start, want, have):
+        """uz_head_walk: one round over the blocks given (head = -1 opens a head) -> (head id, taken, cursor, state) per file"""
+        i64 = lambda a: np.ascontiguousarray(a, np.int64)
+        in_off, blk_first, start, want, have = i64(in_off), i64(blk_first), i64(start), i64(want), i64(have)
+        isize, crc = np.ascontiguousarray(isize, np.int32), np.ascontiguousarray(crc, np.uint32)
+        nf = int(want.size)
+        taken, cursor, state = np.zeros(nf, np.int64), np.zeros(nf, np.int64), np.zeros(nf, np.int32)
+        hid = C.c_int(int(head))
+        self._ck(self.L.uz_head_walk(self.h, C.byref(hid), nf, comp.ctypes.data, int(comp_bytes), int(in_off.size), in_off.ctypes.data, isize.ctypes.data,
+                                     crc.ctypes.data, blk_first.ctypes.data, start.ctypes.data, want.ctypes.data, have.ctypes.data, taken.ctypes.data,
+                                     cursor.ctypes.data, state.ctypes.data), "uz_head_walk")
+        return int(hid.value), taken, cursor, state
+
+    def head_rank(self, head: int, readlen: int, k):
+        """uz_head_rank: per file the keys |tlen - 2 readlen| at ranks k[f] and min(k[f] + 1, n - 1); k[f] < 0 skips the file -> (a, b) uint32"""
+        k = np.ascontiguousarray(k, np.int64)
+        a, b = np.zeros(k.size, np.uint32), np.zeros(k.size, np.uint32)
+        self._ck(self.L.uz_head_rank(self.h, int(head), int(readlen), k.ctypes.data, a.ctypes.data, b.ctypes.data), "uz_head_rank")
+        return a, b
+
+    def head_fetch(self, head: int, file: int, cap: int) -> np.ndarray:
+        out = np.zeros(max(1, int(cap)), np.int32)
+        n = C.c_int64(0)
+        self._ck(self.L.uz_head_fetch(self.h, int(head), int(file), out.ctypes.data, int(cap), C.byref(n)), "uz_head_fetch")
+        return out[: int(n.value)].copy()
+
+    def head_free(self, head: int):
+        self._ck(self.L.uz_head_free(self.h, int(head)), "uz_head_free")
+
+    def _head_pinned(self, nbytes: int) -> np.ndarray:
+        """page-locked memory for the gathered heads of a group, kept and grown from call to call"""
+        pin = getattr(self, "_head_pin", None)
+        if pin is None or pin[1].size < nbytes:
+            if pin is not None:
+                pin[0].free_all()
+            pool = PinnedPool()
+            self._head_pin = pin = (pool, pool.alloc(int(nbytes) + int(nbytes) // 4 + (1 << 20)))
+        return pin[1]
+
+    @staticmethod
+    def _head_first_estimate(src, coff: int, start: int, want: int) -> int:
+        """Round 1's byte estimate of one file: the host inflates the file's first data block itself, takes the mean record size there and asks
+        for `want` times that plus a margin (UZ_HEAD_FIRST_BYTES overrides it).  A block that holds no whole record: 512 bytes a record."""
+        env = os.environ.get("UZ_HEAD_FIRST_BYTES")
+        if env:
+            return max(1, int(env))
+        import zlib
+        b = src.list_blocks(coff, 1, cap=1)
+        mean = 512.0
+        if b["off"].size:
+            with open(src.path, "rb") as fh:
+                fh.seek(int(b["data"][0]))
+                raw = fh.read(int(b["off"][0]) + int(b["csize"][0]) - 8 - int(b["data"][0]))
+            data = zlib.decompressobj(-15).decompress(raw)
+            c, n = int(start), 0
+            while c + 4 <= len(data):
+                bs = int.from_bytes(data[c: c + 4], "little", signed=True)
+                if bs < 32 or c + 4 + bs > len(data):
+                    break
+                c, n = c + 4 + bs, n + 1
+            if n:
+                mean = (c - int(start)) / n
+        return int(want * mean) + int(want * mean) // 16 + (1 << 17)
+
+    def head_ranks(self, files, want: int, readlen: int, stats=None, fetch: bool = False):
+        """The two order statistics behind the insert cutoff of every file (read_collector.py:11-25), from the first `want` records of each:
+        -> per file (n, a, b) -- n records read (the whole file when it holds fewer), a / b the keys |tlen - 2 readlen| at ranks
+        floor((n - 1) 0.995) and the next (hostpath.cutoff_from_ranks makes the cutoff of them) -- or None: the file is handed back to the
+        host route (a record or a block the device refuses, a file the lister refuses, no record at all, more than HEAD_MAX_ROUNDS walks).
+        files: paths of indexed BAMs, or io_native.BamSource objects (opened without a head).  Rounds: every file asks for an estimate of the
+        bytes its `want` records take; a file whose bytes ended before its count goes on in the next round from where the cursor fell.
+        Groups: one uz_head_walk holds at most UZ_HEAD_MAX_BYTES inflated bytes (a larger file is a group of its own, cut by rounds).
+        stats: a dict whose "cutoff_walk_calls" counts the walks.  fetch: -> (the list, the tlen column of every file or None)."""
+        import zlib
+        from .hostpath import head_rank_index
+        from .io_native import BamSource, IoError
+        nf = len(files)
+        out = [None] * nf
+        cols = [None] * nf
+        want = int(want)
+        if nf == 0 or want <= 0 or want > 0x7FFFFFFF or not (0 <= int(readlen) < (1 << 30)):
+            return (out, cols) if fetch else out
+        max_bytes = max(1, int(os.environ.get("UZ_HEAD_MAX_BYTES", HEAD_MAX_BYTES)))
+        srcs, st = [None] * nf, [None] * nf  # st: per file [coff, start, est bytes, rounds] while it is walked
+        for f, x in enumerate(files):
+            try:
+                srcs[f] = x if isinstance(x, BamSource) else BamSource(x, insert_size_max_sample=-1)
+                v = int(srcs[f].first_voff[0])
+                st[f] = [v >> 16, v & 0xFFFF, self._head_first_estimate(srcs[f], v >> 16, v & 0xFFFF, want), 0]
+            except (IoError, OSError, zlib.error):
+                st[f] = None  # the host route answers or raises for it
+        wants = np.full(nf, want, np.int64)
+        have = np.zeros(nf, np.int64)
+        finished = np.zeros(nf, bool)
+        head = -1
+        try:
+            while any(s is not None for s in st):
+                # this round's blocks, file by file
+                listed = {}
+                for f in range(nf):
+                    if st[f] is None:
+                        continue
+                    try:
+                        listed[f] = srcs[f].list_blocks(st[f][0], min(st[f][2], max_bytes))
+                    except IoError:
+                        st[f] = None
+                groups, cur, cur_bytes = [], [], 0
+                for f, b in listed.items():
+                    nb = int(b["isize"].sum())
+                    if cur and cur_bytes + nb > max_bytes:
+                        groups.append(cur)
+                        cur, cur_bytes = [], 0
+                    cur.append(f)
+                    cur_bytes += nb
+                if cur:
+                    groups.append(cur)
+                for grp in groups:
+                    src_off = [int(listed[f]["off"][0]) if listed[f]["off"].size else 0 for f in grp]
+                    nbytes = [int(listed[f]["off"][-1] + listed[f]["csize"][-1]) - so if listed[f]["off"].size else 0 for f, so in zip(grp, src_off)]
+                    dst_off = np.concatenate([[0], np.cumsum(nbytes)]).astype(np.int64)
+                    comp = self._head_pinned(int(dst_off[-1]) + 64)
+                    BamSource.gather_ranges([srcs[f] for f in grp], src_off, nbytes, dst_off[:-1], comp)
+                    blk_first = np.zeros(nf + 1, np.int64)
+                    start = np.zeros(nf, np.int64)
+                    for f in grp:
+                        blk_first[f + 1] = listed[f]["off"].size
+                        start[f] = st[f][1]
+                    blk_first = np.cumsum(blk_first)
+                    in_off = np.concatenate([listed[f]["data"] - so + d for f, so, d in zip(grp, src_off, dst_off[:-1])] + [np.zeros(0, np.int64)])
+                    isize = np.concatenate([listed[f]["isize"] for f in grp] + [np.zeros(0, np.int32)])
+                    crc = np.concatenate([listed[f]["crc"] for f in grp] + [np.zeros(0, np.uint32)])
+                    head, taken, cursor, state = self.head_walk(head, comp, int(dst_off[-1]), in_off, isize, crc, blk_first, start, wants, have)
+                    if stats is not None:
+                        stats["cutoff_walk_calls"] = (stats["cutoff_walk_calls"] if "cutoff_walk_calls" in stats else 0) + 1
+                    have += taken
+                    for f in grp:
+                        b, s = listed[f], st[f]
+                        cum = np.cumsum(b["isize"].astype(np.int64))
+                        total = int(cum[-1]) if cum.size else 0
+                        cu = int(cursor[f])
+                        if state[f] == HEAD_DONE:
+                            finished[f], st[f] = True, None
+                        elif state[f] == HEAD_END and b["at_end"]:
+                            finished[f], st[f] = cu == total, None  # (a record cut off by the file's end: the host route raises for it)
+                        elif state[f] == HEAD_END and s[3] + 1 < HEAD_MAX_ROUNDS:
+                            if cu >= total:
+                                s[0], s[1] = int(b["off"][-1]) + int(b["csize"][-1]), 0
+                            else:
+                                k = int(np.searchsorted(cum, cu, side="right"))
+                                s[0], s[1] = int(b["off"][k]), cu - (int(cum[k - 1]) if k else 0)
+                            left = want - int(have[f])
+                            used = cu - int(start[f])
+                            s[2] = (int(left * used / int(taken[f])) * 17 // 16 + (1 << 17)) if taken[f] > 0 else 2 * max(s[2], total)
+                            s[3] += 1
+                        else:
+                            st[f] = None  # HEAD_BAD, no block listed, or too many rounds: handed back
+            if head >= 0:
+                ks = np.array([head_rank_index(int(have[f])) if finished[f] and have[f] > 0 else -1 for f in range(nf)], np.int64)
+                if (ks >= 0).any():
+                    a, b = self.head_rank(head, int(readlen), ks)
+                    for f in range(nf):
+                        if ks[f] >= 0:
+                            out[f] = (int(have[f]), int(a[f]), int(b[f]))
+                            if fetch:
+                                cols[f] = self.head_fetch(head, f, int(have[f]))
+        finally:
+            if head >= 0:
+                self.head_free(head)
+        return (out, cols) if fetch else out
 
     # ---------------------------------------------------------- measurement
     def prof_enable(self, on=True):

@@ -88,6 +88,37 @@ def concordant_cutoff(tlen_head: np.ndarray, readlen: int, stdevs: int) -> float
     return frag_len + (stdev * stdevs)
 
 
+def head_rank_index(n: int) -> int:
+    """the lower of the two ranks numpy's `linear` percentile at 99.5 reads of n sorted values: floor((n - 1) * 0.995) in float64 -- the k
+    the device's rank selection is asked for (HipEngine.head_ranks) and cutoff_from_ranks interpolates from"""
+    return int(np.floor(np.float64(n - 1) * np.float64(0.995)))
+
+
+def cutoff_from_ranks(n: int, a: int, b: int, readlen: int, stdevs: int) -> float:
+    """concordant_cutoff (read_collector.py:11-25) from the two order statistics the percentile reads instead of the whole column: a / b are the
+    values |tlen - 2 readlen| at ranks k = floor((n - 1) 0.995) and min(k + 1, n - 1) of the ascending order (uz_head_rank).  numpy's `linear`
+    method in float64: vi = (n - 1) 0.995, g = vi - k, v = a + (b - a) g, and where g >= 0.5 v = b - (b - a) (1 - g) (numpy's _lerp); quirk Q8:
+    the standard deviation of the scalar is 0, so --stdevs only decides the result's type.  readlen is in a and b already.
+    tests/test_cutoff_ranks.py holds this against concordant_cutoff."""
+    vi = np.float64(n - 1) * np.float64(0.995)
+    g = vi - np.floor(vi)
+    fa, fb = np.float64(a), np.float64(b)
+    d = fb - fa
+    v = fa + d * g
+    if g >= 0.5:
+        v = fb - d * (np.float64(1) - g)
+    return int(v) + np.float64(0.0) * stdevs
+
+
+def cutoff_route() -> str:
+    """UZ_CUTOFF_ROUTE: "host" (default) -- a kid's insert cutoff comes from the head of its file as the source read it when it was opened;
+    "device" -- the heads of a call's files are walked and ranked on the device before any route asks (PhasingHost.prepare_cutoffs)"""
+    return "device" if __import__("os").environ.get("UZ_CUTOFF_ROUTE", "host").lower() == "device" else "host"
+
+
+_CUTOFF_RANKS: Dict[tuple, tuple] = {}  # (path, size, mtime, want, readlen) -> (n, a, b) the device found, for the process (as session._STAGERS)
+
+
 class _Log:
     def __init__(self, quiet: bool):
         self.quiet = quiet
@@ -202,7 +233,7 @@ class _Stats(dict):
     entered by their first increment"""
 
     ROUTE_KEYS = ("find_cohort_calls", "find_kid_calls", "cnv_cohort_calls", "cnv_kid_calls", "samples_parsed_device", "sites_unsettled",
-                  "bam_walks", "read_tables", "phase_cohort_calls")
+                  "bam_walks", "read_tables", "phase_cohort_calls", "cutoff_device_files", "cutoff_host_files", "cutoff_walk_calls")
 
     def __missing__(self, key):
         if key in self.ROUTE_KEYS:
@@ -676,6 +707,41 @@ class PhasingHost:
                 out[i] = (ref, alts)
         return out
 
+    def prepare_cutoffs(self, batch, readlen: int, stdevs: int, insert_size_max_sample: int) -> None:
+        """UZ_CUTOFF_ROUTE=device: the insert cutoffs of a call's kids before any route asks for one -- the heads of all their files walked
+        and ranked on the device in one go (HipEngine.head_ranks; read_collector.py:11-25), self.cutoffs filled for every kid whose file is an
+        indexed .bam on the staged route and which the device settled.  kid_cutoff answers the rest as ever: a file handed back, no record,
+        want <= 0, a backend without head_ranks, the Python decoders, UZ_IO_STAGE=0.  batch: the call's (kid, bam) groups.
+        cutoff_device_files / cutoff_host_files count the files each route settled, cutoff_walk_calls the device walks."""
+        if cutoff_route() != "device" or not hasattr(self.backend, "head_ranks"):
+            return
+        import os
+        want = int(insert_size_max_sample) + 1
+        stager = getattr(self.reads_by_bam, "stager", None)
+        todo = []
+        for kid, bam in batch:
+            if (kid in self.cutoffs and self.cutoffs[kid]) or want <= 0 or stager is None or not self._indexed(bam):
+                continue
+            src = stager(bam)
+            if src is None or getattr(src, "n_files", 1) != 1:
+                continue
+            st = os.stat(bam)
+            todo.append((kid, src, (os.path.abspath(bam), st.st_size, st.st_mtime_ns, want, int(readlen))))
+        ask = [t for t in todo if t[2] not in _CUTOFF_RANKS]
+        if ask:
+            # (two kids may name one file: it is walked once)
+            uniq = {}
+            for _, src, key in ask:
+                uniq.setdefault(key, src)
+            got = self.backend.head_ranks(list(uniq.values()), want, int(readlen), stats=self.stats)
+            for key, r in zip(uniq, got):
+                _CUTOFF_RANKS[key] = r
+                self.stats["cutoff_device_files" if r is not None else "cutoff_host_files"] += 1
+        for kid, _, key in todo:
+            r = _CUTOFF_RANKS.get(key)
+            if r is not None:
+                self.cutoffs[kid] = cutoff_from_ranks(r[0], r[1], r[2], readlen, stdevs)
+
     def kid_cutoff(self, kid: str, bam: str, readlen: int, stdevs: int, insert_size_max_sample: int) -> float:
         if kid not in self.cutoffs or not self.cutoffs[kid]:  # snv_phaser.py:133-135, read_collector.py:377
             rt = self.reads_header(bam)
@@ -1002,6 +1068,8 @@ class PhasingHost:
         sec_pass1.__exit__()
         call = _ReadCall(host=self, dnms=dnms, pedigrees=pedigrees, prep=prep, found=found, params=params, readlen=readlen, stdevs=stdevs,
                          insert_size_max_sample=insert_size_max_sample, want_lists=want_lists, mode=info["mode"], results=results)
+        with _Sec("cutoffs"):  # (UZ_CUTOFF_ROUTE=device; what scripts/cutoff_route_ab.py times by route)
+            self.prepare_cutoffs(list(batch), readlen, stdevs, insert_size_max_sample)
         with _Sec("chunked"):
           chunked = self._chunked_batch(call, batch, while_first_stages=attach_sites)
         attach_sites()  # (a batch that did not take the chunked route: here; otherwise done already, and this is a no-op)

@@ -33,6 +33,7 @@ IO_EXPORTS = [
     "uz_bam_decode_memory",
     "uz_bamsrc_open", "uz_bamsrc_close", "uz_bamsrc_n_contigs", "uz_bamsrc_contig_name", "uz_bamsrc_contig_length", "uz_bamsrc_tlen_head",
     "uz_bamsrc_open_many", "uz_bamsrc_n_files", "uz_bamsrc_files", "uz_bamsrc_ref_file",
+    "uz_bamsrc_first_voff", "uz_bamsrc_list_blocks", "uz_bamsrc_gather_ranges",
     "uz_index_summary", "uz_inflate_backend", "uz_io_default_threads", "uz_io_cpu_quota", "uz_bam_stage_plan", "uz_bam_stage_begin", "uz_bam_stage_finish", "uz_stage_gather_blocks", "uz_stage_set_inflated", "uz_stage_sizes", "uz_stage_io_stats", "uz_stage_timing", "uz_stage_fill", "uz_stage_qname", "uz_stage_qnames",
     "uz_stage_free", "uz_stage_walk_plan_sizes", "uz_stage_walk_plan", "uz_bam_stage_finish_desc", "uz_stage_kept_sizes", "uz_stage_kept", "uz_stage_walk_host", "uz_stage_kept_debug", "uz_stage_name_records", "uz_packed_block_sums", "uz_stage_merge_subtasks", "uz_bam_stage_finish_sub",
     "uz_stage_walk_flagged", "uz_stage_lookup", "uz_stage_extra", "uz_stage_n_lookup_tasks", "uz_sites_pack", "uz_sites_unpack", "uz_family_pack_het", "uz_family_unpack_het", "uz_samples_pack",
@@ -161,6 +162,10 @@ def load():
     lib.uz_bamsrc_contig_length.argtypes = [C.c_void_p, C.c_int32]
     lib.uz_bamsrc_tlen_head.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     lib.uz_bamsrc_tlen_head.restype = C.c_int64
+    lib.uz_bamsrc_first_voff.argtypes = [C.c_void_p, C.c_void_p]
+    lib.uz_bamsrc_list_blocks.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+    lib.uz_bamsrc_gather_ranges.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]
     lib.uz_inflate_backend.restype = C.c_char_p
     lib.uz_bam_stage_plan.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                       C.POINTER(C.c_void_p)]
@@ -994,6 +999,9 @@ class BamSource:
         self.file_base, self.ref_base = np.zeros(nf + 1, np.int64), np.zeros(nf + 1, np.int32)
         self.salt1, self.salt2 = np.zeros(nf, np.uint64), np.zeros(nf, np.uint32)
         _check(self.lib, self.lib.uz_bamsrc_files(h, self.file_base.ctypes.data, self.ref_base.ctypes.data, self.salt1.ctypes.data, self.salt2.ctypes.data))
+        # where every file's first alignment record starts (its header's end), as a virtual offset of the source
+        self.first_voff = np.zeros(nf, np.uint64)
+        _check(self.lib, self.lib.uz_bamsrc_first_voff(h, self.first_voff.ctypes.data))
 
     @classmethod
     def open_many(cls, paths, bais=None, threads: int = 0, insert_size_max_sample: int = -1) -> "BamSource":
@@ -1014,6 +1022,37 @@ class BamSource:
 
     def ref_file(self, ref: int) -> int:
         return int(self.lib.uz_bamsrc_ref_file(self._h.ptr, int(ref)))
+
+    def list_blocks(self, coff: int, want_bytes: int, cap: int = None) -> dict:
+        """The BGZF blocks of one file of the source from compressed offset `coff` on (uz_bamsrc_list_blocks: header to header, nothing is
+        inflated), until their ISIZE sum reaches want_bytes, the file ends or `cap` blocks are listed -> off, csize, isize, crc, data
+        (where the DEFLATE stream starts) per block, and at_end.  IoError (UZ_IO_E_FORMAT) on a bad header or a block beyond the file."""
+        if cap is None:
+            cap = max(1, int(want_bytes)) // 256 + 64  # (a block of less than 256 inflated bytes is rare: the loop below asks again)
+        out = None
+        while True:
+            cols = dict(off=np.zeros(max(1, cap), np.int64), csize=np.zeros(max(1, cap), np.int32), isize=np.zeros(max(1, cap), np.int32),
+                        crc=np.zeros(max(1, cap), np.uint32), data=np.zeros(max(1, cap), np.int64))
+            n, end = C.c_int64(0), C.c_int(0)
+            _check(self.lib, self.lib.uz_bamsrc_list_blocks(self._h.ptr, int(coff), int(want_bytes), int(cap), cols["off"].ctypes.data, cols["csize"].ctypes.data,
+                                                            cols["isize"].ctypes.data, cols["crc"].ctypes.data, cols["data"].ctypes.data, C.byref(n), C.byref(end)))
+            k = int(n.value)
+            part = {key: v[:k] for key, v in cols.items()}
+            out = part if out is None else {key: np.concatenate([out[key], part[key]]) for key in part}
+            if end.value or k < cap or int(out["isize"].sum()) >= int(want_bytes):
+                out["at_end"] = bool(end.value)
+                return out
+            coff = int(part["off"][-1]) + int(part["csize"][-1])
+
+    @staticmethod
+    def gather_ranges(sources, src_off, nbytes, dst_off, dst: np.ndarray, threads: int = 0) -> None:
+        """range i -- nbytes[i] bytes of source i's file from src_off[i] -- copied to dst[dst_off[i]:] on the library's threads
+        (uz_bamsrc_gather_ranges)"""
+        lib = load()
+        n = len(sources)
+        hs = (C.c_void_p * max(1, n))(*[s._h.ptr for s in sources])
+        so, nb, do = (np.ascontiguousarray(a, np.int64) for a in (src_off, nbytes, dst_off))
+        _check(lib, lib.uz_bamsrc_gather_ranges(hs, n, so.ctypes.data, nb.ctypes.data, do.ctypes.data, dst.ctypes.data, int(dst.size), int(threads)))
 
     def _plan_files(self, plan: dict) -> None:
         """a source over many files: the per-file table the device's walk needs (uz_bam_walk_many) rides on the plan"""

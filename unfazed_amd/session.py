@@ -156,6 +156,23 @@ def load_reads(name: str, insert_size_max_sample: int = 1000000) -> ReadsTable:
     return _READS[name]
 
 
+class _HeadlessHeader(ReadsTable):
+    """`header(bam)` of a file whose staging source was opened without a head (UZ_CUTOFF_ROUTE=device): the contig names now; the head of the
+    file only if somebody asks -- kid_cutoff for a file the device handed back -- and then from a source opened the old way, which answers or
+    raises exactly as the host route does"""
+
+    def __init__(self, contigs, open_head):
+        super().__init__(contigs)
+        self._open_head = open_head
+        self._head = None
+
+    @property
+    def tlen_head(self):
+        if self._head is None:
+            self._head = self._open_head().tlen_head
+        return self._head
+
+
 class _LazyReads(dict):
     """reads_by_bam mapping of the session.  A BAM with a BAI next to it is never decoded whole: `header` gives the
     contig names and the head of the file, `regions` decodes what a batch's fetches return (+ mates) through the index
@@ -167,6 +184,7 @@ class _LazyReads(dict):
         self.cap = insert_size_max_sample
         self._headers: Dict[str, ReadsTable] = {}
         self._stagers: Dict[str, object] = {}
+        self._headless = set()  # files whose staging source was opened without a head (UZ_CUTOFF_ROUTE=device)
 
     def __missing__(self, key):
         self[key] = load_reads(key, self.cap)
@@ -188,8 +206,11 @@ class _LazyReads(dict):
                 raise CramNotSupported(bam)
             elif self.stager(bam) is not None:
                 src = self.stager(bam)
-                t = ReadsTable(src.contigs)
-                t.tlen_head = src.tlen_head
+                if bam in self._headless:
+                    t = _HeadlessHeader(src.contigs, lambda: self._source(bam, int(self.cap)))
+                else:
+                    t = ReadsTable(src.contigs)
+                    t.tlen_head = src.tlen_head
                 self._headers[bam] = t
             else:
                 from .io_native import read_bam_regions
@@ -204,14 +225,22 @@ class _LazyReads(dict):
         if bam not in self._stagers:
             # opening reads the index and the first insert_size_max_sample + 1 records (the reference's insert-size estimate,
             # read_collector.py:11-25): kept for the process, so that the drivers' second call on a file (phase_svs behind phase_snvs:
-            # unfazed.py:601-646) does not pay it again -- as long as the file is the same one
-            from .io_native import BamSource
-            st = os.stat(bam)
-            key = (os.path.abspath(bam), st.st_size, st.st_mtime_ns, int(self.cap))
-            if key not in _STAGERS:
-                _STAGERS[key] = BamSource(bam, insert_size_max_sample=self.cap, threads=_io_threads())
-            self._stagers[bam] = _STAGERS[key]
+            # unfazed.py:601-646) does not pay it again -- as long as the file is the same one.  UZ_CUTOFF_ROUTE=device: no record is
+            # read at opening (cap -1: the key keeps the two kinds of source apart); the device walks the heads (PhasingHost.prepare_cutoffs)
+            from .hostpath import cutoff_route
+            headless = cutoff_route() == "device"
+            self._stagers[bam] = self._source(bam, -1 if headless else int(self.cap))
+            if headless:
+                self._headless.add(bam)
         return self._stagers[bam]
+
+    def _source(self, bam: str, cap: int):
+        from .io_native import BamSource
+        st = os.stat(bam)
+        key = (os.path.abspath(bam), st.st_size, st.st_mtime_ns, cap)
+        if key not in _STAGERS:
+            _STAGERS[key] = BamSource(bam, insert_size_max_sample=cap, threads=_io_threads())
+        return _STAGERS[key]
 
     def stager_many(self, bams):
         """the files of one run of a cohort call opened as ONE source (io_native.BamSource.open_many: hostpath.PhasingHost._joined_run), kept for the
