@@ -10,18 +10,10 @@ import os
 import numpy as np
 import pytest
 
+from deflatecases import Bits as _Bits, bgzf_block  # (the DEFLATE writer and the BGZF framing live with the hand-built cases)
 from unfazed_amd.engine import UnfazedHipError
 
 pytestmark = pytest.mark.gpu
-
-
-def bgzf_block(payload: bytes, level=6, strategy=zlib.Z_DEFAULT_STRATEGY) -> bytes:
-    c = zlib.compressobj(level, zlib.DEFLATED, -15, 9, strategy)
-    body = c.compress(payload) + c.flush()
-    bsize = len(body) + 25
-    assert bsize <= 65536 + 25
-    return (b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + struct.pack("<H", bsize) + body
-            + struct.pack("<II", zlib.crc32(payload) & 0xFFFFFFFF, len(payload)))
 
 
 def payloads():
@@ -159,22 +151,6 @@ def test_random_blocks_against_zlib(engine, seed):
     for k, p in enumerate(want):
         assert bytes(got[off: off + len(p)]) == p, (k, len(p))
         off += len(p)
-
-
-class _Bits:
-    def __init__(self):
-        self.v, self.n = 0, 0
-
-    def put(self, val, nbits):  # LSB first, as DEFLATE packs everything but Huffman codes
-        self.v |= (val & ((1 << nbits) - 1)) << self.n
-        self.n += nbits
-
-    def code(self, code, nbits):  # a Huffman code: most significant bit first
-        for b in range(nbits - 1, -1, -1):
-            self.put((code >> b) & 1, 1)
-
-    def bytes(self):
-        return self.v.to_bytes((self.n + 7) // 8, "little")
 
 
 def test_a_literal_code_of_one_single_code_is_taken_as_zlib_takes_it(engine):

@@ -93,10 +93,11 @@ __device__ __forceinline__ uint32_t bi_take(BitIn &b, int n) { const uint32_t v 
 __device__ __forceinline__ uint32_t bitrev(uint32_t v, int n) { return __brev(v) >> (32 - n); }
 
 // canonical Huffman set-up from lens[0 .. n): counts, symbols in canonical order, the direct table for codes of <= tb bits.
-// false: an over-subscribed or (where it matters) incomplete set of lengths
-// (complete 2: a code-length code must use its code space up; 1: so must a literal / length code, unless it is ONE code of one bit -- zlib's
-// inftrees.c rule ("incomplete set ... max != 1"), which the host inflaters follow; 0: a distance code need not -- the fixed one does not,
-// and a block without matches has none.  An unused code then decodes to "no symbol")
+// false: an over-subscribed or incomplete set of lengths
+// (complete 2: a code-length code must use its code space up; 1: so must a literal / length code and a distance code, unless it is ONE code of
+// one bit -- zlib's inftrees.c rule ("incomplete set ... max != 1"), which the host inflaters follow -- or, the distance code of a block without
+// matches, no code at all (form 2 only: a literal / length code always has its end-of-block).  The fixed block's distance code is built over all
+// 32 of its five-bit lengths and so is complete.  An unused code of the two incomplete sets that pass decodes to "no symbol")
 // The per-length counters live in LDS (work[48]): indexed by a code length, they would otherwise sit in scratch memory or pin 48 registers
 // (the kernel then needs 80 registers and runs 6 waves per SIMD at 86 GB/s instead of 8 at 97).
 // form 0: 16-bit entries (symbol << 4) | code length, 0 for a longer code (the code-length code).
@@ -133,7 +134,7 @@ __device__ bool build_table(const uint8_t *lens, int n, void *tab_, int tb, uint
         total += c;
         if (left < 0) return false;
     }
-    if (left > 0 && (complete == 2 || (complete == 1 && !(total == 1 && uni(count[1]) == 1)))) return false;
+    if (left > 0 && (complete == 2 || !((total == 1 && uni(count[1]) == 1) || (total == 0 && form == 2)))) return false;
     if (lane < 16) cnt[lane] = (uint16_t)count[lane];
     if (lane == 0) {
         for (int s = 0; s < n; s++) {
@@ -247,7 +248,7 @@ __global__ __launch_bounds__(64, UZI_WAVES_PER_EU) void k_bgzf_inflate(int64_t n
             if (type == 1) { // fixed code
                 for (int s = lane; s < 288; s += 64) L.lens[s] = (uint8_t)(s < 144 ? 8 : (s < 256 ? 9 : (s < 280 ? 7 : 8)));
                 if (lane < 32) L.lens[288 + lane] = 5;
-                nlit = 288; ndist = 30;
+                nlit = 288; ndist = 32; // (all 32 five-bit codes: a complete set; 30 and 31 stand for nothing and are refused where they are used)
                 __syncthreads();
             } else { // dynamic code: the code-length code, then the lengths of both codes
                 bi_refill(b, lane);
@@ -376,7 +377,7 @@ __global__ __launch_bounds__(64, UZI_WAVES_PER_EU) void k_bgzf_inflate(int64_t n
                 if (uni((int)L.lens[256]) == 0) { bad = 2; break; } // no end-of-block code
             }
             // (the distance code first: the literal / length code's build leaves every symbol's entry in code_of[])
-            if (!build_table(L.lens + 288, ndist, L.dist_tab, UZI_DIST_BITS, L.dist_sorted, L.dist_cnt, L.code_of, L.work, lane, 0, 2)) { bad = 2; break; }
+            if (!build_table(L.lens + 288, ndist, L.dist_tab, UZI_DIST_BITS, L.dist_sorted, L.dist_cnt, L.code_of, L.work, lane, 1, 2)) { bad = 2; break; }
             if (!build_table(L.lens, nlit, L.lit_tab, UZI_LIT_BITS, L.lit_sorted, L.lit_cnt, L.code_of, L.work, lane, 1, 1, L.lit_walk)) { bad = 2; break; }
             // ---- the symbols of the block.  Literals gather in a register window -- lane l holds the byte for position wbase + l -- and
             // leave it as one coalesced store when it is full or a match needs them in memory.
