@@ -149,6 +149,13 @@ int uz_reads_wait(uz_ctx *ctx, int reads_id);
  * form; `end` derived from the CIGAR when it was left out): [n_segs] each, any pointer may be NULL.  For parity tests of the
  * upload forms; waits for the table like uz_reads_wait. */
 int uz_reads_headers(uz_ctx *ctx, int reads_id, int32_t *start, int32_t *end, int32_t *tlen, int32_t *mate, uint32_t *qname);
+/* parity / debug, like uz_reads_headers: the other columns of a table as the device holds them.  sizes [4] out: records, CIGAR words, base-row
+ * units (16 bytes: 32 four-bit codes), quality-plane units (one 32-bit word: bit b = "base b of the unit lies below the table's threshold").  Every
+ * other pointer may be NULL (call it once for the sizes): fm [n] = flag | mapq << 16 | aux << 24; l_seq, n_cigar, cigar_off (first word in the
+ * CIGAR store), sq_off (first unit of the base row), qoff (first unit of the quality-plane row) [n]; cigar [sizes[1]]; seq4 [16 sizes[2]];
+ * qlow [sizes[3]].  Nothing on the product path calls it. */
+int uz_reads_columns(uz_ctx *ctx, int reads_id, int64_t sizes[4], uint32_t *fm, uint16_t *l_seq, uint16_t *n_cigar, uint32_t *cigar_off, uint32_t *sq_off,
+                     uint32_t *qoff, uint32_t *cigar, uint8_t *seq4, uint32_t *qlow);
 /* BGZF blocks inflated on the device (csrc/k_inflate.hip: one wavefront per block; fixed, dynamic and stored DEFLATE blocks).  This
  * entry is the measured form (repeat / kernel_ms) behind the parity tests; the session's path calls uz_bgzf_inflate_to_host below for
  * every staged batch (HipEngine.upload_reads_staged).  comp: the compressed bytes (host); in_off[k]: where the DEFLATE stream

@@ -1763,6 +1763,38 @@ int uz_reads_headers(uz_ctx *c, int reads_id, int32_t *start, int32_t *end, int3
     });
 }
 
+int uz_reads_columns(uz_ctx *c, int reads_id, int64_t sizes[4], uint32_t *fm, uint16_t *l_seq, uint16_t *n_cigar, uint32_t *cigar_off, uint32_t *sq_off,
+                     uint32_t *qoff, uint32_t *cigar, uint8_t *seq4, uint32_t *qlow) {
+    return guarded(c, [&] {
+        UZ_REQUIRE(sizes, UZ_E_ARG, "uz_reads_columns: sizes is where the stores' sizes go");
+        ReadsDev &r = reads_of(c, reads_id);
+        uz_reads_make_ready(c, r);
+        UZ_HIP(hipStreamSynchronize(c->stream));
+        uz_check_upload_flag(c);
+        sizes[0] = r.n; sizes[1] = r.n_cigar_total; sizes[2] = r.n_seq_units; sizes[3] = (r.qlow && r.qlow_valid) ? r.n_plane_units : 0;
+        struct HA { int32_t start, end; uint32_t cigar_off, sq_off; }; // the record headers (RecA / RecB of phase_body.hpp)
+        struct HB { int32_t mate; uint32_t qname; uint16_t l_seq, n_cigar; int32_t tlen; };
+        const size_t n = (size_t)r.n;
+        if (n && (l_seq || n_cigar || cigar_off || sq_off)) {
+            std::vector<HA> a(n);
+            std::vector<HB> b(n);
+            UZ_HIP(hipMemcpy(a.data(), r.rec_a, n * sizeof(HA), hipMemcpyDeviceToHost));
+            UZ_HIP(hipMemcpy(b.data(), r.rec_b, n * sizeof(HB), hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < n; i++) {
+                if (l_seq) l_seq[i] = b[i].l_seq;
+                if (n_cigar) n_cigar[i] = b[i].n_cigar;
+                if (cigar_off) cigar_off[i] = a[i].cigar_off;
+                if (sq_off) sq_off[i] = a[i].sq_off;
+            }
+        }
+        if (n && fm) UZ_HIP(hipMemcpy(fm, r.fm, n * 4, hipMemcpyDeviceToHost));
+        if (n && qoff) UZ_HIP(hipMemcpy(qoff, r.qoff, n * 4, hipMemcpyDeviceToHost));
+        if (cigar && sizes[1]) UZ_HIP(hipMemcpy(cigar, r.cigar, (size_t)sizes[1] * 4, hipMemcpyDeviceToHost));
+        if (seq4 && sizes[2]) UZ_HIP(hipMemcpy(seq4, r.seq4, (size_t)sizes[2] * UZ_SEQ4_UNIT_BYTES, hipMemcpyDeviceToHost));
+        if (qlow && sizes[3]) UZ_HIP(hipMemcpy(qlow, r.qlow, (size_t)sizes[3] * UZ_QLOW_UNIT_BYTES, hipMemcpyDeviceToHost));
+    });
+}
+
 int uz_bgzf_inflate(uz_ctx *c, const uint8_t *comp, int64_t comp_bytes, int64_t n_blocks, const int64_t *in_off, const int64_t *out_off, uint8_t *out,
                     int repeat, double *kernel_ms) {
     return guarded(c, [&] {

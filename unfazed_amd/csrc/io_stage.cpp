@@ -113,7 +113,7 @@ struct BlockHdr { size_t cdata, clen, blen; uint32_t crc, isize; };
 // what a record's fields and names of one file of the source are shifted and salted by
 struct FileKey { int32_t ref_base, n_ref; uint64_t s1; uint32_t s2; };
 inline FileKey file_key(const uz_bamsrc &S, int32_t ref) { // ref: a reference of the (virtual) source
-    if (!S.many) return FileKey{0, (int32_t)S.contigs.size(), 0, 0};
+    if (!S.many) return FileKey{0, INT32_MAX, 0, 0}; // (one file: its refIDs as they stand, as k_bam_walk reads them -- only a set of files renumbers)
     const size_t f = (size_t)S.ref_file[(size_t)ref];
     return FileKey{S.ref_base[f], S.ref_base[f + 1] - S.ref_base[f], S.salt1[f], S.salt2[f]};
 }

@@ -25,7 +25,7 @@ HEAD_MAX_ROUNDS = 8       # walks of one file before it is handed back to the ho
 
 EXPORTS = [
     "uz_create", "uz_destroy", "uz_last_error", "uz_sync", "uz_set_params",
-    "uz_sites_upload", "uz_family_upload", "uz_sites_family_upload_async", "uz_samples_upload", "uz_samples_from_text", "uz_samples_from_bcf", "uz_samples_unsettled", "uz_samples_settle", "uz_families_from_samples", "uz_family_fetch", "uz_samples_free", "uz_reads_upload", "uz_reads_upload_packed", "uz_reads_wait", "uz_reads_headers", "uz_bgzf_inflate", "uz_bgzf_inflate_to_host", "uz_bam_walk", "uz_bam_walk_many", "uz_reads_files", "uz_crc32_blocks", "uz_bam_walk_fetch", "uz_bam_walk_release", "uz_reads_from_bam",
+    "uz_sites_upload", "uz_family_upload", "uz_sites_family_upload_async", "uz_samples_upload", "uz_samples_from_text", "uz_samples_from_bcf", "uz_samples_unsettled", "uz_samples_settle", "uz_families_from_samples", "uz_family_fetch", "uz_samples_free", "uz_reads_upload", "uz_reads_upload_packed", "uz_reads_wait", "uz_reads_headers", "uz_reads_columns", "uz_bgzf_inflate", "uz_bgzf_inflate_to_host", "uz_bam_walk", "uz_bam_walk_many", "uz_reads_files", "uz_crc32_blocks", "uz_bam_walk_fetch", "uz_bam_walk_release", "uz_reads_from_bam",
     "uz_bam_walk_flags", "uz_bam_join", "uz_bam_join_needs", "uz_bam_join_fetch", "uz_reads_from_walk", "uz_reads_names", "uz_walk_slot_stats", "uz_walk_reserve",
     "uz_pinned_alloc", "uz_pinned_free",
     "uz_sites_adopt_device", "uz_family_adopt_device", "uz_reads_adopt_device",
@@ -65,6 +65,7 @@ def load_library(path: Optional[str] = None):
     L.uz_set_params.argtypes = [vp, vp]
     L.uz_reads_wait.argtypes = [vp, C.c_int]
     L.uz_reads_headers.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    L.uz_reads_columns.argtypes = [vp, C.c_int] + [vp] * 10
     L.uz_bgzf_inflate.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp, vp, C.c_int, C.POINTER(C.c_double)]
     L.uz_bgzf_inflate_to_host.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp, vp]
     L.uz_crc32_blocks.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
@@ -439,6 +440,22 @@ class HipEngine:
         out = {k: np.zeros(max(1, int(n)), np.uint32 if k == "qname" else np.int32) for k in ("start", "end", "tlen", "mate", "qname")}
         self._ck(self.L.uz_reads_headers(self.h, int(rid), *(out[k].ctypes.data for k in ("start", "end", "tlen", "mate", "qname"))), "uz_reads_headers")
         return {k: v[: int(n)] for k, v in out.items()}
+
+    def reads_columns(self, rid: int, n: int) -> dict:
+        """the other columns of a table as the device holds them (uz_reads_columns; a debug read-back like reads_headers): fm (flag | mapq << 16 |
+        aux << 24), l_seq, n_cigar, cigar_off, sq_off, qoff per record; the CIGAR store, the four-bit base rows (16 bytes a unit) and the low-quality
+        plane (a 32-bit word a unit)"""
+        sizes = (C.c_int64 * 4)()
+        self._ck(self.L.uz_reads_columns(self.h, int(rid), sizes, *([None] * 9)), "uz_reads_columns")
+        assert int(sizes[0]) == int(n), "the table holds %d records" % int(sizes[0])
+        m = max(1, int(n))
+        out = dict(fm=np.zeros(m, np.uint32), l_seq=np.zeros(m, np.uint16), n_cigar=np.zeros(m, np.uint16), cigar_off=np.zeros(m, np.uint32),
+                   sq_off=np.zeros(m, np.uint32), qoff=np.zeros(m, np.uint32), cigar=np.zeros(max(1, int(sizes[1])), np.uint32),
+                   seq4=np.zeros(max(1, int(sizes[2])) * 16, np.uint8), qlow=np.zeros(max(1, int(sizes[3])), np.uint32))
+        self._ck(self.L.uz_reads_columns(self.h, int(rid), sizes, *(out[k].ctypes.data for k in ("fm", "l_seq", "n_cigar", "cigar_off", "sq_off", "qoff", "cigar", "seq4", "qlow"))),
+                 "uz_reads_columns")
+        cut = dict(cigar=int(sizes[1]), seq4=16 * int(sizes[2]), qlow=int(sizes[3]))
+        return {k: v[: cut.get(k, int(n))] for k, v in out.items()}
 
     def bgzf_inflate(self, data, repeat: int = 0):
         """Every BGZF block of `data` (bytes / uint8 array: a BGZF file or a run of its blocks) inflated on the device (uz_bgzf_inflate).
