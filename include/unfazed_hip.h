@@ -55,7 +55,9 @@ extern "C" {
 #define UZ_K_HEAD_INFLATE 13 /* k_bgzf_inflate + k_bgzf_crc32 over the heads of a group of files (uz_head_walk) */
 #define UZ_K_HEAD_WALK 14    /* k_head_walk */
 #define UZ_K_HEAD_RANK 15    /* k_head_rank */
-#define UZ_K_COUNT 16
+#define UZ_K_BED_SIZE 16    /* k_bed_size + the scan of the rows' lengths (uz_bed_rows) */
+#define UZ_K_BED_FILL 17    /* k_bed_fill */
+#define UZ_K_COUNT 18
 
 typedef struct uz_ctx uz_ctx;
 
@@ -369,6 +371,27 @@ int uz_phase_groups(uz_ctx *ctx, int64_t *grp_off /* [2n+1] */, int32_t *grp_q);
 #define UZ_SIZING_REDUCED_WORDS 263
 int uz_phase_sizing_fetch(uz_ctx *ctx, int32_t *bounds /* [5n] */, int32_t *pre_win /* [4n] */, int32_t *pre_ha /* [n_het] */,
                           int32_t *pre_hl /* [n_het] */, int64_t *reduced /* [UZ_SIZING_REDUCED_WORDS] */);
+
+/* ---- BED rows as text -------------------------------------------------- */
+/* The BED lines of rows of the LAST finished uz_phase / uz_phase_end / uz_phase_cohort / uz_phase_cohort_joined, written by kernels from the
+ * batch's result where it lies (k_bed_size, a scan, k_bed_fill; csrc/bed_row.hpp is the body): the decision of summarize_record's read-backed
+ * branches (unfazed.py:206-234) with the evidence_min_ratio of uz_set_params, the SEX-CHROM row of summarize_autophased, and the line of
+ * write_bed_output -- nine tab-separated fields, thirteen when verbose, '\n'.  Row k is bytes[off[k] .. off[k + 1]); a row is EMPTY when its DNM's
+ * status is not UZ_ST_OK, or when its origin is None or ambiguous and include_ambiguous is 0.  The host orders the rows and writes the header.
+ * Verbose site lists are sorted as decimal strings (unfazed.py:302-303), read names stand in list order; a verbose row's reads_id names the table
+ * whose names its ids are (a cohort batch hands ids back relative to the group's own table, as uz_phase_votes does).
+ * The text lies in page-locked memory of the context, valid until the next call.
+ * UZ_E_STATE: no finished batch, or an open one (uz_phase_begin); verbose with a table that holds no names on the device (only a table of
+ * uz_reads_from_walk with names does) or a batch that kept no lists; a site list that is not ascending; a name id at or beyond the table's
+ * names; a row whose written bytes differ from its sized length.  UZ_E_ARG: a DNM index, string id or reads id out of range.  UZ_E_RANGE: 4 GiB or
+ * more of text.  A call that is not verbose reads no name and works with any table. */
+int uz_bed_rows(uz_ctx *ctx, const uz_bed_view *rows, int verbose, int include_ambiguous, int64_t *off /* [n_rows + 1] */, const uint8_t **bytes);
+/* Test hook (as uz_phase_sizing_fetch is one): the same kernels over lists the caller supplies, no read stage run -- status [n_dnms], list_off
+ * [4 n_dnms + 1] + list_val in uz_phase_votes' layout, the names as a plain store (name_off [n_qnames + 1] + name_bytes; NULL: no names, as a
+ * table without them), the ratio.  Rows' reads_id is ignored.  Refusals as above; UZ_E_ARG on offsets that descend. */
+int uz_bed_rows_lists(uz_ctx *ctx, const uz_bed_view *rows, int verbose, int include_ambiguous, int32_t n_dnms, const int32_t *status,
+                      const int64_t *list_off, const int32_t *list_val, uint32_t n_qnames, const uint32_t *name_off, const uint8_t *name_bytes,
+                      int32_t evidence_min_ratio, int64_t *off /* [n_rows + 1] */, const uint8_t **bytes);
 
 /* ---- allele-balance (CNV) stage ---------------------------------------- */
 /* K6.  Everything run_cnv_phasing does after its find (sv_phaser.py:357-423: phase_by_snvs :71-85,

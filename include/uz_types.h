@@ -479,6 +479,23 @@ typedef struct uz_cohort_group {
     double cutoff;     /* concordant_upper_len of the kid (read_collector.py:11-25) */
 } uz_cohort_group;
 
+/* BED rows (uz_bed_rows): one row of the output per entry, in the caller's order.  Strings (chrom, vartype, kid, dad, mom) are ids into
+ * the view's string table: string k is str_bytes[str_off[k] .. str_off[k + 1]). */
+typedef struct uz_bed_row {
+    int32_t dnm;        /* the DNM's index in the batch; -1: a SEX-CHROM row (summarize_autophased), which reads no batch */
+    int32_t start, end; /* printed as Python's str(int) */
+    uint32_t chrom, vartype, kid, dad, mom;
+    int32_t reads_id;   /* the reads table the row's read ids name (verbose rows; a cohort batch: the group's own table); -1: none */
+    int32_t sex_origin; /* SEX-CHROM rows: 0 = dad is origin_parent (chrY), 1 = mom */
+} uz_bed_row;
+typedef struct uz_bed_view {
+    int64_t n_rows;
+    const uz_bed_row *rows;
+    int32_t n_strings;
+    const uint32_t *str_off; /* [n_strings + 1], ascending */
+    const uint8_t *str_bytes;
+} uz_bed_view;
+
 #ifdef __cplusplus
 }
 #endif

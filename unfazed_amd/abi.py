@@ -562,8 +562,51 @@ class DnmsView(C.Structure):
     ]
 
 
+# uz_bed_row: one row of uz_bed_rows (dnm -1: a SEX-CHROM row; the five strings are ids into the view's string table)
+BED_ROW = np.dtype([("dnm", np.int32), ("start", np.int32), ("end", np.int32), ("chrom", np.uint32), ("vartype", np.uint32), ("kid", np.uint32),
+                    ("dad", np.uint32), ("mom", np.uint32), ("reads_id", np.int32), ("sex_origin", np.int32)])
+
+
+class BedView(C.Structure):
+    """uz_bed_view"""
+    _fields_ = [("n_rows", C.c_int64), ("rows", _p), ("n_strings", C.c_int32), ("str_off", _p), ("str_bytes", _p)]
+
+
 def _ptr(a: np.ndarray) -> int:
     return a.ctypes.data if a.size else 0
+
+
+class StringTable:
+    """the fixed strings of a uz_bed_rows call: str -> id, the pool and its offsets"""
+
+    def __init__(self):
+        self.ids = {}
+        self.parts = []
+        self.n_bytes = 0
+        self.offs = [0]
+
+    def id(self, s: str) -> int:
+        k = self.ids.get(s)
+        if k is None:
+            k = self.ids[s] = len(self.parts)
+            b = s.encode()
+            self.parts.append(b)
+            self.n_bytes += len(b)
+            self.offs.append(self.n_bytes)
+        return k
+
+    def arrays(self):
+        return np.asarray(self.offs, np.uint32), np.frombuffer(b"".join(self.parts) + b"\0", np.uint8)
+
+
+def bed_view(rows: np.ndarray, str_off: np.ndarray, str_bytes: np.ndarray) -> "Held":
+    arrs = dict(rows=np.ascontiguousarray(rows, BED_ROW), str_off=np.ascontiguousarray(str_off, np.uint32), str_bytes=np.ascontiguousarray(str_bytes, np.uint8))
+    v = BedView()
+    v.n_rows = int(arrs["rows"].size)
+    v.n_strings = int(arrs["str_off"].size) - 1
+    for k, a in arrs.items():
+        setattr(v, k, a.ctypes.data)
+    return Held(v, arrs)
 
 
 def _c(a, dtype) -> np.ndarray:

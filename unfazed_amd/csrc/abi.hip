@@ -472,6 +472,8 @@ void uz_destroy(uz_ctx *c) {
     if (c->dn_stage) (void)hipHostFree(c->dn_stage);
     if (c->find_pin) (void)hipHostFree(c->find_pin);
     if (c->nm_pin) (void)hipHostFree(c->nm_pin);
+    if (c->bed_pin) (void)hipHostFree(c->bed_pin);
+    c->bed_in.release(); c->bed_hook.release(); c->bed_out.release(); c->bed_len.release(); c->bed_off.release();
     c->nm_ids.release(); c->nm_len.release(); c->nm_off.release(); c->nm_out.release(); c->rf_first.release(); c->rf_mm.release();
     c->ab_lut.release(); c->win_range.release();
     c->dn_fam.release(); c->dn_cutoff.release(); c->fam_cls.release();
@@ -2431,6 +2433,18 @@ int uz_phase_sizing_fetch(uz_ctx *c, int32_t *bounds, int32_t *pre_win, int32_t 
         rc = uz_phase_sizing_fetch_impl(c, bounds, pre_win, pre_ha, pre_hl, reduced);
     });
     return g ? g : rc;
+}
+
+int uz_bed_rows(uz_ctx *c, const uz_bed_view *rows, int verbose, int include_ambiguous, int64_t *off, const uint8_t **bytes) {
+    return guarded(c, [&] { (void)uz_bed_rows_impl(c, rows, verbose, include_ambiguous, off, bytes); });
+}
+int uz_bed_rows_lists(uz_ctx *c, const uz_bed_view *rows, int verbose, int include_ambiguous, int32_t n_dnms, const int32_t *status, const int64_t *list_off,
+                      const int32_t *list_val, uint32_t n_qnames, const uint32_t *name_off, const uint8_t *name_bytes, int32_t evidence_min_ratio, int64_t *off,
+                      const uint8_t **bytes) {
+    return guarded(c, [&] {
+        (void)uz_bed_rows_lists_impl(c, rows, verbose, include_ambiguous, n_dnms, status, list_off, list_val, n_qnames, name_off, name_bytes, evidence_min_ratio, off,
+                                     bytes);
+    });
 }
 
 int uz_prof_enable(uz_ctx *c, int on) {

@@ -764,5 +764,18 @@ int uz_phase_sizing_fetch_impl(uz_ctx *c, int32_t *bounds, int32_t *pre_win, int
     return 0;
 }
 
+// uz_bed_rows reads the batch's result where it lies: the per-DNM results in `res` (status [n], counts [4 n]) and, when the batch kept its lists,
+// the pool with its index
+void uz_phase_lists_dev(uz_ctx *c, int32_t *n, const int32_t **status, const int32_t **counts, const int32_t **pool, const long long **list_start,
+                        const int32_t **list_len) {
+    PhaseState *st = (PhaseState *)c->phase_state;
+    UZ_REQUIRE(c->phase_valid && !c->phase_open && st != nullptr && !st->pending, UZ_E_STATE, "no finished batch on this context");
+    *n = st->n > 0 ? st->n : 0;
+    *status = st->res.p; *counts = st->res.p ? st->res.p + (size_t)*n : nullptr;
+    *pool = st->have_lists ? st->pool.p : nullptr;
+    *list_start = st->have_lists ? st->list_start.p : nullptr;
+    *list_len = st->have_lists ? st->list_len.p : nullptr;
+}
+
 int uz_phase_votes_impl(uz_ctx *c, int64_t *vote_off, int32_t *vote_val) { return gather_lists(c, 0, 4, vote_off, vote_val); }
 int uz_phase_groups_impl(uz_ctx *c, int64_t *grp_off, int32_t *grp_q) { return gather_lists(c, 4, 6, grp_off, grp_q); }

@@ -437,6 +437,14 @@ struct uz_ctx {
     uint8_t *nm_pin = nullptr;
     size_t nm_pin_cap = 0;
 
+    // uz_bed_rows (k_bed.hip): the call's rows, strings and tables on the device (bed_in; the caller's lists of uz_bed_rows_lists behind them in
+    // bed_hook), the rows' lengths, their offsets + the flag word, the text; one page-locked block, all kept from call to call
+    DevBuf<uint8_t> bed_in, bed_hook, bed_out;
+    DevBuf<uint32_t> bed_len;
+    DevBuf<int64_t> bed_off;
+    uint8_t *bed_pin = nullptr;
+    size_t bed_pin_cap = 0;
+
     // last phase (k_reads.hip)
     bool phase_valid = false;
     bool phase_open = false; // uz_phase_begin without its uz_phase_end
@@ -573,3 +581,12 @@ int uz_phase_votes_impl(uz_ctx *c, int64_t *vote_off, int32_t *vote_val);
 int uz_phase_groups_impl(uz_ctx *c, int64_t *grp_off, int32_t *grp_q);
 int uz_phase_sizing_fetch_impl(uz_ctx *c, int32_t *bounds, int32_t *pre_win, int32_t *pre_ha, int32_t *pre_hl, int64_t *reduced);
 void uz_phase_state_free(uz_ctx *c);
+// where the finished batch's per-DNM results and lists lie on the device (k_reads.hip): status [n], counts [4 n]; pool / list_start / list_len are
+// null when the batch kept no lists.  UZ_E_STATE: no finished batch
+void uz_phase_lists_dev(uz_ctx *c, int32_t *n, const int32_t **status, const int32_t **counts, const int32_t **pool, const long long **list_start,
+                        const int32_t **list_len);
+// BED rows as text (k_bed.hip; bed_row.hpp is the body): uz_bed_rows over the last batch, uz_bed_rows_lists over the caller's lists
+int uz_bed_rows_impl(uz_ctx *c, const uz_bed_view *rows, int verbose, int include_ambiguous, int64_t *off, const uint8_t **bytes);
+int uz_bed_rows_lists_impl(uz_ctx *c, const uz_bed_view *rows, int verbose, int include_ambiguous, int32_t n_dnms, const int32_t *status, const int64_t *list_off,
+                           const int32_t *list_val, uint32_t n_qnames, const uint32_t *name_off, const uint8_t *name_bytes, int32_t ratio, int64_t *off,
+                           const uint8_t **bytes);

@@ -19,6 +19,7 @@ K_SITE_SCAN, K_WINDOW_COUNT, K_WINDOW_FILL, K_PHASE, K_SIZING, K_CNV, K_FAMILY_P
 K_VCF_TABS, K_VCF_CELLS, K_VCF_COPY = 8, 9, 10  # uz_samples_from_text: the two kernels and (not a kernel) the chunks' copies
 K_BCF_CELLS, K_BCF_COPY = 11, 12  # uz_samples_from_bcf: its kernel and (not a kernel) its chunks' copies
 K_HEAD_INFLATE, K_HEAD_WALK, K_HEAD_RANK = 13, 14, 15  # uz_head_walk: inflate + CRC-32 of a group's heads, k_head_walk; uz_head_rank: k_head_rank
+K_BED_SIZE, K_BED_FILL = 16, 17  # uz_bed_rows: k_bed_size + the scan of the lengths, k_bed_fill
 HEAD_NONE, HEAD_DONE, HEAD_END, HEAD_BAD = 0, 1, 2, 3  # unfazed_hip.h UZ_HEAD_*
 HEAD_MAX_BYTES = 8 << 30  # inflated bytes of one uz_head_walk launch unless UZ_HEAD_MAX_BYTES says otherwise: a choice, not a measurement
 HEAD_MAX_ROUNDS = 8       # walks of one file before it is handed back to the host route
@@ -32,6 +33,7 @@ EXPORTS = [
     "uz_sites_free", "uz_reads_free", "uz_drop_derived",
     "uz_site_scan", "uz_site_scan_many", "uz_site_classes", "uz_find", "uz_find_fetch", "uz_find_cohort",
     "uz_phase", "uz_phase_begin", "uz_phase_end", "uz_phase_cohort", "uz_phase_cohort_joined", "uz_phase_votes", "uz_phase_groups", "uz_phase_sizing_fetch", "uz_phase_cnv", "uz_phase_cnv_cohort", "uz_phase_cnv_sites",
+    "uz_bed_rows", "uz_bed_rows_lists",
     "uz_prof_enable", "uz_prof_reset", "uz_prof_get", "uz_prof_units",
     "uz_head_walk", "uz_head_rank", "uz_head_fetch", "uz_head_free",
 ]
@@ -119,6 +121,8 @@ def load_library(path: Optional[str] = None):
     L.uz_phase_votes.argtypes = [vp, vp, vp]
     L.uz_phase_groups.argtypes = [vp, vp, vp]
     L.uz_phase_sizing_fetch.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.uz_bed_rows.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
+    L.uz_bed_rows_lists.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int32, vp, vp, vp, C.c_uint32, vp, vp, C.c_int32, vp, vp]
     L.uz_head_walk.argtypes = [vp, C.POINTER(C.c_int), C.c_int32, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.uz_head_rank.argtypes = [vp, C.c_int, C.c_int32, vp, vp, vp]
     L.uz_head_fetch.argtypes = [vp, C.c_int, C.c_int32, vp, C.c_int64, C.POINTER(C.c_int64)]
@@ -816,6 +820,38 @@ class HipEngine:
         gq = np.zeros(max(1, int(go[-1])), dtype=np.int32)
         self._ck(self.L.uz_phase_groups(self.h, go.ctypes.data, gq.ctypes.data), "uz_phase_groups")
         return go, gq[: int(go[-1])]
+
+    def _bed_text(self, n: int, off, ptr):
+        total = int(off[n])
+        return (C.string_at(ptr.value, total) if total else b""), off  # (a copy: the context's block is the next call's)
+
+    def bed_rows(self, rows, str_off, str_bytes, verbose: bool, include_ambiguous: bool):
+        """The BED lines of rows of the LAST finished batch (uz_bed_rows), written on the device from the batch's result where it lies.
+        rows: abi.BED_ROW records; -> (bytes, off [n + 1]): row k is bytes[off[k]: off[k + 1]], empty when the row is dropped."""
+        v = abi.bed_view(rows, str_off, str_bytes)
+        n = int(v.view.n_rows)
+        off, ptr = np.zeros(n + 1, np.int64), C.c_void_p()
+        self._ck(self.L.uz_bed_rows(self.h, v.ref(), int(bool(verbose)), int(bool(include_ambiguous)), off.ctypes.data, C.byref(ptr)), "uz_bed_rows")
+        return self._bed_text(n, off, ptr)
+
+    def bed_rows_lists(self, rows, str_off, str_bytes, verbose: bool, include_ambiguous: bool, status, list_off, list_val, name_off, name_bytes, ratio: int):
+        """Test hook (uz_bed_rows_lists): the same kernels over the caller's lists -- uz_phase_votes' layout -- and a plain name store
+        (name_off None: no names); no read stage is run."""
+        v = abi.bed_view(rows, str_off, str_bytes)
+        n = int(v.view.n_rows)
+        status = np.ascontiguousarray(status, np.int32)
+        list_off = np.ascontiguousarray(list_off, np.int64)
+        list_val = np.ascontiguousarray(list_val, np.int32)
+        off, ptr = np.zeros(n + 1, np.int64), C.c_void_p()
+        if name_off is not None:
+            name_off, name_bytes = np.ascontiguousarray(name_off, np.uint32), np.ascontiguousarray(name_bytes, np.uint8)
+            nq, p_no, p_nb = int(name_off.size) - 1, name_off.ctypes.data, name_bytes.ctypes.data if name_bytes.size else None
+        else:
+            nq, p_no, p_nb = 0, None, None
+        self._ck(self.L.uz_bed_rows_lists(self.h, v.ref(), int(bool(verbose)), int(bool(include_ambiguous)), int(status.size), status.ctypes.data,
+                                          list_off.ctypes.data, list_val.ctypes.data if list_val.size else None, nq, p_no, p_nb, int(ratio),
+                                          off.ctypes.data, C.byref(ptr)), "uz_bed_rows_lists")
+        return self._bed_text(n, off, ptr)
 
     def phase_sizing(self, n: int, n_het: int) -> dict:
         """Test hook (uz_phase_sizing_fetch): the sizing pass's output for the last phase_raw / phase_end -- n DNMs, n_het = het_off[n] of the

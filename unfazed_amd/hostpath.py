@@ -233,12 +233,63 @@ class _Stats(dict):
     entered by their first increment"""
 
     ROUTE_KEYS = ("find_cohort_calls", "find_kid_calls", "cnv_cohort_calls", "cnv_kid_calls", "samples_parsed_device", "sites_unsettled",
-                  "bam_walks", "read_tables", "phase_cohort_calls", "cutoff_device_files", "cutoff_host_files", "cutoff_walk_calls")
+                  "bam_walks", "read_tables", "phase_cohort_calls", "cutoff_device_files", "cutoff_host_files", "cutoff_walk_calls",
+                  "bed_device_rows", "bed_host_rows", "bed_calls")  # (the BED sink: rows whose text the device wrote / that took the dict route, uz_bed_rows calls)
 
     def __missing__(self, key):
         if key in self.ROUTE_KEYS:
             return 0
         raise KeyError(key)
+
+
+class _BedSink:
+    """The BED route of a point-variant call (snv_phaser.phase_snvs_bed): every route that produces a device result hands it here WHILE it is
+    still the context's last batch (and before its tables are freed), and the lines of its phased DNMs are written on the device
+    (backend.bed_rows -> uz_bed_rows) -- no vote list, no read name and no records dict come to the host.  Pass 3 then places the lines in
+    `rows` (summarize.BedRows) in the records dict's order and with its key semantics.  The call's SEX-CHROM rows ride with the first batch."""
+
+    def __init__(self, host, rows, dnms, pedigrees):
+        self.host, self.rows, self.dnms, self.pedigrees = host, rows, dnms, pedigrees
+        self.auto: List[int] = []     # DNMs that are autophased (set after pass 1)
+        self.auto_at: Dict[int, tuple] = {}  # DNM -> (blob, first, last) of its SEX-CHROM line
+
+    def collect(self, res: dict, members) -> bool:
+        """members: (index in the result, DNM index, reads handle) of the result's DNMs.  -> False: the device refuses the run for its names
+        (a verbose call on a table that holds none on the device) -- nothing was done, the run takes the dict route."""
+        from .engine import UnfazedHipError
+        from .summarize import sex_chrom_origin
+        dnms, peds, st = self.dnms, self.pedigrees, abi.StringTable()
+        status = res["status"]
+        take = [(k, i, rid) for (k, i, rid) in members if int(status[k]) == abi.ST_OK]
+        auto, self.auto = self.auto, []
+        # the rows column by column (a tuple stored per row into the structured array costs more than everything else here)
+        dd = [dnms[i] for _, i, _ in take] + [dnms[i] for i in auto]
+        rows = np.zeros(len(dd), abi.BED_ROW)
+        rows["dnm"] = [k for k, _, _ in take] + [-1] * len(auto)
+        rows["start"] = [int(dn["start"]) for dn in dd]
+        rows["end"] = [int(dn["end"]) for dn in dd]
+        sid = st.id
+        rows["chrom"] = [sid(dn["chrom"]) for dn in dd]
+        rows["vartype"] = [sid(dn["vartype"]) for dn in dd]
+        rows["kid"] = [sid(dn["kid"]) for dn in dd]
+        rows["dad"] = [sid(peds[dn["kid"]]["dad"]) for dn in dd]
+        rows["mom"] = [sid(peds[dn["kid"]]["mom"]) for dn in dd]
+        rows["reads_id"] = [-1 if rid is None else int(rid) for _, _, rid in take] + [-1] * len(auto)
+        rows["sex_origin"] = [0] * len(take) + [sex_chrom_origin(dnms[i]["chrom"]) for i in auto]
+        try:
+            text, off = self.host.backend.bed_rows(rows, *st.arrays(), self.rows.verbose, self.rows.include_ambiguous)
+        except UnfazedHipError as e:
+            if "(-4)" in str(e) and ("names" in str(e) or "lists" in str(e)):
+                self.auto = auto
+                return False
+            raise
+        self.host.stats["bed_calls"] += 1
+        blob = self.rows.add_blob(text)
+        o = off.tolist()
+        res["bed"] = (blob, o, {k: j for j, (k, _, _) in enumerate(take)})
+        for j, i in enumerate(auto):
+            self.auto_at[i] = (blob, o[len(take) + j], o[len(take) + j + 1])
+        return True
 
 
 @dataclass
@@ -258,6 +309,7 @@ class _ReadCall:
     want_lists: bool
     mode: int
     results: Dict[int, tuple]
+    bed: Optional[_BedSink] = None  # phase_snvs_bed: the lines of every device result are written on the device, no lists are fetched
 
     def kid(self, kid: str, bam: str):
         """-> (family handle, insert cutoff) of one kid's group"""
@@ -832,11 +884,14 @@ class PhasingHost:
               with _Sec("done"):
                 part = parts[k]
                 lists = None
-                if call.want_lists:
+                res = dict(status=rr["status"], counts=rr["counts"], origin=rr["origin"], evidence=rr["evidence"], lists=None)
+                # (the BED sink: the chunk's lines are written on the device while the chunk is the context's last batch; a refused chunk goes on as ever)
+                sunk = call.bed is not None and call.bed.collect(res, [(j, i, rr.get("reads_id")) for j, i in enumerate(part)])
+                if call.want_lists and not sunk:
                     with _Sec("votes"):
                         vo, vv = self.backend.votes(len(part))
                     lists = _VoteLists(vo, vv)
-                res = dict(status=rr["status"], counts=rr["counts"], origin=rr["origin"], evidence=rr["evidence"], lists=lists)
+                res["lists"] = lists
                 table = types.SimpleNamespace(qnames=names.pop(k).qnames)
                 if lists is not None:
                     # the name and position lists of the chunk's records, built HERE -- beside the native decode of the chunks that follow -- and
@@ -917,9 +972,11 @@ class PhasingHost:
         self.stats["read_tables"] += 1
         try:
             dv = call.dnms_view(order, groups[0][4])
-            res = self.backend.phase_cohort_joined(rh, groups, src.ref_base[:-1], dv, call.params, [call.found[i] for i in order], call.want_lists,
-                                                   find_mode=call.mode)
+            res = self.backend.phase_cohort_joined(rh, groups, src.ref_base[:-1], dv, call.params, [call.found[i] for i in order],
+                                                   call.want_lists and call.bed is None, find_mode=call.mode)
             self.stats["phase_cohort_calls"] += 1
+            if call.bed is not None and not call.bed.collect(res, [(k, i, rh) for k, i in enumerate(order)]):
+                self._lists_after_all(res, len(order))
         finally:
             self.backend.free_reads(rh)
         for k, i in enumerate(order):
@@ -956,11 +1013,16 @@ class PhasingHost:
         if order_all:
             dv = call.dnms_view(order_all, groups[0][4])
             fl = [call.found[i] for i in order_all]
+            want = call.want_lists and call.bed is None
             if len(groups) == 1:
-                res = self.backend.phase(groups[0][0], groups[0][1], dv, call.params, fl, call.want_lists, find_mode=call.mode)
+                res = self.backend.phase(groups[0][0], groups[0][1], dv, call.params, fl, want, find_mode=call.mode)
             else:
-                res = self.backend.phase_cohort(groups, dv, call.params, fl, call.want_lists, find_mode=call.mode)
+                res = self.backend.phase_cohort(groups, dv, call.params, fl, want, find_mode=call.mode)
                 self.stats["phase_cohort_calls"] += 1
+            if call.bed is not None:  # (before the tables are freed: a verbose row reads its names out of its group's table)
+                members = [(k, order_all[k], rh) for (fam, rh, first, count, cutoff) in groups for k in range(first, first + count)]
+                if not call.bed.collect(res, members):
+                    self._lists_after_all(res, len(order_all))
             free = getattr(self.backend, "free_reads", None)
             for rh in handles:  # region tables live for one batch
                 if free:
@@ -968,6 +1030,11 @@ class PhasingHost:
             for g, (fam, rh, first, count, cutoff) in enumerate(groups):
                 for k in range(first, first + count):
                     call.results[order_all[k]] = (res, k, tables[g])
+
+    def _lists_after_all(self, res: dict, n: int) -> None:
+        """a result the BED sink's device call refused: its vote lists, fetched while it is still the last batch -- it takes the dict route"""
+        vo, vv = self.backend.votes(n)
+        res["lists"] = _VoteLists(vo, vv)
 
     def run_read_phasing(self, dnms, pedigrees, *args, **kwargs):
         """run_read_phasing_impl, and whatever it raises behind find() -- a reference KeyError mimicked in pass 1, an I/O error of a BAM stage --
@@ -997,10 +1064,14 @@ class PhasingHost:
         want_lists=True,
         sv=False,
         _attach_box=None,
+        bed_sink=None,
     ):
         """reference snv_phaser.py:206-299 (+ multithread_read_phasing :87-203); with sv=True the
         SV variant sv_phaser.py:176-266 (+ :88-173): no REF/ALT lookup, reads collected by
-        collect_reads_sv, and autophase that does not short-circuit (quirk Q18)."""
+        collect_reads_sv, and autophase that does not short-circuit (quirk Q18).
+        bed_sink (_BedSink, point variants only): the BED route -- every device result's lines are written on the device, pass 3 places them in
+        the sink's BedRows instead of building records (the returned dict stays empty), no vote list and no read name is fetched, and the
+        caller's DNM dicts are NOT annotated with `candidate_sites` / `het_sites` (find(attach=False))."""
         log = _Log(quiet_mode)
         self._indexed_memo = {}
         params.no_extended = 1 if no_extended else 0
@@ -1009,7 +1080,7 @@ class PhasingHost:
         with _Sec("find"):
             ret, info = self.find(
                 dnms, pedigrees, search_dist, threads, build, multithread_proc_min, quiet_mode, params,
-                whole_region=False, defer_attach=True,
+                whole_region=False, defer_attach=True, attach=bed_sink is None,
             )
         records: Dict[str, dict] = {}
         if ret is None:
@@ -1067,7 +1138,9 @@ class PhasingHost:
         results: Dict[int, dict] = {}
         sec_pass1.__exit__()
         call = _ReadCall(host=self, dnms=dnms, pedigrees=pedigrees, prep=prep, found=found, params=params, readlen=readlen, stdevs=stdevs,
-                         insert_size_max_sample=insert_size_max_sample, want_lists=want_lists, mode=info["mode"], results=results)
+                         insert_size_max_sample=insert_size_max_sample, want_lists=want_lists, mode=info["mode"], results=results, bed=bed_sink)
+        if bed_sink is not None:
+            bed_sink.auto = [i for i, action in plan if action == "auto"]  # (their lines ride with the first device result)
         with _Sec("cutoffs"):  # (UZ_CUTOFF_ROUTE=device; what scripts/cutoff_route_ab.py times by route)
             self.prepare_cutoffs(list(batch), readlen, stdevs, insert_size_max_sample)
         with _Sec("chunked"):
@@ -1102,7 +1175,10 @@ class PhasingHost:
             dad_id, mom_id = pedigrees[dn["kid"]]["dad"], pedigrees[dn["kid"]]["mom"]
             region = {"chrom": dn["chrom"], "start": dn["start"], "end": dn["end"]}
             key = "_".join([str(v) for v in region.values()] + [dn["kid"], dn["vartype"]])
-            if action == "auto":
+            if action == "auto" and bed_sink is not None and i in bed_sink.auto_at:
+                bed_sink.rows.add(key, dn["chrom"], dn["start"], dn["end"], *bed_sink.auto_at[i])
+                self.stats["bed_device_rows"] += 1
+            elif action == "auto":
                 records[key] = {
                     "region": region, "vartype": dn["vartype"], "kid": dn["kid"], "dad": dad_id, "mom": mom_id,
                     "cnv_dad_sites": "NA", "cnv_mom_sites": "NA", "cnv_evidence_type": "SEX-CHROM",
@@ -1136,6 +1212,11 @@ class PhasingHost:
                     # ST_REF_EXCEPTION: the reference's worker raises (KeyError in connect_reads) and the default
                     # thread pool swallows it: no record, no message
                     continue
+                if "bed" in res:  # (the BED sink: the line lies in the result's blob)
+                    blob, o, at = res["bed"]
+                    bed_sink.rows.add(key, dn["chrom"], dn["start"], dn["end"], blob, o[at[k]], o[at[k] + 1])
+                    self.stats["bed_device_rows"] += 1
+                    continue
                 if res.get("lists") is not None:
                     dad_reads, mom_reads, dad_sites, mom_sites = res["built"][k]
                 else:
@@ -1148,6 +1229,9 @@ class PhasingHost:
                     "dad_reads": dad_reads, "mom_reads": mom_reads,
                     "cnv_dad_sites": "", "cnv_mom_sites": "", "cnv_evidence_type": "",
                 }
+            if bed_sink is not None and key in records:  # (what took the dict route under the sink: placed here, in the plan's order)
+                bed_sink.rows.add_records({key: records.pop(key)})
+                self.stats["bed_host_rows"] += 1
         sec_pass3.__exit__()
         _Sec.report()
         return records

@@ -74,6 +74,7 @@ def run_pipelined(eng, P, mode, n: int, chunks: Sequence[dict], cnv: bool = Fals
 
     def read_stage_end(k):
         pending[k] = eng.phase_end(fids[k], rids[k], chunks[k]["dnms"], P, mode)
+        pending[k]["reads_id"] = rids[k]  # (on_done may ask the device about the chunk while it is the last batch: hostpath's BED sink names its table)
         if on_done is not None:
             on_done(k, pending[k])
         if not cnv:

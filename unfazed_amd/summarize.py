@@ -137,9 +137,19 @@ def summarize_record(rec: dict, include_ambiguous: bool, verbose: bool, evidence
     return out
 
 
+def _bed_cols(verbose: bool) -> List[str]:
+    return list(BED_HEADER) + (BED_VERBOSE if verbose else [])
+
+
+def _bed_line(s: dict, cols: List[str]) -> str:
+    s = dict(s)
+    s["evidence_types"] = ",".join(s["evidence_types"])
+    return "\t".join(str(s[c.lstrip("#")]) for c in cols)
+
+
 def bed_lines(records: Dict[str, dict], include_ambiguous: bool, verbose: bool, evidence_min_ratio: int) -> List[str]:
     """Header + body lines of reference write_bed_output (unfazed.py:444-515)."""
-    cols = list(BED_HEADER) + (BED_VERBOSE if verbose else [])
+    cols = _bed_cols(verbose)
     rows = []
     for key in records:
         s = summarize_record(records[key], include_ambiguous, verbose, evidence_min_ratio)
@@ -148,10 +158,70 @@ def bed_lines(records: Dict[str, dict], include_ambiguous: bool, verbose: bool, 
     rows.sort(key=lambda x: (x["chrom"], x["start"], x["end"]))  # chrom compared as a string (:497-499)
     lines = ["\t".join(cols)]
     for s in rows:
-        s = dict(s)
-        s["evidence_types"] = ",".join(s["evidence_types"])
-        lines.append("\t".join(str(s[c.lstrip("#")]) for c in cols))
+        lines.append(_bed_line(s, cols))
     return lines
+
+
+def sex_chrom_origin(chrom: str) -> int:
+    """summarize_autophased's test, for a SEX-CHROM row of uz_bed_rows: 0 -- chrY, the dad is the origin -- or 1"""
+    return 0 if chrom.lower().strip("chr") == "y" else 1
+
+
+class BedRows:
+    """The body of a BED output as rows of text that were never records: per record key its (chrom, start, end) and where its line lies --
+    blob, first byte, one past the last (the '\\n' included) -- in the order and with the semantics of the records dict: a key that comes
+    again keeps its PLACE and takes the new content, an empty line (first == last: summarize_record gave None) prints nothing.  The lines are
+    the device's (uz_bed_rows, through hostpath's sink) or, for what took the dict route, summarize_record's.
+    lines() / write() order them exactly as bed_lines does: by (chrom as str, start, end), stable."""
+
+    def __init__(self, include_ambiguous: bool, verbose: bool, evidence_min_ratio: int):
+        self.include_ambiguous, self.verbose, self.evidence_min_ratio = bool(include_ambiguous), bool(verbose), evidence_min_ratio
+        self.blobs: List[bytes] = []
+        self.rows: Dict[str, tuple] = {}  # key -> (chrom, start, end, blob, a, b)
+
+    def add_blob(self, blob: bytes) -> int:
+        self.blobs.append(blob)
+        return len(self.blobs) - 1
+
+    def add(self, key: str, chrom: str, start, end, blob: int, a: int, b: int) -> None:
+        self.rows[key] = (chrom, int(start), int(end), blob, int(a), int(b))
+
+    def add_records(self, records: Dict[str, dict]) -> None:
+        """records of the dict route (a backend without bed_rows, a run the device refused, SV records merged in: dict.update's semantics)"""
+        cols = _bed_cols(self.verbose)
+        parts, at, blob = [], 0, len(self.blobs)
+        for key, rec in records.items():
+            s = summarize_record(rec, self.include_ambiguous, self.verbose, self.evidence_min_ratio)
+            line = b"" if s is None else (_bed_line(s, cols) + "\n").encode()
+            region = rec["region"]
+            self.add(key, region["chrom"], region["start"], region["end"], blob, at, at + len(line))
+            parts.append(line)
+            at += len(line)
+        self.blobs.append(b"".join(parts))
+
+    def _sorted(self) -> List[tuple]:
+        rows = [r for r in self.rows.values() if r[5] > r[4]]
+        rows.sort(key=lambda r: (r[0], r[1], r[2]))
+        return rows
+
+    def lines(self) -> List[str]:
+        """what bed_lines gives: the header, then the body lines without their line ends"""
+        blobs = self.blobs
+        return ["\t".join(_bed_cols(self.verbose))] + [blobs[r[3]][r[4]: r[5] - 1].decode() for r in self._sorted()]
+
+    def text(self) -> str:
+        blobs = self.blobs
+        return "\t".join(_bed_cols(self.verbose)) + "\n" + b"".join([blobs[r[3]][r[4]: r[5]] for r in self._sorted()]).decode()
+
+    def write(self, outfile: str, extra_records: Optional[Dict[str, dict]] = None) -> None:
+        """write_bed_output; extra_records (the SV records of the same call) are merged in first, as `records.update(sv_records)` merges them"""
+        if extra_records:
+            self.add_records(extra_records)
+        if outfile == "/dev/stdout":
+            sys.stdout.write(self.text())
+        else:
+            with open(outfile, "w") as fh:
+                fh.write(self.text())
 
 
 def write_bed_output(records, include_ambiguous, verbose, outfile, evidence_min_ratio):

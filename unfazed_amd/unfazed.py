@@ -15,7 +15,7 @@ from . import __reference_version__
 from .hostpath import SNV_TYPES, SV_TYPES
 from .io_vcf import read_vcf
 from .model import HET, HOM_ALT
-from .snv_phaser import phase_snvs
+from .snv_phaser import phase_snvs, phase_snvs_bed
 from .summarize import summarize_record, write_bed_output
 from .sv_phaser import phase_svs
 
@@ -292,6 +292,15 @@ def _ranks(args):
     return rank, world, dist
 
 
+BED_ROUTE_DEFAULT = "host"  # UZ_BED_ROUTE not set: "device" is admitted only once profiles/bed_route_ab.json shows every device run ahead of every host run
+
+
+def bed_route() -> str:
+    """UZ_BED_ROUTE: "device" -- a single-rank call that writes BED gets its point variants' lines from the device (phase_snvs_bed) -- or
+    "host" (the records dict and summarize.bed_lines).  Annotated-VCF output and calls of more than one rank always take the dict route."""
+    return "device" if os.environ.get("UZ_BED_ROUTE", BED_ROUTE_DEFAULT).lower() == "device" else "host"
+
+
 def unfazed(args):
     """reference unfazed.py:518-667: read the DNMs, find each kid's alignment file and pedigree entry, phase
     SVs and point variants through the two phasers, write BED or annotated VCF."""
@@ -347,6 +356,13 @@ def unfazed(args):
         if svs:
             sv_records = phase_svs(svs, kids, pedigrees, args.sites, *thresholds, evidence_min_ratio=args.evidence_min_ratio,
                                    allele_balance_only=getattr(args, "sv_allele_balance_only", False))
+        if snvs and output_type == "bed" and bed_route() == "device":
+            # the point variants' lines are written on the device (snv_phaser.phase_snvs_bed); the SVs keep their records, whose lines are
+            # merged into the sort behind the point variants' -- the order `dict(snv_records); update(sv_records)` gives
+            rows = phase_snvs_bed(snvs, kids, pedigrees, args.sites, *thresholds, evidence_min_ratio=args.evidence_min_ratio,
+                                  include_ambiguous=args.include_ambiguous, verbose=args.verbose)
+            rows.write(args.outfile, extra_records=sv_records)
+            return
         if snvs:
             snv_records = phase_snvs(snvs, kids, pedigrees, args.sites, *thresholds, evidence_min_ratio=args.evidence_min_ratio)
     records = dict(snv_records)
