@@ -44,6 +44,16 @@ typedef struct uz_need_rec {
     uint32_t pad;
 } uz_need_rec;
 
+/* The end of the mate closure -- ONE rule for every route (csrc/io_stage.cpp: plan_finish; csrc/k_bamjoin.hip: uz_join_run; io_native.py:
+ * _joined_on_the_device; tests/joinmodel.py):
+ *   - a closure ends when its frontier is empty;
+ *   - generations in memory are not capped: every non-empty generation makes a record a member that was none, so the number of descriptors bounds
+ *     them, and reaching that bound is an internal error, never an answer;
+ *   - a trip through the index (the members whose mate no walked task can answer, looked up together: uz_stage_lookup) is allowed
+ *     UZ_JOIN_MAX_TRIPS times per batch.  A batch that needs one more is REFUSED with an error that names the cap -- no route answers it with
+ *     the members it happened to have by then. */
+#define UZ_JOIN_MAX_TRIPS 64
+
 /* A batch over many files presented as one (unfazed_io.h: uz_bamsrc_open_many): what the walk needs of the file a walk task lies in, per task
  * (uz_bam_walk_many derives it from the per-file table and the task's first block).  A record's refID / next_refID that the file's header knows
  * (0 <= r < n_ref) get ref_base added, one it does not know becomes INT32_MAX; h1 / h2 are XOR-ed with the salts. */

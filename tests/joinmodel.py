@@ -13,7 +13,13 @@ stable sort.  The device cannot walk records one after the other, so its rules a
   * members = the fetched records, closed under mate(); kept = members, one per virtual offset (the copy a fetch returned wins);
   * order = virtual offset; name ids = rank of a name's first kept record among the first kept records; mate = the kept index of mate(x)'s survivor.
 
-`tests/test_join_model.py` holds this against the one-pass stage on the CPU; `tests/test_bamjoin_gpu.py` holds the kernels against both."""
+  * the closure's end (include/uz_bamwalk.h UZ_JOIN_MAX_TRIPS): generations until the frontier is empty, uncapped; at most MAX_TRIPS trips through
+    the index -- a batch that needs one more is refused (ClosureRefused), never answered with what it had by then.
+
+`join` is the pure statement: descriptors, join tasks, the covering and a `lookup` that answers needs -- nothing of it talks to a library; `run` feeds
+it from the stage library (the host's share of the device route: tasks handed back, mates through the index).  `tests/test_join_model.py` holds
+this against the one-pass stage on the CPU on random pile-ups, `tests/test_join_cases.py` on the hand-built panel of tests/joincases.py;
+`tests/test_bamjoin_gpu.py` and `tests/test_join_cases_gpu.py` hold the kernels against both."""
 import ctypes as C
 
 import numpy as np
@@ -21,6 +27,12 @@ import numpy as np
 from unfazed_amd import io_native
 
 FPAIRED, FMUNMAP, FREAD1, FREAD2 = 0x1, 0x8, 0x40, 0x80
+MAX_TRIPS = 64  # include/uz_bamwalk.h UZ_JOIN_MAX_TRIPS
+REFUSED = "did not end after %d trips through the index" % MAX_TRIPS
+
+
+class ClosureRefused(Exception):
+    """the batch needs more than MAX_TRIPS trips through the index"""
 
 
 def join_tasks(desc, d_first, task, h_flags):
@@ -60,30 +72,18 @@ class Reach:
         return -1
 
 
-def run(lib, stage, desc, d_first, d_flags, plan, n_ref, all_bases=False):
-    """-> dict(voff, qname, mate, bases, n_qnames, src, lookups) of the kept records in output order"""
-    task, reach = plan["task"], plan["reach"]
-    n_host = int(task[:, 9].max()) + 1 if task.shape[0] else 0
-    h_flags = np.zeros(max(1, n_host), np.int32)
-    tot = (C.c_int64 * 2)()
-    d_flags = np.ascontiguousarray(d_flags, np.int32)
-    io_native._check(lib, lib.uz_stage_walk_flagged(stage, d_flags.ctypes.data, h_flags.ctypes.data, tot))
-
-    def extras(d0, a0):
-        x = np.zeros(max(1, int(tot[0]) - d0), io_native.WALK_DESC)
-        io_native._check(lib, lib.uz_stage_extra(stage, d0, a0, x.ctypes.data, None, None))
-        return x[: int(tot[0]) - d0]
-
-    jt, drop = join_tasks(desc, d_first, task, h_flags)
-    x = extras(0, 0)
-    D = np.concatenate([desc[: int(d_first[-1])], x])
-    jt = np.concatenate([jt, (x["task"] & 0x7FFFFFFF).astype(np.int64)])
-    drop = np.concatenate([drop, np.zeros(x.size, bool)])
-    assert (x["task"] & io_native.WALK_TASK_JOIN).all()
-    R = Reach(task, reach)
+def join(D, jt, drop, covering, n_ref, lookup=None, all_bases=False, trace=None):
+    """The joins over descriptors alone -> dict(voff, qname, mate, bases, n_qnames, src, lookups, trips) of the kept records in output order.
+    D: WALK_DESC rows; jt: the join task of each; drop: the dropped copies; covering(tid, pos) -> the join task whose reach holds the position or
+    -1; lookup(D, need) -> (new WALK_DESC rows, whose .task carries WALK_TASK_JOIN + their join task; the join task that answers each need) -- the
+    index; trace: a dict that receives what the closure did (needs per trip, generations per trip, the copies the fold rule silenced, the covering
+    task of every asker, and the final D / jt / keep / mate)"""
+    D, jt, drop = D.copy(), np.asarray(jt, np.int64).copy(), np.asarray(drop, bool).copy()
     keep = np.where(drop, 0, np.where(D["direct"] != 0, 2, 0)).astype(np.int8)
     mate = np.full(D.size, -2, np.int64)
     target = {}  # member -> the look-up task that answers it
+    tr = dict(needs=[], gens=[], folded=[], tc={}) if trace is None else trace
+    tr.update(needs=[], gens=[], folded=[], tc={})
 
     def groups_of(D, drop):
         g = {}
@@ -93,10 +93,12 @@ def run(lib, stage, desc, d_first, d_flags, plan, n_ref, all_bases=False):
 
     groups = groups_of(D, drop)
     frontier = [int(i) for i in np.flatnonzero(keep == 2)]
-    n_lookups = 0
-    for _round in range(64):
-        need = []
+    n_lookups = trips = 0
+    while True:
+        need, gens = [], 0
         while frontier:
+            assert gens <= D.size, "the closure ran more generations than the batch has descriptors"
+            gens += 1
             nxt = []
             for i in frontier:
                 if mate[i] != -2:
@@ -106,10 +108,13 @@ def run(lib, stage, desc, d_first, d_flags, plan, n_ref, all_bases=False):
                 # a copy that will be folded away -- another copy of the same record is a member and wins the fold -- asks for nothing (without this
                 # rule two mates outside every reach interval look each other up for ever: every answer of the index is a new copy)
                 folds = any(e != i and D["voff"][e] == xr["voff"] and (keep[e] > keep[i] or (keep[e] == keep[i] and e < i)) for e in groups.get(int(xr["h1"]), ()))
+                if folds:
+                    tr["folded"].append(i)
                 if folds or not ((fl & FPAIRED) and not (fl & FMUNMAP) and 0 <= int(xr["mtid"]) < n_ref):
                     mate[i] = -1
                     continue
-                tc = target[i] if i in target else R.covering(int(xr["mtid"]), int(xr["mpos"]))
+                tc = target[i] if i in target else covering(int(xr["mtid"]), int(xr["mpos"]))
+                tr["tc"].setdefault(i, tc)
                 if tc < 0:
                     need.append(i)
                     continue
@@ -131,16 +136,16 @@ def run(lib, stage, desc, d_first, d_flags, plan, n_ref, all_bases=False):
                     keep[best] = 1
                     nxt.append(best)
             frontier = nxt
+        tr["gens"].append(gens)
         if not need:
             break
-        nr = np.zeros(len(need), io_native.NEED_REC)
-        for k, i in enumerate(need):
-            nr[k] = (D["h1"][i], D["h2"][i], D["l_name"][i], D["mtid"][i], D["mpos"][i], i, 0)
-        ans = np.zeros(len(need), np.int32)
-        d0 = int(tot[0])
-        io_native._check(lib, lib.uz_stage_lookup(stage, len(need), nr.ctypes.data, ans.ctypes.data, tot))
+        if trips == MAX_TRIPS:
+            raise ClosureRefused("the mate closure of the batch " + REFUSED)
+        trips += 1
+        tr["needs"].append(list(need))
+        x, ans = lookup(D, need)
         n_lookups += len(need)
-        x = extras(d0, 0)
+        assert (x["task"] & io_native.WALK_TASK_JOIN).all()
         D = np.concatenate([D, x])
         jt = np.concatenate([jt, (x["task"] & 0x7FFFFFFF).astype(np.int64)])
         drop = np.concatenate([drop, np.zeros(x.size, bool)])
@@ -175,5 +180,40 @@ def run(lib, stage, desc, d_first, d_flags, plan, n_ref, all_bases=False):
     m = mate[surv]
     mate_out = np.where(m >= 0, gidx[np.maximum(m, 0)], -1)
     bases = (keep[surv] == 2) | bool(all_bases)
+    tr.update(D=D, jt=jt, keep=keep, mate=mate, surv=surv)
     return dict(voff=D["voff"][surv], qname=qname.astype(np.uint32), mate=mate_out.astype(np.int32), bases=bases, n_qnames=int(is_first.sum()),
-                src=D["src"][surv], lookups=n_lookups, n_extra=int(tot[0]), h_flags=h_flags, trips=_round)
+                src=D["src"][surv], lookups=n_lookups, trips=trips)
+
+
+def run(lib, stage, desc, d_first, d_flags, plan, n_ref, all_bases=False, trace=None):
+    """`join` fed from the stage library -> its dict + n_extra, h_flags.  trips: the trips through the index the batch needed"""
+    task, reach = plan["task"], plan["reach"]
+    n_host = int(task[:, 9].max()) + 1 if task.shape[0] else 0
+    h_flags = np.zeros(max(1, n_host), np.int32)
+    tot = (C.c_int64 * 2)()
+    d_flags = np.ascontiguousarray(d_flags, np.int32)
+    io_native._check(lib, lib.uz_stage_walk_flagged(stage, d_flags.ctypes.data, h_flags.ctypes.data, tot))
+
+    def extras(d0, a0):
+        x = np.zeros(max(1, int(tot[0]) - d0), io_native.WALK_DESC)
+        io_native._check(lib, lib.uz_stage_extra(stage, d0, a0, x.ctypes.data, None, None))
+        return x[: int(tot[0]) - d0]
+
+    def lookup(D, need):
+        nr = np.zeros(len(need), io_native.NEED_REC)
+        for k, i in enumerate(need):
+            nr[k] = (D["h1"][i], D["h2"][i], D["l_name"][i], D["mtid"][i], D["mpos"][i], i, 0)
+        ans = np.zeros(len(need), np.int32)
+        d0 = int(tot[0])
+        io_native._check(lib, lib.uz_stage_lookup(stage, len(need), nr.ctypes.data, ans.ctypes.data, tot))
+        return extras(d0, 0), ans
+
+    jt, drop = join_tasks(desc, d_first, task, h_flags)
+    x = extras(0, 0)
+    assert (x["task"] & io_native.WALK_TASK_JOIN).all()
+    D = np.concatenate([desc[: int(d_first[-1])], x])
+    jt = np.concatenate([jt, (x["task"] & 0x7FFFFFFF).astype(np.int64)])
+    drop = np.concatenate([drop, np.zeros(x.size, bool)])
+    out = join(D, jt, drop, Reach(task, reach).covering, n_ref, lookup, all_bases, trace)
+    out.update(n_extra=int(tot[0]), h_flags=h_flags)
+    return out

@@ -1155,7 +1155,43 @@ void plan_finish(uz_stage &P, const uz_walk_desc *d = nullptr, const int64_t *d_
     }
     int64_t n_lookups = 0;
     if (!frontier.empty()) build_by_name();
-    for (int gen = 0; gen < 64 && !frontier.empty(); gen++) {
+    // A copy the index brought of a record that IS a member already -- in a task of the first walk, or as an earlier copy from the index -- will be
+    // folded away at the end (the member wins: it was fetched, or it is as good and comes first), and only the survivor's mate is ever read: it asks
+    // for nothing.  Without this rule two mates outside every reach interval look each other up for ever -- every answer of the index is a new copy
+    // of the partner, which asks for a new copy of the first (k_bamjoin.hip k_join_round and tests/joinmodel.py state the same rule).
+    std::unordered_map<uint64_t, int64_t> look_member; // the members that are copies from the index: virtual offset -> the first such copy
+    auto folds_away = [&](int64_t ref) -> bool {
+        const size_t ti = (size_t)(ref >> 32);
+        if (ti < n_tasks0) return false;
+        const WRec &x = rec_of(P, ref);
+        const auto lm = look_member.find(x.voff);
+        if (lm != look_member.end() && lm->second < ref) return true;
+        const int32_t tid_q = P.tasks[ti].tid;
+        size_t lo_i = 0, hi_i = n_tasks0; // the tasks of the first walk that can have met the record: the first that ends behind its first base, and on
+        while (lo_i < hi_i) {
+            const size_t mid = (lo_i + hi_i) / 2;
+            const Task &M = P.tasks[mid];
+            if (M.tid < tid_q || (M.tid == tid_q && M.b <= x.pos)) lo_i = mid + 1; else hi_i = mid;
+        }
+        for (; lo_i < n_tasks0 && P.tasks[lo_i].tid == tid_q && P.tasks[lo_i].a < x.end; lo_i++) {
+            const Task &T = P.tasks[lo_i];
+            const auto &v = by_name[lo_i].v;
+            for (auto it = std::lower_bound(v.begin(), v.end(), std::make_pair(x.nhash, (uint32_t)0)); it != v.end() && it->first == x.nhash; ++it) {
+                const WRec &y = T.recs[it->second];
+                if (y.voff == x.voff && y.keep != 0) return true;
+            }
+        }
+        return false;
+    };
+    // the closure's end: uz_bamwalk.h UZ_JOIN_MAX_TRIPS states the rule -- generations until the frontier is empty, every one of them makes a record
+    // a member that was none; the trips through the index are counted, and a batch that needs one more than the cap is refused
+    int trips = 0;
+    for (int64_t gen = 0; !frontier.empty(); gen++) {
+        {
+            int64_t n_recs = 0;
+            for (const Task &T : P.tasks) n_recs += (int64_t)T.recs.size();
+            if (gen > n_recs) fail(UZ_IO_E_RANGE, "internal: the mate closure ran more generations than the batch has records");
+        }
         std::vector<Lookup> need;
         {
             const int w = workers_for((int64_t)frontier.size(), threads, 4096);
@@ -1165,12 +1201,14 @@ void plan_finish(uz_stage &P, const uz_walk_desc *d = nullptr, const int64_t *d_
                     const int64_t ref = frontier[(size_t)i];
                     WRec &x = rec_of(P, ref);
                     if (x.mate_ref != -2) continue;
+                    if (folds_away(ref)) { x.mate_ref = -1; continue; }
                     if (!resolve_fast((size_t)(ref >> 32), (size_t)(ref & 0xFFFFFFFF))) part[(size_t)k].push_back(Lookup{ref, x.mtid, x.mpos});
                 }
             });
             for (auto &v : part) need.insert(need.end(), v.begin(), v.end());
         }
         if (!need.empty()) { // through the index: one extra task per look-up position (walked like a one-base fetch)
+            if (++trips > UZ_JOIN_MAX_TRIPS) fail(UZ_IO_E_RANGE, "the mate closure of the batch did not end after %d trips through the index", (int)UZ_JOIN_MAX_TRIPS);
             std::sort(need.begin(), need.end(), [](const Lookup &x, const Lookup &y) { return x.mtid < y.mtid || (x.mtid == y.mtid && (x.mpos < y.mpos || (x.mpos == y.mpos && x.who < y.who))); });
             n_lookups += (int64_t)need.size();
             std::vector<size_t> first; // look-ups of one position share a task
@@ -1222,6 +1260,11 @@ void plan_finish(uz_stage &P, const uz_walk_desc *d = nullptr, const int64_t *d_
             });
             for (auto &v : part) next.insert(next.end(), v.begin(), v.end());
         }
+        for (int64_t m : next)
+            if ((size_t)(m >> 32) >= n_tasks0) {
+                auto ins = look_member.emplace(rec_of(P, m).voff, m);
+                if (!ins.second && m < ins.first->second) ins.first->second = m;
+            }
         frontier.swap(next);
     }
     double t3 = now_s();

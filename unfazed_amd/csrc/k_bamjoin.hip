@@ -7,7 +7,8 @@
 //
 // The host walks records one after the other, task by task (hash tables in file order, a frontier per generation, a stable sort at the end); a
 // device cannot, so the rules are stated ORDER-FREE over all descriptors of the batch (tests/joinmodel.py is this file in numpy; tests/
-// test_join_model.py holds it against the one-pass stage on the CPU, tests/test_bamjoin_gpu.py holds these kernels against both):
+// test_join_model.py holds it against the one-pass stage on the CPU, tests/test_bamjoin_gpu.py holds these kernels against both; tests/joincases.py is
+// the hand-built panel, one case per rule's edge, that tests/test_join_cases_gpu.py holds them to, with tests/joinoracle.py as the plain reference):
 //
 //   join task   of a descriptor: the stage task its walk task is part of (plan column 9) -- or what the host says for a record it walked itself
 //               (a task handed back: uz_stage_walk_flagged; a mate looked up through the index: uz_stage_lookup)
@@ -172,7 +173,7 @@ __global__ __launch_bounds__(256) void k_join_round(JoinArgs a, int r) {
                 // A copy that will be folded away (the same record met by another task, or found once more through the index, whose other copy is a
                 // member already and wins the fold: fetched, or as good and earlier) asks for nothing: only its survivor's mate is ever read.  Without
                 // this rule two mates outside every reach interval look each other up for ever -- every answer of the index is a NEW copy of the
-                // partner, which asks for a new copy of the first (the host's loop runs into its cap of 64 generations there).
+                // partner, which asks for a new copy of the first (io_stage.cpp plan_finish has the rule for the copies the index brings).
                 bool folds = false;
                 {
                     const unsigned long long v = x.voff;
@@ -236,8 +237,8 @@ __global__ __launch_bounds__(256) void k_set_targets(int64_t n, const uint32_t *
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
     const int32_t t = ans[k];
-    if (t < 0 || t >= n_jt) { cnt[C_ERR] = 3; return; }
-    target[need[k]] = t;
+    if (t < 0 || t >= n_jt) cnt[C_ERR] = 3; // (the call is refused behind its first look at the counters; until then the rounds run over a frontier
+    else target[need[k]] = t;               // whose every slot is a record of the batch -- the asker, unanswered -- not over what the buffer held before)
     front[k] = need[k];
 }
 
@@ -444,10 +445,15 @@ void uz_join_run(uz_ctx *c, uz_ctx::WalkSlot &w, const JoinPlanHost &P, const uz
     int64_t n_reach = 0;
     if (first_call) {
         UZ_REQUIRE(P.n_host >= 0 && P.n_ref >= 0 && (P.n_host == 0 || P.h_flags), UZ_E_ARG, "uz_bam_join: bad plan");
-        J.n_host = P.n_host; J.n_ref = P.n_ref; J.all_bases = P.all_bases; J.n_look = 0; J.round = 0; J.n_need = 0; J.aux_bytes = 0;
+        J.n_host = P.n_host; J.n_ref = P.n_ref; J.all_bases = P.all_bases; J.n_look = 0; J.round = 0; J.trips = 0; J.n_need = 0; J.aux_bytes = 0;
         J.n_dev = w.n_desc; J.n_all = w.n_desc;
-    } else
+    } else {
         UZ_REQUIRE((J.n_need > 0) == (need_jtask != nullptr), UZ_E_ARG, "uz_bam_join: the answers to the last call's needs (uz_stage_lookup), and only then");
+        // (uz_bamwalk.h: the closure's end.  The caller counts its trips and refuses the batch itself; this is the rule for a caller that does not)
+        UZ_REQUIRE(!need_jtask || J.trips < UZ_JOIN_MAX_TRIPS, UZ_E_RANGE, "uz_bam_join: the mate closure of the batch did not end after 64 trips through the index");
+        static_assert(UZ_JOIN_MAX_TRIPS == 64, "the message above names the cap");
+        if (need_jtask) J.trips++;
+    }
     const int64_t n_old = J.n_all, n_new = n_old + n_x;
     UZ_REQUIRE(n_new < (int64_t)0x7FFFFFF0, UZ_E_RANGE, "uz_bam_join: more than 2^31 descriptors");
     // ---- room
@@ -502,10 +508,13 @@ void uz_join_run(uz_ctx *c, uz_ctx::WalkSlot &w, const JoinPlanHost &P, const uz
         UZ_HIP(hipMemcpyAsync(J.cnt.p + C_NEED, &set[1], 4, hipMemcpyHostToDevice, st));
         UZ_HIP(hipStreamSynchronize(st)); // (`set` and the caller's arrays are pageable)
     }
-    // ---- the closure: generations until the frontier is empty (four per look at the counters: fetched records, their mates, an empty round)
+    // ---- the closure: generations until the frontier is empty (four per look at the counters: fetched records, their mates, an empty round).
+    // uz_bamwalk.h states the end: no cap on the generations -- every non-empty one makes a descriptor a member that was none, so there are at most
+    // n_new + 1 of them, and more is an internal error; a non-empty frontier never reaches the final pass.
     const unsigned gr = (unsigned)std::min<int64_t>(std::max<int64_t>(1, (n_new + 255) / 256), 2048);
     int32_t cnt[C_COUNT];
-    for (int guard = 0; guard < 64; guard++) {
+    for (int64_t gens = 0;; gens += 4) {
+        UZ_REQUIRE(gens <= n_new + 4, UZ_E_STATE, "uz_bam_join: internal: the mate closure ran more generations than the batch has descriptors");
         for (int k = 0; k < 4; k++) hipLaunchKernelGGL(k_join_round, dim3(gr), dim3(256), 0, st, a, J.round + k);
         J.round += 4;
         UZ_HIP(hipMemcpyAsync(cnt, J.cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));

@@ -400,7 +400,7 @@ struct uz_ctx {
         // behind them what the host walked itself (tasks handed back, mates looked up through the index) -- with their join state
         struct Join {
             int64_t n_dev = 0, n_all = 0, aux_bytes = 0;
-            int32_t n_host = 0, n_look = 0, n_ref = 0, round = 0;
+            int32_t n_host = 0, n_look = 0, n_ref = 0, round = 0, trips = 0; // trips: answered sets of needs (uz_bamwalk.h UZ_JOIN_MAX_TRIPS)
             int64_t n_need = 0;
             bool filled = false, started = false, done = false, all_bases = false;
             UZ_JOIN_BUFS(UZ_X)

@@ -802,6 +802,7 @@ NEED_REC = np.dtype([("h1", "<u8"), ("h2", "<u4"), ("l_name", "<u4"), ("mtid", "
 assert WALK_DESC.itemsize == 64 and KEPT_REC.itemsize == 32 and NEED_REC.itemsize == 32
 WALK_TASK_JOIN = 0x80000000
 WALK_TASK_COLS, WALK_SPAN_COLS = 10, 6
+JOIN_MAX_TRIPS = 64  # include/uz_bamwalk.h UZ_JOIN_MAX_TRIPS: the closure's end, one rule for every route
 KEPT_NO_SEQ = 0xFFFFFFFF
 WALK_SRC_AUX = 1 << 63
 
@@ -1153,8 +1154,8 @@ class BamSource:
                 rounds += 1
                 if n_need == 0:
                     break
-                if rounds > 64:
-                    raise IoError(-4, "the mate closure of the batch did not end after 64 trips through the index")
+                if rounds > JOIN_MAX_TRIPS:  # (the answers of JOIN_MAX_TRIPS trips are in, and members still ask)
+                    raise IoError(-4, "the mate closure of the batch did not end after %d trips through the index" % JOIN_MAX_TRIPS)
                 need = dev.join_needs(token, n_need)
                 need_ans = np.zeros(n_need, np.int32)
                 _check(lib, lib.uz_stage_lookup(sh.ptr, int(n_need), need.ctypes.data, need_ans.ctypes.data, tot))
