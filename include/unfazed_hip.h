@@ -57,7 +57,9 @@ extern "C" {
 #define UZ_K_HEAD_RANK 15    /* k_head_rank */
 #define UZ_K_BED_SIZE 16    /* k_bed_size + the scan of the rows' lengths (uz_bed_rows) */
 #define UZ_K_BED_FILL 17    /* k_bed_fill */
-#define UZ_K_COUNT 18
+#define UZ_K_VCFOUT_SIZE 18 /* k_vcfout_size + the scan of the records' lengths (uz_vcf_rows), one launch per chunk of text */
+#define UZ_K_VCFOUT_FILL 19 /* k_vcfout_fill */
+#define UZ_K_COUNT 20
 
 typedef struct uz_ctx uz_ctx;
 
@@ -392,6 +394,26 @@ int uz_bed_rows(uz_ctx *ctx, const uz_bed_view *rows, int verbose, int include_a
 int uz_bed_rows_lists(uz_ctx *ctx, const uz_bed_view *rows, int verbose, int include_ambiguous, int32_t n_dnms, const int32_t *status,
                       const int64_t *list_off, const int32_t *list_val, uint32_t n_qnames, const uint32_t *name_off, const uint8_t *name_bytes,
                       int32_t evidence_min_ratio, int64_t *off /* [n_rows + 1] */, const uint8_t **bytes);
+
+/* ---- annotated VCF rows as text ---------------------------------------- */
+/* The record lines of the annotated VCF (unfazed.py: write_vcf_output), rewritten by kernels from the DNM file's own text (k_vcfout_size, a scan,
+ * k_vcfout_fill per chunk; csrc/vcf_row.hpp is the body and states the rules): FORMAT gets ":UOPS:UET", every sample column is padded with ":."
+ * to FORMAT's piece count and gets ":<uops>:<uet>" -- ":-1:-1" unless the column has an annotation and the cell's own genotype, read from its
+ * text, is HET or HOM_ALT -- and an applied annotation with gt code 1 / 2 replaces the GT piece by "1|0" / "0|1".  '\n' ends every line.
+ * text: the view of unfazed_io.h: uz_vcf_samples_text; line_at [n_records]: where every record's line starts.  The annotations are a sparse
+ * table over the records: record k has ann_off[k] .. ann_off[k + 1], its columns (ann_col, indices of sample columns) strictly ascending;
+ * ann_gt 0 none, 1 "1|0", 2 "0|1"; ann_uops -1 .. 999 999; ann_uet -1 .. 6.  The text goes up in chunks cut at line ends
+ * (UZ_VCFOUT_CHUNK_BYTES, read per call, 32 MiB), chunk k + 1 copied while chunk k is worked on.
+ * Record k is bytes[off[k] .. off[k + 1]).  A record the kernels will not vouch for is HANDED BACK: handed_back[k] = 1 and off[k + 1] == off[k];
+ * the caller writes it with its own per-record code.  Handed back: a GT piece outside the genotype grammar (an empty one included), a count of
+ * sample columns that differs from text->n_samples, a line without FORMAT, a FORMAT that names GT twice, an annotation outside the ranges above
+ * or at a column >= n_samples, columns that do not ascend, a line that holds a '\r', a line of 4 GiB.
+ * The text lies in page-locked memory of the context, valid until the next call.  No entry point runs the read stage: the annotations are all
+ * the call knows of phasing.  UZ_E_ARG (nothing launched): offsets that descend, a NULL table with annotations, a line outside the text.
+ * UZ_E_RANGE: 4 GiB or more of output from one chunk.  UZ_E_STATE: a record whose written bytes differ from its sized length. */
+int uz_vcf_rows(uz_ctx *ctx, const uz_vcf_text_view *text, const int64_t *line_at /* [n_records] */, const int64_t *ann_off /* [n_records + 1] */,
+                const int32_t *ann_col, const uint8_t *ann_gt, const int32_t *ann_uops, const int8_t *ann_uet, int64_t *off /* [n_records + 1] */,
+                const uint8_t **bytes, uint8_t *handed_back /* [n_records] */);
 
 /* ---- allele-balance (CNV) stage ---------------------------------------- */
 /* K6.  Everything run_cnv_phasing does after its find (sv_phaser.py:357-423: phase_by_snvs :71-85,

@@ -133,6 +133,17 @@ class VcfTextView(C.Structure):
     ]
 
 
+def vcf_text_view(text, samp_at, line_end, n_samples: int) -> VcfTextView:
+    """a uz_vcf_text_view over the caller's arrays (what io_native.vcf_samples_text gives for a decoded table): text uint8, samp_at / line_end
+    uint64 [n_records].  The view keeps the arrays alive; the FORMAT slots are absent (uz_vcf_rows does not read them)."""
+    text, samp_at, line_end = np.ascontiguousarray(text, np.uint8), np.ascontiguousarray(samp_at, np.uint64), np.ascontiguousarray(line_end, np.uint64)
+    v = VcfTextView()
+    v.text, v.text_bytes, v.n_records, v.n_samples = text.ctypes.data, int(text.size), int(samp_at.size), int(n_samples)
+    v.samp_at, v.line_end, v.fmt_slot = samp_at.ctypes.data, line_end.ctypes.data, None
+    v._keep = (text, samp_at, line_end)
+    return v
+
+
 class VcfBcfView(C.Structure):
     """uz_types.h: uz_vcf_bcf_view"""
     _fields_ = [

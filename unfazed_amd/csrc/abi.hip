@@ -474,6 +474,8 @@ void uz_destroy(uz_ctx *c) {
     if (c->nm_pin) (void)hipHostFree(c->nm_pin);
     if (c->bed_pin) (void)hipHostFree(c->bed_pin);
     c->bed_in.release(); c->bed_hook.release(); c->bed_out.release(); c->bed_len.release(); c->bed_off.release();
+    for (uint8_t *p : {c->vo_pin[0], c->vo_pin[1], c->vo_small, c->vo_res}) if (p) (void)hipHostFree(p);
+    c->vo_in[0].release(); c->vo_in[1].release(); c->vo_out.release(); c->vo_off.release(); c->vo_len.release();
     c->nm_ids.release(); c->nm_len.release(); c->nm_off.release(); c->nm_out.release(); c->rf_first.release(); c->rf_mm.release();
     c->ab_lut.release(); c->win_range.release();
     c->dn_fam.release(); c->dn_cutoff.release(); c->fam_cls.release();
@@ -2438,6 +2440,11 @@ int uz_phase_sizing_fetch(uz_ctx *c, int32_t *bounds, int32_t *pre_win, int32_t 
 int uz_bed_rows(uz_ctx *c, const uz_bed_view *rows, int verbose, int include_ambiguous, int64_t *off, const uint8_t **bytes) {
     return guarded(c, [&] { (void)uz_bed_rows_impl(c, rows, verbose, include_ambiguous, off, bytes); });
 }
+int uz_vcf_rows(uz_ctx *c, const uz_vcf_text_view *text, const int64_t *line_at, const int64_t *ann_off, const int32_t *ann_col, const uint8_t *ann_gt,
+                const int32_t *ann_uops, const int8_t *ann_uet, int64_t *off, const uint8_t **bytes, uint8_t *handed_back) {
+    return guarded(c, [&] { (void)uz_vcf_rows_impl(c, text, line_at, ann_off, ann_col, ann_gt, ann_uops, ann_uet, off, bytes, handed_back); });
+}
+
 int uz_bed_rows_lists(uz_ctx *c, const uz_bed_view *rows, int verbose, int include_ambiguous, int32_t n_dnms, const int32_t *status, const int64_t *list_off,
                       const int32_t *list_val, uint32_t n_qnames, const uint32_t *name_off, const uint8_t *name_bytes, int32_t evidence_min_ratio, int64_t *off,
                       const uint8_t **bytes) {

@@ -444,6 +444,12 @@ struct uz_ctx {
     DevBuf<int64_t> bed_off;
     uint8_t *bed_pin = nullptr;
     size_t bed_pin_cap = 0;
+    // uz_vcf_rows (k_vcfout.hip): the two chunk images (page-locked, and their mirrors on the device), a chunk's lengths, its offsets + flag word +
+    // handed-back bytes and their page-locked landing place, a chunk's text on the device, the call's text (page-locked); kept from call to call
+    DevBuf<uint8_t> vo_in[2], vo_out, vo_off;
+    DevBuf<uint32_t> vo_len;
+    uint8_t *vo_pin[2] = {nullptr, nullptr}, *vo_small = nullptr, *vo_res = nullptr;
+    size_t vo_pin_cap[2] = {0, 0}, vo_small_cap = 0, vo_res_cap = 0;
 
     // last phase (k_reads.hip)
     bool phase_valid = false;
@@ -590,3 +596,6 @@ int uz_bed_rows_impl(uz_ctx *c, const uz_bed_view *rows, int verbose, int includ
 int uz_bed_rows_lists_impl(uz_ctx *c, const uz_bed_view *rows, int verbose, int include_ambiguous, int32_t n_dnms, const int32_t *status, const int64_t *list_off,
                            const int32_t *list_val, uint32_t n_qnames, const uint32_t *name_off, const uint8_t *name_bytes, int32_t ratio, int64_t *off,
                            const uint8_t **bytes);
+// the annotated VCF's record lines as text (k_vcfout.hip; vcf_row.hpp is the body)
+int uz_vcf_rows_impl(uz_ctx *c, const uz_vcf_text_view *text, const int64_t *line_at, const int64_t *ann_off, const int32_t *ann_col, const uint8_t *ann_gt,
+                     const int32_t *ann_uops, const int8_t *ann_uet, int64_t *off, const uint8_t **bytes, uint8_t *handed_back);

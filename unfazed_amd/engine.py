@@ -20,6 +20,7 @@ K_VCF_TABS, K_VCF_CELLS, K_VCF_COPY = 8, 9, 10  # uz_samples_from_text: the two 
 K_BCF_CELLS, K_BCF_COPY = 11, 12  # uz_samples_from_bcf: its kernel and (not a kernel) its chunks' copies
 K_HEAD_INFLATE, K_HEAD_WALK, K_HEAD_RANK = 13, 14, 15  # uz_head_walk: inflate + CRC-32 of a group's heads, k_head_walk; uz_head_rank: k_head_rank
 K_BED_SIZE, K_BED_FILL = 16, 17  # uz_bed_rows: k_bed_size + the scan of the lengths, k_bed_fill
+K_VCFOUT_SIZE, K_VCFOUT_FILL = 18, 19  # uz_vcf_rows: k_vcfout_size + the scan of the lengths, k_vcfout_fill (per chunk)
 HEAD_NONE, HEAD_DONE, HEAD_END, HEAD_BAD = 0, 1, 2, 3  # unfazed_hip.h UZ_HEAD_*
 HEAD_MAX_BYTES = 8 << 30  # inflated bytes of one uz_head_walk launch unless UZ_HEAD_MAX_BYTES says otherwise: a choice, not a measurement
 HEAD_MAX_ROUNDS = 8       # walks of one file before it is handed back to the host route
@@ -33,7 +34,7 @@ EXPORTS = [
     "uz_sites_free", "uz_reads_free", "uz_drop_derived",
     "uz_site_scan", "uz_site_scan_many", "uz_site_classes", "uz_find", "uz_find_fetch", "uz_find_cohort",
     "uz_phase", "uz_phase_begin", "uz_phase_end", "uz_phase_cohort", "uz_phase_cohort_joined", "uz_phase_votes", "uz_phase_groups", "uz_phase_sizing_fetch", "uz_phase_cnv", "uz_phase_cnv_cohort", "uz_phase_cnv_sites",
-    "uz_bed_rows", "uz_bed_rows_lists",
+    "uz_bed_rows", "uz_bed_rows_lists", "uz_vcf_rows",
     "uz_prof_enable", "uz_prof_reset", "uz_prof_get", "uz_prof_units",
     "uz_head_walk", "uz_head_rank", "uz_head_fetch", "uz_head_free",
 ]
@@ -123,6 +124,7 @@ def load_library(path: Optional[str] = None):
     L.uz_phase_sizing_fetch.argtypes = [vp, vp, vp, vp, vp, vp]
     L.uz_bed_rows.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
     L.uz_bed_rows_lists.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int32, vp, vp, vp, C.c_uint32, vp, vp, C.c_int32, vp, vp]
+    L.uz_vcf_rows.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.uz_head_walk.argtypes = [vp, C.POINTER(C.c_int), C.c_int32, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.uz_head_rank.argtypes = [vp, C.c_int, C.c_int32, vp, vp, vp]
     L.uz_head_fetch.argtypes = [vp, C.c_int, C.c_int32, vp, C.c_int64, C.POINTER(C.c_int64)]
@@ -852,6 +854,23 @@ class HipEngine:
                                           list_off.ctypes.data, list_val.ctypes.data if list_val.size else None, nq, p_no, p_nb, int(ratio),
                                           off.ctypes.data, C.byref(ptr)), "uz_bed_rows_lists")
         return self._bed_text(n, off, ptr)
+
+    def vcf_rows(self, text: "abi.VcfTextView", line_at, ann_off, ann_col, ann_gt, ann_uops, ann_uet):
+        """The record lines of the annotated VCF (uz_vcf_rows), rewritten on the device from the DNM file's text.  text: io_native.vcf_samples_text's
+        view; line_at [n]: every record's line start; the annotations as a sparse table over the records (ann_off [n + 1]; column, gt code 0 / 1 / 2,
+        uops, uet).  -> (bytes, off [n + 1], handed_back bool [n]): record k is bytes[off[k]: off[k + 1]], empty when the record is handed back."""
+        n = int(text.n_records)
+        line_at, ann_off = np.ascontiguousarray(line_at, np.int64), np.ascontiguousarray(ann_off, np.int64)
+        ann_col, ann_uops = np.ascontiguousarray(ann_col, np.int32), np.ascontiguousarray(ann_uops, np.int32)
+        ann_gt, ann_uet = np.ascontiguousarray(ann_gt, np.uint8), np.ascontiguousarray(ann_uet, np.int8)
+        if line_at.size != n or ann_off.size != n + 1 or not (ann_col.size == ann_gt.size == ann_uops.size == ann_uet.size):
+            raise UnfazedHipError("vcf_rows: the arrays do not fit the records")
+        ptr_or_none = lambda a: a.ctypes.data if a.size else None
+        off, hb, ptr = np.zeros(n + 1, np.int64), np.zeros(max(1, n), np.uint8), C.c_void_p()
+        self._ck(self.L.uz_vcf_rows(self.h, C.addressof(text), line_at.ctypes.data if n else None, ann_off.ctypes.data, ptr_or_none(ann_col), ptr_or_none(ann_gt),
+                                    ptr_or_none(ann_uops), ptr_or_none(ann_uet), off.ctypes.data, C.byref(ptr), hb.ctypes.data), "uz_vcf_rows")
+        total = int(off[n])
+        return (C.string_at(ptr.value, total) if total else b""), off, hb[:n].astype(bool)  # (a copy: the context's block is the next call's)
 
     def phase_sizing(self, n: int, n_het: int) -> dict:
         """Test hook (uz_phase_sizing_fetch): the sizing pass's output for the last phase_raw / phase_end -- n DNMs, n_het = het_off[n] of the

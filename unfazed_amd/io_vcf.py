@@ -79,42 +79,52 @@ def read_vcf(path: str) -> Tuple[List[str], List[SiteRecord], List[str]]:
                 header.append(line)
                 samples = line.split("\t")[9:]
                 continue
-            f = line.split("\t")
-            chrom, pos, ref = f[0], int(f[1]), f[3]
-            alts = [] if f[4] == "." else f[4].split(",")
-            info = {}
-            if len(f) > 7 and f[7] != ".":
-                for kv in f[7].split(";"):
-                    if "=" in kv:
-                        k, v = kv.split("=", 1)
-                        info[k] = v
-                    else:
-                        info[kv] = True
-            start = pos - 1
-            end = start + len(ref)
-            if "END" in info:
-                try:
-                    end = int(info["END"])
-                except ValueError:
-                    pass
-            ns = len(samples)
-            gts, rds, ads, gqs, genos = [GT_UNKNOWN] * ns, [-1] * ns, [-1] * ns, [-1.0] * ns, []
-            fmt = f[8].split(":") if len(f) > 8 else []
-            idx = {k: i for i, k in enumerate(fmt)}
-            for s in range(ns):
-                col = f[9 + s].split(":") if len(f) > 9 + s else ["."]
-                code, g = _parse_gt(col[idx["GT"]]) if "GT" in idx and idx["GT"] < len(col) else (GT_UNKNOWN, [-1, -1, False])
-                gts[s] = code
-                genos.append(g)
-                if "AD" in idx and idx["AD"] < len(col) and col[idx["AD"]] != ".":
-                    ad = col[idx["AD"]].split(",")
-                    rds[s] = _num(ad[0], int)
-                    ads[s] = _num(ad[1], int) if len(ad) > 1 else -1
-                elif "RO" in idx and "AO" in idx and idx["RO"] < len(col) and idx["AO"] < len(col):
-                    rds[s] = _num(col[idx["RO"]], int)
-                    ads[s] = _num(col[idx["AO"]].split(",")[0], int)
-                if "GQ" in idx and idx["GQ"] < len(col):
-                    gqs[s] = float(_num(col[idx["GQ"]], float, -1.0))
-            records.append(SiteRecord(chrom, start, ref, alts, gts, rds, ads, gqs, end=end, info=info,
-                                      genotypes=genos, raw=f))
+            records.append(parse_record(line, samples))
     return samples, records, header
+
+
+def site_of(f: List[str]):
+    """the fixed columns of a record line (split at tabs) -> (chrom, start, ref, alts, end, info)"""
+    chrom, pos, ref = f[0], int(f[1]), f[3]
+    alts = [] if f[4] == "." else f[4].split(",")
+    info = {}
+    if len(f) > 7 and f[7] != ".":
+        for kv in f[7].split(";"):
+            if "=" in kv:
+                k, v = kv.split("=", 1)
+                info[k] = v
+            else:
+                info[kv] = True
+    start = pos - 1
+    end = start + len(ref)
+    if "END" in info:
+        try:
+            end = int(info["END"])
+        except ValueError:
+            pass
+    return chrom, start, ref, alts, end, info
+
+
+def parse_record(line: str, samples: List[str]) -> SiteRecord:
+    """one record line (without its line end) of a file whose header names `samples`"""
+    f = line.split("\t")
+    chrom, start, ref, alts, end, info = site_of(f)
+    ns = len(samples)
+    gts, rds, ads, gqs, genos = [GT_UNKNOWN] * ns, [-1] * ns, [-1] * ns, [-1.0] * ns, []
+    fmt = f[8].split(":") if len(f) > 8 else []
+    idx = {k: i for i, k in enumerate(fmt)}
+    for s in range(ns):
+        col = f[9 + s].split(":") if len(f) > 9 + s else ["."]
+        code, g = _parse_gt(col[idx["GT"]]) if "GT" in idx and idx["GT"] < len(col) else (GT_UNKNOWN, [-1, -1, False])
+        gts[s] = code
+        genos.append(g)
+        if "AD" in idx and idx["AD"] < len(col) and col[idx["AD"]] != ".":
+            ad = col[idx["AD"]].split(",")
+            rds[s] = _num(ad[0], int)
+            ads[s] = _num(ad[1], int) if len(ad) > 1 else -1
+        elif "RO" in idx and "AO" in idx and idx["RO"] < len(col) and idx["AO"] < len(col):
+            rds[s] = _num(col[idx["RO"]], int)
+            ads[s] = _num(col[idx["AO"]].split(",")[0], int)
+        if "GQ" in idx and idx["GQ"] < len(col):
+            gqs[s] = float(_num(col[idx["GQ"]], float, -1.0))
+    return SiteRecord(chrom, start, ref, alts, gts, rds, ads, gqs, end=end, info=info, genotypes=genos, raw=f)

@@ -56,6 +56,11 @@ def get_backend():
     return _BACKEND
 
 
+def current_backend():
+    """the backend in use, or None: nothing is created (unfazed.write_vcf_output asks before it takes the device route by default)"""
+    return _BACKEND
+
+
 def _python_io() -> bool:
     """UZ_IO=python selects the pure-Python decoders (io_bam.py / io_vcf.py: the readable statement of the
     formats, orders of magnitude slower); the default is the native library (io_native.py)."""

@@ -196,7 +196,28 @@ def write_vcf_output(in_vcf_name, read_records, include_ambiguous, verbose, outf
     every sample gets UOPS and UET appended."""
     if in_vcf_name.endswith("bcf") or _is_bcf(in_vcf_name):
         sys.exit(BCF_OUTPUT_MESSAGE)
+    if vcf_route() == "device" and int(os.environ.get("WORLD_SIZE", "1")) <= 1:
+        from . import session
+        # asked for by name, the route makes its backend (and fails loudly without a device); as the default it serves a call that has one --
+        # the driver's always has, from the phasing behind it
+        backend = session.get_backend() if "UZ_VCF_ROUTE" in os.environ else session.current_backend()
+        if hasattr(backend, "vcf_rows") and _write_vcf_device(in_vcf_name, read_records, include_ambiguous, verbose, outfile,
+                                                              evidence_min_ratio, backend):
+            return
     samples, records, header = read_vcf(in_vcf_name)
+    out = _annotated_header(header)
+    for r in records:
+        out.append(_annotated_line(r, samples, read_records, include_ambiguous, verbose, evidence_min_ratio))
+    VCF_STATS["vcf_host_rows"] += len(records)
+    text = "\n".join(out) + "\n"
+    if outfile == "/dev/stdout":
+        sys.stdout.write(text)
+    else:
+        with open(outfile, "w") as fh:
+            fh.write(text)
+
+
+def _annotated_header(header):
     out = []
     out.extend(header[:-1])
     out.append("##unfazed=" + __reference_version__
@@ -204,39 +225,161 @@ def write_vcf_output(in_vcf_name, read_records, include_ambiguous, verbose, outf
     out.append(UOPS_HEADER)
     out.append(UET_HEADER)
     out.append(header[-1])
-    for r in records:
-        f = list(r.raw)
-        fmt = f[8].split(":")
-        gt_i = fmt.index("GT") if "GT" in fmt else None
-        f[8] = f[8] + ":UOPS:UET"
-        for i, gt in enumerate(r.gt_types):
-            uops, uet = -1, -1
-            col = f[9 + i].split(":")
-            # VCF lets a sample drop trailing FORMAT fields (`./.`): pad, so UOPS / UET land in their own columns
-            col += ["."] * (len(fmt) - len(col))
-            if gt in [HET, HOM_ALT]:
-                vartype = r.info.get("SVTYPE")
-                if vartype is None:
-                    vartype = SNV_TYPES[0]
-                key = "{}_{}_{}_{}_{}".format(r.chrom, r.start, r.end, samples[i], vartype)
-                if key in read_records:
-                    s = summarize_record(read_records[key], include_ambiguous, verbose, evidence_min_ratio)
-                    if s is not None:
-                        if gt_i is not None:
-                            if s["origin_parent"] == read_records[key]["dad"]:
-                                col[gt_i] = "1|0"
-                            elif s["origin_parent"] == read_records[key]["mom"]:
-                                col[gt_i] = "0|1"
-                        uops = s["evidence_count"]
-                        uet = uet_code(s["evidence_types"])
-            f[9 + i] = ":".join(col) + ":%g:%g" % (uops, uet)
-        out.append("\t".join(f))
-    text = "\n".join(out) + "\n"
+    return out
+
+
+def _annotated_line(r, samples, read_records, include_ambiguous, verbose, evidence_min_ratio):
+    """one record of the annotated VCF: the per-record part of write_vcf_output, shared by the host writer and by the device route's
+    handed-back records"""
+    f = list(r.raw)
+    fmt = f[8].split(":")
+    gt_i = fmt.index("GT") if "GT" in fmt else None
+    f[8] = f[8] + ":UOPS:UET"
+    for i, gt in enumerate(r.gt_types):
+        uops, uet = -1, -1
+        col = f[9 + i].split(":")
+        # VCF lets a sample drop trailing FORMAT fields (`./.`): pad, so UOPS / UET land in their own columns
+        col += ["."] * (len(fmt) - len(col))
+        if gt in [HET, HOM_ALT]:
+            vartype = r.info.get("SVTYPE")
+            if vartype is None:
+                vartype = SNV_TYPES[0]
+            key = "{}_{}_{}_{}_{}".format(r.chrom, r.start, r.end, samples[i], vartype)
+            if key in read_records:
+                s = summarize_record(read_records[key], include_ambiguous, verbose, evidence_min_ratio)
+                if s is not None:
+                    if gt_i is not None:
+                        if s["origin_parent"] == read_records[key]["dad"]:
+                            col[gt_i] = "1|0"
+                        elif s["origin_parent"] == read_records[key]["mom"]:
+                            col[gt_i] = "0|1"
+                    uops = s["evidence_count"]
+                    uet = uet_code(s["evidence_types"])
+        f[9 + i] = ":".join(col) + ":%g:%g" % (uops, uet)
+    return "\t".join(f)
+
+
+VCF_ROUTE_DEFAULT = "device"  # UZ_VCF_ROUTE not set.  profiles/vcf_route_ab.json: every device run ahead of every host run at both shapes (the rule bed_route() states)
+VCF_STATS = {"vcf_device_rows": 0, "vcf_host_rows": 0, "vcf_calls": 0}  # records whose line the device wrote / the per-record host code wrote, uz_vcf_rows calls
+UOPS_DEVICE_MAX = 999999  # the largest count the device prints ("%g" turns to an exponent at 10^6)
+
+
+def vcf_route() -> str:
+    """UZ_VCF_ROUTE: "device" -- a single-rank call that writes the annotated VCF gets its record lines from the device (uz_vcf_rows) -- or
+    "host" (write_vcf_output's loop over the cells).  Not set: "device" where the call already has a backend with vcf_rows, else "host"."""
+    return "device" if os.environ.get("UZ_VCF_ROUTE", VCF_ROUTE_DEFAULT).lower() == "device" else "host"
+
+
+def vcf_annotations(sites, samples, read_records, include_ambiguous, verbose, evidence_min_ratio):
+    """The annotations of the device route, one loop over RECORDS.  sites: per record the tuple (chrom, start, end, vartype) the host writer
+    forms its key from, or None for a record without one.  -> (ann_off [n + 1], ann_col, ann_gt, ann_uops, ann_uet, host_rows): per record the
+    sample columns that have a summarised record, ascending, with the gt code (0 none, 1 "1|0", 2 "0|1"), the evidence count and uet_code;
+    host_rows: the records the caller writes with the per-record code whatever the device makes of them (a count the device does not print,
+    a key whose summary raises).  None: read_records does not index by its own fields (the caller takes the host route)."""
+    by_site = {}
+    for key, rec in read_records.items():
+        try:
+            site = tuple(str(rec["region"][k]) for k in ("chrom", "start", "end")) + (str(rec["vartype"]),)
+            kid = rec["kid"]
+            if "{}_{}_{}_{}_{}".format(site[0], site[1], site[2], kid, site[3]) != key:
+                return None
+        except (KeyError, TypeError):
+            return None
+        by_site.setdefault(site, []).append((kid, key))
+    columns = {}
+    for i, name in enumerate(samples):
+        columns.setdefault(name, []).append(i)
+    ann_off, col, gtc, uops, uet, host_rows = [0], [], [], [], [], []
+    for k, site in enumerate(sites):
+        rows = []
+        for kid, key in by_site.get(tuple(str(x) for x in site), ()) if site is not None else ():
+            if kid not in columns:
+                continue
+            rec = read_records[key]
+            try:
+                s = summarize_record(rec, include_ambiguous, verbose, evidence_min_ratio)
+            except Exception:  # (the host writer meets it only at a cell that passes the gate: the per-record code decides)
+                rows = None
+                break
+            if s is None:
+                continue
+            n, e = s["evidence_count"], uet_code(s["evidence_types"])
+            if not isinstance(n, int) or isinstance(n, bool) or not -1 <= n <= UOPS_DEVICE_MAX:
+                rows = None
+                break
+            code = 1 if s["origin_parent"] == rec["dad"] else (2 if s["origin_parent"] == rec["mom"] else 0)
+            rows.extend((c, code, n, e) for c in columns[kid])
+        if rows is None:
+            host_rows.append(k)
+            rows = []
+        rows.sort()
+        for c, code, n, e in rows:
+            col.append(c); gtc.append(code); uops.append(n); uet.append(e)
+        ann_off.append(len(col))
+    return (np.asarray(ann_off, np.int64), np.asarray(col, np.int32), np.asarray(gtc, np.uint8), np.asarray(uops, np.int32),
+            np.asarray(uet, np.int8), host_rows)
+
+
+def _write_vcf_device(in_vcf_name, read_records, include_ambiguous, verbose, outfile, evidence_min_ratio, backend):
+    """The annotated VCF with its record lines rewritten on the device (backend.vcf_rows -> uz_vcf_rows; csrc/vcf_row.hpp states the rules).
+    The header is written here; a record the device hands back, and one vcf_annotations names, is written by _annotated_line.  -> False, nothing
+    written: the file takes the host route whole -- the native decoder refuses it, it holds a byte outside ASCII or a '\r' (text mode reads
+    those differently), its header is not one `#CHROM` line behind `##` lines, or its records are not the lines read_vcf would see."""
+    import ctypes as C
+    from . import io_native
+    from .io_vcf import parse_record, site_of
+    try:
+        table = io_native.read_vcf_table(in_vcf_name)
+        view = io_native.vcf_samples_text(table)
+    except (io_native.IoError, OSError):
+        return False
+    n = int(view.n_records)
+    raw = C.string_at(view.text, int(view.text_bytes))
+    header, samples = list(table.header), list(table.samples)
+    if not raw.isascii() or b"\r" in raw or not header or [h[:2] != "##" for h in header] != [False] * (len(header) - 1) + [True]:
+        return False
+    if header[-1].split("\t")[9:] != samples or n != sum(1 for ln in raw.split(b"\n") if ln and ln[:1] != b"#"):
+        return False
+    samp_at = np.ctypeslib.as_array(C.cast(view.samp_at, C.POINTER(C.c_uint64)), (n,)) if n else np.zeros(0, np.uint64)
+    line_end = np.ctypeslib.as_array(C.cast(view.line_end, C.POINTER(C.c_uint64)), (n,)) if n else np.zeros(0, np.uint64)
+    line_at = np.zeros(n, np.int64)
+    sites = []
+    for k in range(n):
+        s, e = int(samp_at[k]), int(line_end[k])
+        a = line_at[k] = raw.rfind(b"\n", 0, s) + 1
+        if raw[a:a + 1] == b"#":
+            return False
+        if s >= e:
+            sites.append(None)  # (no sample column: the device hands it back)
+            continue
+        chrom, start, _, _, end, info = site_of(raw[a:s - 1].decode().split("\t"))
+        vartype = info.get("SVTYPE")
+        sites.append((chrom, start, end, SNV_TYPES[0] if vartype is None else vartype))
+    ann = vcf_annotations(sites, samples, read_records, include_ambiguous, verbose, evidence_min_ratio)
+    if ann is None:
+        return False
+    ann_off, ann_col, ann_gt, ann_uops, ann_uet, host_rows = ann
+    text, off, handed_back = backend.vcf_rows(view, line_at, ann_off, ann_col, ann_gt, ann_uops, ann_uet)
+    VCF_STATS["vcf_calls"] += 1
+    by_host = sorted(set(host_rows) | set(np.flatnonzero(handed_back).tolist()))
+    # read_vcf parses every record before the writer meets the first: so do the records that come back
+    parsed = [parse_record(raw[int(line_at[k]):int(line_end[k])].decode(), samples) for k in by_host]
+    parts = [("\n".join(_annotated_header(header)) + "\n").encode()]
+    body, at = memoryview(text), 0
+    for k, r in zip(by_host, parsed):
+        parts.append(body[at:int(off[k])])
+        parts.append((_annotated_line(r, samples, read_records, include_ambiguous, verbose, evidence_min_ratio) + "\n").encode())
+        at = int(off[k + 1])
+    parts.append(body[at:int(off[n])])
+    VCF_STATS["vcf_device_rows"] += n - len(by_host)
+    VCF_STATS["vcf_host_rows"] += len(by_host)
     if outfile == "/dev/stdout":
-        sys.stdout.write(text)
+        sys.stdout.write(b"".join(parts).decode())
     else:
-        with open(outfile, "w") as fh:
-            fh.write(text)
+        with open(outfile, "wb") as fh:
+            for p in parts:
+                fh.write(p)
+    return True
 
 
 def _dnm_reader(path):
