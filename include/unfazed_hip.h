@@ -59,7 +59,9 @@ extern "C" {
 #define UZ_K_BED_FILL 17    /* k_bed_fill */
 #define UZ_K_VCFOUT_SIZE 18 /* k_vcfout_size + the scan of the records' lengths (uz_vcf_rows), one launch per chunk of text */
 #define UZ_K_VCFOUT_FILL 19 /* k_vcfout_fill */
-#define UZ_K_COUNT 20
+#define UZ_K_BCFOUT_SIZE 20 /* k_bcfout_size + the scan of the records' lengths (uz_bcf_rows), one launch per chunk of records */
+#define UZ_K_BCFOUT_FILL 21 /* k_bcfout_fill */
+#define UZ_K_COUNT 22
 
 typedef struct uz_ctx uz_ctx;
 
@@ -413,6 +415,27 @@ int uz_bed_rows_lists(uz_ctx *ctx, const uz_bed_view *rows, int verbose, int inc
  * UZ_E_RANGE: 4 GiB or more of output from one chunk.  UZ_E_STATE: a record whose written bytes differ from its sized length. */
 int uz_vcf_rows(uz_ctx *ctx, const uz_vcf_text_view *text, const int64_t *line_at /* [n_records] */, const int64_t *ann_off /* [n_records + 1] */,
                 const int32_t *ann_col, const uint8_t *ann_gt, const int32_t *ann_uops, const int8_t *ann_uet, int64_t *off /* [n_records + 1] */,
+                const uint8_t **bytes, uint8_t *handed_back /* [n_records] */);
+
+/* The records of a BCF as VCF text lines (unfazed.py: write_vcf_output on a BCF of DNMs, UZ_BCF_ROUTE=device), written by kernels from the
+ * records' own bytes (k_bcfout_size, a scan, k_bcfout_fill per chunk; csrc/bcf_row.hpp is the body and states the rules): CHROM from the
+ * header's contigs by id, POS + 1, ID, REF, ALT, QUAL by C's "%g" where that prints fixed notation, FILTER and INFO through the dictionary,
+ * FORMAT and one column per sample, GT as alleles joined by '/' or '|'; every line closed by '\n'.  The text is what uz_vcf_rows takes next.
+ * records: unfazed_io.h: uz_vcf_bcf_lines of a decoded BCF, or the caller's own arrays (HOST pointers).  The kernels prove every bound
+ * themselves, against l_shared / l_indiv and the data's end: the bytes need not have passed a decoder.
+ * off [n_records + 1]: record k's line is bytes[off[k], off[k + 1]), empty when the record is handed back; samp_at [n_records]: the offset in
+ * `bytes` of the first byte of column 10 (of the closing '\n' when the line has none; off[k] for a record handed back) -- uz_vcf_text_view's
+ * samp_at, its line_end being off[k + 1] - 1; *bytes: page-locked memory of the context, valid until the next uz_bcf_rows.
+ * handed_back [k] = 1: the kernels do not vouch for the record and the caller writes its line (unfazed_amd/bcf_text.py) -- a float "%g" prints
+ * in exponent form, an infinity or NaN; a record without an allele; a contig or dictionary id without a name; a key that is no scalar
+ * integer; a type outside {0, 1, 2, 3, 5, 7}; a byte outside 0x20 .. 0x7E in a copied string; a typed value, length or array that does not
+ * lie inside its block, or a block outside the data; n_sample different from n_samples while the record has FORMAT fields; a negative GT
+ * entry; a line of 4 GiB.
+ * The record bytes go up in chunks of UZ_BCFOUT_CHUNK_BYTES (read per call, 32 MiB) cut at record ends, chunk k + 1 copied while chunk k is
+ * worked on; a record longer than a chunk gets a chunk of its own.
+ * UZ_E_ARG (nothing launched): a NULL table, name offsets that descend, a rec_at that descends or lies outside `data`.  UZ_E_RANGE: 4 GiB or
+ * more of text from one chunk.  UZ_E_STATE: a record whose written bytes differ from its sized length. */
+int uz_bcf_rows(uz_ctx *ctx, const uz_bcf_lines_view *records, int64_t *off /* [n_records + 1] */, uint64_t *samp_at /* [n_records] */,
                 const uint8_t **bytes, uint8_t *handed_back /* [n_records] */);
 
 /* ---- allele-balance (CNV) stage ---------------------------------------- */

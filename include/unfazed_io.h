@@ -124,6 +124,9 @@ int uz_vcf_samples_text(const uz_vcf *h, uz_vcf_text_view *out);
 /* the bytes of a BCF table and its per-record value arrays of GT, AD, RO, AO, GQ (uz_types.h: uz_vcf_bcf_view), lazy or not; UZ_IO_E_ARG on a
  * text table */
 int uz_vcf_samples_bcf(const uz_vcf *h, uz_vcf_bcf_view *out);
+/* the records of a BCF table, its FILTER / INFO / FORMAT dictionary and the header's contigs by id (uz_types.h: uz_bcf_lines_view): what
+ * unfazed_hip.h: uz_bcf_rows turns into VCF text lines; UZ_IO_E_ARG on a text table */
+int uz_vcf_bcf_lines(const uz_vcf *h, uz_bcf_lines_view *out);
 /* What the eager decode holds for records rec[0 .. n_rec) and sample columns pick[0 .. n_pick): gt u8, int32 depths, f64 GQ, each
  * [n_pick][n_rec] -- the input of uz_samples_pack for the records the device hands back (uz_samples_unsettled).  Raises what the eager
  * decode raises (UZ_IO_E_FORMAT on an unparsable genotype allele).  Text or BCF, lazy or not. */

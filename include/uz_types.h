@@ -217,6 +217,24 @@ typedef struct uz_vcf_bcf_view {
     const uint32_t *fld_desc; /* [n_records][5] BCF type (1 int8, 2 int16, 3 int32, 5 float, 7 char) | values per sample << 4; 0: absent */
 } uz_vcf_bcf_view;
 
+/* The records of a decoded BCF and what their ids name (unfazed_io.h: uz_vcf_bcf_lines; taken by unfazed_hip.h: uz_bcf_rows, which turns every
+ * record into its VCF text line on the device).  Names lie end to end in their byte block, name k at [off[k], off[k + 1]); an id the header
+ * does not define is an empty name.  HOST pointers into the decoder's table: they live as long as it does. */
+typedef struct uz_bcf_lines_view {
+    const uint8_t *data;
+    int64_t data_bytes;
+    int64_t n_records;
+    int32_t n_samples;           /* samples the header names */
+    int32_t n_dict;              /* ids of the FILTER / INFO / FORMAT dictionary */
+    const uint64_t *rec_at;      /* [n_records] offset of each record's l_shared word in `data`, ascending */
+    const uint32_t *dict_off;    /* [n_dict + 1] */
+    const uint8_t *dict_bytes;
+    int32_t n_contigs;           /* the header's contigs, by id */
+    int32_t reserved0;
+    const uint32_t *contig_off;  /* [n_contigs + 1] */
+    const uint8_t *contig_bytes;
+} uz_bcf_lines_view;
+
 /* alignment records of one BAM in file (coordinate) order */
 typedef struct uz_reads_view {
     int64_t n_segs; /* < 2^31 */

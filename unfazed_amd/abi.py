@@ -152,6 +152,48 @@ class VcfBcfView(C.Structure):
     ]
 
 
+class BcfLinesView(C.Structure):
+    """uz_types.h: uz_bcf_lines_view"""
+    _fields_ = [
+        ("data", _p), ("data_bytes", C.c_int64), ("n_records", C.c_int64), ("n_samples", C.c_int32), ("n_dict", C.c_int32),
+        ("rec_at", _p), ("dict_off", _p), ("dict_bytes", _p), ("n_contigs", C.c_int32), ("reserved0", C.c_int32),
+        ("contig_off", _p), ("contig_bytes", _p),
+    ]
+
+
+def _names_flat(names):
+    off, blob = np.zeros(len(names) + 1, np.uint32), b"".join(x.encode() if isinstance(x, str) else bytes(x) for x in names)
+    off[1:] = np.cumsum([len(x.encode() if isinstance(x, str) else bytes(x)) for x in names], dtype=np.int64) if len(names) else []
+    return off, np.frombuffer(blob + b"\0", np.uint8).copy()
+
+
+def bcf_lines_view(data, rec_at, dict_names, contig_names, n_samples: int) -> BcfLinesView:
+    """a uz_bcf_lines_view over the caller's arrays (what io_native.vcf_bcf_lines gives for a decoded table): data uint8, rec_at uint64
+    [n_records], the dictionary's and the contigs' names by id (str or bytes; an empty name: an undefined id).  The view keeps the arrays alive."""
+    data, rec_at = np.ascontiguousarray(data, np.uint8), np.ascontiguousarray(rec_at, np.uint64)
+    d_off, d_bytes = _names_flat(dict_names)
+    c_off, c_bytes = _names_flat(contig_names)
+    v = BcfLinesView()
+    v.data, v.data_bytes, v.n_records, v.n_samples = data.ctypes.data, int(data.size), int(rec_at.size), int(n_samples)
+    v.rec_at, v.n_dict, v.n_contigs = rec_at.ctypes.data, len(dict_names), len(contig_names)
+    v.dict_off, v.dict_bytes, v.contig_off, v.contig_bytes = d_off.ctypes.data, d_bytes.ctypes.data, c_off.ctypes.data, c_bytes.ctypes.data
+    v._keep = (data, rec_at, d_off, d_bytes, c_off, c_bytes)
+    return v
+
+
+def bcf_lines_arrays(v: BcfLinesView):
+    """-> (data bytes, rec_at uint64 [n], dictionary names, contig names) of a view: copies, for bcf_text.line"""
+    n = int(v.n_records)
+    data = C.string_at(v.data, int(v.data_bytes)) if v.data_bytes else b""
+    rec_at = np.ctypeslib.as_array(C.cast(v.rec_at, C.POINTER(C.c_uint64)), (n,)).copy() if n else np.zeros(0, np.uint64)
+
+    def names(off_p, bytes_p, k):
+        off = np.ctypeslib.as_array(C.cast(off_p, C.POINTER(C.c_uint32)), (k + 1,))
+        blob = C.string_at(bytes_p, int(off[k])) if int(off[k]) else b""
+        return [blob[int(off[i]):int(off[i + 1])] for i in range(k)]
+    return data, rec_at, names(v.dict_off, v.dict_bytes, int(v.n_dict)), names(v.contig_off, v.contig_bytes, int(v.n_contigs))
+
+
 class ReadsView(C.Structure):
     _fields_ = [
         ("n_segs", C.c_int64),

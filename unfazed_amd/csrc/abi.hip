@@ -476,6 +476,8 @@ void uz_destroy(uz_ctx *c) {
     c->bed_in.release(); c->bed_hook.release(); c->bed_out.release(); c->bed_len.release(); c->bed_off.release();
     for (uint8_t *p : {c->vo_pin[0], c->vo_pin[1], c->vo_small, c->vo_res}) if (p) (void)hipHostFree(p);
     c->vo_in[0].release(); c->vo_in[1].release(); c->vo_out.release(); c->vo_off.release(); c->vo_len.release();
+    for (uint8_t *p : {c->bo_pin[0], c->bo_pin[1], c->bo_small, c->bo_res}) if (p) (void)hipHostFree(p);
+    c->bo_in[0].release(); c->bo_in[1].release(); c->bo_out.release(); c->bo_off.release(); c->bo_len.release();
     c->nm_ids.release(); c->nm_len.release(); c->nm_off.release(); c->nm_out.release(); c->rf_first.release(); c->rf_mm.release();
     c->ab_lut.release(); c->win_range.release();
     c->dn_fam.release(); c->dn_cutoff.release(); c->fam_cls.release();
@@ -2443,6 +2445,9 @@ int uz_bed_rows(uz_ctx *c, const uz_bed_view *rows, int verbose, int include_amb
 int uz_vcf_rows(uz_ctx *c, const uz_vcf_text_view *text, const int64_t *line_at, const int64_t *ann_off, const int32_t *ann_col, const uint8_t *ann_gt,
                 const int32_t *ann_uops, const int8_t *ann_uet, int64_t *off, const uint8_t **bytes, uint8_t *handed_back) {
     return guarded(c, [&] { (void)uz_vcf_rows_impl(c, text, line_at, ann_off, ann_col, ann_gt, ann_uops, ann_uet, off, bytes, handed_back); });
+}
+int uz_bcf_rows(uz_ctx *c, const uz_bcf_lines_view *records, int64_t *off, uint64_t *samp_at, const uint8_t **bytes, uint8_t *handed_back) {
+    return guarded(c, [&] { (void)uz_bcf_rows_impl(c, records, off, samp_at, bytes, handed_back); });
 }
 
 int uz_bed_rows_lists(uz_ctx *c, const uz_bed_view *rows, int verbose, int include_ambiguous, int32_t n_dnms, const int32_t *status, const int64_t *list_off,

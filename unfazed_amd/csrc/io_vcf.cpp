@@ -42,6 +42,10 @@ struct uz_vcf {
     std::vector<uint64_t> info_at;     // BCF: offset of the INFO section of record i in `text`
     std::vector<uint32_t> n_info;
     std::vector<std::string> dict;     // BCF: FILTER / INFO / FORMAT string dictionary
+    // BCF: the header's contigs by id (`contigs` keeps those that carry records), and both lists of names end to end for uz_vcf_bcf_lines
+    std::vector<std::string> header_contigs;
+    std::vector<uint32_t> dict_off, hctg_off;
+    std::string dict_bytes, hctg_bytes;
     int64_t io_stats[4] = {0, 0, 0, 0}; // compressed bytes read, BGZF blocks inflated (region decode), lines walked, records kept
     // Text tables: where every record's sample columns lie and how they are read -- the absolute offset of the first byte of column 10 (the
     // line end when the line has none), the line end, and the FORMAT slots of GT, AD, RO, AO, GQ (-1: absent, or no sample column to read).
@@ -229,8 +233,16 @@ void decode_bcf(uz_vcf &V, int threads, bool lazy) {
         }
         p = (nl ? (size_t)(nl - H) : l_text) + 1;
     }
-    std::vector<std::string> header_contigs;
+    std::vector<std::string> &header_contigs = V.header_contigs;
+    header_contigs.clear();
     header_contigs.swap(V.contigs); // the table's contigs are those that carry records, in order of appearance
+    auto flatten = [](const std::vector<std::string> &names, std::vector<uint32_t> &off, std::string &bytes) {
+        off.assign(1, 0);
+        bytes.clear();
+        for (const std::string &x : names) { bytes += x; off.push_back((uint32_t)bytes.size()); }
+    };
+    flatten(dict, V.dict_off, V.dict_bytes);
+    flatten(header_contigs, V.hctg_off, V.hctg_bytes);
     int k_gt = -1, k_ad = -1, k_ro = -1, k_ao = -1, k_gq = -1;
     for (size_t k = 0; k < dict.size(); k++) {
         if (dict[k] == "GT") k_gt = (int)k; else if (dict[k] == "AD") k_ad = (int)k; else if (dict[k] == "RO") k_ro = (int)k;
@@ -1055,6 +1067,23 @@ int uz_vcf_samples_bcf(const uz_vcf *h, uz_vcf_bcf_view *v) {
         v->n_records = h->n;
         v->n_samples = (int32_t)h->samples.size();
         v->fld_at = h->fld_at.data(); v->fld_desc = h->fld_desc.data();
+    });
+}
+
+int uz_vcf_bcf_lines(const uz_vcf *h, uz_bcf_lines_view *v) {
+    if (!h || !v) { last_error = "null argument"; return UZ_IO_E_ARG; }
+    return guarded([&] {
+        if (!h->is_bcf) fail(UZ_IO_E_ARG, "uz_vcf_bcf_lines: a text table has no BCF records");
+        memset(v, 0, sizeof(*v));
+        v->data = h->text.data();
+        v->data_bytes = (int64_t)h->text.size();
+        v->n_records = h->n;
+        v->n_samples = (int32_t)h->samples.size();
+        v->rec_at = h->line_at.data();
+        v->n_dict = (int32_t)h->dict.size();
+        v->dict_off = h->dict_off.data(); v->dict_bytes = (const uint8_t *)h->dict_bytes.data();
+        v->n_contigs = (int32_t)h->header_contigs.size();
+        v->contig_off = h->hctg_off.data(); v->contig_bytes = (const uint8_t *)h->hctg_bytes.data();
     });
 }
 

@@ -450,6 +450,11 @@ struct uz_ctx {
     DevBuf<uint32_t> vo_len;
     uint8_t *vo_pin[2] = {nullptr, nullptr}, *vo_small = nullptr, *vo_res = nullptr;
     size_t vo_pin_cap[2] = {0, 0}, vo_small_cap = 0, vo_res_cap = 0;
+    // uz_bcf_rows (k_bcfout.hip): the same set of its own -- the text it returns is the input of the uz_vcf_rows call behind it
+    DevBuf<uint8_t> bo_in[2], bo_out, bo_off;
+    DevBuf<uint32_t> bo_len;
+    uint8_t *bo_pin[2] = {nullptr, nullptr}, *bo_small = nullptr, *bo_res = nullptr;
+    size_t bo_pin_cap[2] = {0, 0}, bo_small_cap = 0, bo_res_cap = 0;
 
     // last phase (k_reads.hip)
     bool phase_valid = false;
@@ -599,3 +604,5 @@ int uz_bed_rows_lists_impl(uz_ctx *c, const uz_bed_view *rows, int verbose, int 
 // the annotated VCF's record lines as text (k_vcfout.hip; vcf_row.hpp is the body)
 int uz_vcf_rows_impl(uz_ctx *c, const uz_vcf_text_view *text, const int64_t *line_at, const int64_t *ann_off, const int32_t *ann_col, const uint8_t *ann_gt,
                      const int32_t *ann_uops, const int8_t *ann_uet, int64_t *off, const uint8_t **bytes, uint8_t *handed_back);
+// a BCF's records as VCF text lines (k_bcfout.hip; bcf_row.hpp is the body)
+int uz_bcf_rows_impl(uz_ctx *c, const uz_bcf_lines_view *records, int64_t *off, uint64_t *samp_at, const uint8_t **bytes, uint8_t *handed_back);

@@ -21,6 +21,7 @@ K_BCF_CELLS, K_BCF_COPY = 11, 12  # uz_samples_from_bcf: its kernel and (not a k
 K_HEAD_INFLATE, K_HEAD_WALK, K_HEAD_RANK = 13, 14, 15  # uz_head_walk: inflate + CRC-32 of a group's heads, k_head_walk; uz_head_rank: k_head_rank
 K_BED_SIZE, K_BED_FILL = 16, 17  # uz_bed_rows: k_bed_size + the scan of the lengths, k_bed_fill
 K_VCFOUT_SIZE, K_VCFOUT_FILL = 18, 19  # uz_vcf_rows: k_vcfout_size + the scan of the lengths, k_vcfout_fill (per chunk)
+K_BCFOUT_SIZE, K_BCFOUT_FILL = 20, 21  # uz_bcf_rows: k_bcfout_size + the scan of the lengths, k_bcfout_fill (per chunk)
 HEAD_NONE, HEAD_DONE, HEAD_END, HEAD_BAD = 0, 1, 2, 3  # unfazed_hip.h UZ_HEAD_*
 HEAD_MAX_BYTES = 8 << 30  # inflated bytes of one uz_head_walk launch unless UZ_HEAD_MAX_BYTES says otherwise: a choice, not a measurement
 HEAD_MAX_ROUNDS = 8       # walks of one file before it is handed back to the host route
@@ -34,7 +35,7 @@ EXPORTS = [
     "uz_sites_free", "uz_reads_free", "uz_drop_derived",
     "uz_site_scan", "uz_site_scan_many", "uz_site_classes", "uz_find", "uz_find_fetch", "uz_find_cohort",
     "uz_phase", "uz_phase_begin", "uz_phase_end", "uz_phase_cohort", "uz_phase_cohort_joined", "uz_phase_votes", "uz_phase_groups", "uz_phase_sizing_fetch", "uz_phase_cnv", "uz_phase_cnv_cohort", "uz_phase_cnv_sites",
-    "uz_bed_rows", "uz_bed_rows_lists", "uz_vcf_rows",
+    "uz_bed_rows", "uz_bed_rows_lists", "uz_vcf_rows", "uz_bcf_rows",
     "uz_prof_enable", "uz_prof_reset", "uz_prof_get", "uz_prof_units",
     "uz_head_walk", "uz_head_rank", "uz_head_fetch", "uz_head_free",
 ]
@@ -125,6 +126,7 @@ def load_library(path: Optional[str] = None):
     L.uz_bed_rows.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
     L.uz_bed_rows_lists.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int32, vp, vp, vp, C.c_uint32, vp, vp, C.c_int32, vp, vp]
     L.uz_vcf_rows.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.uz_bcf_rows.argtypes = [vp, vp, vp, vp, vp, vp]
     L.uz_head_walk.argtypes = [vp, C.POINTER(C.c_int), C.c_int32, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.uz_head_rank.argtypes = [vp, C.c_int, C.c_int32, vp, vp, vp]
     L.uz_head_fetch.argtypes = [vp, C.c_int, C.c_int32, vp, C.c_int64, C.POINTER(C.c_int64)]
@@ -871,6 +873,16 @@ class HipEngine:
                                     ptr_or_none(ann_uops), ptr_or_none(ann_uet), off.ctypes.data, C.byref(ptr), hb.ctypes.data), "uz_vcf_rows")
         total = int(off[n])
         return (C.string_at(ptr.value, total) if total else b""), off, hb[:n].astype(bool)  # (a copy: the context's block is the next call's)
+
+    def bcf_rows(self, view: "abi.BcfLinesView"):
+        """The records of a BCF as VCF text lines (uz_bcf_rows), written on the device.  view: io_native.vcf_bcf_lines's, or abi.bcf_lines_view over
+        the caller's arrays.  -> (bytes, off [n + 1], samp_at uint64 [n], handed_back bool [n]): record k's line, its '\n' included, is
+        bytes[off[k]: off[k + 1]], empty when the record is handed back; samp_at[k]: where its column 10 starts in bytes (its '\n' without one)."""
+        n = int(view.n_records)
+        off, samp_at, hb, ptr = np.zeros(n + 1, np.int64), np.zeros(max(1, n), np.uint64), np.zeros(max(1, n), np.uint8), C.c_void_p()
+        self._ck(self.L.uz_bcf_rows(self.h, C.addressof(view), off.ctypes.data, samp_at.ctypes.data, C.byref(ptr), hb.ctypes.data), "uz_bcf_rows")
+        total = int(off[n])
+        return (C.string_at(ptr.value, total) if total else b""), off, samp_at[:n], hb[:n].astype(bool)  # (a copy: the context's block is the next call's)
 
     def phase_sizing(self, n: int, n_het: int) -> dict:
         """Test hook (uz_phase_sizing_fetch): the sizing pass's output for the last phase_raw / phase_end -- n DNMs, n_het = het_off[n] of the

@@ -37,7 +37,7 @@ IO_EXPORTS = [
     "uz_index_summary", "uz_inflate_backend", "uz_io_default_threads", "uz_io_cpu_quota", "uz_bam_stage_plan", "uz_bam_stage_begin", "uz_bam_stage_finish", "uz_stage_gather_blocks", "uz_stage_set_inflated", "uz_stage_sizes", "uz_stage_io_stats", "uz_stage_timing", "uz_stage_fill", "uz_stage_qname", "uz_stage_qnames",
     "uz_stage_free", "uz_stage_walk_plan_sizes", "uz_stage_walk_plan", "uz_bam_stage_finish_desc", "uz_stage_kept_sizes", "uz_stage_kept", "uz_stage_walk_host", "uz_stage_kept_debug", "uz_stage_name_records", "uz_packed_block_sums", "uz_stage_merge_subtasks", "uz_bam_stage_finish_sub",
     "uz_stage_walk_flagged", "uz_stage_lookup", "uz_stage_extra", "uz_stage_n_lookup_tasks", "uz_sites_pack", "uz_sites_unpack", "uz_family_pack_het", "uz_family_unpack_het", "uz_samples_pack",
-    "uz_vcf_decode_regions_lazy", "uz_vcf_is_lazy", "uz_vcf_fill_samples", "uz_vcf_samples_text", "uz_vcf_samples_bcf", "uz_vcf_record_samples",
+    "uz_vcf_decode_regions_lazy", "uz_vcf_is_lazy", "uz_vcf_fill_samples", "uz_vcf_samples_text", "uz_vcf_samples_bcf", "uz_vcf_record_samples", "uz_vcf_bcf_lines",
 ]
 
 
@@ -95,6 +95,7 @@ def load():
     lib.uz_vcf_fill_samples.argtypes = [C.c_void_p, C.c_int]
     lib.uz_vcf_samples_text.argtypes = [C.c_void_p, C.POINTER(abi.VcfTextView)]
     lib.uz_vcf_samples_bcf.argtypes = [C.c_void_p, C.POINTER(abi.VcfBcfView)]
+    lib.uz_vcf_bcf_lines.argtypes = [C.c_void_p, C.POINTER(abi.BcfLinesView)]
     lib.uz_vcf_record_samples.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.uz_vcf_index_names.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_int64]
     lib.uz_vcf_index_names.restype = C.c_int64
@@ -524,6 +525,15 @@ def vcf_samples_bcf(table: SitesTable) -> "abi.VcfBcfView":
     lib = load()
     v = abi.VcfBcfView()
     _check(lib, lib.uz_vcf_samples_bcf(table._native.ptr, C.byref(v)))
+    return v
+
+
+def vcf_bcf_lines(table: SitesTable) -> "abi.BcfLinesView":
+    """the records of a natively decoded BCF table, its dictionary and the header's contigs by id (uz_vcf_bcf_lines): what HipEngine.bcf_rows
+    turns into VCF text lines, and (abi.bcf_lines_arrays) what bcf_text.line reads.  The view points into the table, which must outlive it."""
+    lib = load()
+    v = abi.BcfLinesView()
+    _check(lib, lib.uz_vcf_bcf_lines(table._native.ptr, C.byref(v)))
     return v
 
 

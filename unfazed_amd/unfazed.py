@@ -65,14 +65,17 @@ def read_vars_vcf(vcfname):
         from .io_native import read_vcf_table
         t = read_vcf_table(vcfname)
         chrom_of = np.repeat(np.arange(len(t.contigs)), np.diff(t.contig_off))
-        for j in range(t.n_sites):
-            vartype = t.info(j, "SVTYPE")
-            if vartype is None:
-                vartype = SNV_TYPES[0]
-            for i in range(len(t.samples)):
-                if int(t.gt[i, j]) in [HET, HOM_ALT]:
-                    yield {"chrom": t.contigs[int(chrom_of[j])], "start": int(t.pos[j]), "end": int(t.end[j]),
-                           "kid": t.samples[i], "vartype": vartype, "bam": ""}
+        # the HET / HOM_ALT cells by one selection over the [samples, records] codes: record-major, samples ascending, as the loops over both gave
+        gt = np.asarray(t.gt).reshape(len(t.samples), t.n_sites)
+        js, cols = np.nonzero(((gt == HET) | (gt == HOM_ALT)).T)
+        last, vartype = -1, None
+        for j, i in zip(js.tolist(), cols.tolist()):
+            if j != last:
+                last, vartype = j, t.info(j, "SVTYPE")
+                if vartype is None:
+                    vartype = SNV_TYPES[0]
+            yield {"chrom": t.contigs[int(chrom_of[j])], "start": int(t.pos[j]), "end": int(t.end[j]),
+                   "kid": t.samples[i], "vartype": vartype, "bam": ""}
         return
     samples, records, _ = read_vcf(vcfname)
     for r in records:
@@ -195,7 +198,9 @@ def write_vcf_output(in_vcf_name, read_records, include_ambiguous, verbose, outf
     """reference unfazed.py:337-441: GT of a phased sample becomes 1|0 (paternal) / 0|1 (maternal),
     every sample gets UOPS and UET appended."""
     if in_vcf_name.endswith("bcf") or _is_bcf(in_vcf_name):
-        sys.exit(BCF_OUTPUT_MESSAGE)
+        if bcf_route() is None:
+            sys.exit(BCF_OUTPUT_MESSAGE)
+        return _write_vcf_from_bcf(in_vcf_name, read_records, include_ambiguous, verbose, outfile, evidence_min_ratio)
     if vcf_route() == "device" and int(os.environ.get("WORLD_SIZE", "1")) <= 1:
         from . import session
         # asked for by name, the route makes its backend (and fails loudly without a device); as the default it serves a call that has one --
@@ -327,7 +332,7 @@ def _write_vcf_device(in_vcf_name, read_records, include_ambiguous, verbose, out
     those differently), its header is not one `#CHROM` line behind `##` lines, or its records are not the lines read_vcf would see."""
     import ctypes as C
     from . import io_native
-    from .io_vcf import parse_record, site_of
+    from .io_vcf import site_of
     try:
         table = io_native.read_vcf_table(in_vcf_name)
         view = io_native.vcf_samples_text(table)
@@ -355,6 +360,19 @@ def _write_vcf_device(in_vcf_name, read_records, include_ambiguous, verbose, out
         chrom, start, _, _, end, info = site_of(raw[a:s - 1].decode().split("\t"))
         vartype = info.get("SVTYPE")
         sites.append((chrom, start, end, SNV_TYPES[0] if vartype is None else vartype))
+    return _annotate_and_write(raw, header, samples, samp_at, line_end, line_at, sites, view, read_records, include_ambiguous, verbose, outfile,
+                               evidence_min_ratio, backend)
+
+
+def _annotate_and_write(raw, header, samples, samp_at, line_end, line_at, sites, view, read_records, include_ambiguous, verbose, outfile, evidence_min_ratio,
+                        backend, keys_from_sites=False):
+    """The annotate-and-write half of the device route, over record text from either source -- a text DNM file's own (_write_vcf_device) or a
+    BCF's converted one (_write_vcf_from_bcf): raw bytes, the header lines, per record line_at / samp_at / line_end in raw and the site its key is
+    formed from; view: the uz_vcf_text_view over them.  keys_from_sites: a record written by the per-record host code takes its key from
+    `sites`, not from its text (a BCF's keys come from its table, as read_vars_vcf forms them).  -> False, nothing written: read_records does
+    not index by its own fields."""
+    from .io_vcf import parse_record
+    n = len(sites)
     ann = vcf_annotations(sites, samples, read_records, include_ambiguous, verbose, evidence_min_ratio)
     if ann is None:
         return False
@@ -364,6 +382,8 @@ def _write_vcf_device(in_vcf_name, read_records, include_ambiguous, verbose, out
     by_host = sorted(set(host_rows) | set(np.flatnonzero(handed_back).tolist()))
     # read_vcf parses every record before the writer meets the first: so do the records that come back
     parsed = [parse_record(raw[int(line_at[k]):int(line_end[k])].decode(), samples) for k in by_host]
+    if keys_from_sites:
+        parsed = [_with_site(r, sites[k]) for k, r in zip(by_host, parsed)]
     parts = [("\n".join(_annotated_header(header)) + "\n").encode()]
     body, at = memoryview(text), 0
     for k, r in zip(by_host, parsed):
@@ -380,6 +400,95 @@ def _write_vcf_device(in_vcf_name, read_records, include_ambiguous, verbose, out
             for p in parts:
                 fh.write(p)
     return True
+
+
+BCF_STATS = {"bcf_device_rows": 0, "bcf_host_rows": 0, "bcf_calls": 0}  # records whose text the device wrote / bcf_text.line wrote, uz_bcf_rows calls
+
+
+def bcf_route():
+    """UZ_BCF_ROUTE: "device" -- a BCF of DNMs becomes record text on the device (uz_bcf_rows; csrc/bcf_row.hpp states the rules), which the
+    annotated-VCF writer then takes -- or "host" (unfazed_amd/bcf_text.py converts every record).  Not set, or any other value: None, and the
+    annotated VCF of a BCF is refused with BCF_OUTPUT_MESSAGE as before."""
+    v = os.environ.get("UZ_BCF_ROUTE", "").lower()
+    return v if v in ("device", "host") else None
+
+
+def _with_site(r, site):
+    """a parsed record with the key fields of `site` (chrom, start, end, vartype): what _annotated_line forms its key from"""
+    chrom, start, end, vartype = site
+    r.chrom, r.start, r.end = chrom, start, end
+    r.info = dict(r.info)
+    r.info["SVTYPE"] = vartype
+    return r
+
+
+def _write_vcf_from_bcf(in_vcf_name, read_records, include_ambiguous, verbose, outfile, evidence_min_ratio):
+    """The annotated VCF of a BCF of DNMs (UZ_BCF_ROUTE; reference unfazed.py:530 takes such a file and writes text from it).  The records become
+    VCF lines -- on the device (backend.bcf_rows), the handed-back ones by bcf_text.line, or all of them by bcf_text.line -- the header lines are
+    the table's, and the lines then go the way a text file's go: _annotate_and_write on the device route, parse_record + _annotated_line on the
+    host route (and for more than one rank).  The keys come from the table (pos, end, INFO SVTYPE), exactly as read_vars_vcf forms them."""
+    from . import abi, bcf_text, io_native
+    from .io_vcf import parse_record
+    table = io_native.read_vcf_table(in_vcf_name)
+    view = io_native.vcf_bcf_lines(table)
+    n = int(view.n_records)
+    header, samples = list(table.header), list(table.samples)
+    chrom_of = np.repeat(np.arange(len(table.contigs)), np.diff(table.contig_off))
+    sites = []
+    for j in range(n):
+        vartype = table.info(j, "SVTYPE")
+        sites.append((table.contigs[int(chrom_of[j])], int(table.pos[j]), int(table.end[j]), SNV_TYPES[0] if vartype is None else vartype))
+    device = bcf_route() == "device" and int(os.environ.get("WORLD_SIZE", "1")) <= 1
+    arrays = None
+
+    def converted(only=None):
+        nonlocal arrays
+        if arrays is None:
+            arrays = abi.bcf_lines_arrays(view)
+        return bcf_text.lines(arrays[0], arrays[1], arrays[2], arrays[3], len(samples), only=only)
+    if device:
+        from . import session
+        backend = session.get_backend()  # asked for by name: the route makes its backend, and fails loudly without a device
+        text, off, samp_at, handed_back = backend.bcf_rows(view)
+        BCF_STATS["bcf_calls"] += 1
+        by_host = np.flatnonzero(handed_back).tolist()
+        line_at, line_end, samp_at = off[:-1].astype(np.int64), off[1:].astype(np.int64) - 1, samp_at.astype(np.int64)
+        if by_host:  # the handed-back records' lines spliced in where they belong: every later offset moves by their bytes
+            lines = [ln.encode() + b"\n" for ln in converted(by_host)]
+            parts, at, grow = [], 0, np.zeros(n + 1, np.int64)
+            for k, ln in zip(by_host, lines):
+                parts += [text[at:int(off[k])], ln]
+                at = int(off[k])
+                grow[k + 1] = len(ln)
+            parts.append(text[at:])
+            text = b"".join(parts)
+            shift = np.cumsum(grow)
+            line_at, line_end = line_at + shift[:-1], off[1:].astype(np.int64) + shift[1:] - 1
+            samp_at = samp_at + shift[:-1]
+            for k, ln in zip(by_host, lines):
+                cols = ln[:-1].split(b"\t")
+                samp_at[k] = line_at[k] + (len(b"\t".join(cols[:9])) + 1 if len(cols) > 9 else len(ln) - 1)
+        BCF_STATS["bcf_device_rows"] += n - len(by_host)
+        BCF_STATS["bcf_host_rows"] += len(by_host)
+        tview = abi.vcf_text_view(np.frombuffer(text, np.uint8), samp_at.astype(np.uint64), line_end.astype(np.uint64), len(samples))
+        if hasattr(backend, "vcf_rows") and _annotate_and_write(text, header, samples, samp_at, line_end, line_at, sites, tview, read_records, include_ambiguous,
+                                                                verbose, outfile, evidence_min_ratio, backend, keys_from_sites=True):
+            return
+        lines = [text[int(a):int(e)].decode() for a, e in zip(line_at, line_end)]
+    else:
+        lines = converted()
+        BCF_STATS["bcf_host_rows"] += n
+    records = [_with_site(parse_record(ln, samples), site) for ln, site in zip(lines, sites)]
+    out = _annotated_header(header)
+    for r in records:
+        out.append(_annotated_line(r, samples, read_records, include_ambiguous, verbose, evidence_min_ratio))
+    VCF_STATS["vcf_host_rows"] += n
+    text = "\n".join(out) + "\n"
+    if outfile == "/dev/stdout":
+        sys.stdout.write(text)
+    else:
+        with open(outfile, "w") as fh:
+            fh.write(text)
 
 
 def _dnm_reader(path):
@@ -457,7 +566,7 @@ def unfazed(args):
               + "Rerun with `--output-type bed` or input dnms as one of the following:", ", ".join(VCF_TYPES),
               file=sys.stderr)
         sys.exit(1)
-    if output_type == "vcf" and (args.dnms.endswith("bcf") or _is_bcf(args.dnms)):
+    if output_type == "vcf" and bcf_route() is None and (args.dnms.endswith("bcf") or _is_bcf(args.dnms)):
         sys.exit(BCF_OUTPUT_MESSAGE)  # known before any phasing is done
     snvs, svs, kids = _route_variants(reader(args.dnms), bam_names, args.reference)
     pedigrees = parse_ped(args.ped, kids)
