@@ -162,6 +162,10 @@ int uz_reads_headers(uz_ctx *ctx, int reads_id, int32_t *start, int32_t *end, in
  * qlow [sizes[3]].  Nothing on the product path calls it. */
 int uz_reads_columns(uz_ctx *ctx, int reads_id, int64_t sizes[4], uint32_t *fm, uint16_t *l_seq, uint16_t *n_cigar, uint32_t *cigar_off, uint32_t *sq_off,
                      uint32_t *qoff, uint32_t *cigar, uint8_t *seq4, uint32_t *qlow);
+/* parity / debug, beside uz_reads_columns: the two per-record columns it leaves out, as the device holds them.  umask [n]: the staged 32-base units of
+ * every record's rows (UZ_UMASK_ALL: every unit; UZ_UMASK_LISTED set when the record's bases came as a list); nlow [n]: the low-quality count that
+ * travelled, saturated at 255.  Either pointer may be NULL.  Nothing on the product path calls it. */
+int uz_reads_marks(uz_ctx *ctx, int reads_id, uint16_t *umask, uint8_t *nlow);
 /* BGZF blocks inflated on the device (csrc/k_inflate.hip: one wavefront per block; fixed, dynamic and stored DEFLATE blocks).  This
  * entry is the measured form (repeat / kernel_ms) behind the parity tests; the session's path calls uz_bgzf_inflate_to_host below for
  * every staged batch (HipEngine.upload_reads_staged).  comp: the compressed bytes (host); in_off[k]: where the DEFLATE stream

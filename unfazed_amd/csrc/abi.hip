@@ -1801,6 +1801,24 @@ int uz_reads_columns(uz_ctx *c, int reads_id, int64_t sizes[4], uint32_t *fm, ui
     });
 }
 
+int uz_reads_marks(uz_ctx *c, int reads_id, uint16_t *umask, uint8_t *nlow) {
+    return guarded(c, [&] {
+        ReadsDev &r = reads_of(c, reads_id);
+        uz_reads_make_ready(c, r);
+        UZ_HIP(hipStreamSynchronize(c->stream));
+        uz_check_upload_flag(c);
+        const size_t n = (size_t)r.n;
+        if (n && umask) {
+            UZ_REQUIRE(r.umask, UZ_E_STATE, "uz_reads_marks: the table holds no unit masks");
+            UZ_HIP(hipMemcpy(umask, r.umask, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        }
+        if (n && nlow) {
+            UZ_REQUIRE(r.nlow, UZ_E_STATE, "uz_reads_marks: the table holds no low-quality counts");
+            UZ_HIP(hipMemcpy(nlow, r.nlow, n, hipMemcpyDeviceToHost));
+        }
+    });
+}
+
 int uz_bgzf_inflate(uz_ctx *c, const uint8_t *comp, int64_t comp_bytes, int64_t n_blocks, const int64_t *in_off, const int64_t *out_off, uint8_t *out,
                     int repeat, double *kernel_ms) {
     return guarded(c, [&] {

@@ -28,7 +28,7 @@ HEAD_MAX_ROUNDS = 8       # walks of one file before it is handed back to the ho
 
 EXPORTS = [
     "uz_create", "uz_destroy", "uz_last_error", "uz_sync", "uz_set_params",
-    "uz_sites_upload", "uz_family_upload", "uz_sites_family_upload_async", "uz_samples_upload", "uz_samples_from_text", "uz_samples_from_bcf", "uz_samples_unsettled", "uz_samples_settle", "uz_families_from_samples", "uz_family_fetch", "uz_samples_free", "uz_reads_upload", "uz_reads_upload_packed", "uz_reads_wait", "uz_reads_headers", "uz_reads_columns", "uz_bgzf_inflate", "uz_bgzf_inflate_to_host", "uz_bam_walk", "uz_bam_walk_many", "uz_reads_files", "uz_crc32_blocks", "uz_bam_walk_fetch", "uz_bam_walk_release", "uz_reads_from_bam",
+    "uz_sites_upload", "uz_family_upload", "uz_sites_family_upload_async", "uz_samples_upload", "uz_samples_from_text", "uz_samples_from_bcf", "uz_samples_unsettled", "uz_samples_settle", "uz_families_from_samples", "uz_family_fetch", "uz_samples_free", "uz_reads_upload", "uz_reads_upload_packed", "uz_reads_wait", "uz_reads_headers", "uz_reads_columns", "uz_reads_marks", "uz_bgzf_inflate", "uz_bgzf_inflate_to_host", "uz_bam_walk", "uz_bam_walk_many", "uz_reads_files", "uz_crc32_blocks", "uz_bam_walk_fetch", "uz_bam_walk_release", "uz_reads_from_bam",
     "uz_bam_walk_flags", "uz_bam_join", "uz_bam_join_needs", "uz_bam_join_fetch", "uz_reads_from_walk", "uz_reads_names", "uz_walk_slot_stats", "uz_walk_reserve",
     "uz_pinned_alloc", "uz_pinned_free",
     "uz_sites_adopt_device", "uz_family_adopt_device", "uz_reads_adopt_device",
@@ -70,6 +70,7 @@ def load_library(path: Optional[str] = None):
     L.uz_reads_wait.argtypes = [vp, C.c_int]
     L.uz_reads_headers.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     L.uz_reads_columns.argtypes = [vp, C.c_int] + [vp] * 10
+    L.uz_reads_marks.argtypes = [vp, C.c_int, vp, vp]
     L.uz_bgzf_inflate.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp, vp, C.c_int, C.POINTER(C.c_double)]
     L.uz_bgzf_inflate_to_host.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp, vp]
     L.uz_crc32_blocks.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
@@ -464,6 +465,14 @@ class HipEngine:
                  "uz_reads_columns")
         cut = dict(cigar=int(sizes[1]), seq4=16 * int(sizes[2]), qlow=int(sizes[3]))
         return {k: v[: cut.get(k, int(n))] for k, v in out.items()}
+
+    def reads_marks(self, rid: int, n: int) -> dict:
+        """the two per-record columns reads_columns leaves out, as the device holds them (uz_reads_marks; a debug read-back): umask (the staged
+        32-base units, UZ_UMASK_LISTED set for a record whose bases came as a list) and nlow (the low-quality count that travelled)"""
+        m = max(1, int(n))
+        out = dict(umask=np.zeros(m, np.uint16), nlow=np.zeros(m, np.uint8))
+        self._ck(self.L.uz_reads_marks(self.h, int(rid), out["umask"].ctypes.data, out["nlow"].ctypes.data), "uz_reads_marks")
+        return {k: v[: int(n)] for k, v in out.items()}
 
     def bgzf_inflate(self, data, repeat: int = 0):
         """Every BGZF block of `data` (bytes / uint8 array: a BGZF file or a run of its blocks) inflated on the device (uz_bgzf_inflate).
