@@ -61,7 +61,9 @@ extern "C" {
 #define UZ_K_VCFOUT_FILL 19 /* k_vcfout_fill */
 #define UZ_K_BCFOUT_SIZE 20 /* k_bcfout_size + the scan of the records' lengths (uz_bcf_rows), one launch per chunk of records */
 #define UZ_K_BCFOUT_FILL 21 /* k_bcfout_fill */
-#define UZ_K_COUNT 22
+#define UZ_K_DEFLATE 22       /* k_bgzf_deflate + k_bgzf_crc32_out + the scan of the blocks' sizes (uz_bgzf_deflate), one launch per chunk of input */
+#define UZ_K_DEFLATE_FRAME 23 /* k_bgzf_frame */
+#define UZ_K_COUNT 24
 
 typedef struct uz_ctx uz_ctx;
 
@@ -441,6 +443,22 @@ int uz_vcf_rows(uz_ctx *ctx, const uz_vcf_text_view *text, const int64_t *line_a
  * more of text from one chunk.  UZ_E_STATE: a record whose written bytes differ from its sized length. */
 int uz_bcf_rows(uz_ctx *ctx, const uz_bcf_lines_view *records, int64_t *off /* [n_records + 1] */, uint64_t *samp_at /* [n_records] */,
                 const uint8_t **bytes, uint8_t *handed_back /* [n_records] */);
+
+/* A host buffer written as BGZF blocks on the device (k_deflate.hip; csrc/deflate_body.hpp states the rules): the mirror image of
+ * uz_bgzf_inflate.  data [n_bytes] is cut into slices of 65 280 bytes (htslib's), the last one shorter; every slice becomes one block: the
+ * 18-byte header (1f 8b 08 04, MTIME 0, XFL 0, OS ff, XLEN 6, "BC", 2, BSIZE = block length - 1), one raw DEFLATE stream -- LZ77 over the
+ * slice alone, one fixed-Huffman block (BTYPE 01), or one stored block (BTYPE 00) where that is shorter -- CRC-32 and ISIZE.  No block is
+ * longer than 65 311 bytes.  *n_blocks: the blocks; *bgzf [*bgzf_bytes]: the blocks back to back, page-locked memory of the context, valid
+ * until the next uz_bgzf_deflate.  The blocks only: the caller writes the 28-byte end-of-file marker behind them.
+ * n_bytes == 0: no block, nothing launched, *bgzf NULL.  The same input gives the same bytes in every call.
+ * repeat / kernel_ms as in uz_bgzf_inflate: repeat > 0 launches k_bgzf_deflate that many more times and *kernel_ms is the mean time of one
+ * pass over the whole input (summed over the chunks).
+ * The input goes up in chunks of UZ_BGZF_CHUNK_BYTES (read per call, 32 MiB, rounded down to a multiple of 65 280: the slices do not depend
+ * on it), chunk k + 1 copied while chunk k is worked on.
+ * UZ_E_ARG (nothing launched): NULL data with n_bytes > 0, a NULL result.  UZ_E_STATE: a framed block whose written size differs from its
+ * scanned size. */
+int uz_bgzf_deflate(uz_ctx *ctx, const uint8_t *data /* host */, int64_t n_bytes, int64_t *n_blocks, const uint8_t **bgzf, int64_t *bgzf_bytes,
+                    int repeat, double *kernel_ms);
 
 /* ---- allele-balance (CNV) stage ---------------------------------------- */
 /* K6.  Everything run_cnv_phasing does after its find (sv_phaser.py:357-423: phase_by_snvs :71-85,

@@ -478,6 +478,8 @@ void uz_destroy(uz_ctx *c) {
     c->vo_in[0].release(); c->vo_in[1].release(); c->vo_out.release(); c->vo_off.release(); c->vo_len.release();
     for (uint8_t *p : {c->bo_pin[0], c->bo_pin[1], c->bo_small, c->bo_res}) if (p) (void)hipHostFree(p);
     c->bo_in[0].release(); c->bo_in[1].release(); c->bo_out.release(); c->bo_off.release(); c->bo_len.release();
+    for (uint8_t *p : {c->df_pin[0], c->df_pin[1], c->df_small_pin, c->df_res}) if (p) (void)hipHostFree(p);
+    c->df_in[0].release(); c->df_in[1].release(); c->df_slots.release(); c->df_small.release(); c->df_out.release();
     c->nm_ids.release(); c->nm_len.release(); c->nm_off.release(); c->nm_out.release(); c->rf_first.release(); c->rf_mm.release();
     c->ab_lut.release(); c->win_range.release();
     c->dn_fam.release(); c->dn_cutoff.release(); c->fam_cls.release();
@@ -2466,6 +2468,10 @@ int uz_vcf_rows(uz_ctx *c, const uz_vcf_text_view *text, const int64_t *line_at,
 }
 int uz_bcf_rows(uz_ctx *c, const uz_bcf_lines_view *records, int64_t *off, uint64_t *samp_at, const uint8_t **bytes, uint8_t *handed_back) {
     return guarded(c, [&] { (void)uz_bcf_rows_impl(c, records, off, samp_at, bytes, handed_back); });
+}
+
+int uz_bgzf_deflate(uz_ctx *c, const uint8_t *data, int64_t n_bytes, int64_t *n_blocks, const uint8_t **bgzf, int64_t *bgzf_bytes, int repeat, double *kernel_ms) {
+    return guarded(c, [&] { (void)uz_bgzf_deflate_impl(c, data, n_bytes, n_blocks, bgzf, bgzf_bytes, repeat, kernel_ms); });
 }
 
 int uz_bed_rows_lists(uz_ctx *c, const uz_bed_view *rows, int verbose, int include_ambiguous, int32_t n_dnms, const int32_t *status, const int64_t *list_off,

@@ -1,0 +1,271 @@
+// k_deflate.hip -- BGZF blocks written on the device (unfazed_hip.h: uz_bgzf_deflate).  deflate_body.hpp is the body: the parse rule, the fixed-
+// Huffman coder, the stored fallback.  Here: the wavefront that runs it, the launches of a chunk and the host side of a call.
+//
+// The input is cut into slices of 65 280 bytes, one BGZF block each, and goes up in chunks of UZ_BGZF_CHUNK_BYTES (32 MiB, rounded down to whole
+// slices: a slice's edges do not depend on the chunk size), chunk k + 1 copied on the copy stream while chunk k is worked on:
+//   k_bgzf_deflate    one wavefront per slice: its raw DEFLATE stream into a scratch slot of UZ_DF_SLOT bytes, and the stream's byte count
+//   k_bgzf_crc32_out  one wavefront per slice: the CRC-32 of its bytes (crc32_wave.hpp, the code k_bgzf_crc32 compares with)
+//   k_bgzf_sizes      exclusive scan of the blocks' sizes (18 + stream + 8) -> off [n + 1] (one workgroup)
+//   k_bgzf_frame      one workgroup per block: header, stream, CRC-32 and ISIZE, back to back at off; a block whose written bytes differ from its
+//                     scanned size raises the flag
+// No global atomics decide a byte: the only one is the OR of the raised flag.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "crc32_wave.hpp"
+#include "deflate_body.hpp"
+#include "uz_ctx.hpp"
+
+#define UZ_DF_F_SIZE 1u /* a framed block's written bytes differ from its scanned size */
+
+namespace {
+
+struct DfWave { // the 64 lanes of a wavefront share a slice
+    template <typename T>
+    struct V {
+        T x;
+        __device__ __forceinline__ T &operator[](uint32_t) { return x; }
+        __device__ __forceinline__ const T &operator[](uint32_t) const { return x; }
+    };
+    __device__ __forceinline__ uint32_t lane0() const { return threadIdx.x & 63u; }
+    __device__ __forceinline__ uint32_t lane1() const { return (threadIdx.x & 63u) + 1u; }
+    __device__ __forceinline__ void sync() const { __syncthreads(); } // (the workgroup is this wavefront)
+    __device__ __forceinline__ void drain() const { __builtin_amdgcn_s_waitcnt(0x0F70); } // vmcnt(0): the stores issued so far have landed
+    __device__ __forceinline__ uint64_t ballot(const V<uint32_t> &p) const { return (uint64_t)__ballot(p.x != 0 ? 1 : 0); }
+    __device__ __forceinline__ void excl_scan(const V<uint32_t> &v, V<uint32_t> &out, uint32_t &total) const {
+        const uint32_t l = threadIdx.x & 63u;
+        uint32_t x = v.x;
+#pragma unroll
+        for (uint32_t d = 1; d < 64; d <<= 1) {
+            const uint32_t y = (uint32_t)__shfl_up((int)x, d, 64);
+            if (l >= d) x += y;
+        }
+        out.x = x - v.x;
+        total = (uint32_t)__shfl((int)x, 63, 64);
+    }
+    __device__ __forceinline__ uint32_t get(const V<uint32_t> &v, uint32_t src) const { return (uint32_t)__shfl((int)v.x, (int)src, 64); }
+    // an entry is raised until no lane holds a higher position for it: the maximum, whichever lane a colliding store lets win
+    __device__ __forceinline__ void insert_max(uint16_t *tab, const V<uint32_t> &h, const V<uint32_t> &val, const V<uint32_t> &ok) const {
+        for (;;) {
+            const bool need = ok.x && (uint32_t)tab[h.x] < val.x;
+            if (!__any(need ? 1 : 0)) break;
+            if (need) tab[h.x] = (uint16_t)val.x;
+            __syncthreads();
+        }
+    }
+    __device__ __forceinline__ void or_word(uint32_t *w, uint32_t v) const { atomicOr(w, v); } // (LDS)
+};
+
+__global__ __launch_bounds__(64) void k_bgzf_deflate(int32_t n_slices, const uint8_t *__restrict__ in, int64_t in_bytes, uint8_t *__restrict__ slots,
+                                                     uint32_t *__restrict__ count /* [n_slices] */) {
+    __shared__ UzDfLds S;
+    const int32_t s = (int32_t)blockIdx.x;
+    if (s >= n_slices) return;
+    const int64_t at = (int64_t)s * UZ_DF_SLICE;
+    const uint32_t n = in_bytes - at < (int64_t)UZ_DF_SLICE ? (uint32_t)(in_bytes - at) : UZ_DF_SLICE;
+    DfWave w;
+    bool stored = false;
+    const uint32_t bytes = uz_deflate_slice(w, S, in + at, n, slots + (size_t)s * UZ_DF_SLOT, UZ_DF_SLOT, stored);
+    if ((threadIdx.x & 63u) == 0) count[s] = bytes;
+}
+
+__global__ __launch_bounds__(64) void k_bgzf_crc32_out(int32_t n_slices, const uint8_t *__restrict__ in, int64_t in_bytes, uint32_t *__restrict__ crc) {
+    __shared__ UzCrcLds S;
+    const int lane = threadIdx.x;
+    uz_crc_setup(S, lane);
+    for (int32_t s = (int32_t)blockIdx.x; s < n_slices; s += (int32_t)gridDim.x) {
+        const int64_t at = (int64_t)s * UZ_DF_SLICE;
+        const uint32_t n = in_bytes - at < (int64_t)UZ_DF_SLICE ? (uint32_t)(in_bytes - at) : UZ_DF_SLICE;
+        const uint32_t c = uz_crc_wave(S, in + at, n, lane);
+        if (lane == 0) crc[s] = c;
+    }
+}
+
+// off[k] = sum over the blocks before k of 18 + count + 8, off[n] the total: one workgroup of 1024 lanes, a tile of 1024 blocks per round
+__global__ __launch_bounds__(1024) void k_bgzf_sizes(int32_t n, const uint32_t *__restrict__ count, int64_t *__restrict__ off) {
+    __shared__ unsigned long long wave_sum[16];
+    __shared__ unsigned long long carry_s;
+    const uint32_t t = threadIdx.x, l = t & 63u, wv = t >> 6;
+    if (t == 0) carry_s = 0;
+    __syncthreads();
+    for (int32_t base = 0; base < n; base += 1024) {
+        const int32_t i = base + (int32_t)t;
+        const unsigned long long v = i < n ? (unsigned long long)count[i] + UZ_BGZF_HEAD + UZ_BGZF_TAIL : 0ull;
+        unsigned long long x = v;
+#pragma unroll
+        for (uint32_t d = 1; d < 64; d <<= 1) {
+            const unsigned long long y = (unsigned long long)__shfl_up((long long)x, d, 64);
+            if (l >= d) x += y;
+        }
+        if (l == 63) wave_sum[wv] = x;
+        __syncthreads();
+        unsigned long long before = carry_s;
+        for (uint32_t k = 0; k < wv; k++) before += wave_sum[k];
+        if (i < n) off[i] = (int64_t)(before + x - v);
+        __syncthreads();
+        if (t == 1023) carry_s = before + x;
+        __syncthreads();
+    }
+    if (t == 0) off[n] = (int64_t)carry_s;
+}
+
+#define UZ_DF_FRAME_LANES 256
+__global__ __launch_bounds__(UZ_DF_FRAME_LANES) void k_bgzf_frame(int32_t n_slices, int64_t in_bytes, const uint8_t *__restrict__ slots, const uint32_t *__restrict__ count,
+                                                                   const uint32_t *__restrict__ crc, const int64_t *__restrict__ off, int64_t out_cap,
+                                                                   uint8_t *__restrict__ out, uint32_t *flags) {
+    const int32_t s = (int32_t)blockIdx.x;
+    if (s >= n_slices) return;
+    const uint32_t t = threadIdx.x, cnt = count[s];
+    const int64_t o0 = off[s], o1 = off[s + 1];
+    const int64_t left = in_bytes - (int64_t)s * UZ_DF_SLICE;
+    const uint32_t isize = left < (int64_t)UZ_DF_SLICE ? (uint32_t)left : UZ_DF_SLICE;
+    const uint32_t block = UZ_BGZF_HEAD + cnt + UZ_BGZF_TAIL; // what this launch writes
+    // (a stream is at most 5 + 65 280 bytes: deflate_body.hpp; held here again, with the block's place in the output)
+    if (cnt == 0 || cnt > 5 + isize || o1 - o0 != (int64_t)block || o0 < 0 || o1 > out_cap) {
+        if (t == 0) atomicOr(flags, UZ_DF_F_SIZE);
+        return;
+    }
+    uint8_t *d = out + o0;
+    if (t < UZ_BGZF_HEAD) {
+        const uint32_t bsize = block - 1;
+        const uint8_t head[UZ_BGZF_HEAD] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, (uint8_t)(bsize & 0xFF), (uint8_t)(bsize >> 8)};
+        d[t] = head[t];
+    } else if (t < UZ_BGZF_HEAD + UZ_BGZF_TAIL) {
+        const uint32_t k = t - UZ_BGZF_HEAD, v = k < 4 ? crc[s] : isize;
+        d[UZ_BGZF_HEAD + cnt + k] = (uint8_t)(v >> (8 * (k & 3u)));
+    }
+    // the stream: bytes up to the destination's first whole word, whole words built from the slot's bytes, the bytes behind the last one
+    const uint8_t *src = slots + (size_t)s * UZ_DF_SLOT;
+    uint8_t *dst = d + UZ_BGZF_HEAD;
+    const uint32_t a4 = (uint32_t)((4u - ((uintptr_t)dst & 3u)) & 3u), a = a4 < cnt ? a4 : cnt;
+    if (t < a) dst[t] = src[t];
+    const uint32_t words = (cnt - a) / 4;
+    for (uint32_t k = t; k < words; k += UZ_DF_FRAME_LANES) {
+        const uint32_t i = a + 4 * k;
+        const uint32_t v = (uint32_t)src[i] | ((uint32_t)src[i + 1] << 8) | ((uint32_t)src[i + 2] << 16) | ((uint32_t)src[i + 3] << 24);
+        *reinterpret_cast<uint32_t *>(dst + i) = v;
+    }
+    const uint32_t rest = a + 4 * words;
+    if (rest + t < cnt && t < 4) dst[rest + t] = src[rest + t];
+}
+
+size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+void pin_room(uint8_t *&p, size_t &cap, size_t need, size_t keep) { // a page-locked block grown to `need`, its first `keep` bytes carried over
+    if (cap >= need) return;
+    const size_t want = need + need / 4 + 4096;
+    uint8_t *q = nullptr;
+    UZ_HIP(hipHostMalloc((void **)&q, want, hipHostMallocDefault));
+    if (keep) memcpy(q, p, keep);
+    if (p) (void)hipHostFree(p);
+    p = q; cap = want;
+}
+
+} // namespace
+
+int uz_bgzf_deflate_impl(uz_ctx *c, const uint8_t *data, int64_t n_bytes, int64_t *n_blocks, const uint8_t **bgzf, int64_t *bgzf_bytes, int repeat, double *kernel_ms) {
+    UZ_REQUIRE(n_blocks && bgzf && bgzf_bytes && n_bytes >= 0, UZ_E_ARG, "BGZF deflate: bad arguments");
+    UZ_REQUIRE(data || n_bytes == 0, UZ_E_ARG, "BGZF deflate: no data");
+    *n_blocks = 0; *bgzf = nullptr; *bgzf_bytes = 0;
+    if (kernel_ms) *kernel_ms = 0;
+    if (n_bytes == 0) return 0; // nothing is launched: no blocks (the caller's end-of-file marker is the whole file)
+    size_t chunk_bytes = (size_t)32 << 20;
+    if (const char *e = getenv("UZ_BGZF_CHUNK_BYTES")) { // (read per call: the tests put chunk edges into small inputs with it)
+        const long long v = atoll(e);
+        if (v > 0) chunk_bytes = (size_t)v;
+    }
+    chunk_bytes = std::min<size_t>(chunk_bytes, (size_t)1 << 30);
+    chunk_bytes = std::max<size_t>(UZ_DF_SLICE, chunk_bytes / UZ_DF_SLICE * UZ_DF_SLICE); // whole slices
+    const size_t n_chunks = ((size_t)n_bytes + chunk_bytes - 1) / chunk_bytes;
+    const int64_t total_slices = (n_bytes + UZ_DF_SLICE - 1) / UZ_DF_SLICE;
+    hipEvent_t copied[2] = {nullptr, nullptr}, e0 = nullptr, e1 = nullptr;
+    auto cleanup = [&] {
+        (void)hipStreamSynchronize(c->copy_stream);
+        (void)hipStreamSynchronize(c->stream);
+        for (hipEvent_t e : {copied[0], copied[1], e0, e1})
+            if (e) (void)hipEventDestroy(e);
+    };
+    auto bytes_of = [&](size_t q) { return std::min<size_t>(chunk_bytes, (size_t)n_bytes - q * chunk_bytes); };
+    auto stage = [&](size_t q) { // a chunk into its page-locked image, and the image onto the copy stream
+        const int b = (int)(q & 1);
+        const size_t nb = bytes_of(q);
+        pin_room(c->df_pin[b], c->df_pin_cap[b], nb, 0);
+        c->df_in[b].ensure(nb + 64);
+        memcpy(c->df_pin[b], data + q * chunk_bytes, nb);
+        UZ_HIP(hipMemcpyAsync(c->df_in[b].p, c->df_pin[b], nb, hipMemcpyHostToDevice, c->copy_stream));
+        UZ_HIP(hipEventRecord(copied[b], c->copy_stream));
+    };
+    try {
+        for (int b = 0; b < 2 && b < (int)n_chunks; b++) UZ_HIP(hipEventCreateWithFlags(&copied[b], hipEventDisableTiming));
+        if (repeat > 0) { UZ_HIP(hipEventCreate(&e0)); UZ_HIP(hipEventCreate(&e1)); }
+        hipStream_t st = c->stream;
+        int64_t total = 0;
+        double ms_sum = 0;
+        stage(0);
+        for (size_t q = 0; q < n_chunks; q++) {
+            const int b = (int)(q & 1);
+            const size_t nb = bytes_of(q);
+            const int32_t ns = (int32_t)((nb + UZ_DF_SLICE - 1) / UZ_DF_SLICE);
+            // a chunk's small results in one block: off [ns + 1], the flag word (+ padding), count [ns], crc [ns]
+            const size_t o_flag = ((size_t)ns + 1) * 8, o_count = o_flag + 8, o_crc = o_count + (size_t)ns * 4, small_bytes = up256(o_crc + (size_t)ns * 4);
+            const size_t out_cap = nb + (size_t)ns * (UZ_BGZF_HEAD + UZ_BGZF_TAIL + 5); // every slice stored
+            c->df_slots.ensure((size_t)ns * UZ_DF_SLOT + 64);
+            c->df_small.ensure(small_bytes + 64);
+            c->df_out.ensure(up256(out_cap) + 64);
+            pin_room(c->df_small_pin, c->df_small_pin_cap, 64, 0);
+            int64_t *d_off = reinterpret_cast<int64_t *>(c->df_small.p);
+            uint32_t *d_flag = reinterpret_cast<uint32_t *>(c->df_small.p + o_flag);
+            uint32_t *d_count = reinterpret_cast<uint32_t *>(c->df_small.p + o_count);
+            uint32_t *d_crc = reinterpret_cast<uint32_t *>(c->df_small.p + o_crc);
+            const uint8_t *d_in = c->df_in[b].p;
+            UZ_HIP(hipStreamWaitEvent(st, copied[b], 0));
+            UZ_HIP(hipMemsetAsync(d_flag, 0, 8, st));
+            {
+                ProfScope ps(c, UZ_K_DEFLATE);
+                hipLaunchKernelGGL(k_bgzf_deflate, dim3((unsigned)ns), dim3(64), 0, st, ns, d_in, (int64_t)nb, c->df_slots.p, d_count);
+                UZ_HIP(hipGetLastError());
+                hipLaunchKernelGGL(k_bgzf_crc32_out, dim3((unsigned)std::min<int32_t>(ns, 256 * 16)), dim3(64), 0, st, ns, d_in, (int64_t)nb, d_crc);
+                UZ_HIP(hipGetLastError());
+                hipLaunchKernelGGL(k_bgzf_sizes, dim3(1), dim3(1024), 0, st, ns, (const uint32_t *)d_count, d_off);
+                UZ_HIP(hipGetLastError());
+            }
+            {
+                ProfScope ps(c, UZ_K_DEFLATE_FRAME);
+                hipLaunchKernelGGL(k_bgzf_frame, dim3((unsigned)ns), dim3(UZ_DF_FRAME_LANES), 0, st, ns, (int64_t)nb, (const uint8_t *)c->df_slots.p, (const uint32_t *)d_count,
+                                   (const uint32_t *)d_crc, (const int64_t *)d_off, (int64_t)out_cap, c->df_out.p, d_flag);
+                UZ_HIP(hipGetLastError());
+            }
+            uz_kcopy(c, c->df_small_pin, d_off + ns, 16); // the chunk's bytes, the flag word
+            if (repeat > 0) { // the measured form: the same launch again, which writes the same bytes into the same slots
+                UZ_HIP(hipEventRecord(e0, st));
+                for (int r = 0; r < repeat; r++) hipLaunchKernelGGL(k_bgzf_deflate, dim3((unsigned)ns), dim3(64), 0, st, ns, d_in, (int64_t)nb, c->df_slots.p, d_count);
+                UZ_HIP(hipGetLastError());
+                UZ_HIP(hipEventRecord(e1, st));
+            }
+            if (q + 1 < n_chunks) stage(q + 1); // (its image and its block were chunk q - 1's, which is done)
+            UZ_HIP(hipStreamSynchronize(st));
+            if (repeat > 0) {
+                float ms = 0;
+                UZ_HIP(hipEventElapsedTime(&ms, e0, e1));
+                ms_sum += (double)ms / repeat;
+            }
+            const int64_t len = *reinterpret_cast<const int64_t *>(c->df_small_pin);
+            const uint32_t flag = *reinterpret_cast<const uint32_t *>(c->df_small_pin + 8);
+            UZ_REQUIRE(!(flag & UZ_DF_F_SIZE) && len >= (int64_t)ns * (UZ_BGZF_HEAD + UZ_BGZF_TAIL) && len <= (int64_t)out_cap, UZ_E_STATE,
+                       "BGZF deflate: a framed block's written bytes differ from its scanned size");
+            // (the first chunk sizes the block for the whole call at its own rate, so that it is allocated once)
+            const size_t guess = q == 0 ? (size_t)((double)len * 1.05 * (double)n_bytes / (double)nb) + 65536 : 0;
+            pin_room(c->df_res, c->df_res_cap, std::max((size_t)(total + len) + 16, guess), (size_t)total);
+            UZ_HIP(hipMemcpyAsync(c->df_res + total, c->df_out.p, (size_t)len, hipMemcpyDeviceToHost, st));
+            UZ_HIP(hipStreamSynchronize(st));
+            total += len;
+        }
+        *n_blocks = total_slices;
+        *bgzf_bytes = total;
+        if (kernel_ms) *kernel_ms = ms_sum;
+    } catch (...) { cleanup(); throw; }
+    cleanup();
+    *bgzf = c->df_res;
+    return 0;
+}

@@ -455,6 +455,11 @@ struct uz_ctx {
     DevBuf<uint32_t> bo_len;
     uint8_t *bo_pin[2] = {nullptr, nullptr}, *bo_small = nullptr, *bo_res = nullptr;
     size_t bo_pin_cap[2] = {0, 0}, bo_small_cap = 0, bo_res_cap = 0;
+    // uz_bgzf_deflate (k_deflate.hip): the two chunk images (page-locked, and their mirrors on the device), the streams' scratch slots, a chunk's
+    // offsets + flag word + counts + CRC-32s and the landing place of its total, its blocks on the device, the call's blocks (page-locked)
+    DevBuf<uint8_t> df_in[2], df_slots, df_small, df_out;
+    uint8_t *df_pin[2] = {nullptr, nullptr}, *df_small_pin = nullptr, *df_res = nullptr;
+    size_t df_pin_cap[2] = {0, 0}, df_small_pin_cap = 0, df_res_cap = 0;
 
     // last phase (k_reads.hip)
     bool phase_valid = false;
@@ -604,5 +609,7 @@ int uz_bed_rows_lists_impl(uz_ctx *c, const uz_bed_view *rows, int verbose, int 
 // the annotated VCF's record lines as text (k_vcfout.hip; vcf_row.hpp is the body)
 int uz_vcf_rows_impl(uz_ctx *c, const uz_vcf_text_view *text, const int64_t *line_at, const int64_t *ann_off, const int32_t *ann_col, const uint8_t *ann_gt,
                      const int32_t *ann_uops, const int8_t *ann_uet, int64_t *off, const uint8_t **bytes, uint8_t *handed_back);
+// BGZF blocks of a host buffer (k_deflate.hip; deflate_body.hpp is the body)
+int uz_bgzf_deflate_impl(uz_ctx *c, const uint8_t *data, int64_t n_bytes, int64_t *n_blocks, const uint8_t **bgzf, int64_t *bgzf_bytes, int repeat, double *kernel_ms);
 // a BCF's records as VCF text lines (k_bcfout.hip; bcf_row.hpp is the body)
 int uz_bcf_rows_impl(uz_ctx *c, const uz_bcf_lines_view *records, int64_t *off, uint64_t *samp_at, const uint8_t **bytes, uint8_t *handed_back);

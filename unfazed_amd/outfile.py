@@ -1,0 +1,84 @@
+"""The one place the driver writes its output file: write_output(outfile, parts), called from every writer of unfazed.py and summarize.py.
+
+UZ_OUT_BGZF decides what an outfile whose name ends in ".gz" holds:
+  not set, or any other value   plain text, whatever the file is called (as before)
+  "host"    BGZF: one block per 65 280 bytes (htslib's slice), zlib's raw DEFLATE at UZ_OUT_BGZF_LEVEL (6), the 28-byte end-of-file marker
+  "device"  the same blocks from backend.bgzf_deflate (uz_bgzf_deflate; csrc/deflate_body.hpp states its rules).  Asked for by name, the
+            route makes its backend and fails loudly without a device, as UZ_BCF_ROUTE=device does
+An outfile without ".gz", and /dev/stdout, stay plain on every setting.  The two routes' files differ in their compressed bytes (the
+compressors differ) and in nothing else: the inflated text, every ISIZE, every CRC-32 and the end-of-file marker are the same."""
+import os
+import struct
+import sys
+import zlib
+
+SLICE = 0xFF00  # bytes of text per BGZF block: htslib's BGZF_BLOCK_SIZE
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+OUT_STATS = {"bgzf_device_blocks": 0, "bgzf_host_blocks": 0, "bgzf_calls": 0}  # blocks the device / zlib wrote, files written as BGZF
+
+
+def out_route():
+    """UZ_OUT_BGZF: "device", "host", or None (not set, or any other value: every outfile is plain text)"""
+    v = os.environ.get("UZ_OUT_BGZF", "").lower()
+    return v if v in ("device", "host") else None
+
+
+def bgzf_block(stream: bytes, payload) -> bytes:
+    """one BGZF block around a raw DEFLATE stream of `payload`"""
+    size = 18 + len(stream) + 8
+    if size > 65536:
+        raise ValueError("a BGZF block of %d bytes" % size)
+    return (b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + struct.pack("<H", size - 1) + stream
+            + struct.pack("<II", zlib.crc32(payload) & 0xFFFFFFFF, len(payload)))
+
+
+def host_blocks(data, level=None):
+    """`data` as BGZF blocks by zlib, one per SLICE bytes, without the end-of-file marker -> (bytes, block count)"""
+    if level is None:
+        level = int(os.environ.get("UZ_OUT_BGZF_LEVEL", "6"))
+    view, out = memoryview(data), []
+    for at in range(0, len(view), SLICE):
+        piece = view[at:at + SLICE]
+        z = zlib.compressobj(level, zlib.DEFLATED, -15)
+        stream = z.compress(piece) + z.flush()
+        if len(stream) > 5 + len(piece):  # bytes that do not compress: one stored block, as the device writes it
+            stream = b"\x01" + struct.pack("<HH", len(piece), len(piece) ^ 0xFFFF) + bytes(piece)
+        out.append(bgzf_block(stream, piece))
+    return b"".join(out), len(out)
+
+
+def _as_bytes(parts):
+    return b"".join(p.encode() if isinstance(p, str) else bytes(p) for p in parts)
+
+
+def write_output(outfile, parts):
+    """parts: the output's pieces in order, str or bytes-like.  Plain: text through sys.stdout for /dev/stdout, the same bytes to a file
+    otherwise.  BGZF (see the module's head): the blocks, then the end-of-file marker."""
+    if outfile == "/dev/stdout":
+        for p in parts:
+            sys.stdout.write(p if isinstance(p, str) else bytes(p).decode())
+        return
+    route = out_route() if outfile.endswith(".gz") else None
+    if route is None:
+        if all(isinstance(p, str) for p in parts):
+            with open(outfile, "w") as fh:
+                for p in parts:
+                    fh.write(p)
+        else:
+            with open(outfile, "wb") as fh:
+                for p in parts:
+                    fh.write(p.encode() if isinstance(p, str) else p)
+        return
+    data = _as_bytes(parts)  # (with --gpus N > 1 only rank 0 gets here: unfazed.unfazed returns on the others before it writes)
+    if route == "device":
+        from . import session
+        backend = session.get_backend()  # asked for by name: the route makes its backend, and fails loudly without a device
+        blocks, n, _ = backend.bgzf_deflate(data)
+        OUT_STATS["bgzf_device_blocks"] += n
+    else:
+        blocks, n = host_blocks(data)
+        OUT_STATS["bgzf_host_blocks"] += n
+    OUT_STATS["bgzf_calls"] += 1
+    with open(outfile, "wb") as fh:
+        fh.write(blocks)
+        fh.write(BGZF_EOF)

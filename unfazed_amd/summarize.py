@@ -8,8 +8,9 @@ and the exact output text, for any backend.
 """
 from __future__ import annotations
 
-import sys
 from typing import Dict, List, Optional
+
+from .outfile import write_output
 
 BED_HEADER = [
     "#chrom", "start", "end", "vartype", "kid", "origin_parent", "other_parent", "evidence_count", "evidence_types",
@@ -217,19 +218,9 @@ class BedRows:
         """write_bed_output; extra_records (the SV records of the same call) are merged in first, as `records.update(sv_records)` merges them"""
         if extra_records:
             self.add_records(extra_records)
-        if outfile == "/dev/stdout":
-            sys.stdout.write(self.text())
-        else:
-            with open(outfile, "w") as fh:
-                fh.write(self.text())
+        write_output(outfile, [self.text()])
 
 
 def write_bed_output(records, include_ambiguous, verbose, outfile, evidence_min_ratio):
     lines = bed_lines(records, include_ambiguous, verbose, evidence_min_ratio)
-    if outfile == "/dev/stdout":
-        for ln in lines:
-            print(ln)
-    else:
-        with open(outfile, "w") as fh:
-            for ln in lines:
-                print(ln, file=fh)
+    write_output(outfile, [ln + "\n" for ln in lines])

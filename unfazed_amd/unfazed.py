@@ -15,6 +15,7 @@ from . import __reference_version__
 from .hostpath import SNV_TYPES, SV_TYPES
 from .io_vcf import read_vcf
 from .model import HET, HOM_ALT
+from .outfile import write_output
 from .snv_phaser import phase_snvs, phase_snvs_bed
 from .summarize import summarize_record, write_bed_output
 from .sv_phaser import phase_svs
@@ -214,12 +215,7 @@ def write_vcf_output(in_vcf_name, read_records, include_ambiguous, verbose, outf
     for r in records:
         out.append(_annotated_line(r, samples, read_records, include_ambiguous, verbose, evidence_min_ratio))
     VCF_STATS["vcf_host_rows"] += len(records)
-    text = "\n".join(out) + "\n"
-    if outfile == "/dev/stdout":
-        sys.stdout.write(text)
-    else:
-        with open(outfile, "w") as fh:
-            fh.write(text)
+    write_output(outfile, ["\n".join(out) + "\n"])
 
 
 def _annotated_header(header):
@@ -393,12 +389,7 @@ def _annotate_and_write(raw, header, samples, samp_at, line_end, line_at, sites,
     parts.append(body[at:int(off[n])])
     VCF_STATS["vcf_device_rows"] += n - len(by_host)
     VCF_STATS["vcf_host_rows"] += len(by_host)
-    if outfile == "/dev/stdout":
-        sys.stdout.write(b"".join(parts).decode())
-    else:
-        with open(outfile, "wb") as fh:
-            for p in parts:
-                fh.write(p)
+    write_output(outfile, parts)
     return True
 
 
@@ -483,12 +474,7 @@ def _write_vcf_from_bcf(in_vcf_name, read_records, include_ambiguous, verbose, o
     for r in records:
         out.append(_annotated_line(r, samples, read_records, include_ambiguous, verbose, evidence_min_ratio))
     VCF_STATS["vcf_host_rows"] += n
-    text = "\n".join(out) + "\n"
-    if outfile == "/dev/stdout":
-        sys.stdout.write(text)
-    else:
-        with open(outfile, "w") as fh:
-            fh.write(text)
+    write_output(outfile, ["\n".join(out) + "\n"])
 
 
 def _dnm_reader(path):
