@@ -215,7 +215,7 @@ def build_cases():
         lines = ["chr1\t%d\t%s\tA\tT\t50\tPASS\t%s\tGT:DP\t0/1:%d\t%s:%d\t./.:." % (10 * k + 1, "id%d" % k if k % 4 else ".", "DP=%d" % k if k % 3 else ".", k,
                                                                               "1|0" if k % 2 else "0/0", k + 1) for k in range(n)]
         return recs, lines
-    for n in (0, 1, 65, 257):
+    for n in (0, 1, 65, 257, 1025, 2049):  # (1025, 2049: past the first and the second tile of the length scan)
         add("records/%d" % n, *many(n), n_samples=3)
     recs, lines = many(9)
     t0 = len(PREFIX) & ~15

@@ -44,6 +44,34 @@ def test_fuzz(engine, monkeypatch):
         _holds(engine, case, monkeypatch, chunk=2048 if i % 3 == 0 else None)
 
 
+def test_the_blocks_grow_from_call_to_call(hip_lib, monkeypatch):
+    """a context's page-locked blocks start empty: a small call, one that outgrows every block (in chunks, so that the result block grows with text
+    in it), the small call again -- each the panel's literals, and what a context of its own returns"""
+    from unfazed_amd.engine import HipEngine
+    small, large, chunk = bcfrowcases.BY_NAME["records/65"], bcfrowcases.BY_NAME["records/2049"], 32768
+    assert len(bcfrowcases.layout(large)[0]) > 3 * chunk  # at least three chunks
+
+    def call(e, case):
+        text, off, samp_at, hb = e.bcf_rows(_view(case))
+        return bytes(text), off.tolist(), samp_at.tolist(), hb.tolist()
+
+    fresh = {}
+    for case in (small, large):
+        monkeypatch.setenv("UZ_BCFOUT_CHUNK_BYTES", str(chunk))
+        e = HipEngine(0)
+        try:
+            fresh[case["name"]] = call(e, case)
+        finally:
+            e.close()
+    e = HipEngine(0)
+    try:
+        for case in (small, large, small):
+            _holds(e, case, monkeypatch, chunk=chunk)
+            assert call(e, case) == fresh[case["name"]], case["name"]
+    finally:
+        e.close()
+
+
 def test_the_view_of_a_decoded_file(engine, tmp_path, monkeypatch):
     from unfazed_amd import io_native
     monkeypatch.delenv("UZ_BCFOUT_CHUNK_BYTES", raising=False)

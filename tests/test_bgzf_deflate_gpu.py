@@ -46,6 +46,19 @@ def test_the_slices_do_not_depend_on_the_chunk_size(engine, host_blocks, monkeyp
         assert engine.bgzf_deflate(payload)[0] == whole, chunk
 
 
+def test_a_chunk_of_more_than_1024_slices(engine, monkeypatch):
+    """1025 slices: three chunks of at most 514 at the default size (the reference, held by zlib), one chunk of 1025 -- the scan's second tile -- at 1 GiB"""
+    unit = panel.BY_NAME["text/vcf"]
+    payload = (unit * (1025 * panel.SLICE // len(unit) + 1))[:1025 * panel.SLICE]
+    monkeypatch.delenv("UZ_BGZF_CHUNK_BYTES", raising=False)
+    chunked, n_blocks, _ = engine.bgzf_deflate(payload)
+    assert n_blocks == 1025
+    panel.check_blocks(payload, chunked)
+    monkeypatch.setenv("UZ_BGZF_CHUNK_BYTES", str(1 << 30))
+    whole, n_blocks, _ = engine.bgzf_deflate(payload)
+    assert n_blocks == 1025 and whole == chunked
+
+
 def test_a_second_call_gives_the_same_bytes(engine):
     payload = panel.BY_NAME["text/vcf"]
     first = engine.bgzf_deflate(payload)[0]

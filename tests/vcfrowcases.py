@@ -136,6 +136,9 @@ def build_cases():
     for n in (0, 1, 65, 257):
         add("records/%d" % n, two, [line(100 + 10 * i, [GATE_FORMS[i % 13] + ":7", GATE_FORMS[(i + 5) % 13] + ":3"]) for i in range(n)],
             [rec("kid", 99 + 10 * i, nd=i % 4, nm=(i + 1) % 3) for i in range(0, n, 2)] + [rec("other", 99 + 10 * i) for i in range(0, n, 3)], amb=True)
+    # 1025 short lines in one chunk: the length scan's second tile
+    add("records/1025", three, [line(100 + 10 * i, ["0/0:1", GATE_FORMS[i % 13] + ":7", "0/1:3"]) for i in range(1025)],
+        [rec("kid", 99 + 10 * i, nd=i % 4, nm=(i + 1) % 3) for i in range(0, 1025, 5)], amb=True)
     # chunks
     wide = ["s%d" % i for i in range(20)]
     add("chunks/4096", wide, [line(100 + i, [GATE_FORMS[(i + j) % 13] + ":%d" % j for j in range(20)]) for i in range(250)],

@@ -260,6 +260,38 @@ void uz_kcopy(uz_ctx *c, void *dst, const void *src, size_t bytes) {
     UZ_HIP(hipGetLastError());
 }
 
+// ---------------------------------------------------------------- length scan (see uz_ctx.hpp)
+__global__ __launch_bounds__(1024) void k_scan_len(int64_t n, const uint32_t *__restrict__ len, uint32_t add, int64_t *__restrict__ off) {
+    __shared__ unsigned long long wave_sum[16];
+    __shared__ unsigned long long carry_s;
+    const uint32_t t = threadIdx.x, l = t & 63u, wv = t >> 6;
+    if (t == 0) carry_s = 0;
+    __syncthreads();
+    for (int64_t base = 0; base < n; base += 1024) {
+        const int64_t i = base + t;
+        const unsigned long long v = i < n ? (unsigned long long)len[i] + add : 0ull;
+        unsigned long long x = v;
+#pragma unroll
+        for (uint32_t d = 1; d < 64; d <<= 1) {
+            const unsigned long long y = (unsigned long long)__shfl_up((long long)x, d, 64);
+            if (l >= d) x += y;
+        }
+        if (l == 63) wave_sum[wv] = x;
+        __syncthreads();
+        unsigned long long before = carry_s;
+        for (uint32_t k = 0; k < wv; k++) before += wave_sum[k];
+        if (i < n) off[i] = (int64_t)(before + x - v);
+        __syncthreads();
+        if (t == 1023) carry_s = before + x;
+        __syncthreads();
+    }
+    if (t == 0) off[n] = (int64_t)carry_s;
+}
+void uz_len_scan(uz_ctx *c, hipStream_t st, int64_t n, const uint32_t *len, uint32_t add, int64_t *off) {
+    hipLaunchKernelGGL(k_scan_len, dim3(1), dim3(1024), 0, st, n, len, add, off);
+    UZ_HIP(hipGetLastError());
+}
+
 // ---------------------------------------------------------------- device block pool
 DevBlock uz_block_get(uz_ctx *c, size_t bytes) {
     int best = -1;
@@ -470,16 +502,9 @@ void uz_destroy(uz_ctx *c) {
     c->dn.block.release();
     if (c->dn_stage_done) (void)hipEventDestroy(c->dn_stage_done);
     if (c->dn_stage) (void)hipHostFree(c->dn_stage);
-    if (c->find_pin) (void)hipHostFree(c->find_pin);
-    if (c->nm_pin) (void)hipHostFree(c->nm_pin);
-    if (c->bed_pin) (void)hipHostFree(c->bed_pin);
+    c->find_pin.release(); c->nm_pin.release(); c->bed_pin.release();
     c->bed_in.release(); c->bed_hook.release(); c->bed_out.release(); c->bed_len.release(); c->bed_off.release();
-    for (uint8_t *p : {c->vo_pin[0], c->vo_pin[1], c->vo_small, c->vo_res}) if (p) (void)hipHostFree(p);
-    c->vo_in[0].release(); c->vo_in[1].release(); c->vo_out.release(); c->vo_off.release(); c->vo_len.release();
-    for (uint8_t *p : {c->bo_pin[0], c->bo_pin[1], c->bo_small, c->bo_res}) if (p) (void)hipHostFree(p);
-    c->bo_in[0].release(); c->bo_in[1].release(); c->bo_out.release(); c->bo_off.release(); c->bo_len.release();
-    for (uint8_t *p : {c->df_pin[0], c->df_pin[1], c->df_small_pin, c->df_res}) if (p) (void)hipHostFree(p);
-    c->df_in[0].release(); c->df_in[1].release(); c->df_slots.release(); c->df_small.release(); c->df_out.release();
+    c->vo.release(); c->bo.release(); c->df.release(); c->df_slots.release();
     c->nm_ids.release(); c->nm_len.release(); c->nm_off.release(); c->nm_out.release(); c->rf_first.release(); c->rf_mm.release();
     c->ab_lut.release(); c->win_range.release();
     c->dn_fam.release(); c->dn_cutoff.release(); c->fam_cls.release();
@@ -2710,39 +2735,30 @@ int uz_reads_names(uz_ctx *c, int reads_id, const uint32_t *ids, int64_t n, int6
         if (n == 0) return;
         for (int64_t k = 0; k < n; k++) UZ_REQUIRE(ids[k] < r.n_qnames, UZ_E_ARG, "uz_reads_names: a name id out of range");
         hipStream_t st = c->stream;
-        auto pin = [&](size_t bytes_needed) {
-            if (c->nm_pin_cap >= bytes_needed) return;
-            if (c->nm_pin) (void)hipHostFree(c->nm_pin);
-            c->nm_pin = nullptr; c->nm_pin_cap = 0;
-            const size_t want = bytes_needed + bytes_needed / 4 + 4096;
-            uint8_t *p = nullptr;
-            UZ_HIP(hipHostMalloc((void **)&p, want, hipHostMallocDefault));
-            c->nm_pin = p; c->nm_pin_cap = want;
-        };
         c->nm_ids.ensure((size_t)n + 16); c->nm_len.ensure((size_t)n + 16); c->nm_off.ensure((size_t)n + 16);
-        pin((size_t)n * 4 + 64);
-        memcpy(c->nm_pin, ids, (size_t)n * 4);
-        uz_kcopy(c, c->nm_ids.p, c->nm_pin, (size_t)n * 4);
+        c->nm_pin.room((size_t)n * 4 + 64);
+        memcpy(c->nm_pin.p, ids, (size_t)n * 4);
+        uz_kcopy(c, c->nm_ids.p, c->nm_pin.p, (size_t)n * 4);
         uz_launch_name_lens(c, st, n, c->nm_ids.p, r.name_rec, r.kept_list, r.n, r.names_bytes, c->nm_len.p);
         UZ_HIP(hipStreamSynchronize(st)); // (the ids have left the staging block)
-        uz_kcopy(c, c->nm_pin, c->nm_len.p, (size_t)n * 4);
+        uz_kcopy(c, c->nm_pin.p, c->nm_len.p, (size_t)n * 4);
         UZ_HIP(hipStreamSynchronize(st));
-        const uint32_t *len = reinterpret_cast<const uint32_t *>(c->nm_pin);
+        const uint32_t *len = reinterpret_cast<const uint32_t *>(c->nm_pin.p);
         for (int64_t k = 0; k < n; k++) off[k + 1] = off[k] + (int64_t)len[k];
         const int64_t total = off[n];
         UZ_REQUIRE(total < ((int64_t)1 << 32), UZ_E_RANGE, "uz_reads_names: more than 4 GiB of names");
-        if (total == 0) { *bytes = c->nm_pin; return; }
+        if (total == 0) { *bytes = c->nm_pin.p; return; }
         std::vector<uint32_t> o32((size_t)n);
         for (int64_t k = 0; k < n; k++) o32[(size_t)k] = (uint32_t)off[k];
-        pin(std::max((size_t)n * 4, (size_t)total) + 64);
-        memcpy(c->nm_pin, o32.data(), (size_t)n * 4);
+        c->nm_pin.room(std::max((size_t)n * 4, (size_t)total) + 64);
+        memcpy(c->nm_pin.p, o32.data(), (size_t)n * 4);
         c->nm_out.ensure((size_t)total + 64);
-        uz_kcopy(c, c->nm_off.p, c->nm_pin, (size_t)n * 4);
+        uz_kcopy(c, c->nm_off.p, c->nm_pin.p, (size_t)n * 4);
         uz_launch_name_gather(c, st, n, c->nm_ids.p, r.name_rec, r.kept_list, r.names, c->nm_len.p, c->nm_off.p, c->nm_out.p);
         UZ_HIP(hipStreamSynchronize(st)); // (the offsets have left the staging block before the names land in it)
-        uz_kcopy(c, c->nm_pin, c->nm_out.p, ((size_t)total + 3) & ~(size_t)3);
+        uz_kcopy(c, c->nm_pin.p, c->nm_out.p, ((size_t)total + 3) & ~(size_t)3);
         UZ_HIP(hipStreamSynchronize(st));
-        *bytes = c->nm_pin;
+        *bytes = c->nm_pin.p;
     });
 }
 

@@ -1,8 +1,8 @@
 // k_bed.hip -- BED rows as text on the device (unfazed_hip.h: uz_bed_rows, uz_bed_rows_lists).  bed_row.hpp is the body: the decision, the field
-// walk, the site order.  Here: the wavefront that runs it, the three launches and the host side of a call.
+// walk, the site order.  Here: the three launches and the host side of a call (the wavefront is RowWave, text_out.hpp).
 //
 //   k_bed_size   one wavefront per row: the row's byte length (0: dropped), the checks of what the walk assumes
-//   k_bed_scan   exclusive scan of the lengths -> off [n + 1] (one workgroup: a call has at most some ten thousand rows)
+//   uz_len_scan  exclusive scan of the lengths -> off [n + 1] (one workgroup: a call has at most some ten thousand rows)
 //   k_bed_fill   one wavefront per row: the bytes.  A field is written by the lanes together -- consecutive lanes, consecutive bytes -- a site
 //                list by one lane per element at the offset its rank gives; no atomics but the OR of a raised flag, no LDS
 #include <hip/hip_runtime.h>
@@ -11,31 +11,9 @@
 #include <vector>
 
 #include "bed_row.hpp"
-#include "uz_ctx.hpp"
+#include "text_out.hpp"
 
 namespace {
-
-struct BedWave { // the 64 lanes of a wavefront share a row
-    static constexpr uint32_t LANES = 64;
-    __device__ __forceinline__ uint32_t lane() const { return threadIdx.x & 63u; }
-    __device__ __forceinline__ uint32_t excl_scan(uint32_t v, uint32_t &total) const {
-        uint32_t x = v;
-        const uint32_t l = lane();
-#pragma unroll
-        for (uint32_t d = 1; d < 64; d <<= 1) {
-            const uint32_t y = (uint32_t)__shfl_up((int)x, d, 64);
-            if (l >= d) x += y;
-        }
-        total = (uint32_t)__shfl((int)x, 63, 64);
-        return x - v;
-    }
-    __device__ __forceinline__ uint32_t bcast(uint32_t v, uint32_t src) const { return (uint32_t)__shfl((int)v, (int)src, 64); }
-    __device__ __forceinline__ const uint8_t *bcast_ptr(const uint8_t *p, uint32_t src) const {
-        const uint64_t a = (uint64_t)(uintptr_t)p;
-        const uint32_t lo = bcast((uint32_t)a, src), hi = bcast((uint32_t)(a >> 32), src);
-        return (const uint8_t *)(uintptr_t)((uint64_t)hi << 32 | lo);
-    }
-};
 
 struct BedArgs {
     int64_t n_rows;
@@ -56,7 +34,7 @@ struct BedArgs {
 __global__ __launch_bounds__(64 * UZ_BED_WAVES) void k_bed_size(BedArgs a) {
     const int64_t r = (int64_t)blockIdx.x * UZ_BED_WAVES + (threadIdx.x >> 6);
     if (r >= a.n_rows) return; // (the whole wavefront)
-    BedWave w;
+    RowWave w;
     uint32_t flags = 0;
     const UzBedRowDev R = a.rows[r];
     const uint32_t n = uz_bed_row_walk<false>(w, R, a.L, a.tables, a.S, a.ratio, a.verbose, a.include_ambiguous, nullptr, 0u, flags);
@@ -69,51 +47,13 @@ __global__ __launch_bounds__(64 * UZ_BED_WAVES) void k_bed_fill(BedArgs a) {
     if (r >= a.n_rows) return;
     const int64_t o0 = a.off[r], o1 = a.off[r + 1];
     if (o1 <= o0) return; // a dropped row
-    BedWave w;
+    RowWave w;
     uint32_t flags = 0;
     const UzBedRowDev R = a.rows[r];
     const uint32_t limit = (uint32_t)(o1 - o0);
     const uint32_t n = uz_bed_row_walk<true>(w, R, a.L, a.tables, a.S, a.ratio, a.verbose, a.include_ambiguous, a.out + o0, limit, flags);
     if (n != limit) flags |= UZ_BED_F_SIZE;
     if (flags) atomicOr(a.flags, flags);
-}
-
-// off[k] = sum of len[0 .. k), off[n] the total: one workgroup of 1024 lanes, a tile of 1024 lengths per round
-__global__ __launch_bounds__(1024) void k_bed_scan(int64_t n, const uint32_t *__restrict__ len, int64_t *__restrict__ off) {
-    __shared__ unsigned long long wave_sum[16];
-    __shared__ unsigned long long carry_s;
-    const uint32_t t = threadIdx.x, l = t & 63u, wv = t >> 6;
-    if (t == 0) carry_s = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < n; base += 1024) {
-        const int64_t i = base + t;
-        const unsigned long long v = i < n ? (unsigned long long)len[i] : 0ull;
-        unsigned long long x = v;
-#pragma unroll
-        for (uint32_t d = 1; d < 64; d <<= 1) {
-            const unsigned long long y = (unsigned long long)__shfl_up((long long)x, d, 64);
-            if (l >= d) x += y;
-        }
-        if (l == 63) wave_sum[wv] = x;
-        __syncthreads();
-        unsigned long long before = carry_s;
-        for (uint32_t k = 0; k < wv; k++) before += wave_sum[k];
-        if (i < n) off[i] = (int64_t)(before + x - v);
-        __syncthreads();
-        if (t == 1023) carry_s = before + x;
-        __syncthreads();
-    }
-    if (t == 0) off[n] = (int64_t)carry_s;
-}
-
-void pin(uz_ctx *c, size_t bytes_needed) {
-    if (c->bed_pin_cap >= bytes_needed) return;
-    if (c->bed_pin) (void)hipHostFree(c->bed_pin);
-    c->bed_pin = nullptr; c->bed_pin_cap = 0;
-    const size_t want = bytes_needed + bytes_needed / 4 + 4096;
-    uint8_t *p = nullptr;
-    UZ_HIP(hipHostMalloc((void **)&p, want, hipHostMallocDefault));
-    c->bed_pin = p; c->bed_pin_cap = want;
 }
 
 size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
@@ -137,14 +77,14 @@ void bed_run(uz_ctx *c, const uz_bed_view *v, int verbose, int include_ambiguous
     const int64_t n = v->n_rows;
     off[0] = 0;
     *bytes = nullptr;
-    if (n == 0) { pin(c, 64); *bytes = c->bed_pin; return; }
+    if (n == 0) { c->bed_pin.room(64); *bytes = c->bed_pin.p; return; }
     const size_t ns = (size_t)v->n_strings, sb = ns ? (size_t)v->str_off[ns] : 0;
     // one image of the call's small inputs: rows, string offsets, string bytes, tables
     const size_t o_rows = 0, o_soff = up16(o_rows + (size_t)n * sizeof(UzBedRowDev)), o_sbytes = up16(o_soff + (ns + 1) * 4), o_tabs = up16(o_sbytes + sb + 1),
                  in_bytes = up16(o_tabs + std::max<size_t>(1, B.tables.size()) * sizeof(UzBedNames));
-    pin(c, in_bytes);
+    c->bed_pin.room(in_bytes);
     c->bed_in.ensure(in_bytes + 64);
-    UzBedRowDev *rows_h = reinterpret_cast<UzBedRowDev *>(c->bed_pin + o_rows);
+    UzBedRowDev *rows_h = reinterpret_cast<UzBedRowDev *>(c->bed_pin.p + o_rows);
     for (int64_t k = 0; k < n; k++) {
         const uz_bed_row &r = v->rows[k];
         UzBedRowDev &d = rows_h[k];
@@ -154,11 +94,11 @@ void bed_run(uz_ctx *c, const uz_bed_view *v, int verbose, int include_ambiguous
         d.qbase = B.row_qbase.empty() ? 0u : B.row_qbase[(size_t)k];
         d.sex_origin = r.sex_origin ? 1 : 0;
     }
-    memcpy(c->bed_pin + o_soff, v->str_off, (ns + 1) * 4);
-    if (sb) memcpy(c->bed_pin + o_sbytes, v->str_bytes, sb);
-    if (!B.tables.empty()) memcpy(c->bed_pin + o_tabs, B.tables.data(), B.tables.size() * sizeof(UzBedNames));
+    memcpy(c->bed_pin.p + o_soff, v->str_off, (ns + 1) * 4);
+    if (sb) memcpy(c->bed_pin.p + o_sbytes, v->str_bytes, sb);
+    if (!B.tables.empty()) memcpy(c->bed_pin.p + o_tabs, B.tables.data(), B.tables.size() * sizeof(UzBedNames));
     hipStream_t st = c->stream;
-    uz_kcopy(c, c->bed_in.p, c->bed_pin, in_bytes);
+    uz_kcopy(c, c->bed_in.p, c->bed_pin.p, in_bytes);
     c->bed_len.ensure((size_t)n + 16);
     c->bed_off.ensure((size_t)n + 2 + 16); // off [n + 1], then the flag word
     BedArgs a;
@@ -176,34 +116,33 @@ void bed_run(uz_ctx *c, const uz_bed_view *v, int verbose, int include_ambiguous
         ProfScope ps(c, UZ_K_BED_SIZE);
         hipLaunchKernelGGL(k_bed_size, dim3(grid), dim3(64 * UZ_BED_WAVES), 0, st, a);
         UZ_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(1024), 0, st, n, (const uint32_t *)c->bed_len.p, c->bed_off.p);
-        UZ_HIP(hipGetLastError());
+        uz_len_scan(c, st, n, c->bed_len.p, 0, c->bed_off.p);
     }
     UZ_HIP(hipStreamSynchronize(st)); // (the inputs have left the page-locked block)
     const size_t off_bytes = ((size_t)n + 2) * 8;
-    pin(c, off_bytes);
-    uz_kcopy(c, c->bed_pin, c->bed_off.p, off_bytes);
+    c->bed_pin.room(off_bytes);
+    uz_kcopy(c, c->bed_pin.p, c->bed_off.p, off_bytes);
     UZ_HIP(hipStreamSynchronize(st));
-    const int64_t *off_h = reinterpret_cast<const int64_t *>(c->bed_pin);
+    const int64_t *off_h = reinterpret_cast<const int64_t *>(c->bed_pin.p);
     raise_flags((uint32_t)off_h[n + 1]);
     const int64_t total = off_h[n];
     UZ_REQUIRE(total >= 0 && total < ((int64_t)1 << 32), UZ_E_RANGE, "BED rows: 4 GiB or more of text in one call");
     memcpy(off, off_h, ((size_t)n + 1) * 8);
-    if (total == 0) { *bytes = c->bed_pin; return; }
+    if (total == 0) { *bytes = c->bed_pin.p; return; }
     const size_t text = ((size_t)total + 15) & ~(size_t)15;
     c->bed_out.ensure(text + 64);
-    pin(c, text + 16);
+    c->bed_pin.room(text + 16);
     a.out = c->bed_out.p;
     {
         ProfScope ps(c, UZ_K_BED_FILL);
         hipLaunchKernelGGL(k_bed_fill, dim3(grid), dim3(64 * UZ_BED_WAVES), 0, st, a);
         UZ_HIP(hipGetLastError());
     }
-    uz_kcopy(c, c->bed_pin, c->bed_out.p, text);
-    uz_kcopy(c, c->bed_pin + text, a.flags, 8);
+    uz_kcopy(c, c->bed_pin.p, c->bed_out.p, text);
+    uz_kcopy(c, c->bed_pin.p + text, a.flags, 8);
     UZ_HIP(hipStreamSynchronize(st));
-    raise_flags(*reinterpret_cast<const uint32_t *>(c->bed_pin + text));
-    *bytes = c->bed_pin;
+    raise_flags(*reinterpret_cast<const uint32_t *>(c->bed_pin.p + text));
+    *bytes = c->bed_pin.p;
 }
 
 // what every call checks of its view: string ids, DNM indices
@@ -286,19 +225,19 @@ int uz_bed_rows_lists_impl(uz_ctx *c, const uz_bed_view *v, int verbose, int inc
     // the caller's lists and names -> the device, one image
     const size_t o_status = 0, o_off = up16(o_status + nd * 4 + 4), o_val = up16(o_off + (4 * nd + 1) * 8), o_noff = up16(o_val + (size_t)n_val * 4 + 4),
                  o_nbytes = up16(o_noff + ((size_t)n_qnames + 1) * 4), total = up16(o_nbytes + nb + 1);
-    pin(c, total);
+    c->bed_pin.room(total);
     c->bed_hook.ensure(total + 64);
-    memset(c->bed_pin, 0, total);
+    memset(c->bed_pin.p, 0, total);
     if (nd) {
-        memcpy(c->bed_pin + o_status, status, nd * 4);
-        memcpy(c->bed_pin + o_off, list_off, (4 * nd + 1) * 8);
-        if (n_val) memcpy(c->bed_pin + o_val, list_val, (size_t)n_val * 4);
+        memcpy(c->bed_pin.p + o_status, status, nd * 4);
+        memcpy(c->bed_pin.p + o_off, list_off, (4 * nd + 1) * 8);
+        if (n_val) memcpy(c->bed_pin.p + o_val, list_val, (size_t)n_val * 4);
     }
     if (names) {
-        memcpy(c->bed_pin + o_noff, name_off, ((size_t)n_qnames + 1) * 4);
-        if (nb) memcpy(c->bed_pin + o_nbytes, name_bytes, nb);
+        memcpy(c->bed_pin.p + o_noff, name_off, ((size_t)n_qnames + 1) * 4);
+        if (nb) memcpy(c->bed_pin.p + o_nbytes, name_bytes, nb);
     }
-    uz_kcopy(c, c->bed_hook.p, c->bed_pin, total);
+    uz_kcopy(c, c->bed_hook.p, c->bed_pin.p, total);
     UZ_HIP(hipStreamSynchronize(c->stream)); // (bed_run stages its own inputs in the same block)
     BedCall B;
     memset(&B.L, 0, sizeof(B.L));

@@ -5,7 +5,7 @@
 // slices: a slice's edges do not depend on the chunk size), chunk k + 1 copied on the copy stream while chunk k is worked on:
 //   k_bgzf_deflate    one wavefront per slice: its raw DEFLATE stream into a scratch slot of UZ_DF_SLOT bytes, and the stream's byte count
 //   k_bgzf_crc32_out  one wavefront per slice: the CRC-32 of its bytes (crc32_wave.hpp, the code k_bgzf_crc32 compares with)
-//   k_bgzf_sizes      exclusive scan of the blocks' sizes (18 + stream + 8) -> off [n + 1] (one workgroup)
+//   uz_len_scan       exclusive scan of the blocks' sizes (18 + stream + 8) -> off [n + 1] (one workgroup)
 //   k_bgzf_frame      one workgroup per block: header, stream, CRC-32 and ISIZE, back to back at off; a block whose written bytes differ from its
 //                     scanned size raises the flag
 // No global atomics decide a byte: the only one is the OR of the raised flag.
@@ -15,7 +15,7 @@
 
 #include "crc32_wave.hpp"
 #include "deflate_body.hpp"
-#include "uz_ctx.hpp"
+#include "text_out.hpp"
 
 #define UZ_DF_F_SIZE 1u /* a framed block's written bytes differ from its scanned size */
 
@@ -82,34 +82,6 @@ __global__ __launch_bounds__(64) void k_bgzf_crc32_out(int32_t n_slices, const u
     }
 }
 
-// off[k] = sum over the blocks before k of 18 + count + 8, off[n] the total: one workgroup of 1024 lanes, a tile of 1024 blocks per round
-__global__ __launch_bounds__(1024) void k_bgzf_sizes(int32_t n, const uint32_t *__restrict__ count, int64_t *__restrict__ off) {
-    __shared__ unsigned long long wave_sum[16];
-    __shared__ unsigned long long carry_s;
-    const uint32_t t = threadIdx.x, l = t & 63u, wv = t >> 6;
-    if (t == 0) carry_s = 0;
-    __syncthreads();
-    for (int32_t base = 0; base < n; base += 1024) {
-        const int32_t i = base + (int32_t)t;
-        const unsigned long long v = i < n ? (unsigned long long)count[i] + UZ_BGZF_HEAD + UZ_BGZF_TAIL : 0ull;
-        unsigned long long x = v;
-#pragma unroll
-        for (uint32_t d = 1; d < 64; d <<= 1) {
-            const unsigned long long y = (unsigned long long)__shfl_up((long long)x, d, 64);
-            if (l >= d) x += y;
-        }
-        if (l == 63) wave_sum[wv] = x;
-        __syncthreads();
-        unsigned long long before = carry_s;
-        for (uint32_t k = 0; k < wv; k++) before += wave_sum[k];
-        if (i < n) off[i] = (int64_t)(before + x - v);
-        __syncthreads();
-        if (t == 1023) carry_s = before + x;
-        __syncthreads();
-    }
-    if (t == 0) off[n] = (int64_t)carry_s;
-}
-
 #define UZ_DF_FRAME_LANES 256
 __global__ __launch_bounds__(UZ_DF_FRAME_LANES) void k_bgzf_frame(int32_t n_slices, int64_t in_bytes, const uint8_t *__restrict__ slots, const uint32_t *__restrict__ count,
                                                                    const uint32_t *__restrict__ crc, const int64_t *__restrict__ off, int64_t out_cap,
@@ -150,17 +122,13 @@ __global__ __launch_bounds__(UZ_DF_FRAME_LANES) void k_bgzf_frame(int32_t n_slic
     if (rest + t < cnt && t < 4) dst[rest + t] = src[rest + t];
 }
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-void pin_room(uint8_t *&p, size_t &cap, size_t need, size_t keep) { // a page-locked block grown to `need`, its first `keep` bytes carried over
-    if (cap >= need) return;
-    const size_t want = need + need / 4 + 4096;
-    uint8_t *q = nullptr;
-    UZ_HIP(hipHostMalloc((void **)&q, want, hipHostMallocDefault));
-    if (keep) memcpy(q, p, keep);
-    if (p) (void)hipHostFree(p);
-    p = q; cap = want;
-}
+struct Timer { // the two events of the measured form
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~Timer() {
+        for (hipEvent_t e : {e0, e1})
+            if (e) (void)hipEventDestroy(e);
+    }
+};
 
 } // namespace
 
@@ -179,93 +147,74 @@ int uz_bgzf_deflate_impl(uz_ctx *c, const uint8_t *data, int64_t n_bytes, int64_
     chunk_bytes = std::max<size_t>(UZ_DF_SLICE, chunk_bytes / UZ_DF_SLICE * UZ_DF_SLICE); // whole slices
     const size_t n_chunks = ((size_t)n_bytes + chunk_bytes - 1) / chunk_bytes;
     const int64_t total_slices = (n_bytes + UZ_DF_SLICE - 1) / UZ_DF_SLICE;
-    hipEvent_t copied[2] = {nullptr, nullptr}, e0 = nullptr, e1 = nullptr;
-    auto cleanup = [&] {
-        (void)hipStreamSynchronize(c->copy_stream);
-        (void)hipStreamSynchronize(c->stream);
-        for (hipEvent_t e : {copied[0], copied[1], e0, e1})
-            if (e) (void)hipEventDestroy(e);
-    };
+    Timer T; // (goes behind the loop, which drains the streams)
+    ChunkLoop L(c, c->df, n_chunks);
     auto bytes_of = [&](size_t q) { return std::min<size_t>(chunk_bytes, (size_t)n_bytes - q * chunk_bytes); };
     auto stage = [&](size_t q) { // a chunk into its page-locked image, and the image onto the copy stream
-        const int b = (int)(q & 1);
         const size_t nb = bytes_of(q);
-        pin_room(c->df_pin[b], c->df_pin_cap[b], nb, 0);
-        c->df_in[b].ensure(nb + 64);
-        memcpy(c->df_pin[b], data + q * chunk_bytes, nb);
-        UZ_HIP(hipMemcpyAsync(c->df_in[b].p, c->df_pin[b], nb, hipMemcpyHostToDevice, c->copy_stream));
-        UZ_HIP(hipEventRecord(copied[b], c->copy_stream));
+        memcpy(L.image(q, nb), data + q * chunk_bytes, nb);
+        L.send(q, nb);
     };
-    try {
-        for (int b = 0; b < 2 && b < (int)n_chunks; b++) UZ_HIP(hipEventCreateWithFlags(&copied[b], hipEventDisableTiming));
-        if (repeat > 0) { UZ_HIP(hipEventCreate(&e0)); UZ_HIP(hipEventCreate(&e1)); }
-        hipStream_t st = c->stream;
-        int64_t total = 0;
-        double ms_sum = 0;
-        stage(0);
-        for (size_t q = 0; q < n_chunks; q++) {
-            const int b = (int)(q & 1);
-            const size_t nb = bytes_of(q);
-            const int32_t ns = (int32_t)((nb + UZ_DF_SLICE - 1) / UZ_DF_SLICE);
-            // a chunk's small results in one block: off [ns + 1], the flag word (+ padding), count [ns], crc [ns]
-            const size_t o_flag = ((size_t)ns + 1) * 8, o_count = o_flag + 8, o_crc = o_count + (size_t)ns * 4, small_bytes = up256(o_crc + (size_t)ns * 4);
-            const size_t out_cap = nb + (size_t)ns * (UZ_BGZF_HEAD + UZ_BGZF_TAIL + 5); // every slice stored
-            c->df_slots.ensure((size_t)ns * UZ_DF_SLOT + 64);
-            c->df_small.ensure(small_bytes + 64);
-            c->df_out.ensure(up256(out_cap) + 64);
-            pin_room(c->df_small_pin, c->df_small_pin_cap, 64, 0);
-            int64_t *d_off = reinterpret_cast<int64_t *>(c->df_small.p);
-            uint32_t *d_flag = reinterpret_cast<uint32_t *>(c->df_small.p + o_flag);
-            uint32_t *d_count = reinterpret_cast<uint32_t *>(c->df_small.p + o_count);
-            uint32_t *d_crc = reinterpret_cast<uint32_t *>(c->df_small.p + o_crc);
-            const uint8_t *d_in = c->df_in[b].p;
-            UZ_HIP(hipStreamWaitEvent(st, copied[b], 0));
-            UZ_HIP(hipMemsetAsync(d_flag, 0, 8, st));
-            {
-                ProfScope ps(c, UZ_K_DEFLATE);
-                hipLaunchKernelGGL(k_bgzf_deflate, dim3((unsigned)ns), dim3(64), 0, st, ns, d_in, (int64_t)nb, c->df_slots.p, d_count);
-                UZ_HIP(hipGetLastError());
-                hipLaunchKernelGGL(k_bgzf_crc32_out, dim3((unsigned)std::min<int32_t>(ns, 256 * 16)), dim3(64), 0, st, ns, d_in, (int64_t)nb, d_crc);
-                UZ_HIP(hipGetLastError());
-                hipLaunchKernelGGL(k_bgzf_sizes, dim3(1), dim3(1024), 0, st, ns, (const uint32_t *)d_count, d_off);
-                UZ_HIP(hipGetLastError());
-            }
-            {
-                ProfScope ps(c, UZ_K_DEFLATE_FRAME);
-                hipLaunchKernelGGL(k_bgzf_frame, dim3((unsigned)ns), dim3(UZ_DF_FRAME_LANES), 0, st, ns, (int64_t)nb, (const uint8_t *)c->df_slots.p, (const uint32_t *)d_count,
-                                   (const uint32_t *)d_crc, (const int64_t *)d_off, (int64_t)out_cap, c->df_out.p, d_flag);
-                UZ_HIP(hipGetLastError());
-            }
-            uz_kcopy(c, c->df_small_pin, d_off + ns, 16); // the chunk's bytes, the flag word
-            if (repeat > 0) { // the measured form: the same launch again, which writes the same bytes into the same slots
-                UZ_HIP(hipEventRecord(e0, st));
-                for (int r = 0; r < repeat; r++) hipLaunchKernelGGL(k_bgzf_deflate, dim3((unsigned)ns), dim3(64), 0, st, ns, d_in, (int64_t)nb, c->df_slots.p, d_count);
-                UZ_HIP(hipGetLastError());
-                UZ_HIP(hipEventRecord(e1, st));
-            }
-            if (q + 1 < n_chunks) stage(q + 1); // (its image and its block were chunk q - 1's, which is done)
-            UZ_HIP(hipStreamSynchronize(st));
-            if (repeat > 0) {
-                float ms = 0;
-                UZ_HIP(hipEventElapsedTime(&ms, e0, e1));
-                ms_sum += (double)ms / repeat;
-            }
-            const int64_t len = *reinterpret_cast<const int64_t *>(c->df_small_pin);
-            const uint32_t flag = *reinterpret_cast<const uint32_t *>(c->df_small_pin + 8);
-            UZ_REQUIRE(!(flag & UZ_DF_F_SIZE) && len >= (int64_t)ns * (UZ_BGZF_HEAD + UZ_BGZF_TAIL) && len <= (int64_t)out_cap, UZ_E_STATE,
-                       "BGZF deflate: a framed block's written bytes differ from its scanned size");
-            // (the first chunk sizes the block for the whole call at its own rate, so that it is allocated once)
-            const size_t guess = q == 0 ? (size_t)((double)len * 1.05 * (double)n_bytes / (double)nb) + 65536 : 0;
-            pin_room(c->df_res, c->df_res_cap, std::max((size_t)(total + len) + 16, guess), (size_t)total);
-            UZ_HIP(hipMemcpyAsync(c->df_res + total, c->df_out.p, (size_t)len, hipMemcpyDeviceToHost, st));
-            UZ_HIP(hipStreamSynchronize(st));
-            total += len;
+    if (repeat > 0) { UZ_HIP(hipEventCreate(&T.e0)); UZ_HIP(hipEventCreate(&T.e1)); }
+    hipStream_t st = c->stream;
+    double ms_sum = 0;
+    stage(0);
+    for (size_t q = 0; q < n_chunks; q++) {
+        const size_t nb = bytes_of(q);
+        const int32_t ns = (int32_t)((nb + UZ_DF_SLICE - 1) / UZ_DF_SLICE);
+        // a chunk's small results in one block: off [ns + 1], the flag word (+ padding), count [ns], crc [ns]
+        const size_t o_flag = ((size_t)ns + 1) * 8, o_count = o_flag + 8, o_crc = o_count + (size_t)ns * 4, small_bytes = up256(o_crc + (size_t)ns * 4);
+        const size_t out_cap = nb + (size_t)ns * (UZ_BGZF_HEAD + UZ_BGZF_TAIL + 5); // every slice stored
+        c->df_slots.ensure((size_t)ns * UZ_DF_SLOT + 64);
+        c->df.small.ensure(small_bytes + 64);
+        c->df.out.ensure(up256(out_cap) + 64);
+        c->df.small_pin.room(64);
+        int64_t *d_off = reinterpret_cast<int64_t *>(c->df.small.p);
+        uint32_t *d_flag = reinterpret_cast<uint32_t *>(c->df.small.p + o_flag);
+        uint32_t *d_count = reinterpret_cast<uint32_t *>(c->df.small.p + o_count);
+        uint32_t *d_crc = reinterpret_cast<uint32_t *>(c->df.small.p + o_crc);
+        const uint8_t *d_in = c->df.in[q & 1].p;
+        L.wait(q);
+        UZ_HIP(hipMemsetAsync(d_flag, 0, 8, st));
+        {
+            ProfScope ps(c, UZ_K_DEFLATE);
+            hipLaunchKernelGGL(k_bgzf_deflate, dim3((unsigned)ns), dim3(64), 0, st, ns, d_in, (int64_t)nb, c->df_slots.p, d_count);
+            UZ_HIP(hipGetLastError());
+            hipLaunchKernelGGL(k_bgzf_crc32_out, dim3((unsigned)std::min<int32_t>(ns, 256 * 16)), dim3(64), 0, st, ns, d_in, (int64_t)nb, d_crc);
+            UZ_HIP(hipGetLastError());
+            uz_len_scan(c, st, ns, d_count, UZ_BGZF_HEAD + UZ_BGZF_TAIL, d_off);
         }
-        *n_blocks = total_slices;
-        *bgzf_bytes = total;
-        if (kernel_ms) *kernel_ms = ms_sum;
-    } catch (...) { cleanup(); throw; }
-    cleanup();
-    *bgzf = c->df_res;
+        {
+            ProfScope ps(c, UZ_K_DEFLATE_FRAME);
+            hipLaunchKernelGGL(k_bgzf_frame, dim3((unsigned)ns), dim3(UZ_DF_FRAME_LANES), 0, st, ns, (int64_t)nb, (const uint8_t *)c->df_slots.p, (const uint32_t *)d_count,
+                               (const uint32_t *)d_crc, (const int64_t *)d_off, (int64_t)out_cap, c->df.out.p, d_flag);
+            UZ_HIP(hipGetLastError());
+        }
+        uz_kcopy(c, c->df.small_pin.p, d_off + ns, 16); // the chunk's bytes, the flag word
+        if (repeat > 0) { // the measured form: the same launch again, which writes the same bytes into the same slots
+            UZ_HIP(hipEventRecord(T.e0, st));
+            for (int r = 0; r < repeat; r++) hipLaunchKernelGGL(k_bgzf_deflate, dim3((unsigned)ns), dim3(64), 0, st, ns, d_in, (int64_t)nb, c->df_slots.p, d_count);
+            UZ_HIP(hipGetLastError());
+            UZ_HIP(hipEventRecord(T.e1, st));
+        }
+        L.turn(q, stage);
+        if (repeat > 0) {
+            float ms = 0;
+            UZ_HIP(hipEventElapsedTime(&ms, T.e0, T.e1));
+            ms_sum += (double)ms / repeat;
+        }
+        const int64_t len = *reinterpret_cast<const int64_t *>(c->df.small_pin.p);
+        const uint32_t flag = *reinterpret_cast<const uint32_t *>(c->df.small_pin.p + 8);
+        UZ_REQUIRE(!(flag & UZ_DF_F_SIZE) && len >= (int64_t)ns * (UZ_BGZF_HEAD + UZ_BGZF_TAIL) && len <= (int64_t)out_cap, UZ_E_STATE,
+                   "BGZF deflate: a framed block's written bytes differ from its scanned size");
+        L.result_room(q, (size_t)len, 1.05, (double)n_bytes, (double)nb, 65536);
+        L.fetch(c->df.out.p, (size_t)len);
+        UZ_HIP(hipStreamSynchronize(st));
+        L.total += len;
+    }
+    *n_blocks = total_slices;
+    *bgzf_bytes = L.total;
+    if (kernel_ms) *kernel_ms = ms_sum;
+    *bgzf = c->df.res.p;
     return 0;
 }

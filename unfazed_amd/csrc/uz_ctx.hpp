@@ -66,6 +66,41 @@ struct DevBuf {
     }
 };
 
+// grow-only page-locked block
+struct PinBuf {
+    uint8_t *p = nullptr;
+    size_t cap = 0;
+    void room(size_t need, size_t keep = 0) { // grown to `need`, its first `keep` bytes carried over
+        if (cap >= need) return;
+        const size_t want = need + need / 4 + 4096;
+        uint8_t *q = nullptr;
+        UZ_HIP(hipHostMalloc((void **)&q, want, hipHostMallocDefault));
+        if (keep) memcpy(q, p, keep);
+        if (p) (void)hipHostFree(p);
+        p = q;
+        cap = want;
+    }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// The buffers of a call that writes a file's bytes chunk by chunk (text_out.hpp: ChunkLoop), kept from call to call: the two chunk images
+// (page-locked, and their mirrors on the device), a chunk's lengths, its small results (offsets + flag word + what the call adds) and their page-
+// locked landing place, a chunk's bytes on the device, the call's bytes (page-locked)
+struct OutBufs {
+    PinBuf pin[2], small_pin, res;
+    DevBuf<uint8_t> in[2], small, out;
+    DevBuf<uint32_t> len;
+    void release() {
+        for (int b = 0; b < 2; b++) { pin[b].release(); in[b].release(); }
+        small_pin.release(); res.release(); small.release(); out.release(); len.release();
+    }
+};
+
 // what a set of window lists was computed for
 struct FindKey {
     bool valid = false;
@@ -340,8 +375,7 @@ struct uz_ctx {
     int find_fam = -1, find_mode = 0;
     DnmsDev dn;
     uint8_t *dn_stage = nullptr; // pinned staging of a DNM batch
-    uint8_t *find_pin = nullptr; // pinned landing place of a find's offsets (copied there by a kernel: see uz_kcopy)
-    size_t find_pin_cap = 0;
+    PinBuf find_pin; // landing place of a find's offsets (copied there by a kernel: see uz_kcopy)
     size_t dn_stage_cap = 0;
     hipEvent_t dn_stage_done = nullptr; // behind the copies out of dn_stage: a batch queued by uz_phase_begin may still be reading it
     DevBuf<int64_t> scan_part;   // tile sums of the find's two count arrays (k_scan2_sums -> k_scan2)
@@ -434,32 +468,18 @@ struct uz_ctx {
     DevBuf<int64_t> rf_first; // uz_reads_files: the files' first records, and ...
     DevBuf<uint32_t> rf_mm;   // ... their smallest and largest name ids
     DevBuf<uint8_t> nm_out;
-    uint8_t *nm_pin = nullptr;
-    size_t nm_pin_cap = 0;
+    PinBuf nm_pin;
 
     // uz_bed_rows (k_bed.hip): the call's rows, strings and tables on the device (bed_in; the caller's lists of uz_bed_rows_lists behind them in
     // bed_hook), the rows' lengths, their offsets + the flag word, the text; one page-locked block, all kept from call to call
     DevBuf<uint8_t> bed_in, bed_hook, bed_out;
     DevBuf<uint32_t> bed_len;
     DevBuf<int64_t> bed_off;
-    uint8_t *bed_pin = nullptr;
-    size_t bed_pin_cap = 0;
-    // uz_vcf_rows (k_vcfout.hip): the two chunk images (page-locked, and their mirrors on the device), a chunk's lengths, its offsets + flag word +
-    // handed-back bytes and their page-locked landing place, a chunk's text on the device, the call's text (page-locked); kept from call to call
-    DevBuf<uint8_t> vo_in[2], vo_out, vo_off;
-    DevBuf<uint32_t> vo_len;
-    uint8_t *vo_pin[2] = {nullptr, nullptr}, *vo_small = nullptr, *vo_res = nullptr;
-    size_t vo_pin_cap[2] = {0, 0}, vo_small_cap = 0, vo_res_cap = 0;
-    // uz_bcf_rows (k_bcfout.hip): the same set of its own -- the text it returns is the input of the uz_vcf_rows call behind it
-    DevBuf<uint8_t> bo_in[2], bo_out, bo_off;
-    DevBuf<uint32_t> bo_len;
-    uint8_t *bo_pin[2] = {nullptr, nullptr}, *bo_small = nullptr, *bo_res = nullptr;
-    size_t bo_pin_cap[2] = {0, 0}, bo_small_cap = 0, bo_res_cap = 0;
-    // uz_bgzf_deflate (k_deflate.hip): the two chunk images (page-locked, and their mirrors on the device), the streams' scratch slots, a chunk's
-    // offsets + flag word + counts + CRC-32s and the landing place of its total, its blocks on the device, the call's blocks (page-locked)
-    DevBuf<uint8_t> df_in[2], df_slots, df_small, df_out;
-    uint8_t *df_pin[2] = {nullptr, nullptr}, *df_small_pin = nullptr, *df_res = nullptr;
-    size_t df_pin_cap[2] = {0, 0}, df_small_pin_cap = 0, df_res_cap = 0;
+    PinBuf bed_pin;
+    // uz_vcf_rows (k_vcfout.hip), uz_bcf_rows (k_bcfout.hip) -- a set of its own: the text it returns is the input of the uz_vcf_rows call behind
+    // it -- and uz_bgzf_deflate (k_deflate.hip: counts and CRC-32s among the small results, no lengths; df_slots: the streams' scratch slots)
+    OutBufs vo, bo, df;
+    DevBuf<uint8_t> df_slots;
 
     // last phase (k_reads.hip)
     bool phase_valid = false;
@@ -507,6 +527,9 @@ void uz_block_put(uz_ctx *c, DevBlock b);
 // the kernels of the current table back until every later table has landed (measured: copies and kernels did not
 // overlap at all).  dst / src: device memory or pinned host memory.
 void uz_kcopy(uz_ctx *c, void *dst, const void *src, size_t bytes);
+// off[k] = sum of len[i] + add over i < k, off[n] the total, on stream `st`: one workgroup, a tile of 1024 lengths per round (a call's rows, a
+// chunk's records or blocks: some ten thousand at most)
+void uz_len_scan(uz_ctx *c, hipStream_t st, int64_t n, const uint32_t *len, uint32_t add, int64_t *off);
 // waits for an asynchronous upload and builds its headers, on the compute stream (no-op for a table that is ready)
 void uz_reads_make_ready(uz_ctx *c, ReadsDev &r);
 // uz_reads_make_ready, and the table's quality plane brought to the threshold of the parameters.  The plane holds ONE threshold: a table that
