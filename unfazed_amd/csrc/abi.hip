@@ -38,17 +38,6 @@ int guarded(uz_ctx *c, F &&fn) {
     }
 }
 
-template <typename T>
-T *upload(uz_ctx *c, const T *host, size_t n) {
-    T *d = nullptr;
-    UZ_HIP(hipMalloc((void **)&d, (n ? n : 1) * sizeof(T) + 64)); // +64: vector tail reads stay in-bounds
-    if (n) {
-        UZ_REQUIRE(host != nullptr, UZ_E_ARG, "null column pointer");
-        UZ_HIP(hipMemcpyAsync(d, host, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
-    }
-    return d;
-}
-
 // One copy instead of one per column: when the host columns of a table sit back to back in one slab of (pinned) memory --
 // a decoder that carves its output from one allocation -- the slab goes over the link as a whole into a mirror block and
 // the columns' device addresses follow from their offsets in it.  Every separate copy costs the link ~8 us of set-up, and
@@ -114,23 +103,6 @@ static void slab_commit(uz_ctx *c, hipStream_t st, SlabPlan &plan, DevBlock &mir
         plan.mode = 2;
     } else
         g_slab = nullptr;
-}
-
-template <typename T>
-void stage(uz_ctx *c, DevBuf<T> &b, const T *host, size_t n) {
-    b.ensure(n + 1);
-    if (n) {
-        UZ_REQUIRE(host != nullptr, UZ_E_ARG, "null DNM column pointer");
-        UZ_HIP(hipMemcpyAsync(b.p, host, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
-    }
-}
-
-template <typename V>
-int new_slot(std::vector<V> &v) {
-    for (size_t i = 0; i < v.size(); i++)
-        if (!v[i].live) return (int)i;
-    v.emplace_back();
-    return (int)v.size() - 1;
 }
 
 SitesDev &sites_of(uz_ctx *c, int id) {
@@ -1524,11 +1496,9 @@ void check_walk_plan(const WalkPlan &p) {
     UZ_REQUIRE(p.n_blocks >= 0 && p.comp_bytes >= 0 && p.n_tasks >= 0 && p.n_spans >= 0 && p.n_reach >= 0 && p.n_fetch >= 0, UZ_E_ARG, "bad arguments");
     UZ_REQUIRE(p.n_blocks == 0 || (p.comp && p.in_off && p.out_off && p.blk_coff), UZ_E_ARG, "null block table");
     UZ_REQUIRE(p.n_tasks == 0 || (p.task && p.span && p.reach && p.fetch), UZ_E_ARG, "null walk plan");
-    const int64_t *in_off = p.in_off, *out_off = p.out_off;
-    for (int64_t k = 0; k < p.n_blocks; k++)
-        UZ_REQUIRE(in_off[k] >= 0 && in_off[k] < p.comp_bytes && (k == 0 || in_off[k] > in_off[k - 1]) && out_off[k] >= 0 && out_off[k] <= out_off[k + 1] &&
-                       out_off[k + 1] - out_off[k] <= 65536,
-                   UZ_E_ARG, "bad block table (blocks in the order they lie in `comp`; a BGZF block inflates to at most 64 KiB)");
+    const int64_t *out_off = p.out_off;
+    UZ_REQUIRE(!uz_bgzf_check_tables(p.n_blocks, p.comp_bytes, p.in_off, out_off, true), UZ_E_ARG,
+               "bad block table (blocks in the order they lie in `comp`; a BGZF block inflates to at most 64 KiB)");
     // the plan is the kernel's only guard: every index it names must lie inside the arrays it names
     for (int32_t t = 0; t < p.n_tasks; t++) {
         const int32_t *tc = p.task + UZ_WALK_TASK_COLS * (size_t)t;
@@ -1558,38 +1528,19 @@ std::vector<int64_t> desc_slices(const WalkPlan &p) {
     return first;
 }
 
-// the blocks go up and are inflated in slices of ~8 k: the first block of every slice (+ the end)
-std::vector<int64_t> block_slices(int64_t n_blocks) {
-    std::vector<int64_t> cut{0};
-    for (int64_t b = 1; b <= n_blocks; b++)
-        if (b == n_blocks || (b - cut.back() >= 8192 && n_blocks - b >= 4096)) cut.push_back(b);
-    return cut;
-}
-
-// ... on two streams, as uz_bgzf_inflate_to_host sends them: slice i + 1 goes up while slice i is inflated; then every block against the CRC-32 of
-// its footer.  w.iflags: two words per slice, then the CRC's
+// The batch's blocks up and inflated in slices on the slot's two streams (uz_queue_inflate), which the first then waits for: the walk reads what
+// both inflated; then every block against the CRC-32 of its footer.  w.iflags: two words per slice, then the CRC's
 void queue_blocks(uz_ctx *c, uz_ctx::WalkSlot &w, const WalkPlan &p, const std::vector<int64_t> &cut) {
-    const int64_t n_blocks = p.n_blocks, comp_bytes = p.comp_bytes, out_bytes = p.out_bytes();
+    const int64_t n_blocks = p.n_blocks;
     const size_t ns = cut.size() - 1;
     hipStream_t st = w.s0;
     UZ_WGROW(w, iflags, 2 * ns + 8); UZ_WGROW(w, blk_crc, (size_t)n_blocks + 1);
     if (n_blocks == 0) return;
-    hipStream_t s2[2] = {w.s0, w.s1};
-    UZ_HIP(hipMemsetAsync(w.comp.p + comp_bytes, 0, 1024, st));
-    UZ_HIP(hipMemsetAsync(w.out.p + out_bytes, 0, uz_bam_walk_pad(), st));
-    UZ_HIP(hipMemcpyAsync(w.in_off.p, p.in_off, (size_t)n_blocks * 8, hipMemcpyHostToDevice, st));
-    UZ_HIP(hipMemcpyAsync(w.out_off.p, p.out_off, (size_t)(n_blocks + 1) * 8, hipMemcpyHostToDevice, st));
+    UZ_HIP(hipMemsetAsync(w.out.p + p.out_bytes(), 0, uz_bam_walk_pad(), st));
     UZ_HIP(hipMemcpyAsync(w.blk_coff.p, p.blk_coff, (size_t)n_blocks * 8, hipMemcpyHostToDevice, st));
-    UZ_HIP(hipEventRecord(w.ev, st));
-    UZ_HIP(hipStreamWaitEvent(s2[1], w.ev, 0));
-    for (size_t i = 0; i < ns; i++) {
-        const int64_t b0 = cut[i], b1 = cut[i + 1];
-        const int64_t c0 = i == 0 ? 0 : std::max<int64_t>(p.in_off[b0] - 18, 0), c1 = i + 1 == ns ? comp_bytes : std::max<int64_t>(p.in_off[b1] - 18, c0);
-        UZ_HIP(hipMemcpyAsync(w.comp.p + c0, p.comp + c0, (size_t)(c1 - c0), hipMemcpyHostToDevice, s2[i & 1]));
-        uz_launch_inflate(c, s2[i & 1], b1 - b0, w.comp.p, (comp_bytes + 1024) & ~(int64_t)3, w.in_off.p + b0, w.out_off.p + b0, w.out.p, w.iflags.p + 2 * i);
-    }
-    if (ns > 1) { // the walk (first stream) reads what both streams inflated
-        UZ_HIP(hipEventRecord(w.ev, s2[1]));
+    uz_queue_inflate(c, InflateBatch{p.comp, p.comp_bytes, n_blocks, p.in_off, p.out_off, w.comp.p, w.in_off.p, w.out_off.p, w.out.p, w.iflags.p, {w.s0, w.s1}, w.ev}, cut);
+    if (ns > 1) {
+        UZ_HIP(hipEventRecord(w.ev, w.s1));
         UZ_HIP(hipStreamWaitEvent(st, w.ev, 0));
     }
     if (p.blk_crc) { // as htslib's reader (and the host's walk) holds it
@@ -1630,10 +1581,8 @@ void queue_walk(uz_ctx *c, uz_ctx::WalkSlot &w, const WalkPlan &p, const std::ve
 // what the inflate and the CRC check left in iflags (queue_blocks), as the call's error
 void throw_block_errors(const WalkPlan &p, const std::vector<int64_t> &cut, const std::vector<int32_t> &iflags) {
     const size_t ns = cut.size() - 1;
-    for (size_t i = 0; i < ns; i++)
-        if (iflags[2 * i + 1])
-            throw UzError{UZ_E_RANGE, "BGZF block " + std::to_string(cut[i] + (iflags[2 * i + 1] >> 4)) + " of the batch: not a valid DEFLATE stream of the declared size (code " +
-                                          std::to_string(iflags[2 * i + 1] & 15) + ")"};
+    const UzBlockFault f = uz_bgzf_first_fault(cut, iflags.data());
+    if (f.block >= 0) throw UzError{UZ_E_RANGE, uz_bgzf_fault_text(f, true)};
     if (p.blk_crc && p.n_blocks && iflags[2 * ns])
         throw UzError{UZ_E_RANGE, "CRC mismatch in BGZF block " + std::to_string(iflags[2 * ns] - 1) + " of the batch (file offset " +
                                       std::to_string((long long)p.blk_coff[iflags[2 * ns] - 1]) + ")"};
@@ -1848,108 +1797,11 @@ int uz_reads_marks(uz_ctx *c, int reads_id, uint16_t *umask, uint8_t *nlow) {
 
 int uz_bgzf_inflate(uz_ctx *c, const uint8_t *comp, int64_t comp_bytes, int64_t n_blocks, const int64_t *in_off, const int64_t *out_off, uint8_t *out,
                     int repeat, double *kernel_ms) {
-    return guarded(c, [&] {
-        UZ_REQUIRE(comp && in_off && out_off && out && n_blocks >= 0 && comp_bytes >= 0, UZ_E_ARG, "bad arguments");
-        if (kernel_ms) *kernel_ms = 0;
-        if (n_blocks == 0) return;
-        const int64_t out_bytes = out_off[n_blocks];
-        UZ_REQUIRE(out_off[0] >= 0, UZ_E_ARG, "bad block table");
-        for (int64_t k = 0; k < n_blocks; k++)
-            UZ_REQUIRE(in_off[k] >= 0 && in_off[k] < comp_bytes && out_off[k] <= out_off[k + 1] && out_off[k + 1] - out_off[k] <= 65536, UZ_E_ARG,
-                       "bad block table (a BGZF block inflates to at most 64 KiB)");
-        uint8_t *d_comp = nullptr, *d_out = nullptr;
-        int64_t *d_in = nullptr, *d_off = nullptr;
-        int32_t *d_flags = nullptr;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        auto cleanup = [&] {
-            (void)hipFree(d_comp); (void)hipFree(d_out); (void)hipFree(d_in); (void)hipFree(d_off); (void)hipFree(d_flags);
-            if (e0) (void)hipEventDestroy(e0);
-            if (e1) (void)hipEventDestroy(e1);
-        };
-        try {
-            UZ_HIP(hipMalloc((void **)&d_comp, (size_t)comp_bytes + 1024));
-            UZ_HIP(hipMalloc((void **)&d_out, (size_t)out_bytes + 64));
-            UZ_HIP(hipMalloc((void **)&d_in, (size_t)n_blocks * 8));
-            UZ_HIP(hipMalloc((void **)&d_off, (size_t)(n_blocks + 1) * 8));
-            UZ_HIP(hipMalloc((void **)&d_flags, 64));
-            UZ_HIP(hipMemsetAsync(d_comp + comp_bytes, 0, 1024, c->stream));
-            UZ_HIP(hipMemcpyAsync(d_comp, comp, (size_t)comp_bytes, hipMemcpyHostToDevice, c->stream));
-            UZ_HIP(hipMemcpyAsync(d_in, in_off, (size_t)n_blocks * 8, hipMemcpyHostToDevice, c->stream));
-            UZ_HIP(hipMemcpyAsync(d_off, out_off, (size_t)(n_blocks + 1) * 8, hipMemcpyHostToDevice, c->stream));
-            UZ_HIP(hipEventCreate(&e0));
-            UZ_HIP(hipEventCreate(&e1));
-            uz_launch_inflate(c, c->stream, n_blocks, d_comp, (comp_bytes + 1024) & ~(int64_t)3, d_in, d_off, d_out, d_flags); // (warm-up and the run that is checked)
-            UZ_HIP(hipEventRecord(e0, c->stream));
-            for (int r = 0; r < std::max(repeat, 0); r++) uz_launch_inflate(c, c->stream, n_blocks, d_comp, (comp_bytes + 1024) & ~(int64_t)3, d_in, d_off, d_out, d_flags);
-            UZ_HIP(hipEventRecord(e1, c->stream));
-            int32_t flags[2] = {0, 0};
-            UZ_HIP(hipMemcpyAsync(flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
-            UZ_HIP(hipMemcpyAsync(out, d_out, (size_t)out_bytes, hipMemcpyDeviceToHost, c->stream));
-            UZ_HIP(hipStreamSynchronize(c->stream));
-            if (kernel_ms && repeat > 0) {
-                float ms = 0;
-                UZ_HIP(hipEventElapsedTime(&ms, e0, e1));
-                *kernel_ms = (double)ms / repeat;
-            }
-            if (flags[1]) throw UzError{UZ_E_RANGE, "BGZF block " + std::to_string(flags[1] >> 4) + ": not a valid DEFLATE stream of the declared size (code " + std::to_string(flags[1] & 15) + ")"};
-        } catch (...) { cleanup(); throw; }
-        cleanup();
-    });
+    return guarded(c, [&] { uz_bgzf_inflate_impl(c, comp, comp_bytes, n_blocks, in_off, out_off, out, repeat, kernel_ms); });
 }
-
 int uz_bgzf_inflate_to_host(uz_ctx *c, const uint8_t *comp, int64_t comp_bytes, int64_t n_blocks, const int64_t *in_off, const int64_t *out_off,
                             uint8_t *out) {
-    return guarded(c, [&] {
-        UZ_REQUIRE(n_blocks >= 0 && comp_bytes >= 0 && (n_blocks == 0 || (comp && in_off && out_off && out)), UZ_E_ARG, "bad arguments");
-        if (n_blocks == 0) return;
-        const int64_t out_bytes = out_off[n_blocks];
-        UZ_REQUIRE(out_bytes >= 0 && out_off[0] >= 0, UZ_E_ARG, "bad block table");
-        for (int64_t k = 0; k < n_blocks; k++)
-            UZ_REQUIRE(in_off[k] >= 0 && in_off[k] < comp_bytes && (k == 0 || in_off[k] > in_off[k - 1]) && out_off[k] <= out_off[k + 1] &&
-                           out_off[k + 1] - out_off[k] <= 65536,
-                       UZ_E_ARG, "bad block table (blocks in the order they lie in `comp`; a BGZF block inflates to at most 64 KiB)");
-        UZ_HIP(hipSetDevice(c->device)); // (a decoder's worker thread calls this: the current device is per thread)
-        if (!c->inf_stream) {
-            UZ_HIP(hipStreamCreateWithFlags(&c->inf_stream, hipStreamNonBlocking));
-            UZ_HIP(hipStreamCreateWithFlags(&c->inf_stream2, hipStreamNonBlocking));
-            UZ_HIP(hipEventCreateWithFlags(&c->inf_ready, hipEventDisableTiming));
-        }
-        // The batch in slices of ~8 k blocks, alternating between two streams: the blocks of slice i + 1 go up and are inflated
-        // while the bytes of slice i come down (the two directions of the link and the kernel overlap: the call takes about as long as
-        // its slowest leg, the way down).  The blocks lie in `comp` in the order of the table, so a slice is a contiguous piece of it.
-        std::vector<int64_t> cut{0};
-        {
-            const int64_t SLICE = 8192; // blocks: a wave is one block's decoder, and the chip holds 6 000 ... 8 000 waves -- a smaller launch leaves slots idle
-            for (int64_t k = 1; k <= n_blocks; k++)
-                if (k == n_blocks || (k - cut.back() >= SLICE && n_blocks - k >= SLICE / 2)) cut.push_back(k);
-        }
-        const size_t ns = cut.size() - 1;
-        c->inf_comp.ensure((size_t)comp_bytes + 1024); c->inf_out.ensure((size_t)out_bytes + 64);
-        c->inf_in.ensure((size_t)n_blocks); c->inf_off.ensure((size_t)n_blocks + 1); c->inf_flags.ensure(2 * ns + 2);
-        hipStream_t st[2] = {c->inf_stream, c->inf_stream2};
-        UZ_HIP(hipMemsetAsync(c->inf_comp.p + comp_bytes, 0, 1024, st[0]));
-        UZ_HIP(hipMemcpyAsync(c->inf_in.p, in_off, (size_t)n_blocks * 8, hipMemcpyHostToDevice, st[0]));
-        UZ_HIP(hipMemcpyAsync(c->inf_off.p, out_off, (size_t)(n_blocks + 1) * 8, hipMemcpyHostToDevice, st[0]));
-        UZ_HIP(hipEventRecord(c->inf_ready, st[0]));
-        UZ_HIP(hipStreamWaitEvent(st[1], c->inf_ready, 0));
-        std::vector<int32_t> flags(2 * ns, 0);
-        for (size_t i = 0; i < ns; i++) {
-            hipStream_t s = st[i & 1];
-            const int64_t b0 = cut[i], b1 = cut[i + 1];
-            // (whole blocks travel: a slice's bytes run from the framing of its first block to the start of the next slice's)
-            const int64_t c0 = i == 0 ? 0 : in_off[b0] - 18 < 0 ? 0 : in_off[b0] - 18, c1 = i + 1 == ns ? comp_bytes : std::max<int64_t>(in_off[b1] - 18, c0);
-            UZ_HIP(hipMemcpyAsync(c->inf_comp.p + c0, comp + c0, (size_t)(c1 - c0), hipMemcpyHostToDevice, s));
-            uz_launch_inflate(c, s, b1 - b0, c->inf_comp.p, (comp_bytes + 1024) & ~(int64_t)3, c->inf_in.p + b0, c->inf_off.p + b0, c->inf_out.p, c->inf_flags.p + 2 * i);
-            UZ_HIP(hipMemcpyAsync(flags.data() + 2 * i, c->inf_flags.p + 2 * i, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            UZ_HIP(hipMemcpyAsync(out + out_off[b0], c->inf_out.p + out_off[b0], (size_t)(out_off[b1] - out_off[b0]), hipMemcpyDeviceToHost, s));
-        }
-        UZ_HIP(hipStreamSynchronize(st[0]));
-        UZ_HIP(hipStreamSynchronize(st[1]));
-        for (size_t i = 0; i < ns; i++)
-            if (flags[2 * i + 1])
-                throw UzError{UZ_E_RANGE, "BGZF block " + std::to_string(cut[i] + (flags[2 * i + 1] >> 4)) + " of the batch: not a valid DEFLATE stream of the declared size (code " +
-                                              std::to_string(flags[2 * i + 1] & 15) + ")"};
-    });
+    return guarded(c, [&] { uz_bgzf_inflate_to_host_impl(c, comp, comp_bytes, n_blocks, in_off, out_off, out); });
 }
 
 int uz_reads_adopt_device(uz_ctx *c, const uz_reads_packed_view *v, int *id) {
@@ -2544,14 +2396,14 @@ static int bam_walk(uz_ctx *c, const WalkPlan &p, int *walk_id, int64_t *n_desc)
         check_walk_plan(p);
         const std::vector<uz_walk_file> tfile = p.n_files ? task_files(p) : std::vector<uz_walk_file>();
         UZ_HIP(hipSetDevice(c->device));
-        const std::vector<int64_t> first = desc_slices(p), cut = block_slices(n_blocks);
+        const std::vector<int64_t> first = desc_slices(p), cut = uz_bgzf_slices(n_blocks);
         const size_t ns = cut.size() - 1;
         std::vector<int32_t> iflags(2 * ns + 4, 0); // (what the slot's streams copy into is declared before the claim: it outlives their drain)
         int64_t tab_total = 0, kept = 0;
         // Nothing is freed while batches are in flight (hipFree waits for the whole device -- round 5: a process's second call, whose larger last
         // chunk met another slot than in the first call, stood still for 0.9 s): an outgrown block is parked, and the book hands the parked blocks
         // over only at a claim that finds no other batch in flight (WalkBook::claim).
-        const size_t need_out = (size_t)p.out_bytes() + uz_bam_walk_pad(), need_comp = (size_t)comp_bytes + 1024, need_desc = (size_t)first.back() + 1;
+        const size_t need_out = (size_t)p.out_bytes() + uz_bam_walk_pad(), need_comp = (size_t)uz_bgzf_room(comp_bytes), need_desc = (size_t)first.back() + 1;
         std::vector<void *> drained;
         const int k = c->book.claim([&](int i) { return WalkBook::Caps{c->walk[i].out.cap, c->walk[i].comp.cap, c->walk[i].desc.cap}; }, need_out, need_comp, need_desc, drained);
         for (void *b : drained) (void)hipFree(b);
@@ -2820,182 +2672,23 @@ int uz_reads_from_bam(uz_ctx *c, int walk_id, const uz_kept_rec *kept, int64_t n
 }
 
 int uz_crc32_blocks(uz_ctx *c, const uint8_t *data, int64_t n_blocks, const int64_t *off, const uint32_t *want, int64_t *first_bad) {
-    return guarded(c, [&] {
-        UZ_REQUIRE(n_blocks >= 0 && first_bad && (n_blocks == 0 || (data && off && want)), UZ_E_ARG, "bad arguments");
-        *first_bad = -1;
-        if (n_blocks == 0) return;
-        for (int64_t k = 0; k < n_blocks; k++) UZ_REQUIRE(off[k] >= 0 && off[k] <= off[k + 1] && off[k + 1] - off[k] <= 65536, UZ_E_ARG, "bad block table");
-        uint8_t *d = upload(c, data, (size_t)off[n_blocks]);
-        int64_t *d_off = upload(c, off, (size_t)n_blocks + 1);
-        uint32_t *d_want = upload(c, want, (size_t)n_blocks);
-        int32_t *d_err = nullptr, e = 0;
-        UZ_HIP(hipMalloc((void **)&d_err, 64));
-        uz_launch_crc32(c, c->stream, n_blocks, d, d_off, d_want, d_err);
-        UZ_HIP(hipMemcpyAsync(&e, d_err, 4, hipMemcpyDeviceToHost, c->stream));
-        UZ_HIP(hipStreamSynchronize(c->stream));
-        (void)hipFree(d); (void)hipFree(d_off); (void)hipFree(d_want); (void)hipFree(d_err);
-        if (e) *first_bad = e - 1;
-    });
+    return guarded(c, [&] { uz_crc32_blocks_impl(c, data, n_blocks, off, want, first_bad); });
 }
 
-// ---- the heads of a cohort's alignment files (read_collector.py:11-25; csrc/k_bamhead.hip, csrc/headwalk.hpp)
-static uz_ctx::HeadDev &head_of(uz_ctx *c, int id) {
-    UZ_REQUIRE(id >= 0 && id < (int)c->heads.size() && c->heads[(size_t)id].live, UZ_E_ARG, "unknown head id");
-    return c->heads[(size_t)id];
-}
-
+// ---- the heads of a cohort's alignment files (csrc/k_bamhead.hip, csrc/headwalk.hpp)
 int uz_head_walk(uz_ctx *c, int *head_id, int32_t n_files, const uint8_t *comp, int64_t comp_bytes, int64_t n_blocks, const int64_t *in_off,
                  const int32_t *isize, const uint32_t *crc, const int64_t *blk_first, const int64_t *start, const int64_t *want, const int64_t *have,
                  int64_t *taken, int64_t *cursor, int32_t *state) {
-    return guarded(c, [&] {
-        UZ_REQUIRE(head_id && n_files >= 1 && n_files < (1 << 24) && n_blocks >= 0 && n_blocks < ((int64_t)1 << 31) && comp_bytes >= 0 && blk_first && start && want && have &&
-                       taken && cursor && state && (n_blocks == 0 || (comp && in_off && isize && crc)),
-                   UZ_E_ARG, "bad arguments");
-        const size_t nf = (size_t)n_files, nb = (size_t)n_blocks;
-        UZ_REQUIRE(blk_first[0] == 0 && blk_first[nf] == n_blocks, UZ_E_ARG, "bad block table (blk_first)");
-        for (size_t f = 0; f < nf; f++) UZ_REQUIRE(blk_first[f] <= blk_first[f + 1], UZ_E_ARG, "bad block table (blk_first)");
-        std::vector<int64_t> out_off(nb + 1, 0);
-        for (size_t k = 0; k < nb; k++) {
-            UZ_REQUIRE(in_off[k] >= 0 && in_off[k] < comp_bytes && isize[k] >= 0 && isize[k] <= 65536, UZ_E_ARG, "bad block table (a BGZF block inflates to at most 64 KiB)");
-            out_off[k + 1] = out_off[k] + isize[k];
-        }
-        // the head: a new one is entered only when the whole call has gone through
-        const bool fresh = *head_id < 0;
-        uz_ctx::HeadDev made;
-        uz_ctx::HeadDev *H = fresh ? &made : &head_of(c, *head_id);
-        if (fresh) {
-            made.n_files = n_files; made.want.assign(want, want + nf); made.have.assign(nf, 0); made.first.assign(nf + 1, 0);
-            for (size_t f = 0; f < nf; f++) {
-                UZ_REQUIRE(want[f] >= 0 && want[f] <= INT32_MAX, UZ_E_ARG, "bad record count wanted");
-                made.first[f + 1] = made.first[f] + want[f];
-            }
-        } else {
-            UZ_REQUIRE(H->n_files == n_files, UZ_E_ARG, "the head holds another number of files");
-            for (size_t f = 0; f < nf; f++) UZ_REQUIRE(H->want[f] == want[f], UZ_E_ARG, "the head was opened with other record counts");
-        }
-        std::vector<int32_t> ok(nf, 0);
-        for (size_t f = 0; f < nf; f++) {
-            UZ_REQUIRE(have[f] == H->have[f], UZ_E_ARG, "have[] is not what the head's walks have taken so far");
-            const int64_t len = out_off[(size_t)blk_first[f + 1]] - out_off[(size_t)blk_first[f]];
-            ok[f] = blk_first[f + 1] > blk_first[f] ? 1 : 0;
-            UZ_REQUIRE(!ok[f] || (start[f] >= 0 && start[f] <= len), UZ_E_ARG, "a file's start offset lies outside its bytes");
-        }
-        try {
-            if (fresh) {
-                made.tlen.ensure((size_t)made.first[nf] + 1);
-                made.first_d.ensure(nf + 1);
-                UZ_HIP(hipMemcpyAsync(made.first_d.p, made.first.data(), (nf + 1) * 8, hipMemcpyHostToDevice, c->stream));
-            }
-            // one table of 64-bit columns, one of 32-bit ones
-            enum { I_IN = 0 };
-            const size_t o_out = nb, o_base = o_out + nb + 1, o_start = o_base + nf + 1, o_want = o_start + nf, o_have = o_want + nf, o_taken = o_have + nf,
-                         o_cursor = o_taken + nf, n64 = o_cursor + nf;
-            std::vector<int64_t> t64(n64, 0);
-            for (size_t k = 0; k < nb; k++) t64[I_IN + k] = in_off[k];
-            std::copy(out_off.begin(), out_off.end(), t64.begin() + (ptrdiff_t)o_out);
-            for (size_t f = 0; f <= nf; f++) t64[o_base + f] = out_off[(size_t)blk_first[f]];
-            for (size_t f = 0; f < nf; f++) { t64[o_start + f] = ok[f] ? start[f] : 0; t64[o_want + f] = want[f]; t64[o_have + f] = have[f]; }
-            const size_t o_ok = 0, o_state = nf, o_flags = 2 * nf, n32 = o_flags + 4 * (nf + 1); // flags: [cursor, err, crc err, -] for the group, then per file
-            c->hd_comp.ensure((size_t)comp_bytes + 1024); c->hd_out.ensure((size_t)out_off[nb] + 64);
-            c->hd_i64.ensure(n64); c->hd_i32.ensure(n32); c->hd_u32.ensure(nb + 1);
-            hipStream_t st = c->stream;
-            int64_t *d64 = c->hd_i64.p;
-            int32_t *d32 = c->hd_i32.p;
-            UZ_HIP(hipMemcpyAsync(d64, t64.data(), n64 * 8, hipMemcpyHostToDevice, st));
-            std::vector<int32_t> flags(4 * (nf + 1), 0);
-            if (nb) {
-                UZ_HIP(hipMemsetAsync(c->hd_comp.p + comp_bytes, 0, 1024, st));
-                UZ_HIP(hipMemcpyAsync(c->hd_comp.p, comp, (size_t)comp_bytes, hipMemcpyHostToDevice, st));
-                UZ_HIP(hipMemcpyAsync(c->hd_u32.p, crc, nb * 4, hipMemcpyHostToDevice, st));
-                const int64_t padded = (comp_bytes + 1024) & ~(int64_t)3;
-                auto inflate_and_check = [&](size_t b0, size_t b1, size_t slot) {
-                    uz_launch_inflate(c, st, (int64_t)(b1 - b0), c->hd_comp.p, padded, d64 + I_IN + b0, d64 + o_out + b0, c->hd_out.p, d32 + o_flags + 4 * slot);
-                    uz_launch_crc32(c, st, (int64_t)(b1 - b0), c->hd_out.p, d64 + o_out + b0, c->hd_u32.p + b0, d32 + o_flags + 4 * slot + 2);
-                };
-                {
-                    ProfScope ps(c, UZ_K_HEAD_INFLATE);
-                    inflate_and_check(0, nb, 0);
-                }
-                UZ_HIP(hipMemcpyAsync(flags.data(), d32 + o_flags, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-                UZ_HIP(hipStreamSynchronize(st));
-                if (flags[1] || flags[2]) { // some block is bad: file by file, to know whose -- the FILE is marked, the call goes on
-                    for (size_t f = 0; f < nf; f++)
-                        if (ok[f]) inflate_and_check((size_t)blk_first[f], (size_t)blk_first[f + 1], f + 1);
-                    UZ_HIP(hipMemcpyAsync(flags.data(), d32 + o_flags, flags.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-                    UZ_HIP(hipStreamSynchronize(st));
-                    for (size_t f = 0; f < nf; f++)
-                        if (ok[f] && (flags[4 * (f + 1) + 1] || flags[4 * (f + 1) + 2])) ok[f] = -1;
-                }
-            }
-            UZ_HIP(hipMemcpyAsync(d32 + o_ok, ok.data(), nf * 4, hipMemcpyHostToDevice, st));
-            {
-                ProfScope ps(c, UZ_K_HEAD_WALK);
-                uz_launch_head_walk(c, st, n_files, c->hd_out.p, d64 + o_base, d32 + o_ok, d64 + o_start, d64 + o_want, d64 + o_have, fresh ? made.first_d.p : H->first_d.p,
-                                    fresh ? made.tlen.p : H->tlen.p, d64 + o_taken, d64 + o_cursor, d32 + o_state);
-            }
-            UZ_HIP(hipMemcpyAsync(taken, d64 + o_taken, nf * 8, hipMemcpyDeviceToHost, st));
-            UZ_HIP(hipMemcpyAsync(cursor, d64 + o_cursor, nf * 8, hipMemcpyDeviceToHost, st));
-            UZ_HIP(hipMemcpyAsync(state, d32 + o_state, nf * 4, hipMemcpyDeviceToHost, st));
-            UZ_HIP(hipStreamSynchronize(st));
-        } catch (...) {
-            (void)hipStreamSynchronize(c->stream);
-            if (fresh) { made.tlen.release(); made.first_d.release(); }
-            throw;
-        }
-        for (size_t f = 0; f < nf; f++) {
-            UZ_REQUIRE(taken[f] >= 0 && H->have[f] + taken[f] <= H->want[f], UZ_E_STATE, "the head walk took more records than wanted");
-            H->have[f] += taken[f];
-        }
-        if (fresh) {
-            made.live = true;
-            const int k = new_slot(c->heads);
-            c->heads[(size_t)k] = made;
-            *head_id = k;
-        }
-    });
+    return guarded(c, [&] { uz_head_walk_impl(c, head_id, n_files, comp, comp_bytes, n_blocks, in_off, isize, crc, blk_first, start, want, have, taken, cursor, state); });
 }
-
 int uz_head_rank(uz_ctx *c, int head_id, int32_t readlen, const int64_t *k, uint32_t *a, uint32_t *b) {
-    return guarded(c, [&] {
-        uz_ctx::HeadDev &H = head_of(c, head_id);
-        UZ_REQUIRE(k && a && b && readlen >= 0 && readlen < (1 << 30), UZ_E_ARG, "bad arguments (0 <= readlen < 2^30)");
-        const size_t nf = (size_t)H.n_files;
-        std::vector<int64_t> t64(2 * nf);
-        for (size_t f = 0; f < nf; f++) {
-            UZ_REQUIRE(k[f] < H.have[f] || k[f] < 0, UZ_E_ARG, "a rank beyond the records the file's column holds");
-            t64[f] = k[f] < 0 ? 0 : H.have[f]; // (a skipped file: no records as far as the kernel is concerned)
-            t64[nf + f] = k[f];
-        }
-        c->hd_i64.ensure(2 * nf); c->hd_u32.ensure(2 * nf);
-        hipStream_t st = c->stream;
-        UZ_HIP(hipMemcpyAsync(c->hd_i64.p, t64.data(), 2 * nf * 8, hipMemcpyHostToDevice, st));
-        {
-            ProfScope ps(c, UZ_K_HEAD_RANK);
-            uz_launch_head_rank(c, st, H.n_files, H.tlen.p, H.first_d.p, c->hd_i64.p, c->hd_i64.p + nf, readlen, c->hd_u32.p, c->hd_u32.p + nf);
-        }
-        UZ_HIP(hipMemcpyAsync(a, c->hd_u32.p, nf * 4, hipMemcpyDeviceToHost, st));
-        UZ_HIP(hipMemcpyAsync(b, c->hd_u32.p + nf, nf * 4, hipMemcpyDeviceToHost, st));
-        UZ_HIP(hipStreamSynchronize(st));
-    });
+    return guarded(c, [&] { uz_head_rank_impl(c, head_id, readlen, k, a, b); });
 }
-
 int uz_head_fetch(uz_ctx *c, int head_id, int32_t file, int32_t *out, int64_t cap, int64_t *n) {
-    return guarded(c, [&] {
-        uz_ctx::HeadDev &H = head_of(c, head_id);
-        UZ_REQUIRE(file >= 0 && file < H.n_files && n && cap >= 0 && (cap == 0 || out), UZ_E_ARG, "bad arguments");
-        *n = std::min<int64_t>(cap, H.have[(size_t)file]);
-        if (*n) UZ_HIP(hipMemcpyAsync(out, H.tlen.p + H.first[(size_t)file], (size_t)*n * 4, hipMemcpyDeviceToHost, c->stream));
-        UZ_HIP(hipStreamSynchronize(c->stream));
-    });
+    return guarded(c, [&] { uz_head_fetch_impl(c, head_id, file, out, cap, n); });
 }
-
 int uz_head_free(uz_ctx *c, int head_id) {
-    return guarded(c, [&] {
-        uz_ctx::HeadDev &H = head_of(c, head_id);
-        UZ_HIP(hipStreamSynchronize(c->stream));
-        H.tlen.release(); H.first_d.release();
-        H = uz_ctx::HeadDev();
-    });
+    return guarded(c, [&] { uz_head_free_impl(c, head_id); });
 }
 
 } // extern "C"

@@ -777,3 +777,131 @@ void uz_launch_inflate(uz_ctx *c, hipStream_t st, int64_t n_blocks, const uint8_
     hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)grid), dim3(64), 0, st, n_blocks, comp, in_off, out_off, out, comp_bytes_padded / 4, cursor_and_err, cursor_and_err + 1);
     UZ_HIP(hipGetLastError());
 }
+
+// (uz_ctx.hpp: InflateBatch)
+void uz_queue_inflate(uz_ctx *c, const InflateBatch &b, const std::vector<int64_t> &cut) {
+    if (b.n_blocks <= 0) return;
+    const hipStream_t st[2] = {b.st[0], b.st[1] ? b.st[1] : b.st[0]};
+    UZ_HIP(hipMemsetAsync(b.d_comp + b.comp_bytes, 0, UZ_BGZF_PAD, st[0]));
+    if (!b.tables_there) {
+        UZ_HIP(hipMemcpyAsync(b.d_in, b.in_off, (size_t)b.n_blocks * 8, hipMemcpyHostToDevice, st[0]));
+        UZ_HIP(hipMemcpyAsync(b.d_off, b.out_off, (size_t)(b.n_blocks + 1) * 8, hipMemcpyHostToDevice, st[0]));
+    }
+    if (b.st[1]) {
+        UZ_HIP(hipEventRecord(b.ev, st[0]));
+        UZ_HIP(hipStreamWaitEvent(st[1], b.ev, 0));
+    }
+    for (size_t i = 0; i + 1 < cut.size(); i++) {
+        const hipStream_t s = st[i & 1];
+        const UzByteRange r = uz_bgzf_slice_bytes(cut, i, b.in_off, b.comp_bytes);
+        UZ_HIP(hipMemcpyAsync(b.d_comp + r.c0, b.comp + r.c0, (size_t)(r.c1 - r.c0), hipMemcpyHostToDevice, s));
+        if (b.before) b.before(i, s);
+        uz_launch_inflate(c, s, cut[i + 1] - cut[i], b.d_comp, uz_bgzf_padded(b.comp_bytes), b.d_in + cut[i], b.d_off + cut[i], b.d_out, b.d_flags + 2 * i);
+        if (b.after) b.after(i, s);
+    }
+}
+
+namespace {
+// device memory and an event of one call (the two probes below keep nothing in the context): gone at every exit
+template <typename T>
+struct CallBuf {
+    T *p = nullptr;
+    explicit CallBuf(size_t n) { UZ_HIP(hipMalloc((void **)&p, n * sizeof(T))); }
+    ~CallBuf() { (void)hipFree(p); }
+    CallBuf(const CallBuf &) = delete;
+};
+struct CallEvent {
+    hipEvent_t e = nullptr;
+    CallEvent() { UZ_HIP(hipEventCreate(&e)); }
+    ~CallEvent() { (void)hipEventDestroy(e); }
+    CallEvent(const CallEvent &) = delete;
+};
+} // namespace
+
+// the probe: one launch over the whole batch on the compute stream, then `repeat` timed ones
+void uz_bgzf_inflate_impl(uz_ctx *c, const uint8_t *comp, int64_t comp_bytes, int64_t n_blocks, const int64_t *in_off, const int64_t *out_off, uint8_t *out,
+                         int repeat, double *kernel_ms) {
+    UZ_REQUIRE(comp && in_off && out_off && out && n_blocks >= 0 && comp_bytes >= 0, UZ_E_ARG, "bad arguments");
+    if (kernel_ms) *kernel_ms = 0;
+    if (n_blocks == 0) return;
+    const int bad = uz_bgzf_check_tables(n_blocks, comp_bytes, in_off, out_off, false);
+    UZ_REQUIRE(bad != UZ_TABLE_FIRST, UZ_E_ARG, "bad block table");
+    UZ_REQUIRE(!bad, UZ_E_ARG, "bad block table (a BGZF block inflates to at most 64 KiB)");
+    const int64_t out_bytes = out_off[n_blocks];
+    CallBuf<uint8_t> d_comp((size_t)uz_bgzf_room(comp_bytes)), d_out((size_t)out_bytes + 64);
+    CallBuf<int64_t> d_in((size_t)n_blocks), d_off((size_t)n_blocks + 1);
+    CallBuf<int32_t> d_flags(16);
+    CallEvent e0, e1;
+    const std::vector<int64_t> cut{0, n_blocks};
+    uz_queue_inflate(c, InflateBatch{comp, comp_bytes, n_blocks, in_off, out_off, d_comp.p, d_in.p, d_off.p, d_out.p, d_flags.p, {c->stream, nullptr}, nullptr}, cut); // (warm-up and the run that is checked)
+    UZ_HIP(hipEventRecord(e0.e, c->stream));
+    for (int r = 0; r < std::max(repeat, 0); r++) uz_launch_inflate(c, c->stream, n_blocks, d_comp.p, uz_bgzf_padded(comp_bytes), d_in.p, d_off.p, d_out.p, d_flags.p);
+    UZ_HIP(hipEventRecord(e1.e, c->stream));
+    int32_t flags[2] = {0, 0};
+    UZ_HIP(hipMemcpyAsync(flags, d_flags.p, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
+    UZ_HIP(hipMemcpyAsync(out, d_out.p, (size_t)out_bytes, hipMemcpyDeviceToHost, c->stream));
+    UZ_HIP(hipStreamSynchronize(c->stream));
+    if (kernel_ms && repeat > 0) {
+        float ms = 0;
+        UZ_HIP(hipEventElapsedTime(&ms, e0.e, e1.e));
+        *kernel_ms = (double)ms / repeat;
+    }
+    const UzBlockFault f = uz_bgzf_first_fault(cut, flags);
+    if (f.block >= 0) throw UzError{UZ_E_RANGE, uz_bgzf_fault_text(f, false)};
+}
+
+// The staged route: the batch in slices on the two inf_ streams (bgzf_batch.hpp: uz_bgzf_slices), every slice's flag words and bytes coming down
+// behind its launch -- the call takes about as long as its slowest leg, the way down.  May run on a decoder's worker thread beside the owner's calls.
+void uz_bgzf_inflate_to_host_impl(uz_ctx *c, const uint8_t *comp, int64_t comp_bytes, int64_t n_blocks, const int64_t *in_off, const int64_t *out_off,
+                                 uint8_t *out) {
+    UZ_REQUIRE(n_blocks >= 0 && comp_bytes >= 0 && (n_blocks == 0 || (comp && in_off && out_off && out)), UZ_E_ARG, "bad arguments");
+    if (n_blocks == 0) return;
+    const int64_t out_bytes = out_off[n_blocks];
+    const int bad = uz_bgzf_check_tables(n_blocks, comp_bytes, in_off, out_off, true);
+    UZ_REQUIRE(out_bytes >= 0 && bad != UZ_TABLE_FIRST, UZ_E_ARG, "bad block table");
+    UZ_REQUIRE(!bad, UZ_E_ARG, "bad block table (blocks in the order they lie in `comp`; a BGZF block inflates to at most 64 KiB)");
+    UZ_HIP(hipSetDevice(c->device)); // (a decoder's worker thread calls this: the current device is per thread)
+    if (!c->inf_stream) {
+        UZ_HIP(hipStreamCreateWithFlags(&c->inf_stream, hipStreamNonBlocking));
+        UZ_HIP(hipStreamCreateWithFlags(&c->inf_stream2, hipStreamNonBlocking));
+        UZ_HIP(hipEventCreateWithFlags(&c->inf_ready, hipEventDisableTiming));
+    }
+    const std::vector<int64_t> cut = uz_bgzf_slices(n_blocks);
+    const size_t ns = cut.size() - 1;
+    c->inf_comp.ensure((size_t)uz_bgzf_room(comp_bytes)); c->inf_out.ensure((size_t)out_bytes + 64);
+    c->inf_in.ensure((size_t)n_blocks); c->inf_off.ensure((size_t)n_blocks + 1); c->inf_flags.ensure(2 * ns + 2);
+    std::vector<int32_t> flags(2 * ns, 0);
+    InflateBatch b{comp, comp_bytes, n_blocks, in_off, out_off, c->inf_comp.p, c->inf_in.p, c->inf_off.p, c->inf_out.p, c->inf_flags.p,
+                   {c->inf_stream, c->inf_stream2}, c->inf_ready};
+    b.after = [&](size_t i, hipStream_t s) {
+        const int64_t o0 = out_off[cut[i]], o1 = out_off[cut[i + 1]];
+        UZ_HIP(hipMemcpyAsync(flags.data() + 2 * i, c->inf_flags.p + 2 * i, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        UZ_HIP(hipMemcpyAsync(out + o0, c->inf_out.p + o0, (size_t)(o1 - o0), hipMemcpyDeviceToHost, s));
+    };
+    uz_queue_inflate(c, b, cut);
+    UZ_HIP(hipStreamSynchronize(c->inf_stream));
+    UZ_HIP(hipStreamSynchronize(c->inf_stream2));
+    const UzBlockFault f = uz_bgzf_first_fault(cut, flags.data());
+    if (f.block >= 0) throw UzError{UZ_E_RANGE, uz_bgzf_fault_text(f, true)};
+}
+
+// the probe of k_bgzf_crc32: blocks data[off[k] .. off[k + 1]) of host memory against want[k] -> *first_bad: -1, or a block whose CRC-32 differs
+void uz_crc32_blocks_impl(uz_ctx *c, const uint8_t *data, int64_t n_blocks, const int64_t *off, const uint32_t *want, int64_t *first_bad) {
+    UZ_REQUIRE(n_blocks >= 0 && first_bad && (n_blocks == 0 || (data && off && want)), UZ_E_ARG, "bad arguments");
+    *first_bad = -1;
+    if (n_blocks == 0) return;
+    for (int64_t k = 0; k < n_blocks; k++) UZ_REQUIRE(off[k] >= 0 && off[k] <= off[k + 1] && off[k + 1] - off[k] <= 65536, UZ_E_ARG, "bad block table");
+    const size_t nb = (size_t)n_blocks, bytes = (size_t)off[n_blocks];
+    CallBuf<uint8_t> d(bytes + 64); // (+64: vector tail reads stay in-bounds)
+    CallBuf<int64_t> d_off(nb + 1);
+    CallBuf<uint32_t> d_want(nb);
+    CallBuf<int32_t> d_err(16);
+    int32_t e = 0;
+    if (bytes) UZ_HIP(hipMemcpyAsync(d.p, data, bytes, hipMemcpyHostToDevice, c->stream));
+    UZ_HIP(hipMemcpyAsync(d_off.p, off, (nb + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    UZ_HIP(hipMemcpyAsync(d_want.p, want, nb * 4, hipMemcpyHostToDevice, c->stream));
+    uz_launch_crc32(c, c->stream, n_blocks, d.p, d_off.p, d_want.p, d_err.p);
+    UZ_HIP(hipMemcpyAsync(&e, d_err.p, 4, hipMemcpyDeviceToHost, c->stream));
+    UZ_HIP(hipStreamSynchronize(c->stream));
+    if (e) *first_bad = e - 1;
+}

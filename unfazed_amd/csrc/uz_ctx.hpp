@@ -4,6 +4,7 @@
 
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <memory>
@@ -11,6 +12,7 @@
 
 #include "unfazed_hip.h"
 #include "uz_bamwalk.h"
+#include "bgzf_batch.hpp"
 #include "walk_book.hpp"
 
 struct UzError {
@@ -413,8 +415,9 @@ struct uz_ctx {
     std::vector<int32_t> cnv_counts_h;
     std::vector<int64_t> cnv_off_h;
 
-    // BGZF inflate (k_inflate.hip, uz_bgzf_inflate_to_host): buffers kept from call to call, a stream of its own (a batch's blocks can
-    // be inflated while the read stage of the batch before is still queued on the compute stream)
+    // BGZF inflate (k_inflate.hip, uz_bgzf_inflate_to_host): buffers kept from call to call, streams of its own (a batch's blocks can
+    // be inflated while the read stage of the batch before is still queued on the compute stream) -- what it hands uz_queue_inflate.  The call
+    // may run on a decoder's worker thread beside the owner's: nothing of it is shared with the other routes
     DevBuf<uint8_t> inf_comp, inf_out;
     DevBuf<int64_t> inf_in, inf_off;
     DevBuf<int32_t> inf_flags;
@@ -449,7 +452,8 @@ struct uz_ctx {
     WalkBook book; // which slots are held, the largest request every kind of buffer has seen, the blocks that were outgrown (its own lock)
 
     // the heads of a cohort's alignment files (k_bamhead.hip, uz_head_walk): a head holds the tlen columns of its files, file f's at first[f] with
-    // room for want[f] records, have[f] of them written by the walks so far; the walk's own buffers (hd_*) are the context's and grow like the others
+    // room for want[f] records, have[f] of them written by the walks so far; the walk's own buffers (hd_*: what it hands uz_queue_inflate, on the
+    // compute stream) are the context's and grow like the others
     struct HeadDev {
         bool live = false;
         int32_t n_files = 0;
@@ -504,6 +508,15 @@ inline void uz_walk_grow(uz_ctx *c, DevBuf<T> &b, WalkKind kind, size_t n, size_
 }
 #define UZ_WGROW(w, name, ...) uz_walk_grow(c, (w).name, WK_##name, __VA_ARGS__)
 #define UZ_JGROW(J, name, ...) uz_walk_grow(c, (J).name, JK_##name, __VA_ARGS__)
+
+// the first slot of a handle table that is not live (a new one at its end)
+template <typename V>
+int new_slot(std::vector<V> &v) {
+    for (size_t i = 0; i < v.size(); i++)
+        if (!v[i].live) return (int)i;
+    v.emplace_back();
+    return (int)v.size() - 1;
+}
 
 // profiling helpers (abi.hip)
 void uz_prof_begin(uz_ctx *c, int kernel, hipEvent_t *a, hipEvent_t *b);
@@ -573,9 +586,22 @@ void uz_launch_cnv_dense(uz_ctx *c, const int32_t *cnv_counts, const int32_t *cn
 void uz_launch_phase(uz_ctx *c, FamilyDev &f, const SitesDev &s, ReadsDev &r, int32_t *status, int32_t *counts,
                      int32_t *origin, int32_t *evidence, bool defer = false);
 bool uz_finish_phase(uz_ctx *c, int32_t *status, int32_t *counts, int32_t *origin, int32_t *evidence);
-// BGZF blocks inflated on the device (k_inflate.hip): device pointers; comp padded by 1 KiB; cursor_and_err: two int32 of device memory
+// BGZF blocks inflated on the device (k_inflate.hip): device pointers; comp padded by UZ_BGZF_PAD, comp_bytes_padded: uz_bgzf_padded (bgzf_batch.hpp);
+// cursor_and_err: two int32 of device memory
 void uz_launch_inflate(uz_ctx *c, hipStream_t st, int64_t n_blocks, const uint8_t *comp, int64_t comp_bytes_padded, const int64_t *in_off,
                        const int64_t *out_off, uint8_t *out, int32_t *cursor_and_err);
+// A batch of gathered BGZF blocks queued for the device (k_inflate.hip; bgzf_batch.hpp states the rules): the pad behind d_comp cleared and the
+// tables sent on st[0], st[1] made to wait for them, then slice i of `cut` on st[i & 1] -- its bytes up, `before`, one uz_launch_inflate that
+// leaves its flag words at d_flags + 2 i, `after`.  Nothing is waited for.  The routine owns no memory and touches nothing of the context but
+// what it is handed: the caller has grown the buffers (d_comp: uz_bgzf_room(comp_bytes)), and brings the streams and the event.
+struct InflateBatch {
+    const uint8_t *comp; int64_t comp_bytes, n_blocks; const int64_t *in_off, *out_off; // the host's: tables that passed uz_bgzf_check_tables
+    uint8_t *d_comp; int64_t *d_in, *d_off; uint8_t *d_out; int32_t *d_flags;           // the device's
+    hipStream_t st[2]; hipEvent_t ev; // st[1] (and ev) null: everything on st[0]
+    bool tables_there = false;        // d_in and d_off have been queued on st[0] by the caller
+    std::function<void(size_t, hipStream_t)> before, after; // (slice, its stream), around the slice's launch; empty: nothing
+};
+void uz_queue_inflate(uz_ctx *c, const InflateBatch &b, const std::vector<int64_t> &cut);
 // the record walk on the device (k_bamwalk.hip): every pointer device memory; fill = false: counts + offsets (count, first, walked, flags), fill = true: the descriptors
 void uz_launch_bam_walk(uz_ctx *c, hipStream_t st, int n_tasks, const uint8_t *buf, const int64_t *blk_at, const int64_t *blk_coff, const int32_t *task,
                         const int64_t *span, const int32_t *reach, const int32_t *fetch, int64_t *count, const int64_t *first, int64_t *walked, int32_t *flags,
@@ -609,11 +635,6 @@ void uz_launch_bam_extract(uz_ctx *c, hipStream_t st, int64_t n, const uint8_t *
                            int thr, int32_t *start, int32_t *tlen, int32_t *mate, uint32_t *qname, uint16_t *flag, uint16_t *l_seq, uint16_t *n_cigar, uint8_t *mapq,
                            uint8_t *aux_col, uint32_t *cigar, uint8_t *seq4, uint32_t *plane, int32_t *err, uint8_t *names, int64_t n_cigar_total, int64_t n_row_units,
                            int64_t n_seq_units, int64_t names_bytes);
-// the head walk and the rank selection (k_bamhead.hip): device pointers
-void uz_launch_head_walk(uz_ctx *c, hipStream_t st, int32_t n_files, const uint8_t *buf, const int64_t *base, const int32_t *ok, const int64_t *start,
-                         const int64_t *want, const int64_t *have, const int64_t *first, int32_t *tlen, int64_t *taken, int64_t *cursor, int32_t *state);
-void uz_launch_head_rank(uz_ctx *c, hipStream_t st, int32_t n_files, const int32_t *tlen, const int64_t *first, const int64_t *n_of, const int64_t *k_of,
-                         int32_t readlen, uint32_t *out_a, uint32_t *out_b);
 // CRC-32 of inflated blocks against their BGZF footers (k_inflate.hip): device pointers; *err: 0, or 1 + a block whose checksum differs
 void uz_launch_crc32(uz_ctx *c, hipStream_t st, int64_t n_blocks, const uint8_t *out, const int64_t *out_off, const uint32_t *want, int32_t *err);
 int uz_phase_votes_impl(uz_ctx *c, int64_t *vote_off, int32_t *vote_val);
@@ -632,6 +653,18 @@ int uz_bed_rows_lists_impl(uz_ctx *c, const uz_bed_view *rows, int verbose, int 
 // the annotated VCF's record lines as text (k_vcfout.hip; vcf_row.hpp is the body)
 int uz_vcf_rows_impl(uz_ctx *c, const uz_vcf_text_view *text, const int64_t *line_at, const int64_t *ann_off, const int32_t *ann_col, const uint8_t *ann_gt,
                      const int32_t *ann_uops, const int8_t *ann_uet, int64_t *off, const uint8_t **bytes, uint8_t *handed_back);
+// the blocks of a host buffer inflated and checked (k_inflate.hip), the heads of a cohort's alignment files (k_bamhead.hip)
+void uz_bgzf_inflate_impl(uz_ctx *c, const uint8_t *comp, int64_t comp_bytes, int64_t n_blocks, const int64_t *in_off, const int64_t *out_off, uint8_t *out,
+                         int repeat, double *kernel_ms);
+void uz_bgzf_inflate_to_host_impl(uz_ctx *c, const uint8_t *comp, int64_t comp_bytes, int64_t n_blocks, const int64_t *in_off, const int64_t *out_off,
+                                 uint8_t *out);
+void uz_crc32_blocks_impl(uz_ctx *c, const uint8_t *data, int64_t n_blocks, const int64_t *off, const uint32_t *want, int64_t *first_bad);
+void uz_head_walk_impl(uz_ctx *c, int *head_id, int32_t n_files, const uint8_t *comp, int64_t comp_bytes, int64_t n_blocks, const int64_t *in_off,
+                      const int32_t *isize, const uint32_t *crc, const int64_t *blk_first, const int64_t *start, const int64_t *want, const int64_t *have,
+                      int64_t *taken, int64_t *cursor, int32_t *state);
+void uz_head_rank_impl(uz_ctx *c, int head_id, int32_t readlen, const int64_t *k, uint32_t *a, uint32_t *b);
+void uz_head_fetch_impl(uz_ctx *c, int head_id, int32_t file, int32_t *out, int64_t cap, int64_t *n);
+void uz_head_free_impl(uz_ctx *c, int head_id);
 // BGZF blocks of a host buffer (k_deflate.hip; deflate_body.hpp is the body)
 int uz_bgzf_deflate_impl(uz_ctx *c, const uint8_t *data, int64_t n_bytes, int64_t *n_blocks, const uint8_t **bgzf, int64_t *bgzf_bytes, int repeat, double *kernel_ms);
 // a BCF's records as VCF text lines (k_bcfout.hip; bcf_row.hpp is the body)
