@@ -307,6 +307,28 @@ int uz_site_classes(uz_ctx *ctx, int fam_id, uint8_t *cls_out /* [n_sites] */);
 int uz_find(uz_ctx *ctx, int fam_id, const uz_dnms_view *dnms, int mode,
             int64_t *cand_off /* [n+1] */, int64_t *het_off /* [n+1] */);
 int uz_find_fetch(uz_ctx *ctx, int32_t *cand_idx, uint8_t *cand_flags, int32_t *het_idx);
+/* uz_find and uz_find_fetch in one call with ONE wait of the host, for a caller that reads the lists at once (a staged pass: the het lists of
+ * a chunk tell its decoder what to stage): behind the fill pass one kernel writes the whole answer into `block` -- page-locked memory of this
+ * library (uz_pinned_alloc), 256-byte aligned, block_bytes long -- and the call waits for the stream once.  The list lengths are read on the
+ * device.  Layout of the block, every part starting at a multiple of 256 bytes, back to back in this order (csrc/find_answer.hpp):
+ *     header     int64 [8]: n_cand, n_het, 1 (the answer is whole), the bytes this batch's answer takes, n, 0, 0, 0
+ *     cand_off   int64 [n + 1]
+ *     het_off    int64 [n + 1]
+ *     cand_idx   int32 [n_cand]
+ *     cand_flags uint8 [n_cand]
+ *     het_idx    int32 [n_het]
+ * out [4]: UZ_FA_* bits, the bytes a block for this batch needs, n_cand, n_het.  out[0] == 0: the block holds the answer.  Otherwise it holds
+ * none -- the batch outgrew the room its lists had in HBM (UZ_FA_GREW_LISTS: they have been grown and filled again, as uz_find does) or the
+ * block (UZ_FA_BLOCK_SMALL) -- and the caller calls again, same batch, with a block of out[1] bytes or more: that call finds the lists in
+ * HBM and only writes the answer.  The lists stay in HBM for uz_phase under the same key as uz_find's. */
+#define UZ_FA_GREW_LISTS 1
+#define UZ_FA_BLOCK_SMALL 2
+int uz_find_answer(uz_ctx *ctx, int fam_id, const uz_dnms_view *dnms, int mode, void *block, size_t block_bytes, int64_t out[4]);
+/* test / debug: the last uz_find (with its uz_find_fetch) or uz_find_answer (with the call after a fall-back) of the context -- out [4]: stream
+ * waits of the host, kernel launches of the find's own (site scan, DNM staging, window passes, scan, copies; not the kernels that finish an
+ * asynchronous upload at its first use), UZ_FA_* bits of every call of it, the bytes its answer takes.  Only what these calls launch and
+ * wait for is counted: other calls on the context in between (uz_phase_begin, uploads) leave the figures as they are. */
+int uz_find_stats(uz_ctx *ctx, int64_t out[4]);
 /* Cohort form: the window emit for the DNMs of many kids -- each group with its own trio columns -- in ONE launch sequence instead of one
  * uz_find per kid (the per-family loop of find, informative_site_finder.py:213, :558-568).  `groups` as in uz_phase_cohort, but only fam_id,
  * dnm_first and dnm_count count (reads_id and cutoff are ignored); `dnms` holds all groups' DNMs.  The groups must cover [0, dnms->n) exactly

@@ -1,6 +1,7 @@
 // abi.hip -- the extern "C" entry points of include/unfazed_hip.h: context, staging of
 // the decoded columns into HBM, and the launch sequence of the stages.
 #include "uz_ctx.hpp"
+#include "find_answer.hpp"
 
 #include <chrono>
 #include <algorithm>
@@ -224,11 +225,43 @@ __global__ __launch_bounds__(256) void k_copy(W *__restrict__ dst, const W *__re
 }
 void uz_kcopy(uz_ctx *c, void *dst, const void *src, size_t bytes) {
     if (!bytes) return;
+    uz_find_launched(c, 1);
     const uintptr_t a = (uintptr_t)dst | (uintptr_t)src | (uintptr_t)bytes;
     auto grid = [](size_t n) { return dim3((unsigned)std::min<size_t>((n + 255) / 256, 1024)); };
     if (a % 16 == 0) hipLaunchKernelGGL(k_copy<uint4>, grid(bytes / 16), dim3(256), 0, c->stream, (uint4 *)dst, (const uint4 *)src, bytes / 16);
     else if (a % 4 == 0) hipLaunchKernelGGL(k_copy<uint32_t>, grid(bytes / 4), dim3(256), 0, c->stream, (uint32_t *)dst, (const uint32_t *)src, bytes / 4);
     else hipLaunchKernelGGL(k_copy<uint8_t>, grid(bytes), dim3(256), 0, c->stream, (uint8_t *)dst, (const uint8_t *)src, bytes);
+    UZ_HIP(hipGetLastError());
+}
+struct KCopySegs { KCopySeg s[UZ_KCOPY_SEGS]; };
+template <typename W>
+__device__ __forceinline__ void copy_seg(void *dst, const void *src, size_t n) {
+    W *__restrict__ d = (W *)dst;
+    const W *__restrict__ s = (const W *)src;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) d[i] = s[i];
+}
+__global__ __launch_bounds__(256) void k_copy_many(KCopySegs g) {
+    const KCopySeg sg = g.s[blockIdx.y];
+    const uintptr_t a = (uintptr_t)sg.dst | (uintptr_t)sg.src | (uintptr_t)sg.bytes; // (uniform over the workgroup)
+    if (a % 16 == 0) copy_seg<uint4>(sg.dst, sg.src, sg.bytes / 16);
+    else if (a % 4 == 0) copy_seg<uint32_t>(sg.dst, sg.src, sg.bytes / 4);
+    else copy_seg<uint8_t>(sg.dst, sg.src, sg.bytes);
+}
+void uz_kcopy_many(uz_ctx *c, const KCopySeg *segs, int n_segs) {
+    KCopySegs g;
+    int m = 0;
+    size_t units = 0; // of the segment with the most of them, in the width it is copied at
+    for (int k = 0; k < n_segs; k++) {
+        if (!segs[k].bytes) continue;
+        UZ_REQUIRE(m < UZ_KCOPY_SEGS, UZ_E_ARG, "uz_kcopy_many: too many segments");
+        g.s[m++] = segs[k];
+        const uintptr_t a = (uintptr_t)segs[k].dst | (uintptr_t)segs[k].src | (uintptr_t)segs[k].bytes;
+        units = std::max(units, segs[k].bytes / (a % 16 == 0 ? 16 : a % 4 == 0 ? 4 : 1));
+    }
+    if (!m) return;
+    uz_find_launched(c, 1);
+    for (int k = m; k < UZ_KCOPY_SEGS; k++) g.s[k] = KCopySeg{nullptr, nullptr, 0};
+    hipLaunchKernelGGL(k_copy_many, dim3((unsigned)std::min<size_t>((units + 255) / 256, 1024), (unsigned)m), dim3(256), 0, c->stream, g);
     UZ_HIP(hipGetLastError());
 }
 
@@ -1907,6 +1940,9 @@ int uz_find(uz_ctx *c, int fam_id, const uz_dnms_view *d, int mode, int64_t *can
         SitesDev &s = sites_of(c, f.sites_id);
         UZ_REQUIRE(d != nullptr && d->n >= 0, UZ_E_ARG, "bad DNM view");
         c->phase_valid = false;
+        FindCount counting(c);
+        c->find_stat[0] = c->find_stat[1] = c->find_stat[2] = c->find_stat[3] = 0;
+        c->find_answer_again = false;
         const bool cnv = (mode & UZ_FIND_WHOLE_REGION) != 0;
         if (cnv) refuse_het_only(f, "a whole-region find");
         if (!uz_site_scan_fresh(c, f, cnv)) uz_launch_site_scan(c, f, s, cnv); // (reads nothing of the batch: queued before the batch is staged)
@@ -1922,18 +1958,75 @@ int uz_find(uz_ctx *c, int fam_id, const uz_dnms_view *d, int mode, int64_t *can
     });
 }
 
+int uz_find_answer(uz_ctx *c, int fam_id, const uz_dnms_view *d, int mode, void *block, size_t block_bytes, int64_t out[4]) {
+    return guarded(c, [&] {
+        FamilyDev &f = fam_of(c, fam_id);
+        SitesDev &s = sites_of(c, f.sites_id);
+        UZ_REQUIRE(d != nullptr && d->n >= 0, UZ_E_ARG, "bad DNM view");
+        FindCount counting(c);
+        UZ_REQUIRE(block != nullptr && (uintptr_t)block % UZ_FA_ALIGN == 0 && inside_one_pinned_block((const uint8_t *)block, (const uint8_t *)block + block_bytes),
+                   UZ_E_ARG, "uz_find_answer: the block must be page-locked memory of this library (uz_pinned_alloc), 256-byte aligned");
+        c->phase_valid = false;
+        const bool cnv = (mode & UZ_FIND_WHOLE_REGION) != 0;
+        if (cnv) refuse_het_only(f, "a whole-region find");
+        FindAnswer ans{(uint8_t *)block, block_bytes, 0, 0};
+        const size_t n = (size_t)d->n;
+        // the call after a fall-back, same batch with a block grown to what that call reported: the lists are in HBM, whole (grown and filled
+        // again where they had to be) -- only the answer is written.  The counters go on from the first call's.
+        // (the recall first: the totals the block is held against are then this batch's, whatever ran on the context in between; a block that
+        // is still too small takes the whole find below, which reports the size again)
+        if (c->find_answer_again && n > 0 && find_recall(c, find_key_of(c, fam_id, mode, d)) &&
+            uz_find_answer_fits(uz_find_answer_layout(d->n, c->n_cand, c->n_het), block_bytes)) {
+            c->dn_n_of_find = d->n;
+            UZ_REQUIRE(uz_launch_find_answer(c, &ans, INT64_MAX, INT64_MAX), UZ_E_STATE, "uz_find_answer: the block reported as sufficient is not");
+        } else {
+            c->find_stat[0] = c->find_stat[1] = c->find_stat[2] = c->find_stat[3] = 0;
+            if (!uz_site_scan_fresh(c, f, cnv)) uz_launch_site_scan(c, f, s, cnv); // (reads nothing of the batch: queued before the batch is staged)
+            uz_stage_dnms(c, d);
+            const FindKey key = find_key_of(c, fam_id, mode, d); // (behind the site scan's launch: host work beside the device's)
+            find_target(c);
+            uz_launch_find(c, f, s, mode, true, &ans);
+            if (f.het_only) uz_check_upload_flag(c);
+            find_done(c, key);
+            c->find_fam = fam_id;
+            if (n == 0) { // nothing was launched: the answer of an empty batch is written here
+                const FindAnswerLayout L = uz_find_answer_layout(0, 0, 0);
+                ans.need = L.total;
+                if (!uz_find_answer_fits(L, block_bytes)) ans.code |= UZ_FA_BLOCK_SMALL;
+                else {
+                    memset(block, 0, (size_t)L.total);
+                    int64_t *head = (int64_t *)block;
+                    head[2] = 1; head[3] = (int64_t)L.total;
+                }
+            }
+        }
+        c->find_answer_again = ans.code != 0;
+        c->find_stat[2] |= ans.code;
+        c->find_stat[3] = (int64_t)ans.need;
+        if (out) { out[0] = ans.code; out[1] = (int64_t)ans.need; out[2] = c->n_cand; out[3] = c->n_het; }
+    });
+}
+int uz_find_stats(uz_ctx *c, int64_t out[4]) {
+    if (!c || !out) return UZ_E_ARG;
+    for (int k = 0; k < 4; k++) out[k] = c->find_stat[k];
+    return 0;
+}
+
 int uz_find_fetch(uz_ctx *c, int32_t *cand_idx, uint8_t *cand_flags, int32_t *het_idx) {
     return guarded(c, [&] {
         UZ_REQUIRE(c->find_valid, UZ_E_STATE, "uz_find_fetch before uz_find");
+        FindCount counting(c);
         // destinations in page-locked memory of this library (uz_pinned_alloc): by copy kernels, past the DMA engine's queue (uz_launch_find)
         const bool pinned = (!cand_idx || !c->n_cand || inside_one_pinned_block((const uint8_t *)cand_idx, (const uint8_t *)(cand_idx + c->n_cand))) &&
                             (!cand_flags || !c->n_cand || inside_one_pinned_block(cand_flags, cand_flags + c->n_cand)) &&
                             (!het_idx || !c->n_het || inside_one_pinned_block((const uint8_t *)het_idx, (const uint8_t *)(het_idx + c->n_het)));
         if (pinned) {
-            if (cand_idx && c->n_cand) uz_kcopy(c, cand_idx, c->cand_idx.p, (size_t)c->n_cand * sizeof(int32_t));
-            if (cand_flags && c->n_cand) uz_kcopy(c, cand_flags, c->cand_flags.p, (size_t)c->n_cand);
-            if (het_idx && c->n_het) uz_kcopy(c, het_idx, c->het_idx.p, (size_t)c->n_het * sizeof(int32_t));
+            const KCopySeg lists[3] = {{cand_idx, c->cand_idx.p, cand_idx ? (size_t)c->n_cand * sizeof(int32_t) : 0},
+                                       {cand_flags, c->cand_flags.p, cand_flags ? (size_t)c->n_cand : 0},
+                                       {het_idx, c->het_idx.p, het_idx ? (size_t)c->n_het * sizeof(int32_t) : 0}};
+            uz_kcopy_many(c, lists, 3); // ONE launch for the three lists
             UZ_HIP(hipStreamSynchronize(c->stream));
+            uz_find_waited(c);
             return;
         }
         if (cand_idx && c->n_cand)
@@ -1943,6 +2036,7 @@ int uz_find_fetch(uz_ctx *c, int32_t *cand_idx, uint8_t *cand_flags, int32_t *he
         if (het_idx && c->n_het)
             UZ_HIP(hipMemcpyAsync(het_idx, c->het_idx.p, (size_t)c->n_het * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
         UZ_HIP(hipStreamSynchronize(c->stream));
+        uz_find_waited(c);
     });
 }
 

@@ -60,10 +60,20 @@ __device__ __forceinline__ int32_t grp_lower_bound(F ld, int32_t a, int32_t b, i
     }
     return a;
 }
-__global__ __launch_bounds__(256, UZ_BW_MIN_WAVES) void k_phase_bounds(PhaseArgs a, int32_t *bounds /* [5n] */) {
+// The pass is the first kernel of a batch's read stage, so it also clears what the kernels behind it in stream order fill or count in -- the
+// reduced record (k_bounds_reduce), the work cursors with both give-up counts and the list pool's fill level (k_phase): 1.8 KB by its first
+// workgroup, where four hipMemsetAsync stood in the stream -- and writes the empty het ranges of the DNMs it does not search for.
+struct PhaseClears { int32_t *red; int32_t *cursor; unsigned long long *pool_cursor; int red_words, cursor_words; long long n_het; };
+__global__ __launch_bounds__(256, UZ_BW_MIN_WAVES) void k_phase_bounds(PhaseArgs a, int32_t *bounds /* [5n] */, PhaseClears z) {
     constexpr int GL = UZ_BW_LANES, NCH = 2 * UZ_BW_SITES;
     static_assert(GL == 1 || GL == 2 || GL == 4 || GL == 8 || GL == 16 || GL == 32 || GL == 64, "a group is a power of two inside a wavefront");
     __shared__ int32_t s_stage[256 / GL][UZ_BW_STAGE];
+    if (blockIdx.x == 0) {
+        for (int i = threadIdx.x; i < z.red_words; i += 256) z.red[i] = 0;
+        for (int i = threadIdx.x; i < z.cursor_words; i += 256) z.cursor[i] = 0;
+        if (threadIdx.x < 2) z.pool_cursor[threadIdx.x] = 0;
+        if (threadIdx.x == 2) { a.pre_ha[z.n_het] = 0; a.pre_hl[z.n_het] = 0; } // (the slot behind each column)
+    }
     const int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / GL;
     const int lane = threadIdx.x & (GL - 1), gbase = (threadIdx.x & 63) & ~(GL - 1);
     const int d = g < a.n ? (int)g : a.n - 1; // whole groups stay converged for the shuffles below
@@ -76,6 +86,10 @@ __global__ __launch_bounds__(256, UZ_BW_MIN_WAVES) void k_phase_bounds(PhaseArgs
             b[0] = b[1] = b[4] = 0;
             b[2] = nh; b[3] = nc;
             for (int k = 0; k < 4; k++) a.pre_win[4 * d + k] = 0;
+        }
+        if (nc <= 0 || a.no_extended) { // no search writes this DNM's het ranges (uz_phase_bounds_w): they must read as empty
+            const long long h0 = a.het_off[d];
+            for (int h = lane; h < nh; h += GL) { a.pre_ha[h0 + h] = 0; a.pre_hl[h0 + h] = 0; }
         }
         const RD &R = a.R;
         const int tid = a.rcontig[d];
@@ -181,6 +195,11 @@ __global__ __launch_bounds__(WG_NT, LDS ? UZ_PHASE_MIN_WAVES : 5) void k_phase(P
     // segment its layout (PhaseArgs is the kernel's first and only explicit argument: offset 0)
     (void)a_by_value;
     const PhaseArgsK ap = (PhaseArgsK)__builtin_amdgcn_kernarg_segment_ptr();
+    if constexpr (!LDS) {
+        // the HBM build only ever runs over a list (what both arena launches gave up), and that list is usually empty: out before the cursor's
+        // atomic -- 2 048 workgroups taking their turn on one word were the 27 us of this launch in every chunk of a staged pass
+        if (*uz_g(ap->src_count) <= 0) return;
+    }
     uint8_t *const scr_base = uz_g(ap->scratch) + (size_t)blockIdx.x * ap->scratch_per_wg;
 #ifdef UZ_PHASE_TIMING
     if (threadIdx.x < 24) sh.tick[threadIdx.x] = 0;
@@ -423,13 +442,19 @@ void uz_launch_phase(uz_ctx *c, FamilyDev &f, const SitesDev &s, ReadsDev &r, in
     st->pre_win.ensure((size_t)4 * n); st->pre_h.ensure(2 * ((size_t)c->n_het + 1));
     a.pre_win = st->pre_win.p; a.pre_ha = st->pre_h.p; a.pre_hl = st->pre_h.p + (size_t)c->n_het + 1;
     st->n_het = c->n_het;
-    // DNMs without candidates leave their het ranges untouched: they must read as empty
-    UZ_HIP(hipMemsetAsync(st->pre_h.p, 0, 2 * ((size_t)c->n_het + 1) * sizeof(int32_t), c->stream));
+    const size_t res_ints = (size_t)7 * n + ((7 * (size_t)n) & 1); // the results, padded to eight bytes; the pool's fill level behind them
+    st->res.ensure(res_ints + 4);
+    st->pool_cursor = (unsigned long long *)(st->res.p + res_ints);
+    // the work cursors, and behind them the counts of the two lists of given-up DNMs: ONE block, cleared as one
+    constexpr int cursor_words = 16 * (UZ_PHASE_PARTS + 2) + 32;
+    st->cursor.ensure(cursor_words);
+    st->bounds_red.ensure(sizeof(BoundsRed) / sizeof(int32_t) + 16);
     {
         const unsigned nb = (unsigned)(((int64_t)n * UZ_BW_LANES + 255) / 256);
+        const PhaseClears z = {st->bounds_red.p, st->cursor.p, st->pool_cursor, (int)(sizeof(BoundsRed) / sizeof(int32_t)), cursor_words, (long long)c->n_het};
         ProfScope ps(c, UZ_K_SIZING);
         UZ_TRACE("k_phase_bounds");
-        hipLaunchKernelGGL(k_phase_bounds, dim3(nb), dim3(256), 0, c->stream, a, st->bounds.p);
+        hipLaunchKernelGGL(k_phase_bounds, dim3(nb), dim3(256), 0, c->stream, a, st->bounds.p, z);
         UZ_HIP(hipGetLastError());
     }
     if (st->bounds_h_cap < sizeof(BoundsRed) / sizeof(int32_t)) {
@@ -438,8 +463,6 @@ void uz_launch_phase(uz_ctx *c, FamilyDev &f, const SitesDev &s, ReadsDev &r, in
         st->bounds_h_cap = sizeof(BoundsRed) / sizeof(int32_t) + 64;
         UZ_HIP(hipHostMalloc((void **)&st->bounds_h, st->bounds_h_cap * sizeof(int32_t), hipHostMallocDefault));
     }
-    st->bounds_red.ensure(sizeof(BoundsRed) / sizeof(int32_t) + 16);
-    UZ_HIP(hipMemsetAsync(st->bounds_red.p, 0, sizeof(BoundsRed), c->stream));
     hipLaunchKernelGGL(k_bounds_reduce, dim3((unsigned)std::max(1, std::min(UZ_BR_BLOCKS, (n + 255) / 256))), dim3(256), 0, c->stream, (const int32_t *)st->bounds.p, n,
                        reinterpret_cast<BoundsRed *>(st->bounds_red.p));
     UZ_HIP(hipGetLastError());
@@ -449,9 +472,6 @@ void uz_launch_phase(uz_ctx *c, FamilyDev &f, const SitesDev &s, ReadsDev &r, in
     // bounds come back with the results, and only when they exceed what was assumed is the batch run again on its own sizes.
     // (UZ_PHASE_NO_SPEC=1, the capacity / arena test hooks and the first batch of a context take the exact path.)
     const BoundsRed *const bh_own = reinterpret_cast<const BoundsRed *>(st->bounds_h); // (kept apart from the result staging below: both are read after the run)
-    uz_kcopy(c, st->bounds_h, st->bounds_red.p, sizeof(BoundsRed));
-    if (!st->bounds_ready) UZ_HIP(hipEventCreateWithFlags(&st->bounds_ready, hipEventDisableTiming));
-    UZ_HIP(hipEventRecord(st->bounds_ready, c->stream));
     auto check_upload_flags = [&] { uz_check_upload_flag(c); };
     auto exact_sizes = [&](const BoundsRed *bh) { return phase_exact_sizes(bh, n); };
     if (st->n_cus <= 0) { // asked once: the query is not cheap
@@ -463,11 +483,14 @@ void uz_launch_phase(uz_ctx *c, FamilyDev &f, const SitesDev &s, ReadsDev &r, in
     const bool hooks = getenv("UZ_TEST_CAP_T") || getenv("UZ_TEST_PHASE_ARENA");
     bool speculative = st->spec_valid && !no_spec && !hooks && !st->force_exact;
     st->force_exact = false;
-    const size_t res_ints = (size_t)7 * n + ((7 * (size_t)n) & 1); // the results, padded to eight bytes; the pool's fill level behind them
-    st->res.ensure(res_ints + 4);
-    st->pool_cursor = (unsigned long long *)(st->res.p + res_ints);
-    // the work cursors, and behind them the counts of the two lists of given-up DNMs: ONE block, cleared by one memset per attempt
-    st->cursor.ensure(16 * (UZ_PHASE_PARTS + 2) + 32);
+    // An exact run waits for the reduced record in front of its launches: it comes back now, by a copy of its own.  A speculative run reads it
+    // behind the run: it rides with the results (ONE copy launch at the end of the sequence).
+    const bool bounds_early = !speculative;
+    if (bounds_early) {
+        uz_kcopy(c, st->bounds_h, st->bounds_red.p, sizeof(BoundsRed));
+        if (!st->bounds_ready) UZ_HIP(hipEventCreateWithFlags(&st->bounds_ready, hipEventDisableTiming));
+        UZ_HIP(hipEventRecord(st->bounds_ready, c->stream));
+    }
     // two lists of given-up DNMs: what the first launch leaves for the second (larger arenas), what the second leaves for the HBM build
     st->retry.ensure(2 * ((size_t)n + 16));
     int32_t *const retry1_list = st->retry.p, *const retry2_list = st->retry.p + (size_t)n + 16;
@@ -504,7 +527,7 @@ void uz_launch_phase(uz_ctx *c, FamilyDev &f, const SitesDev &s, ReadsDev &r, in
             z.caps = st->spec_caps; z.arena = st->spec_arena; z.arena2 = st->spec_arena2;
             z.sumP = (long long)(st->spec_sumP_per_dnm * (double)n) + 4096;
         } else {
-            UZ_HIP(hipEventSynchronize(st->bounds_ready));
+            if (bounds_early) UZ_HIP(hipEventSynchronize(st->bounds_ready)); // (else: the speculative run before this one brought the record back)
             check_upload_flags();
             z = exact_sizes(bh_own);
             if (const char *e = getenv("UZ_TEST_CAP_T")) { // test hook: a scratch too small for some DNMs -> they must come back as UZ_ST_CAPACITY
@@ -546,8 +569,10 @@ void uz_launch_phase(uz_ctx *c, FamilyDev &f, const SitesDev &s, ReadsDev &r, in
         st->pool.ensure(pool_cap);
         a.pool = st->pool.p; a.pool_cap = pool_cap;
         for (int attempt = 0; attempt < 4; attempt++) {
-            UZ_HIP(hipMemsetAsync(st->cursor.p, 0, (16 * (UZ_PHASE_PARTS + 2) + 32) * sizeof(int32_t), c->stream)); // (cursors + both give-up counts)
-            UZ_HIP(hipMemsetAsync(st->pool_cursor, 0, 2 * sizeof(unsigned long long), c->stream));
+            if (round > 0 || attempt > 0) { // a batch run again (rare): the first run's counts are cleared here; the first run's by k_phase_bounds
+                UZ_HIP(hipMemsetAsync(st->cursor.p, 0, cursor_words * sizeof(int32_t), c->stream)); // (cursors + both give-up counts)
+                UZ_HIP(hipMemsetAsync(st->pool_cursor, 0, 2 * sizeof(unsigned long long), c->stream));
+            }
             {
                 // Three launches.  The arena is sized for most of the batch's DNMs, not all (the more DNMs a CU holds, the faster the batch);
                 // the rest are redone by a second launch of the same build with arenas for the largest estimate -- a DNM's latency in the
@@ -574,10 +599,13 @@ void uz_launch_phase(uz_ctx *c, FamilyDev &f, const SitesDev &s, ReadsDev &r, in
             }
             UZ_TRACE("after k_phase");
             *hused = 0;
-            uz_kcopy(c, hres, st->res.p, res_ints * sizeof(int32_t) + sizeof(unsigned long long)); // the results and the pool's fill level: one copy
             int32_t *const hretry = (int32_t *)(hused + 1);
             *hretry = 0;
-            uz_kcopy(c, hretry, retry2, sizeof(int32_t)); // DNMs that took the HBM build
+            // ONE copy launch: the results with the pool's fill level, the DNMs that took the HBM build, and (speculative run) the reduced record
+            const KCopySeg back[3] = {{hres, st->res.p, res_ints * sizeof(int32_t) + sizeof(unsigned long long)},
+                                      {hretry, retry2, sizeof(int32_t)},
+                                      {st->bounds_h, st->bounds_red.p, speculative ? sizeof(BoundsRed) : 0}};
+            uz_kcopy_many(c, back, 3);
             if (defer && speculative) { // uz_phase_begin: the run stays in flight; uz_finish_phase waits for it and judges it
                 st->pending = true;
                 st->pend_caps = caps; st->pend_pool_cap = a.pool_cap; st->pend_want_lists = a.want_lists;

@@ -12,6 +12,7 @@
 // (:46-73), get_kid_allele (:76-134), the per-variant body of find (:239-339, duplicated at
 // :442-543) and get_position (:10-43).  No MFMA: there is no contraction here.
 #include "uz_ctx.hpp"
+#include "find_answer.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -534,10 +535,10 @@ __global__ __launch_bounds__(256) void k_window_region(WinArgs a, int32_t *cnt_c
     if (!FILL && lane == 0) { cnt_c[d] = (int32_t)nc; cnt_h[d] = (int32_t)nh; }
 }
 
-// exclusive scan of two count arrays into int64 offsets (n+1 entries), a tile of 4096 counts per workgroup: the tiles' sums first
-// (k_scan2_sums), then every workgroup adds up the sums of the tiles before its own and scans its tile (coalesced 16-byte loads,
-// wave-shuffle scan).  (Through round 6 ONE workgroup walked the arrays tile by tile: 88 us for the 100 k DNMs of the bench batch,
-// 3.5 us per tile of load latency and two barriers with the rest of the chip idle.)
+// exclusive scan of two count arrays into int64 offsets (n+1 entries), a tile of UZ_SCAN2_TILE counts per workgroup (coalesced 16-byte
+// loads, wave-shuffle scan).  (Through round 6 ONE workgroup walked the arrays tile by tile: 88 us for the 100 k DNMs of the bench batch,
+// 3.5 us per tile of load latency and two barriers with the rest of the chip idle.  Through round 16 two launches in workgroups of 1024: the
+// tiles' sums, then the tiles.)
 __device__ __forceinline__ void scan2_load(int32_t n, int32_t i0, const int32_t *c0, const int32_t *c1, int (&v0)[4], int (&v1)[4]) {
     v0[0] = v0[1] = v0[2] = v0[3] = 0; v1[0] = v1[1] = v1[2] = v1[3] = 0;
     if (i0 + 3 < n) {
@@ -548,6 +549,73 @@ __device__ __forceinline__ void scan2_load(int32_t n, int32_t i0, const int32_t 
         for (int k = 0; k < 4; k++) if (i0 + k < n) { v0[k] = c0[i0 + k]; v1[k] = c1[i0 + k]; }
     }
 }
+// A batch of up to UZ_SCAN2_ONE_MAX counts (every chunk of a staged pass): ONE launch in workgroups of 256, the sum of the counts in front of a tile is added up by the tile's own workgroup from the raw counts --
+// L2 reads (170 KB for the last tile of a 21 k-DNM chunk, 800 KB at 100 k DNMs), no kernel in front and nothing any workgroup waits for.
+// (Workgroups of 256, not 1024: inside a staged pass the header build holds every CU with workgroups of its own, and a 16-wave workgroup
+// finds room only when several of them have left the same CU.)
+// A larger batch takes the two launches in workgroups of 1 024 below (k_scan2_sums, k_scan2: the tiles' sums, then the tiles): the read of everything
+// in front of a tile grows with the batch -- at the 100 k DNMs of the resident pass the one launch was 0.033 ms slower than the pair (round 17).
+#define UZ_SCAN2_TILE 2048
+#define UZ_SCAN2_ONE_MAX (16 * UZ_SCAN2_TILE)
+__global__ __launch_bounds__(256) void k_scan2_tile(int32_t n, const int32_t *__restrict__ c0, const int32_t *__restrict__ c1, int64_t *__restrict__ o0,
+                                                    int64_t *__restrict__ o1) {
+    constexpr int IPT = UZ_SCAN2_TILE / 256; // counts per lane, four to a load
+    static_assert(IPT % 4 == 0 && IPT * 256 == UZ_SCAN2_TILE, "a lane loads whole int4s");
+    __shared__ int wsum[2][4];
+    __shared__ long long csum[2][4];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int32_t tile0 = (int32_t)blockIdx.x * UZ_SCAN2_TILE; // (a multiple of four, and in front of the tile every count exists: whole int4s)
+    long long q0 = 0, q1 = 0;
+    {
+        const int4 *__restrict__ a4 = reinterpret_cast<const int4 *>(c0), *__restrict__ b4 = reinterpret_cast<const int4 *>(c1);
+        const int32_t m = tile0 / 4;
+#pragma unroll 8
+        for (int32_t i = t; i < m; i += 256) {
+            const int4 a = a4[i], b = b4[i];
+            q0 += (long long)a.x + a.y + a.z + a.w;
+            q1 += (long long)b.x + b.y + b.z + b.w;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { q0 += __shfl_xor(q0, off, 64); q1 += __shfl_xor(q1, off, 64); }
+    const int32_t i0 = tile0 + IPT * t;
+    int v0[IPT], v1[IPT];
+#pragma unroll
+    for (int k = 0; k < IPT; k += 4) {
+        int w0[4], w1[4];
+        scan2_load(n, i0 + k, c0, c1, w0, w1);
+#pragma unroll
+        for (int j = 0; j < 4; j++) { v0[k + j] = w0[j]; v1[k + j] = w1[j]; }
+    }
+    int s0 = 0, s1 = 0;
+#pragma unroll
+    for (int k = 0; k < IPT; k++) { s0 += v0[k]; s1 += v1[k]; }
+    int in0 = s0, in1 = s1;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int u0 = __shfl_up(in0, off, 64), u1 = __shfl_up(in1, off, 64);
+        if (lane >= off) { in0 += u0; in1 += u1; }
+    }
+    if (lane == 63) { wsum[0][wv] = in0; wsum[1][wv] = in1; }
+    if (lane == 0) { csum[0][wv] = q0; csum[1][wv] = q1; }
+    __syncthreads();
+    int64_t base0 = 0, base1 = 0, pre0 = 0, pre1 = 0, tot0 = 0, tot1 = 0;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+        const int a = wsum[0][w], b = wsum[1][w];
+        if (w < wv) { pre0 += a; pre1 += b; }
+        tot0 += a; tot1 += b;
+        base0 += csum[0][w]; base1 += csum[1][w];
+    }
+    int64_t p0 = base0 + pre0 + (in0 - s0), p1 = base1 + pre1 + (in1 - s1);
+#pragma unroll
+    for (int k = 0; k < IPT; k++) {
+        if (i0 + k < n) { o0[i0 + k] = p0; o1[i0 + k] = p1; }
+        p0 += v0[k]; p1 += v1[k];
+    }
+    if (t == 0 && blockIdx.x == gridDim.x - 1) { o0[n] = base0 + tot0; o1[n] = base1 + tot1; }
+}
+
 __global__ __launch_bounds__(1024) void k_scan2_sums(int32_t n, const int32_t *c0, const int32_t *c1, int64_t *part /* [2 tiles] */) {
     __shared__ long long wsum[2][16];
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
@@ -1093,6 +1161,7 @@ void ensure_ab_lut(uz_ctx *c, const SiteParams &sp) {
     int special = 0;
     UZ_HIP(hipMemcpyAsync(&special, flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     UZ_HIP(hipStreamSynchronize(c->stream));
+    uz_find_waited(c); uz_find_launched(c, 2); // (once per parameter set)
     c->ab_lut_t0_special = special != 0;
     c->ab_lut_valid = true;
     c->ab_lut_params = c->P;
@@ -1119,6 +1188,7 @@ void launch_site_scan(uz_ctx *c, const FamPtrs &fp, uint8_t *cls, int64_t n, boo
             const int64_t per = (wgs + n_fam - 1) / n_fam;
             nb = std::max<int64_t>(1, std::min<int64_t>(n_chunks, std::max<int64_t>(per, 16)));
         }
+        uz_find_launched(c, 1);
         hipLaunchKernelGGL(kern, dim3((unsigned)nb, (unsigned)(batch ? n_fam : 1)), dim3(256), 0, c->stream, fp, cls, n, sp,
                            (const int2 *)c->ab_lut.p, (const uint32_t *)(c->ab_lut.p + (size_t)4 * UZ_AB_LUT_N * 2 + 4), batch);
     };
@@ -1140,6 +1210,7 @@ static void launch_site_scan_wide(uz_ctx *c, FamilyDev &f, bool with_cnv) {
     if (f.n_wide <= 0) return;
     const SiteParams P = make_site_params(c->P);
     const unsigned nb = (unsigned)((f.n_wide + 255) / 256);
+    uz_find_launched(c, 1);
     if (with_cnv) hipLaunchKernelGGL(k_site_scan_wide<true>, dim3(nb), dim3(256), 0, c->stream, fam_ptrs(f), f.cls, f.n_wide, f.wide_site, f.wide_depth, P);
     else hipLaunchKernelGGL(k_site_scan_wide<false>, dim3(nb), dim3(256), 0, c->stream, fam_ptrs(f), f.cls, f.n_wide, f.wide_site, f.wide_depth, P);
     UZ_HIP(hipGetLastError());
@@ -1181,13 +1252,76 @@ void uz_launch_site_scan_many(uz_ctx *c, FamilyDev *const *fams, int n_fam, cons
     }
 }
 
-void uz_launch_find(uz_ctx *c, FamilyDev &f, const SitesDev &s, int mode, bool host_offsets) {
+// The answer of a find in ONE block of the caller's page-locked memory (unfazed_hip.h: uz_find_answer; layout: find_answer.hpp), by ONE launch
+// behind the fill pass: the list lengths are read here, on the device, from the ends of the two offset columns, so the host need not learn
+// them first (through round 16: offsets back, wait, then three list copies and a second wait).  Every workgroup works the layout out for
+// itself; blockIdx.y picks the part.  A batch that outgrew the lists' room (the fill pass wrote only what fitted) or the block gets the header
+// alone, with what it would have needed.
+struct FindAnswerArgs {
+    uint8_t *block; uint64_t bytes;
+    int32_t n;
+    const int64_t *cand_off, *het_off;
+    const int32_t *cand_idx, *het_idx;
+    const uint8_t *cand_flags;
+    int64_t room_c, room_h;
+};
+template <typename W>
+__device__ __forceinline__ void answer_part(uint8_t *dst, const void *src, uint64_t n) {
+    W *__restrict__ d = (W *)dst;
+    const W *__restrict__ s = (const W *)src;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) d[i] = s[i];
+}
+__global__ __launch_bounds__(256) void k_find_answer(FindAnswerArgs g) {
+    const int64_t nc = g.cand_off[g.n], nh = g.het_off[g.n];
+    const FindAnswerLayout L = uz_find_answer_layout(g.n, nc, nh);
+    const bool fits = nc <= g.room_c && nh <= g.room_h && uz_find_answer_fits(L, g.bytes);
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < UZ_FA_HEAD_WORDS) { // (the launcher has held the block against the header and the offsets)
+        const int64_t head[UZ_FA_HEAD_WORDS] = {nc, nh, fits ? 1 : 0, (int64_t)L.total, g.n, 0, 0, 0};
+        reinterpret_cast<int64_t *>(g.block)[threadIdx.x] = head[threadIdx.x];
+    }
+    if (!fits) return;
+    switch (blockIdx.y) {
+    case 0: answer_part<int64_t>(g.block + L.off[1], g.cand_off, (uint64_t)g.n + 1); break;
+    case 1: answer_part<int64_t>(g.block + L.off[2], g.het_off, (uint64_t)g.n + 1); break;
+    case 2: answer_part<int32_t>(g.block + L.off[3], g.cand_idx, (uint64_t)nc); break;
+    case 3: { // the flag bytes: whole words, then the last one to three bytes on their own (no read beyond the list)
+        const uint64_t words = (uint64_t)nc / 4;
+        answer_part<uint32_t>(g.block + L.off[4], g.cand_flags, words);
+        if (blockIdx.x == 0 && threadIdx.x < (unsigned)((uint64_t)nc - 4 * words)) (g.block + L.off[4])[4 * words + threadIdx.x] = g.cand_flags[4 * words + threadIdx.x];
+        break;
+    }
+    default: answer_part<int32_t>(g.block + L.off[5], g.het_idx, (uint64_t)nh); break;
+    }
+}
+bool uz_launch_find_answer(uz_ctx *c, FindAnswer *ans, int64_t room_c, int64_t room_h) {
+    const int32_t n = c->dn_n_of_find;
+    const FindAnswerLayout L0 = uz_find_answer_layout(n, 0, 0);
+    UZ_REQUIRE(uz_find_answer_fits_offsets(L0, ans->bytes), UZ_E_STATE, "uz_launch_find_answer: a block without room for the offsets");
+    FindAnswerArgs g;
+    g.block = ans->block; g.bytes = ans->bytes; g.n = n;
+    g.cand_off = c->cand_off.p; g.het_off = c->het_off.p; g.cand_idx = c->cand_idx.p; g.het_idx = c->het_idx.p; g.cand_flags = c->cand_flags.p;
+    g.room_c = room_c; g.room_h = room_h;
+    const unsigned nbx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(128, ((int64_t)n * 8 + 255) / 256)); // (a DNM has some ten sites in its lists)
+    hipLaunchKernelGGL(k_find_answer, dim3(nbx, 5), dim3(256), 0, c->stream, g);
+    UZ_HIP(hipGetLastError());
+    uz_find_launched(c, 1);
+    UZ_HIP(hipStreamSynchronize(c->stream));
+    uz_find_waited(c);
+    const int64_t *head = reinterpret_cast<const int64_t *>(ans->block);
+    c->n_cand = head[0]; c->n_het = head[1];
+    if (!c->cand_off_h.empty()) { c->cand_off_h[(size_t)n] = head[0]; c->het_off_h[(size_t)n] = head[1]; }
+    ans->need = (uint64_t)head[3];
+    return head[2] != 0;
+}
+
+void uz_launch_find(uz_ctx *c, FamilyDev &f, const SitesDev &s, int mode, bool host_offsets, FindAnswer *ans) {
     const int32_t n = c->dn.n;
+    c->dn_n_of_find = n;
     c->cnt_c.ensure((size_t)n + 1);
     c->cnt_h.ensure((size_t)n + 1);
     c->cand_off.ensure((size_t)n + 1);
     c->het_off.ensure((size_t)n + 1);
-    if (host_offsets || n <= 0) { c->cand_off_h.assign((size_t)n + 1, 0); c->het_off_h.assign((size_t)n + 1, 0); }
+    if ((host_offsets && !ans) || n <= 0) { c->cand_off_h.assign((size_t)n + 1, 0); c->het_off_h.assign((size_t)n + 1, 0); }
     else { c->cand_off_h.resize((size_t)n + 1); c->het_off_h.resize((size_t)n + 1); } // only the totals are read back
     c->n_cand = c->n_het = 0;
     if (n > 0) {
@@ -1215,15 +1349,25 @@ void uz_launch_find(uz_ctx *c, FamilyDev &f, const SitesDev &s, int mode, bool h
                                    (const int64_t *)nullptr, (const int64_t *)nullptr, (int32_t *)nullptr,
                                    (uint8_t *)nullptr, (int32_t *)nullptr);
             UZ_HIP(hipGetLastError());
-            const unsigned tiles = (unsigned)(((int64_t)n + 4095) / 4096);
-            c->scan_part.ensure((size_t)2 * tiles);
-            hipLaunchKernelGGL(k_scan2_sums, dim3(tiles), dim3(1024), 0, c->stream, n, c->cnt_c.p, c->cnt_h.p, c->scan_part.p);
-            UZ_HIP(hipGetLastError());
-            hipLaunchKernelGGL(k_scan2, dim3(tiles), dim3(1024), 0, c->stream, n, c->cnt_c.p, c->cnt_h.p, (const int64_t *)c->scan_part.p, c->cand_off.p,
-                               c->het_off.p);
-            UZ_HIP(hipGetLastError());
+            if (n <= UZ_SCAN2_ONE_MAX) {
+                const unsigned tiles = (unsigned)(((int64_t)n + UZ_SCAN2_TILE - 1) / UZ_SCAN2_TILE);
+                hipLaunchKernelGGL(k_scan2_tile, dim3(tiles), dim3(256), 0, c->stream, n, (const int32_t *)c->cnt_c.p, (const int32_t *)c->cnt_h.p, c->cand_off.p,
+                                   c->het_off.p);
+                UZ_HIP(hipGetLastError());
+                uz_find_launched(c, 2);
+            } else {
+                const unsigned tiles = (unsigned)(((int64_t)n + 4095) / 4096);
+                c->scan_part.ensure((size_t)2 * tiles);
+                hipLaunchKernelGGL(k_scan2_sums, dim3(tiles), dim3(1024), 0, c->stream, n, c->cnt_c.p, c->cnt_h.p, c->scan_part.p);
+                UZ_HIP(hipGetLastError());
+                hipLaunchKernelGGL(k_scan2, dim3(tiles), dim3(1024), 0, c->stream, n, c->cnt_c.p, c->cnt_h.p, (const int64_t *)c->scan_part.p, c->cand_off.p,
+                                   c->het_off.p);
+                UZ_HIP(hipGetLastError());
+                uz_find_launched(c, 3);
+            }
         }
         auto fill = [&](int64_t cap_c, int64_t cap_h) {
+            uz_find_launched(c, 1);
             a.cap_c = cap_c; a.cap_h = cap_h;
             ProfScope ps(c, UZ_K_WINDOW_FILL);
             if (mode & UZ_FIND_WHOLE_REGION)
@@ -1245,28 +1389,38 @@ void uz_launch_find(uz_ctx *c, FamilyDev &f, const SitesDev &s, int mode, bool h
         if (const char *e = getenv("UZ_TEST_FIND_CAP")) { room_c = std::min<int64_t>(room_c, atoll(e)); room_h = std::min<int64_t>(room_h, atoll(e)); }
         const bool tried = room_c > 0 && room_h > 0;
         if (tried) fill(room_c, room_h);
-        if (host_offsets) {
+        if (ans && tried && uz_find_answer_fits_offsets(uz_find_answer_layout(n, 0, 0), ans->bytes)) {
+            // everything into the caller's block by one launch, ONE wait; a batch that outgrew the lists' room or the block left the header alone
+            if (!uz_launch_find_answer(c, ans, room_c, room_h) && ans->need > ans->bytes) ans->code |= UZ_FA_BLOCK_SMALL;
+        } else if (host_offsets && !ans) {
             // By a copy kernel into page-locked memory, not by hipMemcpyAsync: the DMA engine is in order, and inside a staged pass these two small
             // copies would wait behind the records of the chunk before (65 MB: 1.4 ms per chunk of the 100 k pass, round 5's trace) -- the host
             // sat in uz_find while the link idled, and enqueued the next chunk's records only afterwards
             const size_t ob = ((size_t)n + 1) * sizeof(int64_t), obr = (ob + 255) & ~(size_t)255;
             c->find_pin.room(2 * obr);
-            uz_kcopy(c, c->find_pin.p, c->cand_off.p, ob);
-            uz_kcopy(c, c->find_pin.p + obr, c->het_off.p, ob);
+            const KCopySeg offs[2] = {{c->find_pin.p, c->cand_off.p, ob}, {c->find_pin.p + obr, c->het_off.p, ob}};
+            uz_kcopy_many(c, offs, 2);
             UZ_HIP(hipStreamSynchronize(c->stream));
+            uz_find_waited(c);
             memcpy(c->cand_off_h.data(), c->find_pin.p, ob);
             memcpy(c->het_off_h.data(), c->find_pin.p + obr, ob);
         } else { // the read stage only needs the two totals to size the lists: into the pinned mailbox, by a kernel
             int64_t *box = reinterpret_cast<int64_t *>(c->hflags + 4);
-            uz_kcopy(c, box, c->cand_off.p + n, sizeof(int64_t));
-            uz_kcopy(c, box + 1, c->het_off.p + n, sizeof(int64_t));
+            const KCopySeg tots[2] = {{box, c->cand_off.p + n, sizeof(int64_t)}, {box + 1, c->het_off.p + n, sizeof(int64_t)}};
+            uz_kcopy_many(c, tots, 2);
             UZ_HIP(hipStreamSynchronize(c->stream));
+            uz_find_waited(c);
             c->cand_off_h[n] = box[0];
             c->het_off_h[n] = box[1];
+            if (ans) { // (no room for the offsets in the block, or lists without room yet)
+                ans->need = uz_find_answer_layout(n, box[0], box[1]).total;
+                if (ans->need > ans->bytes) ans->code |= UZ_FA_BLOCK_SMALL;
+            }
         }
         c->n_cand = c->cand_off_h[n];
         c->n_het = c->het_off_h[n];
         if (!tried || c->n_cand > room_c || c->n_het > room_h) {
+            if (ans) ans->code |= UZ_FA_GREW_LISTS;
             c->cand_idx.ensure((size_t)c->n_cand + 1);
             c->cand_flags.ensure((size_t)c->n_cand + 1);
             c->het_idx.ensure((size_t)c->n_het + 1);

@@ -378,9 +378,14 @@ struct uz_ctx {
     DnmsDev dn;
     uint8_t *dn_stage = nullptr; // pinned staging of a DNM batch
     PinBuf find_pin; // landing place of a find's offsets (copied there by a kernel: see uz_kcopy)
+    // the last find call of the context (uz_find_stats): stream waits of the host, kernel launches, UZ_FA_* of a uz_find_answer, the block it needs
+    int64_t find_stat[4] = {0, 0, 0, 0};
+    bool find_counting = false; // inside a find call (FindCount): the copy helpers' launches are the find's
+    bool find_answer_again = false; // the last find call was a uz_find_answer that fell back: the same batch may come again for its answer
+    int32_t dn_n_of_find = 0; // DNMs of the batch the context's window lists are of
     size_t dn_stage_cap = 0;
     hipEvent_t dn_stage_done = nullptr; // behind the copies out of dn_stage: a batch queued by uz_phase_begin may still be reading it
-    DevBuf<int64_t> scan_part;   // tile sums of the find's two count arrays (k_scan2_sums -> k_scan2)
+    DevBuf<int64_t> scan_part;   // tile sums of a large find's two count arrays (k_scan2_sums -> k_scan2) and of the allele-balance stage's (k_scan1_sums -> k_scan1)
     DevBuf<int32_t> cnt_c, cnt_h;
     DevBuf<int64_t> win_range;
     DevBuf<int64_t> cand_off, het_off;
@@ -540,6 +545,11 @@ void uz_block_put(uz_ctx *c, DevBlock b);
 // the kernels of the current table back until every later table has landed (measured: copies and kernels did not
 // overlap at all).  dst / src: device memory or pinned host memory.
 void uz_kcopy(uz_ctx *c, void *dst, const void *src, size_t bytes);
+// up to UZ_KCOPY_SEGS such transfers by ONE launch (blockIdx.y picks the segment; empty segments are skipped): the small pieces a stage
+// hands back together -- every launch on the compute stream stands in stream order between one chunk's read stage and the next
+#define UZ_KCOPY_SEGS 4
+struct KCopySeg { void *dst; const void *src; size_t bytes; };
+void uz_kcopy_many(uz_ctx *c, const KCopySeg *segs, int n_segs);
 // off[k] = sum of len[i] + add over i < k, off[n] the total, on stream `st`: one workgroup, a tile of 1024 lengths per round (a call's rows, a
 // chunk's records or blocks: some ten thousand at most)
 void uz_len_scan(uz_ctx *c, hipStream_t st, int64_t n, const uint32_t *len, uint32_t add, int64_t *off);
@@ -578,7 +588,19 @@ void uz_launch_vcf_settle(uz_ctx *c, int64_t n, int32_t n_rows, const int64_t *s
                           const uint16_t *gq_in, SamplesDev &m);
 void uz_launch_site_scan(uz_ctx *c, FamilyDev &f, const SitesDev &s, bool with_cnv);
 void uz_launch_site_scan_many(uz_ctx *c, FamilyDev *const *fams, int n_fam, const SitesDev &s, bool with_cnv);
-void uz_launch_find(uz_ctx *c, FamilyDev &f, const SitesDev &s, int mode, bool host_offsets = true);
+// the caller's block of a uz_find_answer (find_answer.hpp); code / need: what became of it (UZ_FA_*), the block this batch needs
+// a find call's scope: only launches made inside one count for uz_find_stats (uz_kcopy / uz_kcopy_many serve every stage)
+struct FindCount {
+    uz_ctx *c;
+    explicit FindCount(uz_ctx *c_) : c(c_) { c->find_counting = true; }
+    ~FindCount() { c->find_counting = false; }
+};
+inline void uz_find_launched(uz_ctx *c, int k) { if (c->find_counting) c->find_stat[1] += k; }
+inline void uz_find_waited(uz_ctx *c) { if (c->find_counting) c->find_stat[0]++; }
+struct FindAnswer { uint8_t *block; size_t bytes; int code; uint64_t need; };
+void uz_launch_find(uz_ctx *c, FamilyDev &f, const SitesDev &s, int mode, bool host_offsets = true, FindAnswer *ans = nullptr);
+// the lists the context holds (a find's, or recalled) written into the block by one kernel, one wait: false -- the block is too small
+bool uz_launch_find_answer(uz_ctx *c, FindAnswer *ans, int64_t room_c, int64_t room_h);
 void uz_stage_dnms(uz_ctx *c, const uz_dnms_view *d);
 void uz_launch_cnv(uz_ctx *c, const SitesDev &s, const int32_t *rb_counts_dev, int32_t *cnv_counts, int32_t *cnv_pos, int32_t *origin,
                    int32_t *evidence, int32_t *etype);

@@ -34,7 +34,7 @@ EXPORTS = [
     "uz_pinned_alloc", "uz_pinned_free",
     "uz_sites_adopt_device", "uz_family_adopt_device", "uz_reads_adopt_device",
     "uz_sites_free", "uz_reads_free", "uz_drop_derived",
-    "uz_site_scan", "uz_site_scan_many", "uz_site_classes", "uz_find", "uz_find_fetch", "uz_find_cohort",
+    "uz_site_scan", "uz_site_scan_many", "uz_site_classes", "uz_find", "uz_find_fetch", "uz_find_answer", "uz_find_stats", "uz_find_cohort",
     "uz_phase", "uz_phase_begin", "uz_phase_end", "uz_phase_cohort", "uz_phase_cohort_joined", "uz_phase_votes", "uz_phase_groups", "uz_phase_sizing_fetch", "uz_phase_cnv", "uz_phase_cnv_cohort", "uz_phase_cnv_sites",
     "uz_bed_rows", "uz_bed_rows_lists", "uz_vcf_rows", "uz_bcf_rows", "uz_bgzf_deflate",
     "uz_prof_enable", "uz_prof_reset", "uz_prof_get", "uz_prof_units",
@@ -113,6 +113,8 @@ def load_library(path: Optional[str] = None):
     L.uz_site_classes.argtypes = [vp, C.c_int, vp]
     L.uz_find.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp]
     L.uz_find_fetch.argtypes = [vp, vp, vp, vp]
+    L.uz_find_answer.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_size_t, vp]
+    L.uz_find_stats.argtypes = [vp, vp]
     L.uz_find_cohort.argtypes = [vp, vp, C.c_int32, vp, C.c_int, vp, vp]
     L.uz_phase.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]
     L.uz_phase_begin.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int]
@@ -716,13 +718,68 @@ class HipEngine:
         return out[:n_sites]
 
     def find(self, fam: int, dv: abi.Held, params: abi.Params, mode: int, fetch: bool = True, transient: bool = False):
-        """transient: the index lists come back as views of page-locked buffers this engine re-uses (valid until the find after next) -- what a
-        pipeline that reads them at once wants (pipeline.run_pipelined)"""
+        """-> cand_off, cand_idx, cand_flags, het_off, het_idx.  transient: all five come back as views of ONE page-locked block this engine
+        re-uses (three in turn: valid until the find after next), filled by uz_find_answer behind one wait of the host -- what a pipeline that
+        reads them at once wants (pipeline.run_pipelined).  Without it: arrays of the caller's own (uz_find + uz_find_fetch)."""
         self.set_params(params)
-        return self._find_out(dv.view.n, fetch, transient,
+        if transient and fetch:
+            return self._find_answer(int(fam), dv, int(mode))
+        return self._find_out(dv.view.n, fetch,
                               lambda co, ho: self._ck(self.L.uz_find(self.h, int(fam), dv.ref(), int(mode), co, ho), "uz_find"))
 
-    def _find_out(self, n, fetch, transient, run):
+    @staticmethod
+    def find_answer_layout(n: int, nc: int, nh: int):
+        """(offsets of the six parts, total bytes) of a uz_find_answer block (unfazed_hip.h; csrc/find_answer.hpp)"""
+        sizes = (64, 8 * (n + 1), 8 * (n + 1), 4 * nc, nc, 4 * nh)
+        off, at = [], 0
+        for b in sizes:
+            off.append(at)
+            at += (b + 255) & ~255
+        return off, at
+
+    def _find_answer(self, fam: int, dv: abi.Held, mode: int, block_bytes: Optional[int] = None):
+        """find() through uz_find_answer: offsets and lists come back as views of ONE page-locked block (three in turn: the lists of a find are
+        read before the find after next returns), written by one kernel behind the fill pass -- one wait of the host per find.  A block sized
+        from the finds before (with head room) usually fits; one that does not is grown to what the call reports and the call made again.
+        block_bytes: test hook, the size of the block handed to the first call."""
+        n = dv.view.n
+        if not hasattr(self, "_answer_pins"):
+            self._answer_pins, self._answer_turn, self._answer_hint = [None, None, None], 0, 0
+        self._answer_turn = (self._answer_turn + 1) % 3
+
+        def block(need):
+            pin = self._answer_pins[self._answer_turn]
+            if pin is None or pin[1].size < need:
+                if pin is not None:
+                    pin[0].free_all()
+                pool = PinnedPool()
+                pin = self._answer_pins[self._answer_turn] = (pool, pool.alloc(need + need // 4 + (1 << 16)))
+            return pin[1]
+
+        out = np.zeros(4, dtype=np.int64)
+        first = self.find_answer_layout(n, 0, 0)[1] if block_bytes is None else int(block_bytes)
+        buf = block(max(first, self._answer_hint if block_bytes is None else 0, 256))
+        size = buf.size if block_bytes is None else int(block_bytes)
+        self._ck(self.L.uz_find_answer(self.h, fam, dv.ref(), mode, buf.ctypes.data, size, out.ctypes.data), "uz_find_answer")
+        if out[0] != 0:  # the batch outgrew the lists' room or the block: once more, on a block of the size it needs
+            buf = block(int(out[1]))
+            self._ck(self.L.uz_find_answer(self.h, fam, dv.ref(), mode, buf.ctypes.data, buf.size, out.ctypes.data), "uz_find_answer")
+            if out[0] != 0:
+                raise UnfazedHipError("uz_find_answer: no answer on a block of the size it asked for (%d bytes, code %d)" % (int(out[1]), int(out[0])))
+        self._answer_hint = max(self._answer_hint, int(out[1]) + int(out[1]) // 4)
+        nc, nh = int(out[2]), int(out[3])
+        off, _ = self.find_answer_layout(n, nc, nh)
+        co = buf[off[1]: off[1] + 8 * (n + 1)].view(np.int64)
+        ho = buf[off[2]: off[2] + 8 * (n + 1)].view(np.int64)
+        return co, buf[off[3]: off[3] + 4 * nc].view(np.int32), buf[off[4]: off[4] + nc], ho, buf[off[5]: off[5] + 4 * nh].view(np.int32)
+
+    def find_stats(self):
+        """(host waits, kernel launches, fall-back bits, bytes of the answer) of the last find of this engine (uz_find_stats)"""
+        out = np.zeros(4, dtype=np.int64)
+        self._ck(self.L.uz_find_stats(self.h, out.ctypes.data), "uz_find_stats")
+        return tuple(int(x) for x in out)
+
+    def _find_out(self, n, fetch, run):
         """The outputs of a find over n DNMs: run(cand_off, het_off) makes the call on the two offset arrays' addresses; the index lists behind
         them are fetched when asked for."""
         co = np.zeros(n + 1, dtype=np.int64)
@@ -730,7 +787,7 @@ class HipEngine:
         run(co.ctypes.data, ho.ctypes.data)
         if not fetch:
             return co, None, None, ho, None
-        ci, cf, hi = self._fetch(int(co[n]), int(ho[n]), transient=transient)
+        ci, cf, hi = self._fetch(int(co[n]), int(ho[n]))
         return co, ci, cf, ho, hi
 
     @staticmethod
@@ -748,32 +805,13 @@ class HipEngine:
         family columns), one launch sequence (uz_find_cohort).  Same result layout as find(), in DNM order."""
         self.set_params(params)
         arr = self._groups(groups)
-        return self._find_out(dv.view.n, fetch, False,
+        return self._find_out(dv.view.n, fetch,
                               lambda co, ho: self._ck(self.L.uz_find_cohort(self.h, arr, len(groups), dv.ref(), int(mode), co, ho), "uz_find_cohort"))
 
-    def _fetch(self, nc: int, nh: int, transient: bool = False):
-        if transient:
-            # Into page-locked memory kept from call to call (three sets in turn: the lists of a find are read before the find after next
-            # returns): the library then copies by kernels, past the DMA engine's queue -- inside a staged pass a plain copy back waits
-            # behind the records of the chunk before (abi.hip: uz_find_fetch)
-            if not hasattr(self, "_find_pins"):
-                self._find_pins, self._find_turn = [None, None, None], 0
-            self._find_turn = (self._find_turn + 1) % 3
-            need = 4 * max(1, nc) + 256 + max(1, nc) + 256 + 4 * max(1, nh) + 256
-            pin = self._find_pins[self._find_turn]
-            if pin is None or pin[1].size < need:
-                if pin is not None:
-                    pin[0].free_all()
-                pool = PinnedPool()
-                pin = self._find_pins[self._find_turn] = (pool, pool.alloc(need + need // 4 + (1 << 16)))
-            buf = pin[1]
-            a = (4 * max(1, nc) + 255) & ~255
-            b = a + ((max(1, nc) + 255) & ~255)
-            ci, cf, hi = buf[: 4 * max(1, nc)].view(np.int32), buf[a: a + max(1, nc)], buf[b: b + 4 * max(1, nh)].view(np.int32)
-        else:
-            ci = np.zeros(max(1, nc), dtype=np.int32)
-            cf = np.zeros(max(1, nc), dtype=np.uint8)
-            hi = np.zeros(max(1, nh), dtype=np.int32)
+    def _fetch(self, nc: int, nh: int):
+        ci = np.zeros(max(1, nc), dtype=np.int32)
+        cf = np.zeros(max(1, nc), dtype=np.uint8)
+        hi = np.zeros(max(1, nh), dtype=np.int32)
         self._ck(self.L.uz_find_fetch(self.h, ci.ctypes.data, cf.ctypes.data, hi.ctypes.data), "uz_find_fetch")
         return ci[:nc], cf[:nc], hi[:nh]
 

@@ -4,7 +4,8 @@
 Reference seam: snv_phaser.py:206-299 / sv_phaser.py:176-266 run one task per DNM on a thread pool; each task opens the sites
 file and the alignment file for its own window.  Here a batch is cut into chunks (shard.chunk_plan) and every chunk goes through
     site stage   its windows' site + genotype columns up (copy stream), K1 + K2, het lists back: they tell the decoder which fetches the
-                 read stage will make -- the ONE host round trip of a chunk
+                 read stage will make -- the ONE host round trip of a chunk (uz_find_answer: offsets and lists land in one page-locked
+                 block behind one wait)
     records      the records those fetches return (+ mates), in the link form, queued on the copy stream
     read stage   queued on the compute stream (uz_phase_begin), picked up later (uz_phase_end)
     (config 5)   allele balance of the chunk's events on its own windows, merged with the read-backed counts
@@ -62,7 +63,7 @@ def run_pipelined(eng, P, mode, n: int, chunks: Sequence[dict], cnv: bool = Fals
     except (TypeError, ValueError):
         _transient = False
 
-    def find_of(k):  # K1 + K2 + the het lists back on the host (read at once by the chunk's decoder: into re-used page-locked buffers where the engine offers them)
+    def find_of(k):  # K1 + K2 + the het lists back on the host (read at once by the chunk's decoder: views of re-used page-locked blocks where the engine offers them)
         if _transient:
             return eng.find(fids[k], chunks[k]["dnms"], P, mode, transient=True)
         return eng.find(fids[k], chunks[k]["dnms"], P, mode)
