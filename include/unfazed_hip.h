@@ -106,6 +106,10 @@ int uz_families_from_samples(uz_ctx *ctx, int samples_id, int32_t n, const int32
 /* Any family's device columns back on the host, whatever route made it: gt [S] (complex bit included), cols [9][S] = ref depth of
  * kid, dad, mom, alt depth of the three, GQ of the three.  For parity tests of the two routes. */
 int uz_family_fetch(uz_ctx *ctx, int fam_id, uint8_t *gt, uint16_t *cols /* [9][S] */);
+/* Any sites table's four device columns back on the host, S entries each: a table staged in the compact form (uz_sites_view.pos_d16 ...) is
+ * expanded first if nothing has used it yet -- without its family, whose own first use then readies it.  For tests that hold the
+ * expansion to the form's description; nothing on the product path calls it. */
+int uz_sites_fetch(uz_ctx *ctx, int sites_id, int32_t *pos, uint8_t *sflags, uint8_t *ref_base, uint8_t *alt_base);
 /* The same sample table WITHOUT the host parsing a sample cell: the record text of a lazily decoded text VCF (unfazed_io.h:
  * uz_vcf_decode_regions_lazy, uz_vcf_samples_text) goes up in bounded chunks cut at line ends -- chunk k + 1 copied while chunk k is parsed
  * -- and two kernels (csrc/k_vcf.hip) read GT, AD (or RO / AO) and GQ of the picked sample columns into rows [n_pick][S] of the layout

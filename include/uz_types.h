@@ -111,10 +111,12 @@ typedef struct uz_sites_view {
     /* The compact link form (uz_sites_pack writes it; pos / sflags / ref_base / alt_base are then NULL): 4 bytes per site cross the link
      * instead of 7.  Sites are taken in spans of UZ_SITE_SPAN; span s starts at site s * UZ_SITE_SPAN.
      *   pos_d16[i]      pos[i] - pos[i - 1] where that lies in [0, UZ_POS_D16_LIMIT) (anything where site i starts a span or escapes)
-     *   bases8[i]       UZ_BASE3 code of ref_base | code of alt_base << 3 | complex (UZ_SF_COMPLEX) << 6
+     *   bases8[i]       UZ_BASE3 code of ref_base | code of alt_base << 3 | complex (UZ_SF_COMPLEX) << 6.  Both readers (k_sites_expand,
+     *                   uz_sites_unpack) decode the codes 6 and 7 as 'N' and ignore bit 7; uz_sites_pack writes neither.
      *   span_pos[s]     pos of the span's first site
      *   pos_esc_*       the escapes, ascending by site index: every other site whose difference does not fit, and the first site of every
-     *                   contig -- index and absolute pos; pos_esc_off[s] = first escape of span s (n_spans + 1 entries, the last n_pos_esc)
+     *                   contig -- index and absolute pos; pos_esc_off[s] = first escape of span s (n_spans + 1 entries, the last n_pos_esc).
+     *                   A span's first site is never an escape (span_pos holds its pos): both readers refuse a list that names one.
      * pos[i] is then the value of the last anchor at or before i within its span (the span's first site, or an escape) plus the pos_d16 of
      * the sites after that anchor up to i.  Only uz_sites_family_upload_async takes this form; the device expands it into the plain
      * columns at first use. */

@@ -1,5 +1,6 @@
 """The compact link form of a site table (uz_types.h: uz_sites_view.pos_d16 ...): uz_sites_pack and its host twin uz_sites_unpack, which
-computes what the device's expansion (k_sites_expand) writes.  No GPU."""
+computes what the device's expansion (k_sites_expand) writes.  No GPU.  (The twin and the device are both held to a model written from the
+header: tests/test_site_form_model.py on the CPU, tests/test_site_forms_gpu.py on the device.)"""
 import numpy as np
 import pytest
 

@@ -631,9 +631,9 @@ static bool sites_view_compact(const uz_sites_view *v) {
     for (int64_t sp = 0; sp < n_spans; sp++) {
         const int64_t a = v->pos_esc_off[sp], b = v->pos_esc_off[sp + 1];
         UZ_REQUIRE(a <= b, UZ_E_ARG, "pos_esc_off must ascend");
-        for (int64_t e = a; e < b; e++)
-            UZ_REQUIRE(v->pos_esc_idx[e] >= sp * UZ_SITE_SPAN && v->pos_esc_idx[e] < std::min(n, (sp + 1) * UZ_SITE_SPAN) &&
-                           (e == a || v->pos_esc_idx[e] > v->pos_esc_idx[e - 1]), UZ_E_ARG, "an escape outside its span, or out of order");
+        for (int64_t e = a; e < b; e++) // (a span's first site takes span_pos, in the kernel and in uz_sites_unpack: no escape may name it)
+            UZ_REQUIRE(v->pos_esc_idx[e] > sp * UZ_SITE_SPAN && v->pos_esc_idx[e] < std::min(n, (sp + 1) * UZ_SITE_SPAN) &&
+                           (e == a || v->pos_esc_idx[e] > v->pos_esc_idx[e - 1]), UZ_E_ARG, "an escape outside its span, at its span's first site, or out of order");
     }
     return true;
 }
@@ -1096,6 +1096,20 @@ int uz_family_fetch(uz_ctx *c, int fam_id, uint8_t *gt, uint16_t *cols) {
             UZ_HIP(hipMemcpy(cols + (size_t)(3 + q) * n, f.ad[q], n * 2, hipMemcpyDeviceToHost));
             UZ_HIP(hipMemcpy(cols + (size_t)(6 + q) * n, f.gq[q], n * 2, hipMemcpyDeviceToHost));
         }
+    });
+}
+
+int uz_sites_fetch(uz_ctx *c, int sites_id, int32_t *pos, uint8_t *sflags, uint8_t *ref_base, uint8_t *alt_base) {
+    return guarded(c, [&] {
+        SitesDev &s = sites_of(c, sites_id); // (a pending compact table: expanded here, without its family)
+        const size_t n = (size_t)s.n;
+        if (!n) return;
+        UZ_REQUIRE(pos != nullptr && sflags != nullptr && ref_base != nullptr && alt_base != nullptr, UZ_E_ARG, "null output");
+        UZ_HIP(hipStreamSynchronize(c->stream));
+        UZ_HIP(hipMemcpy(pos, s.pos, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        UZ_HIP(hipMemcpy(sflags, s.sflags, n, hipMemcpyDeviceToHost));
+        UZ_HIP(hipMemcpy(ref_base, s.ref_base, n, hipMemcpyDeviceToHost));
+        UZ_HIP(hipMemcpy(alt_base, s.alt_base, n, hipMemcpyDeviceToHost));
     });
 }
 

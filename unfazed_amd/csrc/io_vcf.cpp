@@ -1331,6 +1331,7 @@ int uz_sites_unpack(const uz_sites_view *v, int32_t *pos, uint8_t *sflags, uint8
             const int64_t e1 = v->pos_esc_off[s + 1];
             if (e < 0 || e1 < e || e1 > v->n_pos_esc) fail(UZ_IO_E_ARG, "bad escape offsets");
             uint32_t p = (uint32_t)v->span_pos[s];
+            if (e < e1 && v->pos_esc_idx[e] == lo) fail(UZ_IO_E_ARG, "span %lld: an escape at the span's first site (span_pos holds its pos)", (long long)s);
             for (int64_t i = lo; i < hi; i++) {
                 if (e < e1 && v->pos_esc_idx[e] == i) p = (uint32_t)v->pos_esc_val[e++];
                 else if (i > lo) p += v->pos_d16[i];

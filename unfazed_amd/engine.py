@@ -29,7 +29,7 @@ HEAD_MAX_ROUNDS = 8       # walks of one file before it is handed back to the ho
 
 EXPORTS = [
     "uz_create", "uz_destroy", "uz_last_error", "uz_sync", "uz_set_params",
-    "uz_sites_upload", "uz_family_upload", "uz_sites_family_upload_async", "uz_samples_upload", "uz_samples_from_text", "uz_samples_from_bcf", "uz_samples_unsettled", "uz_samples_settle", "uz_families_from_samples", "uz_family_fetch", "uz_samples_free", "uz_reads_upload", "uz_reads_upload_packed", "uz_reads_wait", "uz_reads_headers", "uz_reads_columns", "uz_reads_marks", "uz_bgzf_inflate", "uz_bgzf_inflate_to_host", "uz_bam_walk", "uz_bam_walk_many", "uz_reads_files", "uz_crc32_blocks", "uz_bam_walk_fetch", "uz_bam_walk_release", "uz_reads_from_bam",
+    "uz_sites_upload", "uz_family_upload", "uz_sites_family_upload_async", "uz_samples_upload", "uz_samples_from_text", "uz_samples_from_bcf", "uz_samples_unsettled", "uz_samples_settle", "uz_families_from_samples", "uz_family_fetch", "uz_sites_fetch", "uz_samples_free", "uz_reads_upload", "uz_reads_upload_packed", "uz_reads_wait", "uz_reads_headers", "uz_reads_columns", "uz_reads_marks", "uz_bgzf_inflate", "uz_bgzf_inflate_to_host", "uz_bam_walk", "uz_bam_walk_many", "uz_reads_files", "uz_crc32_blocks", "uz_bam_walk_fetch", "uz_bam_walk_release", "uz_reads_from_bam",
     "uz_bam_walk_flags", "uz_bam_join", "uz_bam_join_needs", "uz_bam_join_fetch", "uz_reads_from_walk", "uz_reads_names", "uz_walk_slot_stats", "uz_walk_reserve",
     "uz_pinned_alloc", "uz_pinned_free",
     "uz_sites_adopt_device", "uz_family_adopt_device", "uz_reads_adopt_device",
@@ -104,6 +104,7 @@ def load_library(path: Optional[str] = None):
     L.uz_samples_unsettled.argtypes = [vp, C.c_int, vp]
     L.uz_samples_settle.argtypes = [vp, C.c_int, C.c_int64, vp, vp]
     L.uz_family_fetch.argtypes = [vp, C.c_int, vp, vp]
+    L.uz_sites_fetch.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.uz_samples_free.argtypes = [vp, C.c_int]
     L.uz_drop_derived.argtypes = [vp]
     L.uz_sites_free.argtypes = [vp, C.c_int]
@@ -298,6 +299,14 @@ class HipEngine:
         gt, cols = np.zeros(max(1, n_sites), np.uint8), np.zeros((9, max(1, n_sites)), np.uint16)
         self._ck(self.L.uz_family_fetch(self.h, int(fam), gt.ctypes.data, cols.ctypes.data), "uz_family_fetch")
         return gt[:n_sites], cols[:, :n_sites] if n_sites else cols[:, :0]
+
+    def sites_fetch(self, sid: int, n_sites: int):
+        """a sites table's device columns (uz_sites_fetch; a test aid): a pending compact table is expanded first, without its family
+        -> (pos i32 [S], sflags u8 [S], ref_base u8 [S], alt_base u8 [S])"""
+        n = max(1, int(n_sites))
+        pos, sf, rb, ab = np.zeros(n, np.int32), np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        self._ck(self.L.uz_sites_fetch(self.h, int(sid), pos.ctypes.data, sf.ctypes.data, rb.ctypes.data, ab.ctypes.data), "uz_sites_fetch")
+        return pos[:n_sites], sf[:n_sites], rb[:n_sites], ab[:n_sites]
 
     def free_samples(self, samples_h: int):
         self._ck(self.L.uz_samples_free(self.h, int(samples_h)), "uz_samples_free")
