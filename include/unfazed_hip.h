@@ -486,6 +486,20 @@ int uz_bcf_rows(uz_ctx *ctx, const uz_bcf_lines_view *records, int64_t *off /* [
 int uz_bgzf_deflate(uz_ctx *ctx, const uint8_t *data /* host */, int64_t n_bytes, int64_t *n_blocks, const uint8_t **bgzf, int64_t *bgzf_bytes,
                     int repeat, double *kernel_ms);
 
+/* The same call with the choice of the coder.  code = UZ_DF_CODE_FIXED: uz_bgzf_deflate, byte for byte.  code = UZ_DF_CODE_DYNAMIC
+ * (k_bgzf_deflate_dyn; csrc/deflate_dyn.hpp states the rules): the same LZ77 parse, taken over the whole slice; then per slice the shortest, in
+ * whole bytes, of one dynamic-Huffman block (BTYPE 10: optimal code lengths under the 15- and 7-bit limits, run-length coded header), the
+ * fixed-Huffman block (taken unless the dynamic one is strictly shorter: then uz_bgzf_deflate's bytes) and the stored block of 5 + n bytes.  So
+ * no block is longer than the fixed code's block of the same slice.  The tokens wait between the two passes in a device buffer of the context
+ * of 65 280 words per slice of a chunk: 131 MB at the default chunk size, 4.3 GB at the 1 GiB cap of UZ_BGZF_CHUNK_BYTES.
+ * kinds: NULL, or [3]: the blocks that came out stored / fixed / dynamic (read from the blocks' BTYPE).  repeat times the kernel of the
+ * chosen code.  Everything else as in uz_bgzf_deflate; the two share *bgzf.
+ * UZ_E_ARG (nothing launched): any other code, and what uz_bgzf_deflate refuses. */
+#define UZ_DF_CODE_FIXED 0
+#define UZ_DF_CODE_DYNAMIC 1
+int uz_bgzf_deflate_coded(uz_ctx *ctx, const uint8_t *data /* host */, int64_t n_bytes, int code, int64_t *kinds /* NULL or [3] */, int64_t *n_blocks,
+                          const uint8_t **bgzf, int64_t *bgzf_bytes, int repeat, double *kernel_ms);
+
 /* ---- allele-balance (CNV) stage ---------------------------------------- */
 /* K6.  Everything run_cnv_phasing does after its find (sv_phaser.py:357-423: phase_by_snvs :71-85,
  * multithread_cnv_phasing :269-301) and the decision of summarize_record (unfazed.py:193-298): runs the window

@@ -1,17 +1,20 @@
 #!/usr/bin/env python
-"""A/B of the three ways the annotated VCF reaches a file called out.vcf.gz (UZ_OUT_BGZF):
+"""A/B of the four ways the annotated VCF reaches a file called out.vcf.gz (UZ_OUT_BGZF, UZ_OUT_BGZF_CODE):
   unset   plain text under the ".gz" name (what the driver did before the switch)
   host    BGZF by zlib, one block per 65 280 bytes, UZ_OUT_BGZF_LEVEL (6)
   device  the same blocks by k_bgzf_deflate / k_bgzf_frame (uz_bgzf_deflate)
+  device-dynamic  the device route with UZ_OUT_BGZF_CODE=dynamic: k_bgzf_deflate_dyn in k_bgzf_deflate's place (uz_bgzf_deflate_coded)
 The protocol of scripts/vcf_route_ab.py, whose generator and records dict this script uses: one MI355X, every run a FRESH process (this script
 started again with --child), the routes alternating, --repeat runs each, page cache warm.  Timed in the child: wall and host CPU seconds of
 unfazed.write_vcf_output from "records dict known" to "output file written"; the annotated text itself comes from the device route of
 UZ_VCF_ROUTE on all three; HIP start-up and library load are outside (the context is made before the timer).
 Shapes: `cohort` 600 samples x 20 000 records, `trio` 3 samples x 20 000 records.
-The three files must hold the same text (the BGZF ones inflated by gzip): asserted per shape.  Device runs also record, outside the timer,
-kernel_ms of k_bgzf_deflate over the whole text (repeat=3), the profile slots of the timed call, and the kernel's distance from one copy of its
-input plus its output at the 6.3 TB/s a copy reaches on the box.  It decides no default: unset stays unset.
-    timeout -k 10 1100 python scripts/bgzf_route_ab.py [--shape cohort|trio] [--repeat 3] [--dir D] [--out profiles/bgzf_route_ab.json]"""
+The four files must hold the same text (the BGZF ones inflated by gzip): asserted per shape.  Device runs also record, outside the timer,
+kernel_ms of their code's kernel over the whole text (repeat=3), the profile slots of the timed call, and the kernel's distance from one copy of
+its input plus its output at the 6.3 TB/s a copy reaches on the box; a device-dynamic run records kernel_ms of both kernels, same process,
+alternating (fixed, dynamic, fixed, dynamic), and the split of its blocks.  It decides no default: unset stays unset.
+(profiles/bgzf_route_ab.json is the three-leg measurement from before the fourth leg.)
+    timeout -k 10 1100 python scripts/bgzf_route_ab.py [--shape cohort|trio] [--repeat 3] [--dir D] [--out profiles/bgzf_dynamic_ab.json]"""
 import argparse
 import gzip
 import hashlib
@@ -28,15 +31,18 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import vcf_route_ab as shape  # noqa: E402 -- the generator, the records dict, the shapes
 
-ROUTES = ("unset", "host", "device")
+ROUTES = ("unset", "host", "device", "device-dynamic")
 COPY_BYTES_PER_S = 6.3e12
 
 
 def child(a):
     """one run of one route in this (fresh) process -> a JSON line on stdout"""
     os.environ.pop("UZ_OUT_BGZF", None)
+    os.environ.pop("UZ_OUT_BGZF_CODE", None)
     if a.child != "unset":
-        os.environ["UZ_OUT_BGZF"] = a.child
+        os.environ["UZ_OUT_BGZF"] = a.child.split("-")[0]
+    if a.child == "device-dynamic":
+        os.environ["UZ_OUT_BGZF_CODE"] = "dynamic"
     from unfazed_amd import engine, outfile, session, unfazed
     n_samples, n_records = shape.SHAPES[a.shape]
     eng = session.get_backend()  # (HIP start-up, the library, the context: before the timer)
@@ -51,11 +57,15 @@ def child(a):
     text = raw if a.child == "unset" else gzip.decompress(raw)
     run = dict(wall_s=wall, host_cpu_s=cpu, file_bytes=len(raw), text_bytes=len(text), text_sha=hashlib.sha256(text).hexdigest()[:16],
                counters=dict(outfile.OUT_STATS), vcf_counters=dict(unfazed.VCF_STATS))
-    if a.child == "device":
+    if a.child.startswith("device"):
+        code = "dynamic" if a.child == "device-dynamic" else "fixed"
         run["prof_ms"] = {name: dict(zip(("total_ms", "launches"), eng.prof_get(k))) for name, k in kernels.items()}
-        blocks, n_blocks, ms = eng.bgzf_deflate(text, repeat=3)
+        run["kinds"] = dict(outfile.OUT_KINDS)
+        blocks, n_blocks, ms = eng.bgzf_deflate(text, repeat=3, code=code)
         bound_ms = (len(text) + len(blocks)) / COPY_BYTES_PER_S * 1e3
         run.update(kernel_ms=ms, blocks=n_blocks, copy_bound_ms=bound_ms, times_the_bound=ms / bound_ms, kernel_gb_per_s=len(text) / ms / 1e6)
+        if code == "dynamic":  # both kernels in one process, alternating
+            run["kernel_ms_alternating"] = [dict(code=c, kernel_ms=eng.bgzf_deflate(text, repeat=3, code=c)[2]) for c in ("fixed", "dynamic", "fixed", "dynamic")]
     os.remove(out)
     print("BGZF_ROUTE_AB " + json.dumps(run), flush=True)
     return 0
@@ -67,7 +77,7 @@ def main():
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--dir", default=None)
     ap.add_argument("--child", default=None, choices=list(ROUTES))
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bgzf_route_ab.json"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bgzf_dynamic_ab.json"))
     a = ap.parse_args()
     if a.child:
         return child(a)
@@ -95,12 +105,12 @@ def main():
                   file=sys.stderr, flush=True)
     same = len({r["text_sha"] for rr in runs.values() for r in rr}) == 1
     assert same, "the routes' files hold different text (shape %s)" % a.shape
-    res = dict(what="records dict -> out.vcf.gz, UZ_OUT_BGZF unset (plain text) / host (zlib level 6) / device (uz_bgzf_deflate); a fresh process per run, "
+    res = dict(what="records dict -> out.vcf.gz, UZ_OUT_BGZF unset (plain text) / host (zlib level 6) / device (uz_bgzf_deflate) / device-dynamic (UZ_OUT_BGZF_CODE=dynamic); a fresh process per run, "
                     "routes alternating, page cache warm; wall and host CPU seconds of unfazed.write_vcf_output, HIP start-up excluded",
                shape=a.shape, samples=n_samples, records=n_records, input_bytes=os.path.getsize(src), repeat=a.repeat, runs=runs, same_text_on_every_route=same)
     for route in ROUTES:
-        res[route + "_median_wall_s"] = statistics.median(r["wall_s"] for r in runs[route])
-        res[route + "_file_bytes"] = runs[route][0]["file_bytes"]
+        res[route.replace("-", "_") + "_median_wall_s"] = statistics.median(r["wall_s"] for r in runs[route])
+        res[route.replace("-", "_") + "_file_bytes"] = runs[route][0]["file_bytes"]
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     allres = json.load(open(a.out)) if os.path.exists(a.out) else {}
     allres[a.shape] = res

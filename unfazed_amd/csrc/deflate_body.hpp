@@ -1,6 +1,7 @@
 // deflate_body.hpp -- one slice of at most 65 280 bytes (htslib's 0xff00) turned into one raw DEFLATE stream: the body of k_bgzf_deflate
 // (k_deflate.hip), where its 64 lanes are a wavefront, and of tests/bgzf_body_main.cpp, where they are a plain loop.  Both builds emit THE SAME
 // BYTES: every step below is either lane-private, or a cross-lane step whose result does not depend on the order the lanes run in.
+// deflate_dyn.hpp is a second coder over the same parse (uz_df_group, the one statement of the group step) which may choose dynamic Huffman.
 //
 // How the body is written.  A value a lane keeps from step to step is a W::V<T> (the device: a register; the host: an array of 64); a step is
 // a loop UZ_DF_EACH(w, l) over the lanes the caller runs (the device: its own; the host: all 64, ascending) that touches only v[l]; between
@@ -78,20 +79,29 @@ UZ_DF_HD uint32_t uz_df_litlen(uint32_t sym, uint32_t &nbits) {
     nbits = 8;
     return uz_df_rev(0xC0u + (sym - 280), 8);
 }
-// a match as its token: length symbol, its extra bits, distance symbol, its extra bits
-UZ_DF_HD uint32_t uz_df_match_token(uint32_t len, uint32_t dist, uint32_t &nbits) {
-    uint32_t sym, le = 0, lx = 0;
+// a match length as its symbol, the count of its extra bits and their value; length 258 is symbol 285
+UZ_DF_HD void uz_df_len_sym(uint32_t len, uint32_t &sym, uint32_t &le, uint32_t &lx) {
     const uint32_t l = len - 3;
+    le = 0; lx = 0;
     if (len == UZ_DF_MAX_MATCH) sym = 285;
     else if (l < 8) sym = 257 + l;
     else { le = uz_df_log2(l) - 2; sym = 261 + 4 * le + ((l >> le) & 3u); lx = l & ((1u << le) - 1); }
+}
+// a distance likewise
+UZ_DF_HD void uz_df_dist_sym(uint32_t dist, uint32_t &dsym, uint32_t &de, uint32_t &dx) {
+    const uint32_t d = dist - 1;
+    de = 0; dx = 0;
+    if (d < 4) dsym = d;
+    else { const uint32_t nb = uz_df_log2(d); de = nb - 1; dsym = 2 * nb + ((d >> de) & 1u); dx = d & ((1u << de) - 1); }
+}
+// a match as its token: length symbol, its extra bits, distance symbol, its extra bits
+UZ_DF_HD uint32_t uz_df_match_token(uint32_t len, uint32_t dist, uint32_t &nbits) {
+    uint32_t sym, le, lx, dsym, de, dx;
+    uz_df_len_sym(len, sym, le, lx);
     uint32_t n = 0;
     uint32_t tok = uz_df_litlen(sym, n);
     tok |= lx << n; n += le;
-    const uint32_t d = dist - 1;
-    uint32_t dsym, de = 0, dx = 0;
-    if (d < 4) dsym = d;
-    else { const uint32_t nb = uz_df_log2(d); de = nb - 1; dsym = 2 * nb + ((d >> de) & 1u); dx = d & ((1u << de) - 1); }
+    uz_df_dist_sym(dist, dsym, de, dx);
     tok |= uz_df_rev(dsym, 5) << n; n += 5;
     tok |= dx << n; n += de;
     nbits = n;
@@ -126,6 +136,7 @@ struct UzDfHostWave {
             if (ok[l]) tab[h[l]] = (uint16_t)val[l]; // ascending: the highest stays
     }
     void or_word(uint32_t *w, uint32_t v) const { *w |= v; }
+    void add_word(uint32_t *w, uint32_t v) const { *w += v; } // (deflate_dyn.hpp: the histograms)
 };
 
 struct UzDfLds { // a wave's LDS
@@ -142,6 +153,74 @@ UZ_DF_HD void uz_df_store_words(W &w, const uint32_t *win, uint32_t wbase, uint3
             if (k < count && ((size_t)wbase + k) * 4 + 4 <= cap) reinterpret_cast<uint32_t *>(out)[wbase + k] = win[k];
         }
     }
+}
+
+// One group of the parse rule (the head of this file): the 64 positions from g probe, then insert; the greedy walk takes its matches.
+// -> false: the whole group lies inside a match (inserted only, nothing to emit).  Otherwise mlen / mdist hold every lane's kept match,
+// `taken` the lanes whose match the walk took, `covered` the lanes a token of an earlier lane covers, and `next` has moved.
+template <typename W>
+UZ_DF_HD bool uz_df_group(W &w, uint16_t *tab, const uint8_t *in, uint32_t n, uint32_t g, uint32_t &next, typename W::template V<uint32_t> &mlen,
+                          typename W::template V<uint32_t> &mdist, uint64_t &taken, uint64_t &covered) {
+    typedef typename W::template V<uint32_t> Lane;
+    const uint32_t cnt = n - g < 64 ? n - g : 64;
+    const bool inside = next >= g + cnt; // the whole group lies inside a match
+    Lane h, val, can, has;
+    UZ_DF_EACH(w, l) {
+        const uint32_t p = g + l;
+        can[l] = p + 4 <= n ? 1u : 0u;
+        h[l] = can[l] ? uz_df_hash(uz_df_load32(in + p)) : 0u;
+        val[l] = p + 1;
+        mlen[l] = 0; mdist[l] = 0; has[l] = 0;
+        if (can[l] && !inside) {
+            const uint32_t c1 = tab[h[l]];
+            if (c1) {
+                const uint32_t c = c1 - 1, dist = p - c; // c < g <= p
+                const uint32_t cap_len = n - p < UZ_DF_MAX_MATCH ? n - p : UZ_DF_MAX_MATCH;
+                uint32_t m = 0;
+                if (dist <= UZ_DF_MAX_DIST) {
+                    while (m + 4 <= cap_len && uz_df_load32(in + c + m) == uz_df_load32(in + p + m)) m += 4;
+                    while (m < cap_len && in[c + m] == in[p + m]) m++;
+                }
+                if (m >= UZ_DF_MIN_MATCH) { mlen[l] = m; mdist[l] = dist; has[l] = 1; }
+            }
+        }
+    }
+    w.sync(); // every probe before the first insert
+    w.insert_max(tab, h, val, can);
+    if (inside) return false;
+    // greedy, left to right
+    const uint64_t kept = w.ballot(has);
+    uint32_t cur = next > g ? next - g : 0;
+    covered = uz_df_below(cur);
+    taken = 0;
+    while (cur < cnt) {
+        const uint64_t m = kept & ~uz_df_below(cur);
+        if (!m) break;
+        const uint32_t j = (uint32_t)__builtin_ctzll(m);
+        const uint32_t len = w.get(mlen, j);
+        taken |= 1ull << j;
+        covered |= uz_df_below(j + len) & ~uz_df_below(j + 1);
+        cur = j + len;
+        next = g + cur;
+    }
+    if (next < g + cnt) next = g + cnt;
+    return true;
+}
+
+// the slice as one stored block (BTYPE = 00): 5 + n bytes
+template <typename W>
+UZ_DF_HD uint32_t uz_df_store_raw(W &w, const uint8_t *in, uint32_t n, uint8_t *out) {
+    w.drain(); // (the words that left before must not land on top of the stored bytes)
+    w.sync();
+    UZ_DF_EACH(w, l) {
+        if (l == 0) {
+            out[0] = 1; // BFINAL = 1, BTYPE = 00
+            out[1] = (uint8_t)(n & 0xFF); out[2] = (uint8_t)(n >> 8);
+            out[3] = (uint8_t)(~n & 0xFF); out[4] = (uint8_t)((~n >> 8) & 0xFF);
+        }
+        for (uint32_t i = l; i < n; i += 64) out[5 + i] = in[i];
+    }
+    return 5 + n;
 }
 
 // in [n] (0 < n <= UZ_DF_SLICE) -> out (a slot of cap >= 5 + n bytes, 4-byte aligned) -> the stream's bytes.  *stored: the fallback was taken.
@@ -162,46 +241,9 @@ UZ_DF_HD uint32_t uz_deflate_slice(W &w, UzDfLds &S, const uint8_t *in, uint32_t
     bool give_up = false;
     for (uint32_t g = 0; g < n; g += 64) {
         const uint32_t cnt = n - g < 64 ? n - g : 64;
-        const bool inside = next >= g + cnt; // the whole group lies inside a match
-        Lane h, val, can, mlen, mdist, has;
-        UZ_DF_EACH(w, l) {
-            const uint32_t p = g + l;
-            can[l] = p + 4 <= n ? 1u : 0u;
-            h[l] = can[l] ? uz_df_hash(uz_df_load32(in + p)) : 0u;
-            val[l] = p + 1;
-            mlen[l] = 0; mdist[l] = 0; has[l] = 0;
-            if (can[l] && !inside) {
-                const uint32_t c1 = S.tab[h[l]];
-                if (c1) {
-                    const uint32_t c = c1 - 1, dist = p - c; // c < g <= p
-                    const uint32_t cap_len = n - p < UZ_DF_MAX_MATCH ? n - p : UZ_DF_MAX_MATCH;
-                    uint32_t m = 0;
-                    if (dist <= UZ_DF_MAX_DIST) {
-                        while (m + 4 <= cap_len && uz_df_load32(in + c + m) == uz_df_load32(in + p + m)) m += 4;
-                        while (m < cap_len && in[c + m] == in[p + m]) m++;
-                    }
-                    if (m >= UZ_DF_MIN_MATCH) { mlen[l] = m; mdist[l] = dist; has[l] = 1; }
-                }
-            }
-        }
-        w.sync(); // every probe before the first insert
-        w.insert_max(S.tab, h, val, can);
-        if (inside) continue;
-        // greedy, left to right
-        const uint64_t kept = w.ballot(has);
-        uint32_t cur = next > g ? next - g : 0;
-        uint64_t covered = uz_df_below(cur), taken = 0;
-        while (cur < cnt) {
-            const uint64_t m = kept & ~uz_df_below(cur);
-            if (!m) break;
-            const uint32_t j = (uint32_t)__builtin_ctzll(m);
-            const uint32_t len = w.get(mlen, j);
-            taken |= 1ull << j;
-            covered |= uz_df_below(j + len) & ~uz_df_below(j + 1);
-            cur = j + len;
-            next = g + cur;
-        }
-        if (next < g + cnt) next = g + cnt;
+        Lane mlen, mdist;
+        uint64_t taken = 0, covered = 0;
+        if (!uz_df_group(w, S.tab, in, n, g, next, mlen, mdist, taken, covered)) continue;
         // tokens, their bit lengths, their places
         Lane tok, nb, at;
         UZ_DF_EACH(w, l) {
@@ -237,17 +279,7 @@ UZ_DF_HD uint32_t uz_deflate_slice(W &w, UzDfLds &S, const uint8_t *in, uint32_t
     }
     if (give_up) { // one stored block
         stored = true;
-        w.drain(); // (the words that left before must not land on top of the stored bytes)
-        w.sync();
-        UZ_DF_EACH(w, l) {
-            if (l == 0) {
-                out[0] = 1; // BFINAL = 1, BTYPE = 00
-                out[1] = (uint8_t)(n & 0xFF); out[2] = (uint8_t)(n >> 8);
-                out[3] = (uint8_t)(~n & 0xFF); out[4] = (uint8_t)((~n >> 8) & 0xFF);
-            }
-            for (uint32_t i = l; i < n; i += 64) out[5 + i] = in[i];
-        }
-        return limit;
+        return uz_df_store_raw(w, in, n, out);
     }
     bitpos += 7; // end of block: seven zero bits, which the window holds already
     const uint32_t words = ((bitpos + 31) >> 5) - wbase;

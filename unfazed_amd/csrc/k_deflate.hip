@@ -1,9 +1,12 @@
-// k_deflate.hip -- BGZF blocks written on the device (unfazed_hip.h: uz_bgzf_deflate).  deflate_body.hpp is the body: the parse rule, the fixed-
-// Huffman coder, the stored fallback.  Here: the wavefront that runs it, the launches of a chunk and the host side of a call.
+// k_deflate.hip -- BGZF blocks written on the device (unfazed_hip.h: uz_bgzf_deflate, uz_bgzf_deflate_coded).  deflate_body.hpp is the body: the
+// parse rule, the fixed-Huffman coder, the stored fallback; deflate_dyn.hpp the second coder over the same parse, which picks the shortest of a
+// dynamic, a fixed and a stored block per slice.  Here: the wavefront that runs them, the launches of a chunk and the host side of a call.
 //
 // The input is cut into slices of 65 280 bytes, one BGZF block each, and goes up in chunks of UZ_BGZF_CHUNK_BYTES (32 MiB, rounded down to whole
 // slices: a slice's edges do not depend on the chunk size), chunk k + 1 copied on the copy stream while chunk k is worked on:
 //   k_bgzf_deflate    one wavefront per slice: its raw DEFLATE stream into a scratch slot of UZ_DF_SLOT bytes, and the stream's byte count
+//   k_bgzf_deflate_dyn  (UZ_DF_CODE_DYNAMIC: in k_bgzf_deflate's place) the same through deflate_dyn.hpp: two passes over the slice, its tokens
+//                     parked between them in a buffer of the context, 65 280 words a slice: 131 MB for a 32 MiB chunk, 4.3 GB at the 1 GiB cap
 //   k_bgzf_crc32_out  one wavefront per slice: the CRC-32 of its bytes (crc32_wave.hpp, the code k_bgzf_crc32 compares with)
 //   uz_len_scan       exclusive scan of the blocks' sizes (18 + stream + 8) -> off [n + 1] (one workgroup)
 //   k_bgzf_frame      one workgroup per block: header, stream, CRC-32 and ISIZE, back to back at off; a block whose written bytes differ from its
@@ -14,7 +17,7 @@
 #include <algorithm>
 
 #include "crc32_wave.hpp"
-#include "deflate_body.hpp"
+#include "deflate_dyn.hpp"
 #include "text_out.hpp"
 
 #define UZ_DF_F_SIZE 1u /* a framed block's written bytes differ from its scanned size */
@@ -55,6 +58,7 @@ struct DfWave { // the 64 lanes of a wavefront share a slice
         }
     }
     __device__ __forceinline__ void or_word(uint32_t *w, uint32_t v) const { atomicOr(w, v); } // (LDS)
+    __device__ __forceinline__ void add_word(uint32_t *w, uint32_t v) const { atomicAdd(w, v); } // (LDS)
 };
 
 __global__ __launch_bounds__(64) void k_bgzf_deflate(int32_t n_slices, const uint8_t *__restrict__ in, int64_t in_bytes, uint8_t *__restrict__ slots,
@@ -67,6 +71,19 @@ __global__ __launch_bounds__(64) void k_bgzf_deflate(int32_t n_slices, const uin
     DfWave w;
     bool stored = false;
     const uint32_t bytes = uz_deflate_slice(w, S, in + at, n, slots + (size_t)s * UZ_DF_SLOT, UZ_DF_SLOT, stored);
+    if ((threadIdx.x & 63u) == 0) count[s] = bytes;
+}
+
+__global__ __launch_bounds__(64) void k_bgzf_deflate_dyn(int32_t n_slices, const uint8_t *__restrict__ in, int64_t in_bytes, uint8_t *__restrict__ slots,
+                                                         uint32_t *tokens /* [n_slices * UZ_DY_TOKENS] */, uint32_t *__restrict__ count /* [n_slices] */) {
+    __shared__ UzDyLds S;
+    const int32_t s = (int32_t)blockIdx.x;
+    if (s >= n_slices) return;
+    const int64_t at = (int64_t)s * UZ_DF_SLICE;
+    const uint32_t n = in_bytes - at < (int64_t)UZ_DF_SLICE ? (uint32_t)(in_bytes - at) : UZ_DF_SLICE;
+    DfWave w;
+    uint32_t kind = 0;
+    const uint32_t bytes = uz_deflate_slice_dyn(w, S, in + at, n, slots + (size_t)s * UZ_DF_SLOT, UZ_DF_SLOT, tokens + (size_t)s * UZ_DY_TOKENS, UZ_DY_TOKENS, kind);
     if ((threadIdx.x & 63u) == 0) count[s] = bytes;
 }
 
@@ -132,8 +149,12 @@ struct Timer { // the two events of the measured form
 
 } // namespace
 
-int uz_bgzf_deflate_impl(uz_ctx *c, const uint8_t *data, int64_t n_bytes, int64_t *n_blocks, const uint8_t **bgzf, int64_t *bgzf_bytes, int repeat, double *kernel_ms) {
+int uz_bgzf_deflate_impl(uz_ctx *c, const uint8_t *data, int64_t n_bytes, int code, int64_t *kinds, int64_t *n_blocks, const uint8_t **bgzf, int64_t *bgzf_bytes,
+                         int repeat, double *kernel_ms) {
     UZ_REQUIRE(n_blocks && bgzf && bgzf_bytes && n_bytes >= 0, UZ_E_ARG, "BGZF deflate: bad arguments");
+    UZ_REQUIRE(code == UZ_DF_CODE_FIXED || code == UZ_DF_CODE_DYNAMIC, UZ_E_ARG, "BGZF deflate: bad code argument (UZ_DF_CODE_FIXED or UZ_DF_CODE_DYNAMIC)");
+    const bool dyn = code == UZ_DF_CODE_DYNAMIC;
+    if (kinds) kinds[0] = kinds[1] = kinds[2] = 0;
     UZ_REQUIRE(data || n_bytes == 0, UZ_E_ARG, "BGZF deflate: no data");
     *n_blocks = 0; *bgzf = nullptr; *bgzf_bytes = 0;
     if (kernel_ms) *kernel_ms = 0;
@@ -166,6 +187,7 @@ int uz_bgzf_deflate_impl(uz_ctx *c, const uint8_t *data, int64_t n_bytes, int64_
         const size_t o_flag = ((size_t)ns + 1) * 8, o_count = o_flag + 8, o_crc = o_count + (size_t)ns * 4, small_bytes = up256(o_crc + (size_t)ns * 4);
         const size_t out_cap = nb + (size_t)ns * (UZ_BGZF_HEAD + UZ_BGZF_TAIL + 5); // every slice stored
         c->df_slots.ensure((size_t)ns * UZ_DF_SLOT + 64);
+        if (dyn) c->df_tokens.ensure((size_t)ns * UZ_DY_TOKENS);
         c->df.small.ensure(small_bytes + 64);
         c->df.out.ensure(up256(out_cap) + 64);
         c->df.small_pin.room(64);
@@ -174,11 +196,15 @@ int uz_bgzf_deflate_impl(uz_ctx *c, const uint8_t *data, int64_t n_bytes, int64_
         uint32_t *d_count = reinterpret_cast<uint32_t *>(c->df.small.p + o_count);
         uint32_t *d_crc = reinterpret_cast<uint32_t *>(c->df.small.p + o_crc);
         const uint8_t *d_in = c->df.in[q & 1].p;
+        auto deflate = [&] { // the kernel of the chosen code
+            if (dyn) hipLaunchKernelGGL(k_bgzf_deflate_dyn, dim3((unsigned)ns), dim3(64), 0, st, ns, d_in, (int64_t)nb, c->df_slots.p, c->df_tokens.p, d_count);
+            else hipLaunchKernelGGL(k_bgzf_deflate, dim3((unsigned)ns), dim3(64), 0, st, ns, d_in, (int64_t)nb, c->df_slots.p, d_count);
+        };
         L.wait(q);
         UZ_HIP(hipMemsetAsync(d_flag, 0, 8, st));
         {
             ProfScope ps(c, UZ_K_DEFLATE);
-            hipLaunchKernelGGL(k_bgzf_deflate, dim3((unsigned)ns), dim3(64), 0, st, ns, d_in, (int64_t)nb, c->df_slots.p, d_count);
+            deflate();
             UZ_HIP(hipGetLastError());
             hipLaunchKernelGGL(k_bgzf_crc32_out, dim3((unsigned)std::min<int32_t>(ns, 256 * 16)), dim3(64), 0, st, ns, d_in, (int64_t)nb, d_crc);
             UZ_HIP(hipGetLastError());
@@ -193,7 +219,7 @@ int uz_bgzf_deflate_impl(uz_ctx *c, const uint8_t *data, int64_t n_bytes, int64_
         uz_kcopy(c, c->df.small_pin.p, d_off + ns, 16); // the chunk's bytes, the flag word
         if (repeat > 0) { // the measured form: the same launch again, which writes the same bytes into the same slots
             UZ_HIP(hipEventRecord(T.e0, st));
-            for (int r = 0; r < repeat; r++) hipLaunchKernelGGL(k_bgzf_deflate, dim3((unsigned)ns), dim3(64), 0, st, ns, d_in, (int64_t)nb, c->df_slots.p, d_count);
+            for (int r = 0; r < repeat; r++) deflate();
             UZ_HIP(hipGetLastError());
             UZ_HIP(hipEventRecord(T.e1, st));
         }
@@ -211,6 +237,15 @@ int uz_bgzf_deflate_impl(uz_ctx *c, const uint8_t *data, int64_t n_bytes, int64_
         L.fetch(c->df.out.p, (size_t)len);
         UZ_HIP(hipStreamSynchronize(st));
         L.total += len;
+    }
+    if (kinds) { // each block's form is its stream's BTYPE: 00 stored, 01 fixed, 10 dynamic
+        const uint8_t *p = c->df.res.p;
+        for (int64_t at = 0; at + (int64_t)UZ_BGZF_HEAD < L.total;) {
+            const uint32_t btype = (p[at + UZ_BGZF_HEAD] >> 1) & 3u;
+            UZ_REQUIRE(btype < 3, UZ_E_STATE, "BGZF deflate: a block of no known form");
+            kinds[btype]++;
+            at += ((int64_t)p[at + 16] | ((int64_t)p[at + 17] << 8)) + 1;
+        }
     }
     *n_blocks = total_slices;
     *bgzf_bytes = L.total;

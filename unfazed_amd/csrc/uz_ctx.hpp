@@ -486,9 +486,11 @@ struct uz_ctx {
     DevBuf<int64_t> bed_off;
     PinBuf bed_pin;
     // uz_vcf_rows (k_vcfout.hip), uz_bcf_rows (k_bcfout.hip) -- a set of its own: the text it returns is the input of the uz_vcf_rows call behind
-    // it -- and uz_bgzf_deflate (k_deflate.hip: counts and CRC-32s among the small results, no lengths; df_slots: the streams' scratch slots)
+    // it -- and uz_bgzf_deflate (k_deflate.hip: counts and CRC-32s among the small results, no lengths; df_slots: the streams' scratch slots;
+    // df_tokens: the dynamic code's tokens between its passes, 65 280 words a slice of the chunk, allocated by the first call that asks for it)
     OutBufs vo, bo, df;
     DevBuf<uint8_t> df_slots;
+    DevBuf<uint32_t> df_tokens;
 
     // last phase (k_reads.hip)
     bool phase_valid = false;
@@ -688,6 +690,7 @@ void uz_head_rank_impl(uz_ctx *c, int head_id, int32_t readlen, const int64_t *k
 void uz_head_fetch_impl(uz_ctx *c, int head_id, int32_t file, int32_t *out, int64_t cap, int64_t *n);
 void uz_head_free_impl(uz_ctx *c, int head_id);
 // BGZF blocks of a host buffer (k_deflate.hip; deflate_body.hpp is the body)
-int uz_bgzf_deflate_impl(uz_ctx *c, const uint8_t *data, int64_t n_bytes, int64_t *n_blocks, const uint8_t **bgzf, int64_t *bgzf_bytes, int repeat, double *kernel_ms);
+int uz_bgzf_deflate_impl(uz_ctx *c, const uint8_t *data, int64_t n_bytes, int code, int64_t *kinds, int64_t *n_blocks, const uint8_t **bgzf, int64_t *bgzf_bytes,
+                         int repeat, double *kernel_ms);
 // a BCF's records as VCF text lines (k_bcfout.hip; bcf_row.hpp is the body)
 int uz_bcf_rows_impl(uz_ctx *c, const uz_bcf_lines_view *records, int64_t *off, uint64_t *samp_at, const uint8_t **bytes, uint8_t *handed_back);

@@ -4,7 +4,9 @@ UZ_OUT_BGZF decides what an outfile whose name ends in ".gz" holds:
   not set, or any other value   plain text, whatever the file is called (as before)
   "host"    BGZF: one block per 65 280 bytes (htslib's slice), zlib's raw DEFLATE at UZ_OUT_BGZF_LEVEL (6), the 28-byte end-of-file marker
   "device"  the same blocks from backend.bgzf_deflate (uz_bgzf_deflate; csrc/deflate_body.hpp states its rules).  Asked for by name, the
-            route makes its backend and fails loudly without a device, as UZ_BCF_ROUTE=device does
+            route makes its backend and fails loudly without a device, as UZ_BCF_ROUTE=device does.  UZ_OUT_BGZF_CODE=dynamic (read on this
+            route alone; any case) asks for the dynamic coder (csrc/deflate_dyn.hpp): per block the shortest of a dynamic-Huffman, the fixed and
+            a stored block; not set, or any other value: the fixed code, as before
 An outfile without ".gz", and /dev/stdout, stay plain on every setting.  The two routes' files differ in their compressed bytes (the
 compressors differ) and in nothing else: the inflated text, every ISIZE, every CRC-32 and the end-of-file marker are the same."""
 import os
@@ -15,12 +17,18 @@ import zlib
 SLICE = 0xFF00  # bytes of text per BGZF block: htslib's BGZF_BLOCK_SIZE
 BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
 OUT_STATS = {"bgzf_device_blocks": 0, "bgzf_host_blocks": 0, "bgzf_calls": 0}  # blocks the device / zlib wrote, files written as BGZF
+OUT_KINDS = {"stored": 0, "fixed": 0, "dynamic": 0}  # the device's blocks by their form
 
 
 def out_route():
     """UZ_OUT_BGZF: "device", "host", or None (not set, or any other value: every outfile is plain text)"""
     v = os.environ.get("UZ_OUT_BGZF", "").lower()
     return v if v in ("device", "host") else None
+
+
+def out_code():
+    """UZ_OUT_BGZF_CODE on the device route: "dynamic", or "fixed" (not set, or any other value)"""
+    return "dynamic" if os.environ.get("UZ_OUT_BGZF_CODE", "").lower() == "dynamic" else "fixed"
 
 
 def bgzf_block(stream: bytes, payload) -> bytes:
@@ -73,8 +81,10 @@ def write_output(outfile, parts):
     if route == "device":
         from . import session
         backend = session.get_backend()  # asked for by name: the route makes its backend, and fails loudly without a device
-        blocks, n, _ = backend.bgzf_deflate(data)
+        blocks, n, _, kinds = backend.bgzf_deflate(data, code=out_code(), kinds=True)
         OUT_STATS["bgzf_device_blocks"] += n
+        for key, k in zip(("stored", "fixed", "dynamic"), kinds):
+            OUT_KINDS[key] += k
     else:
         blocks, n = host_blocks(data)
         OUT_STATS["bgzf_host_blocks"] += n
