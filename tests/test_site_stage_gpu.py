@@ -142,7 +142,7 @@ def test_cohort_scan_matches_per_family_scans(engine, n_sites, n_fam):
 def test_asynchronous_site_stage_equals_the_synchronous_one(engine, slab):
     """uz_sites_family_upload_async: sites + genotype columns queued on the copy stream, the first use waits for them and folds
     the complex flag -- the same classes and the same windows as the synchronous uploads.  slab: the host columns sit back to
-    back in one pinned block and cross the link as ONE copy into a mirror block (abi.hip: SlabPlan)."""
+    back in one pinned block and cross the link as ONE copy into a mirror block (uz_stage.hpp: SlabPlan)."""
     from unfazed_amd.engine import PinnedPool
     sc = make_sites(200_000, seed=21, contig_lens=[4e7, 2e7], weird_frac=0.03)
     idx, contig, start, end = place_dnms(sc, 1500, seed=6)

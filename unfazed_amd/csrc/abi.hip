@@ -1,6 +1,6 @@
 // abi.hip -- the extern "C" entry points of include/unfazed_hip.h: context, staging of
-// the decoded columns into HBM, and the launch sequence of the stages.
-#include "uz_ctx.hpp"
+// the decoded alignment columns into HBM, and the launch sequence of the stages (the site, family and sample tables: tables.hip).
+#include "uz_stage.hpp"
 #include "find_answer.hpp"
 
 #include <chrono>
@@ -8,48 +8,12 @@
 #include <map>
 #include <mutex>
 
-void uz_fold_complex(uz_ctx *c, uint8_t *gt, const uint8_t *sflags, int64_t n);
 bool uz_site_scan_fresh(const uz_ctx *c, const FamilyDev &f, bool need_cnv);
 
-namespace {
-
-// The message of a failed call.  uz_bgzf_inflate_to_host may run on a decoder's worker thread beside the owner's calls, so the
-// context's message is written under a lock, and uz_last_error hands out a copy that belongs to the calling thread.
-void set_error(uz_ctx *c, const std::string &msg) {
-    std::lock_guard<std::mutex> lk(c->err_mu);
-    c->err = msg;
-}
-
-template <typename F>
-int guarded(uz_ctx *c, F &&fn) {
-    if (!c) return UZ_E_ARG;
-    try {
-        (void)hipSetDevice(c->device);
-        fn();
-        return 0;
-    } catch (const UzError &e) {
-        set_error(c, e.msg);
-        return e.code;
-    } catch (const std::exception &e) {
-        set_error(c, e.what());
-        return UZ_E_ARG;
-    } catch (...) {
-        set_error(c, "unknown error");
-        return UZ_E_ARG;
-    }
-}
-
-// One copy instead of one per column: when the host columns of a table sit back to back in one slab of (pinned) memory --
-// a decoder that carves its output from one allocation -- the slab goes over the link as a whole into a mirror block and
-// the columns' device addresses follow from their offsets in it.  Every separate copy costs the link ~8 us of set-up, and
-// a staged table has about twenty columns, half of them tiny.  A staging routine runs its h2d() calls twice: a planning
-// pass that only looks at the host addresses, then -- mirrored or not -- the pass that yields the device pointers.
-// the page-locked blocks this library handed out (uz_pinned_alloc): the one-copy path ships a span of host memory as a whole, so the
-// span must lie inside ONE block the caller really owns -- never a guess from address density (columns of separate allocations
-// that happen to sit close together, with unmapped or foreign memory between them)
+// the page-locked blocks this library handed out (uz_pinned_alloc), for the one-copy path of uz_stage.hpp
 static std::mutex g_pinned_mu;
 static std::map<uintptr_t, size_t> g_pinned;
-static bool inside_one_pinned_block(const uint8_t *lo, const uint8_t *hi) {
+bool inside_one_pinned_block(const uint8_t *lo, const uint8_t *hi) {
     std::lock_guard<std::mutex> g(g_pinned_mu);
     auto it = g_pinned.upper_bound((uintptr_t)lo);
     if (it == g_pinned.begin()) return false;
@@ -57,163 +21,19 @@ static bool inside_one_pinned_block(const uint8_t *lo, const uint8_t *hi) {
     return (uintptr_t)lo >= it->first && (uintptr_t)hi <= it->first + it->second;
 }
 
-struct SlabPlan {
-    int mode = 1; // 1 planning, 2 mirrored
-    const uint8_t *lo = nullptr, *hi = nullptr;
-    size_t sum = 0;
-    std::vector<const uint8_t *> at;
-    uint8_t *dev = nullptr;
-    void add(const void *p, size_t bytes) {
-        const uint8_t *q = (const uint8_t *)p;
-        if (!lo || q < lo) lo = q;
-        if (!hi || q + bytes > hi) hi = q + bytes;
-        sum += bytes;
-        at.push_back(q);
-    }
-    size_t span() const { return (size_t)(hi - lo); }
-    bool worth() const {
-        if (at.size() < 2 || span() > sum + sum / 8 + 1024 * at.size()) return false;
-        for (const uint8_t *q : at)
-            if ((size_t)(q - lo) % 256) return false; // the kernels' vector loads want the carver's alignment
-        return inside_one_pinned_block(lo, hi);
-    }
-};
-static thread_local SlabPlan *g_slab = nullptr;
-struct SlabScope {
-    explicit SlabScope(SlabPlan *p) { g_slab = p; }
-    ~SlabScope() { g_slab = nullptr; }
-};
-static const bool g_slab_off = getenv("UZ_NO_SLAB_COPY") != nullptr;
+namespace {
 
-template <typename T>
-const T *h2d(hipStream_t st, T *dst, const T *host, size_t n) {
-    if (n) {
-        UZ_REQUIRE(host != nullptr, UZ_E_ARG, "null column pointer");
-        if (g_slab && g_slab->mode == 1) { g_slab->add(host, n * sizeof(T)); return dst; }
-        if (g_slab && g_slab->mode == 2) return reinterpret_cast<const T *>(g_slab->dev + ((const uint8_t *)host - g_slab->lo));
-        UZ_HIP(hipMemcpyAsync(dst, host, n * sizeof(T), hipMemcpyHostToDevice, st));
-    }
-    return dst;
-}
-// after the planning pass: ship the slab (mirror: the device block that receives it) or fall back to column copies
-static void slab_commit(uz_ctx *c, hipStream_t st, SlabPlan &plan, DevBlock &mirror) {
-    if (!g_slab_off && plan.worth()) {
-        mirror = uz_block_get(c, plan.span() + 512);
-        UZ_HIP(hipMemcpyAsync(mirror.p, plan.lo, plan.span(), hipMemcpyHostToDevice, st));
-        plan.dev = mirror.p;
-        plan.mode = 2;
-    } else
-        g_slab = nullptr;
-}
-
-SitesDev &sites_of(uz_ctx *c, int id) {
-    UZ_REQUIRE(id >= 0 && id < (int)c->sites.size() && c->sites[id].live, UZ_E_ARG, "unknown sites handle");
-    SitesDev &s = c->sites[id];
-    if (s.pending) { // queued by uz_sites_family_upload_async
-        s.pending = false;
-        UZ_HIP(hipStreamWaitEvent(c->stream, s.ready, 0));
-    }
-    uz_sites_expand(c, s, nullptr); // (compact form used before its family: the sites alone)
-    return s;
-}
-FamilyDev &fam_of(uz_ctx *c, int id) {
-    UZ_REQUIRE(id >= 0 && id < (int)c->fams.size() && c->fams[id].live, UZ_E_ARG, "unknown family handle");
-    FamilyDev &f = c->fams[id];
-    if (f.pending) { // queued by uz_sites_family_upload_async: the compute stream waits for the copies, then folds the complex flag
-        f.pending = false;
-        UZ_HIP(hipStreamWaitEvent(c->stream, f.ready, 0));
-        SitesDev &s0 = c->sites[f.sites_id];
-        if (f.het_only && s0.n) s0.expand_pending = true; // (sites used before their family: expanded again, now with the het columns)
-        if (s0.expand_pending) { // compact site form: ONE launch expands the sites and readies the family
-            if (s0.pending) { s0.pending = false; UZ_HIP(hipStreamWaitEvent(c->stream, s0.ready, 0)); }
-            uz_sites_expand(c, s0, &f);
-        } else {
-            SitesDev &s = sites_of(c, f.sites_id);
-            uz_family_widen(c, f, s.n);
-            uz_fold_complex(c, f.gt, s.sflags, s.n);
-        }
-    }
-    return f;
-}
 ReadsDev &reads_of(uz_ctx *c, int id) {
     UZ_REQUIRE(id >= 0 && id < (int)c->reads.size() && c->reads[id].live, UZ_E_ARG, "unknown reads handle");
     return c->reads[id];
 }
 
-void free_family(uz_ctx *c, FamilyDev &f) {
-    if (f.ready) { (void)hipEventSynchronize(f.ready); (void)hipEventDestroy(f.ready); f.ready = nullptr; }
-    f.pending = false;
-    if (f.samples_id >= 0 && f.samples_id < (int)c->samples.size()) c->samples[(size_t)f.samples_id].live_fams--; // (its gt / cls / wide depths lie in a block of the table's)
-    uz_block_put(c, f.block);
-    uz_block_put(c, f.wide_block);
-    f = FamilyDev();
-}
-void free_samples(uz_ctx *c, SamplesDev &m) {
-    if (m.ready) { (void)hipEventSynchronize(m.ready); (void)hipEventDestroy(m.ready); }
-    uz_block_put(c, m.block);
-    uz_block_put(c, m.wide_block);
-    for (DevBlock &b : m.fam_blocks) uz_block_put(c, b);
-    m = SamplesDev();
-}
-SamplesDev &samples_of(uz_ctx *c, int id) {
-    UZ_REQUIRE(id >= 0 && id < (int)c->samples.size() && c->samples[id].live, UZ_E_ARG, "unknown sample table handle");
-    return c->samples[id];
-}
-void free_sites(uz_ctx *c, SitesDev &s) {
-    if (s.ready) { (void)hipEventSynchronize(s.ready); (void)hipEventDestroy(s.ready); }
-    uz_block_put(c, s.block);
-    uz_block_put(c, s.mirror);
-    s = SitesDev();
-}
 void free_reads(uz_ctx *c, ReadsDev &r) {
     if (r.built) { (void)hipEventSynchronize(r.built); (void)hipEventDestroy(r.built); } // (a table freed before its first use: its build may still run)
     if (r.ready) (void)hipEventDestroy(r.ready);
     uz_block_put(c, r.block);
     uz_block_put(c, r.mirror);
     r = ReadsDev();
-}
-
-// carve arrays out of a table's block
-struct Carver {
-    uint8_t *base;
-    size_t off = 0;
-    explicit Carver(uint8_t *b) : base(b) {}
-    template <typename T>
-    T *take(size_t n) {
-        off = (off + 255) & ~(size_t)255;
-        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
-        off += (n ? n : 1) * sizeof(T) + 64; // +64: vector tail reads stay in-bounds
-        return p;
-    }
-};
-
-// the table of uz_samples_from_text / uz_samples_from_bcf: rows carved at the stride of uz_samples_upload, filled by parse(m, chunk bytes)
-template <typename F>
-void samples_from_records(uz_ctx *c, int sites_id, int64_t n_sites, int32_t n_pick, int *id, int64_t *n_unsettled, F parse) {
-    size_t chunk = (size_t)32 << 20;
-    if (const char *e = getenv("UZ_VCF_CHUNK_BYTES")) { // (read per call: a test hook for the multi-chunk path)
-        const long long v = atoll(e);
-        if (v > 0) chunk = (size_t)v;
-    }
-    chunk = std::min<size_t>(chunk, (size_t)1 << 31);
-    const size_t n = (size_t)n_sites, ns = (size_t)n_pick;
-    SamplesDev m;
-    m.live = true; m.sites_id = sites_id; m.n_samples = n_pick; m.n_wide = 0;
-    m.stride = (n + 64 + 255) & ~(size_t)255;
-    for (int pass = 0; pass < 2; pass++) {
-        Carver cv(pass ? m.block.p : nullptr);
-        m.gt = cv.take<uint8_t>(ns * m.stride);
-        m.rd = cv.take<uint16_t>(ns * m.stride); m.ad = cv.take<uint16_t>(ns * m.stride); m.gq = cv.take<uint16_t>(ns * m.stride);
-        if (!pass) m.block = uz_block_get(c, cv.off + 256);
-    }
-    try {
-        parse(m, chunk);
-    } catch (...) { uz_block_put(c, m.block); throw; }
-    m.need_settle = !m.unsettled.empty();
-    *n_unsettled = (int64_t)m.unsettled.size();
-    const int k = new_slot(c->samples);
-    c->samples[(size_t)k] = m;
-    *id = k;
 }
 
 } // namespace
@@ -458,7 +278,7 @@ static bool find_recall(uz_ctx *c, const FindKey &k) {
         if (find_key_eq(c->find_alt[a].key, k)) { find_swap(c, a); c->find_valid = true; c->find_mode = k.mode; return true; }
     return false;
 }
-static void find_forget(uz_ctx *c, int fam_id /* -1: everything */) {
+void find_forget(uz_ctx *c, int fam_id /* -1: everything */) {
     if (fam_id < 0 || c->find_key.fam == fam_id) { c->find_key.valid = false; c->find_valid = false; }
     for (int a = 0; a < UZ_FIND_ALTS; a++)
         if (fam_id < 0 || c->find_alt[a].key.fam == fam_id) c->find_alt[a].key.valid = false;
@@ -561,564 +381,6 @@ int uz_set_params(uz_ctx *c, const uz_params *p) {
     return guarded(c, [&] {
         UZ_REQUIRE(p != nullptr, UZ_E_ARG, "null params");
         c->P = *p;
-    });
-}
-
-int uz_sites_upload(uz_ctx *c, const uz_sites_view *v, int *id) {
-    return guarded(c, [&] {
-        UZ_REQUIRE(v && id && v->n_sites >= 0 && v->n_contigs >= 0, UZ_E_ARG, "bad sites view");
-        UZ_REQUIRE(!v->pos_d16 && !v->bases8, UZ_E_ARG, "the compact site form is taken by uz_sites_family_upload_async only");
-        UZ_REQUIRE(v->n_sites < (int64_t)0x7FFFFFF0, UZ_E_RANGE, "more than 2^31 sites");
-        const int k = new_slot(c->sites);
-        SitesDev s;
-        s.live = true; s.owned = true;
-        s.n = v->n_sites; s.n_contigs = v->n_contigs;
-        s.contig_off_h.assign(v->contig_off, v->contig_off + v->n_contigs + 1);
-        const size_t n = (size_t)s.n;
-        for (int pass = 0; pass < 2; pass++) { // one pooled block for the table: no hipMalloc / hipFree per staged pass
-            Carver cv(pass ? s.block.p : nullptr);
-            s.contig_off = cv.take<int64_t>((size_t)v->n_contigs + 1);
-            s.pos = cv.take<int32_t>(n); s.sflags = cv.take<uint8_t>(n); s.ref_base = cv.take<uint8_t>(n); s.alt_base = cv.take<uint8_t>(n);
-            if (!pass) s.block = uz_block_get(c, cv.off + 256);
-        }
-        try {
-            h2d(c->stream, s.contig_off, v->contig_off, (size_t)v->n_contigs + 1);
-            h2d(c->stream, s.pos, v->pos, n); h2d(c->stream, s.sflags, v->sflags, n);
-            h2d(c->stream, s.ref_base, v->ref_base, n); h2d(c->stream, s.alt_base, v->alt_base, n);
-            UZ_HIP(hipStreamSynchronize(c->stream));
-        } catch (...) { uz_block_put(c, s.block); throw; }
-        c->sites[k] = s;
-        *id = k;
-    });
-}
-
-int uz_sites_adopt_device(uz_ctx *c, const uz_sites_view *v, int *id) {
-    return guarded(c, [&] {
-        UZ_REQUIRE(v && id && v->n_sites >= 0 && v->n_contigs >= 0, UZ_E_ARG, "bad sites view");
-        UZ_REQUIRE(!v->pos_d16 && !v->bases8, UZ_E_ARG, "the compact site form is taken by uz_sites_family_upload_async only");
-        const int k = new_slot(c->sites);
-        SitesDev s;
-        s.live = true; s.owned = false;
-        s.n = v->n_sites; s.n_contigs = v->n_contigs;
-        s.contig_off_h.resize((size_t)v->n_contigs + 1);
-        UZ_HIP(hipMemcpy(s.contig_off_h.data(), v->contig_off, ((size_t)v->n_contigs + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
-        for (int pass = 0; pass < 2; pass++) {
-            Carver cv(pass ? s.block.p : nullptr);
-            s.contig_off = cv.take<int64_t>((size_t)v->n_contigs + 1);
-            if (!pass) s.block = uz_block_get(c, cv.off + 256);
-        }
-        h2d(c->stream, s.contig_off, (const int64_t *)s.contig_off_h.data(), (size_t)v->n_contigs + 1);
-        s.pos = const_cast<int32_t *>(v->pos);
-        s.sflags = const_cast<uint8_t *>(v->sflags);
-        s.ref_base = const_cast<uint8_t *>(v->ref_base);
-        s.alt_base = const_cast<uint8_t *>(v->alt_base);
-        UZ_HIP(hipStreamSynchronize(c->stream));
-        c->sites[k] = s;
-        *id = k;
-    });
-}
-
-// which form the site columns of a view come in: true = compact (uz_sites_view.pos_d16 ...), its escape list checked here, on the host,
-// since the expansion kernel places every escape in its span by it
-static bool sites_view_compact(const uz_sites_view *v) {
-    if (!v->pos_d16 && !v->bases8) return false;
-    const int64_t n = v->n_sites, n_spans = (n + UZ_SITE_SPAN - 1) / UZ_SITE_SPAN;
-    UZ_REQUIRE(v->pos_d16 && v->bases8 && !v->pos && !v->sflags && !v->ref_base && !v->alt_base, UZ_E_ARG,
-               "a compact sites view sets pos_d16 and bases8 and leaves pos / sflags / ref_base / alt_base null");
-    UZ_REQUIRE(v->span_pos && v->pos_esc_off && v->n_pos_esc >= 0 && (v->n_pos_esc == 0 || (v->pos_esc_idx && v->pos_esc_val)), UZ_E_ARG,
-               "a compact sites view needs span_pos, pos_esc_off and its escape list");
-    UZ_REQUIRE(v->pos_esc_off[0] == 0 && v->pos_esc_off[n_spans] == v->n_pos_esc, UZ_E_ARG, "pos_esc_off does not cover the escape list");
-    for (int64_t sp = 0; sp < n_spans; sp++) {
-        const int64_t a = v->pos_esc_off[sp], b = v->pos_esc_off[sp + 1];
-        UZ_REQUIRE(a <= b, UZ_E_ARG, "pos_esc_off must ascend");
-        for (int64_t e = a; e < b; e++) // (a span's first site takes span_pos, in the kernel and in uz_sites_unpack: no escape may name it)
-            UZ_REQUIRE(v->pos_esc_idx[e] > sp * UZ_SITE_SPAN && v->pos_esc_idx[e] < std::min(n, (sp + 1) * UZ_SITE_SPAN) &&
-                           (e == a || v->pos_esc_idx[e] > v->pos_esc_idx[e - 1]), UZ_E_ARG, "an escape outside its span, at its span's first site, or out of order");
-    }
-    return true;
-}
-
-// which form the nine columns of a family view come in: true = eight bits (all nine of ref_depth8 / alt_depth8 / gq8 set, the 16-bit ones null)
-static bool family_view_eight(const uz_family_view *v) {
-    int n8 = 0, n16 = 0;
-    for (int m = 0; m < 3; m++) {
-        n8 += (v->ref_depth8[m] != nullptr) + (v->alt_depth8[m] != nullptr) + (v->gq8[m] != nullptr);
-        n16 += (v->ref_depth[m] != nullptr) + (v->alt_depth[m] != nullptr) + (v->gq[m] != nullptr);
-    }
-    // (a table without sites may leave every pointer null)
-    UZ_REQUIRE((n8 == 9 && n16 == 0) || (n8 == 0 && n16 == 9) || (n8 == 0 && n16 == 0), UZ_E_ARG,
-               "a family view carries its nine columns in 16 bits OR in 8 bits (ref_depth8 / alt_depth8 / gq8), all nine");
-    return n8 == 9;
-}
-
-// which form ...: true = the het form (uz_family_view.het9 ...: nine bytes per kid-het site), its offsets checked here -- that they ascend
-// from 0 to n_het; the expansion kernel holds every span's count against them (no host pass over gt)
-static bool family_view_het(const uz_family_view *v, int64_t n_sites) {
-    if (!v->het9 && !v->het_span_off) return false;
-    const int64_t n_spans = (n_sites + UZ_SITE_SPAN - 1) / UZ_SITE_SPAN;
-    UZ_REQUIRE(v->het_span_off && v->n_het >= 0 && v->n_het <= n_sites && (v->n_het == 0 || v->het9), UZ_E_ARG,
-               "a het-form family view sets het_span_off, n_het and -- for any het site -- het9");
-    UZ_REQUIRE(v->het_span_off[0] == 0 && v->het_span_off[n_spans] == v->n_het, UZ_E_ARG, "het_span_off does not cover het9");
-    for (int64_t sp = 0; sp < n_spans; sp++) UZ_REQUIRE(v->het_span_off[sp] <= v->het_span_off[sp + 1], UZ_E_ARG, "het_span_off must ascend");
-    return true;
-}
-
-// What needs the genotype columns of sites where the kid is not het -- the DEL / DUP classes, the columns themselves -- refuses a family
-// that was staged in the het form
-static void refuse_het_only(const FamilyDev &f, const char *what) {
-    if (f.het_only) throw UzError{UZ_E_STATE, std::string(what) + ": this family was staged in the het form (genotype columns of the kid-het sites only)"};
-}
-
-// the too-deep sites of a family view (host pointers) -> the family's side table on the device
-static void family_wide(uz_ctx *c, hipStream_t st, const uz_family_view *v, FamilyDev &f, int64_t n_sites) {
-    f.n_wide = 0;
-    if (!v || v->n_wide <= 0) return;
-    UZ_REQUIRE(v->wide_site != nullptr, UZ_E_ARG, "n_wide set but wide_site is null");
-    const size_t w = (size_t)v->n_wide;
-    f.wide_host = std::make_shared<std::vector<int32_t>>(6 * w);
-    std::vector<int32_t> &dep = *f.wide_host;
-    for (int m = 0; m < 3; m++) {
-        UZ_REQUIRE(v->wide_ref_depth[m] && v->wide_alt_depth[m], UZ_E_ARG, "null wide depth column");
-        for (size_t k = 0; k < w; k++) {
-            const int32_t r = v->wide_ref_depth[m][k], a = v->wide_alt_depth[m][k];
-            UZ_REQUIRE(r >= -1 && a >= -1 && r <= (1 << 30) && a <= (1 << 30), UZ_E_RANGE, "wide depth outside [-1, 2^30]");
-            dep[(size_t)m * w + k] = r; dep[(size_t)(3 + m) * w + k] = a;
-        }
-    }
-    for (size_t k = 0; k < w; k++) {
-        UZ_REQUIRE(v->wide_site[k] >= 0 && v->wide_site[k] < n_sites && (k == 0 || v->wide_site[k] > v->wide_site[k - 1]), UZ_E_ARG,
-                   "wide_site must be ascending site indices of the table");
-    }
-    for (int pass = 0; pass < 2; pass++) {
-        Carver cv(pass ? f.wide_block.p : nullptr);
-        f.wide_site = cv.take<int64_t>(w);
-        f.wide_depth = cv.take<int32_t>(6 * w);
-        if (!pass) f.wide_block = uz_block_get(c, cv.off + 256);
-    }
-    UZ_HIP(hipMemcpyAsync(f.wide_site, v->wide_site, w * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    UZ_HIP(hipMemcpyAsync(f.wide_depth, dep.data(), 6 * w * sizeof(int32_t), hipMemcpyHostToDevice, st)); // (`dep` lives as long as the family)
-    f.n_wide = (int64_t)w;
-}
-
-static void family_common(uz_ctx *c, int sites_id, FamilyDev &f) {
-    SitesDev &s = sites_of(c, sites_id);
-    f.live = true;
-    f.sites_id = sites_id;
-    uz_fold_complex(c, f.gt, s.sflags, s.n);
-    UZ_HIP(hipStreamSynchronize(c->stream));
-}
-
-int uz_family_upload(uz_ctx *c, int sites_id, const uz_family_view *v, int *id) {
-    return guarded(c, [&] {
-        UZ_REQUIRE(v && id, UZ_E_ARG, "bad family view");
-        SitesDev &s = sites_of(c, sites_id);
-        FamilyDev f;
-        f.owned = true;
-        const size_t n = (size_t)s.n;
-        const bool eight = family_view_eight(v);
-        uint8_t *st8[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        for (int pass = 0; pass < 2; pass++) {
-            Carver cv(pass ? f.block.p : nullptr);
-            f.cls = cv.take<uint8_t>(n);
-            f.gt = cv.take<uint8_t>(n);
-            for (int m = 0; m < 3; m++) { f.rd[m] = cv.take<uint16_t>(n); f.ad[m] = cv.take<uint16_t>(n); f.gq[m] = cv.take<uint16_t>(n); }
-            if (eight) for (int k = 0; k < 9; k++) st8[k] = cv.take<uint8_t>(n);
-            if (!pass) f.block = uz_block_get(c, cv.off + 256);
-        }
-        try {
-            h2d(c->stream, f.gt, v->gt, n);
-            if (eight) {
-                for (int m = 0; m < 3; m++) {
-                    f.stage8[m] = h2d(c->stream, st8[m], v->ref_depth8[m], n); f.stage8[3 + m] = h2d(c->stream, st8[3 + m], v->alt_depth8[m], n);
-                    f.stage8[6 + m] = h2d(c->stream, st8[6 + m], v->gq8[m], n);
-                }
-                f.widen_pending = true; f.gq_clamped = true;
-                uz_family_widen(c, f, s.n);
-            } else
-                for (int m = 0; m < 3; m++) {
-                    h2d(c->stream, f.rd[m], v->ref_depth[m], n); h2d(c->stream, f.ad[m], v->alt_depth[m], n); h2d(c->stream, f.gq[m], v->gq[m], n);
-                }
-            family_wide(c, c->stream, v, f, s.n);
-            family_common(c, sites_id, f);
-        } catch (...) { uz_block_put(c, f.block); uz_block_put(c, f.wide_block); throw; }
-        const int k = new_slot(c->fams);
-        c->fams[k] = f;
-        *id = k;
-    });
-}
-
-int uz_sites_family_upload_async(uz_ctx *c, const uz_sites_view *v, const uz_family_view *fv, int *sites_id, int *fam_id) {
-    return guarded(c, [&] {
-        UZ_REQUIRE(v && fv && sites_id && fam_id && v->n_sites >= 0 && v->n_contigs >= 0, UZ_E_ARG, "bad sites / family view");
-        UZ_REQUIRE(v->n_sites < (int64_t)0x7FFFFFF0, UZ_E_RANGE, "more than 2^31 sites");
-        SitesDev s;
-        s.live = true; s.owned = true;
-        s.n = v->n_sites; s.n_contigs = v->n_contigs;
-        s.contig_off_h.assign(v->contig_off, v->contig_off + v->n_contigs + 1);
-        const size_t n = (size_t)s.n;
-        FamilyDev f;
-        f.owned = true;
-        const bool eight = family_view_eight(fv);
-        const bool compact = sites_view_compact(v);
-        const bool het = family_view_het(fv, s.n);
-        UZ_REQUIRE(!het || (compact && !eight && !fv->ref_depth[0]), UZ_E_ARG,
-                   "the het form of a family travels with the compact site form and without the nine plain columns");
-        const size_t n_spans = (n + UZ_SITE_SPAN - 1) / UZ_SITE_SPAN, n_esc = compact ? (size_t)v->n_pos_esc : 0, n_het = het ? (size_t)fv->n_het : 0;
-        uint8_t *st8[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        uint8_t *st_het9 = nullptr;
-        int32_t *st_hoff = nullptr;
-        uint16_t *c_d16 = nullptr;
-        uint8_t *c_b8 = nullptr;
-        int32_t *c_span = nullptr, *c_eidx = nullptr, *c_eval = nullptr, *c_eoff = nullptr;
-        for (int pass = 0; pass < 2; pass++) {
-            Carver cv(pass ? s.block.p : nullptr);
-            s.contig_off = cv.take<int64_t>((size_t)v->n_contigs + 1);
-            s.pos = cv.take<int32_t>(n); s.sflags = cv.take<uint8_t>(n); s.ref_base = cv.take<uint8_t>(n); s.alt_base = cv.take<uint8_t>(n);
-            if (compact) {
-                c_d16 = cv.take<uint16_t>(n); c_b8 = cv.take<uint8_t>(n); c_span = cv.take<int32_t>(n_spans);
-                c_eidx = cv.take<int32_t>(n_esc); c_eval = cv.take<int32_t>(n_esc); c_eoff = cv.take<int32_t>(n_spans + 1);
-            }
-            if (!pass) s.block = uz_block_get(c, cv.off + 256);
-        }
-        for (int pass = 0; pass < 2; pass++) {
-            Carver cv(pass ? f.block.p : nullptr);
-            f.cls = cv.take<uint8_t>(n);
-            f.gt = cv.take<uint8_t>(n);
-            for (int m = 0; m < 3; m++) { f.rd[m] = cv.take<uint16_t>(n); f.ad[m] = cv.take<uint16_t>(n); f.gq[m] = cv.take<uint16_t>(n); }
-            if (eight) for (int k = 0; k < 9; k++) st8[k] = cv.take<uint8_t>(n);
-            if (het) { st_het9 = cv.take<uint8_t>(9 * n_het); st_hoff = cv.take<int32_t>(n_spans + 1); }
-            if (!pass) f.block = uz_block_get(c, cv.off + 256);
-        }
-        try {
-            hipStream_t st = c->copy_stream;
-            SlabPlan plan;
-            SlabScope slab_scope(&plan);
-            for (int stage_pass = 0; stage_pass < 2; stage_pass++) {
-                if (stage_pass) slab_commit(c, st, plan, s.mirror);
-                s.contig_off = const_cast<int64_t *>(h2d(st, s.contig_off, v->contig_off, (size_t)v->n_contigs + 1));
-                if (compact) { // (the staged bytes may end up in the mirror block: the plain columns are always the table's own)
-                    s.c_d16 = h2d(st, c_d16, v->pos_d16, n); s.c_b8 = h2d(st, c_b8, v->bases8, n); s.c_span = h2d(st, c_span, v->span_pos, n_spans);
-                    s.c_eidx = h2d(st, c_eidx, v->pos_esc_idx, n_esc); s.c_eval = h2d(st, c_eval, v->pos_esc_val, n_esc);
-                    s.c_eoff = h2d(st, c_eoff, v->pos_esc_off, n_spans + 1);
-                } else {
-                    s.pos = const_cast<int32_t *>(h2d(st, s.pos, v->pos, n)); s.sflags = const_cast<uint8_t *>(h2d(st, s.sflags, v->sflags, n));
-                    s.ref_base = const_cast<uint8_t *>(h2d(st, s.ref_base, v->ref_base, n)); s.alt_base = const_cast<uint8_t *>(h2d(st, s.alt_base, v->alt_base, n));
-                }
-                f.gt = const_cast<uint8_t *>(h2d(st, f.gt, fv->gt, n)); // (bit 6 is written by the library: the mirror is the library's own memory)
-                if (eight) { // (the staged bytes may end up in the mirror block: the 16-bit columns are always the family's own)
-                    for (int m = 0; m < 3; m++) {
-                        f.stage8[m] = h2d(st, st8[m], fv->ref_depth8[m], n); f.stage8[3 + m] = h2d(st, st8[3 + m], fv->alt_depth8[m], n);
-                        f.stage8[6 + m] = h2d(st, st8[6 + m], fv->gq8[m], n);
-                    }
-                } else if (het) { // (the same: the expansion writes the family's own 16-bit columns from them)
-                    f.het9 = h2d(st, st_het9, fv->het9, 9 * n_het); f.het_off = h2d(st, st_hoff, fv->het_span_off, n_spans + 1);
-                } else
-                    for (int m = 0; m < 3; m++) {
-                        f.rd[m] = const_cast<uint16_t *>(h2d(st, f.rd[m], fv->ref_depth[m], n));
-                        f.ad[m] = const_cast<uint16_t *>(h2d(st, f.ad[m], fv->alt_depth[m], n));
-                        f.gq[m] = const_cast<uint16_t *>(h2d(st, f.gq[m], fv->gq[m], n));
-                    }
-            }
-            if (eight) { f.widen_pending = true; f.gq_clamped = true; }
-            if (het) { f.het_only = true; f.n_het = (int64_t)n_het; f.gq_clamped = true; }
-            s.expand_pending = compact && n;
-            family_wide(c, st, fv, f, s.n);
-            UZ_HIP(hipEventCreateWithFlags(&f.ready, hipEventDisableTiming));
-            UZ_HIP(hipEventRecord(f.ready, st));
-            UZ_HIP(hipEventCreateWithFlags(&s.ready, hipEventDisableTiming));
-            UZ_HIP(hipEventRecord(s.ready, st));
-            s.pending = true;
-        } catch (...) { uz_block_put(c, s.block); uz_block_put(c, s.mirror); uz_block_put(c, f.block); uz_block_put(c, f.wide_block); throw; }
-        const int ks = new_slot(c->sites);
-        c->sites[ks] = s;
-        f.live = true; f.sites_id = ks; f.pending = true;
-        const int kf = new_slot(c->fams);
-        c->fams[kf] = f;
-        *sites_id = ks; *fam_id = kf;
-    });
-}
-
-int uz_family_adopt_device(uz_ctx *c, int sites_id, const uz_family_view *v, int *id) {
-    return guarded(c, [&] {
-        UZ_REQUIRE(v && id, UZ_E_ARG, "bad family view");
-        UZ_REQUIRE(!family_view_eight(v), UZ_E_ARG, "uz_family_adopt_device takes the 16-bit columns (the kernels read them in place)");
-        FamilyDev f;
-        f.owned = false;
-        f.gt = const_cast<uint8_t *>(v->gt); // bit 6 is written by the library (complex flag)
-        for (int m = 0; m < 3; m++) {
-            f.rd[m] = const_cast<uint16_t *>(v->ref_depth[m]);
-            f.ad[m] = const_cast<uint16_t *>(v->alt_depth[m]);
-            f.gq[m] = const_cast<uint16_t *>(v->gq[m]);
-            UZ_REQUIRE(((uintptr_t)f.rd[m] | (uintptr_t)f.ad[m] | (uintptr_t)f.gq[m]) % 16 == 0, UZ_E_ARG,
-                       "device columns must be 16-byte aligned");
-        }
-        UZ_REQUIRE((uintptr_t)f.gt % 16 == 0, UZ_E_ARG, "device columns must be 16-byte aligned");
-        {
-            SitesDev &s = sites_of(c, sites_id);
-            for (int pass = 0; pass < 2; pass++) {
-                Carver cv(pass ? f.block.p : nullptr);
-                f.cls = cv.take<uint8_t>((size_t)s.n);
-                if (!pass) f.block = uz_block_get(c, cv.off + 256);
-            }
-        }
-        try {
-            family_wide(c, c->stream, v, f, sites_of(c, sites_id).n);
-            family_common(c, sites_id, f);
-        } catch (...) { uz_block_put(c, f.block); uz_block_put(c, f.wide_block); throw; }
-        const int k = new_slot(c->fams);
-        c->fams[k] = f;
-        *id = k;
-    });
-}
-
-// ---- the cohort form: a sample table, and trios made from it (unfazed_hip.h) ----------------------------------------------------------
-int uz_samples_upload(uz_ctx *c, int sites_id, const uz_samples_view *v, int *id) {
-    return guarded(c, [&] {
-        UZ_REQUIRE(v && id && v->n_samples >= 0 && v->n_wide >= 0, UZ_E_ARG, "bad samples view");
-        SitesDev &s = sites_of(c, sites_id);
-        const size_t n = (size_t)s.n, ns = (size_t)v->n_samples, w = (size_t)v->n_wide;
-        UZ_REQUIRE(!(n && ns) || (v->gt && v->ref_depth && v->alt_depth && v->gq), UZ_E_ARG, "null column pointer");
-        UZ_REQUIRE(!w || v->wide_site, UZ_E_ARG, "n_wide set but wide_site is null");
-        UZ_REQUIRE(!(w && ns) || (v->wide_ref_depth && v->wide_alt_depth), UZ_E_ARG, "null wide depth column");
-        for (size_t k = 0; k < w; k++)
-            UZ_REQUIRE(v->wide_site[k] >= 0 && v->wide_site[k] < s.n && (k == 0 || v->wide_site[k] > v->wide_site[k - 1]), UZ_E_ARG,
-                       "wide_site must be ascending site indices of the table");
-        for (size_t k = 0; k < w * ns; k++) {
-            const int32_t r = v->wide_ref_depth[k], a = v->wide_alt_depth[k];
-            UZ_REQUIRE(r >= -1 && a >= -1 && r <= (1 << 30) && a <= (1 << 30), UZ_E_RANGE, "wide depth outside [-1, 2^30]");
-        }
-        SamplesDev m;
-        m.live = true; m.sites_id = sites_id; m.n_samples = v->n_samples; m.n_wide = v->n_wide;
-        m.stride = (n + 64 + 255) & ~(size_t)255; // every row 256-byte aligned, vector tail reads stay in-bounds
-        for (int pass = 0; pass < 2; pass++) {
-            Carver cv(pass ? m.block.p : nullptr);
-            m.gt = cv.take<uint8_t>(ns * m.stride);
-            m.rd = cv.take<uint16_t>(ns * m.stride); m.ad = cv.take<uint16_t>(ns * m.stride); m.gq = cv.take<uint16_t>(ns * m.stride);
-            m.wide_site = cv.take<int64_t>(w); m.wide_rd = cv.take<int32_t>(ns * w); m.wide_ad = cv.take<int32_t>(ns * w);
-            if (!pass) m.block = uz_block_get(c, cv.off + 256);
-        }
-        try {
-            hipStream_t st = c->copy_stream;
-            if (n && ns) { // one strided copy per column: the host rows lie back to back, the device rows at the aligned stride
-                UZ_HIP(hipMemcpy2DAsync(m.gt, m.stride, v->gt, n, n, ns, hipMemcpyHostToDevice, st));
-                UZ_HIP(hipMemcpy2DAsync(m.rd, m.stride * 2, v->ref_depth, n * 2, n * 2, ns, hipMemcpyHostToDevice, st));
-                UZ_HIP(hipMemcpy2DAsync(m.ad, m.stride * 2, v->alt_depth, n * 2, n * 2, ns, hipMemcpyHostToDevice, st));
-                UZ_HIP(hipMemcpy2DAsync(m.gq, m.stride * 2, v->gq, n * 2, n * 2, ns, hipMemcpyHostToDevice, st));
-            }
-            if (w) {
-                UZ_HIP(hipMemcpyAsync(m.wide_site, v->wide_site, w * sizeof(int64_t), hipMemcpyHostToDevice, st));
-                if (ns) {
-                    UZ_HIP(hipMemcpyAsync(m.wide_rd, v->wide_ref_depth, ns * w * sizeof(int32_t), hipMemcpyHostToDevice, st));
-                    UZ_HIP(hipMemcpyAsync(m.wide_ad, v->wide_alt_depth, ns * w * sizeof(int32_t), hipMemcpyHostToDevice, st));
-                }
-            }
-            UZ_HIP(hipEventCreateWithFlags(&m.ready, hipEventDisableTiming));
-            UZ_HIP(hipEventRecord(m.ready, st));
-            m.pending = true;
-        } catch (...) { if (m.ready) (void)hipEventDestroy(m.ready); (void)hipStreamSynchronize(c->copy_stream); uz_block_put(c, m.block); throw; }
-        const int k = new_slot(c->samples);
-        c->samples[(size_t)k] = m;
-        *id = k;
-    });
-}
-
-int uz_samples_from_text(uz_ctx *c, int sites_id, const uz_vcf_text_view *t, int32_t n_pick, const int32_t *pick, int *id, int64_t *n_unsettled) {
-    return guarded(c, [&] {
-        UZ_REQUIRE(t && id && n_unsettled && n_pick >= 0 && (n_pick == 0 || pick) && t->n_samples >= 0, UZ_E_ARG, "bad text view or pick list");
-        SitesDev &s = sites_of(c, sites_id);
-        UZ_REQUIRE(t->n_records == s.n, UZ_E_ARG, "the text's records are not the sites of the table");
-        UZ_REQUIRE(s.n == 0 || (t->text && t->samp_at && t->line_end && t->fmt_slot && t->text_bytes >= 0), UZ_E_ARG, "null pointer in the text view");
-        for (int32_t r = 0; r < n_pick; r++) UZ_REQUIRE(pick[r] >= 0 && pick[r] < t->n_samples, UZ_E_ARG, "picked sample column outside the file's");
-        samples_from_records(c, sites_id, s.n, n_pick, id, n_unsettled, [&](SamplesDev &m, size_t chunk) { uz_vcf_parse_text(c, t, n_pick, pick, m, chunk, m.unsettled); });
-    });
-}
-
-int uz_samples_from_bcf(uz_ctx *c, int sites_id, const uz_vcf_bcf_view *t, int32_t n_pick, const int32_t *pick, int *id, int64_t *n_unsettled) {
-    return guarded(c, [&] {
-        UZ_REQUIRE(t && id && n_unsettled && n_pick >= 0 && (n_pick == 0 || pick) && t->n_samples >= 0, UZ_E_ARG, "bad BCF view or pick list");
-        SitesDev &s = sites_of(c, sites_id);
-        UZ_REQUIRE(t->n_records == s.n, UZ_E_ARG, "the BCF's records are not the sites of the table");
-        UZ_REQUIRE(s.n == 0 || (t->data && t->fld_at && t->fld_desc && t->data_bytes >= 0), UZ_E_ARG, "null pointer in the BCF view");
-        for (int32_t r = 0; r < n_pick; r++) UZ_REQUIRE(pick[r] >= 0 && pick[r] < t->n_samples, UZ_E_ARG, "picked sample outside the file's");
-        samples_from_records(c, sites_id, s.n, n_pick, id, n_unsettled, [&](SamplesDev &m, size_t chunk) { uz_vcf_parse_bcf(c, t, n_pick, pick, m, chunk, m.unsettled); });
-    });
-}
-
-int uz_samples_unsettled(uz_ctx *c, int samples_id, int64_t *site) {
-    return guarded(c, [&] {
-        SamplesDev &m = samples_of(c, samples_id);
-        UZ_REQUIRE(m.unsettled.empty() || site, UZ_E_ARG, "null output");
-        for (size_t k = 0; k < m.unsettled.size(); k++) site[k] = m.unsettled[k];
-    });
-}
-
-int uz_samples_settle(uz_ctx *c, int samples_id, int64_t n, const int64_t *site, const uz_samples_view *v) {
-    return guarded(c, [&] {
-        SamplesDev &m = samples_of(c, samples_id);
-        UZ_REQUIRE(n >= 0 && (n == 0 || (site && v)), UZ_E_ARG, "bad settle arguments");
-        UZ_REQUIRE(m.need_settle || n == 0, UZ_E_STATE, "the sample table has no unsettled sites");
-        UZ_REQUIRE((size_t)n == m.unsettled.size() && std::equal(m.unsettled.begin(), m.unsettled.end(), site), UZ_E_ARG,
-                   "uz_samples_settle takes exactly the sites of uz_samples_unsettled, in that order");
-        if (n == 0) return;
-        const size_t un = (size_t)n, ns = (size_t)m.n_samples, w = (size_t)v->n_wide;
-        UZ_REQUIRE(v->n_samples == m.n_samples && v->n_wide >= 0, UZ_E_ARG, "the cells are not a sample table of the table's rows");
-        UZ_REQUIRE(!ns || (v->gt && v->ref_depth && v->alt_depth && v->gq), UZ_E_ARG, "null column pointer");
-        UZ_REQUIRE(!w || v->wide_site, UZ_E_ARG, "n_wide set but wide_site is null");
-        UZ_REQUIRE(!(w && ns) || (v->wide_ref_depth && v->wide_alt_depth), UZ_E_ARG, "null wide depth column");
-        std::vector<int64_t> wide_site(w);
-        for (size_t k = 0; k < w; k++) {
-            UZ_REQUIRE(v->wide_site[k] >= 0 && v->wide_site[k] < n && (k == 0 || v->wide_site[k] > v->wide_site[k - 1]), UZ_E_ARG,
-                       "wide_site must be ascending indices of the settled sites");
-            wide_site[k] = site[v->wide_site[k]];
-        }
-        for (size_t k = 0; k < w * ns; k++) {
-            const int32_t r = v->wide_ref_depth[k], a = v->wide_alt_depth[k];
-            UZ_REQUIRE(r >= -1 && a >= -1 && r <= (1 << 30) && a <= (1 << 30), UZ_E_RANGE, "wide depth outside [-1, 2^30]");
-        }
-        DevBlock tmp, wide;
-        try {
-            int64_t *d_site = nullptr;
-            uint8_t *d_gt = nullptr;
-            uint16_t *d_rd = nullptr, *d_ad = nullptr, *d_gq = nullptr;
-            for (int pass = 0; pass < 2; pass++) {
-                Carver cv(pass ? tmp.p : nullptr);
-                d_site = cv.take<int64_t>(un); d_gt = cv.take<uint8_t>(ns * un);
-                d_rd = cv.take<uint16_t>(ns * un); d_ad = cv.take<uint16_t>(ns * un); d_gq = cv.take<uint16_t>(ns * un);
-                if (!pass) tmp = uz_block_get(c, cv.off + 256);
-            }
-            UZ_HIP(hipMemcpyAsync(d_site, site, un * 8, hipMemcpyHostToDevice, c->stream));
-            if (ns) {
-                UZ_HIP(hipMemcpyAsync(d_gt, v->gt, ns * un, hipMemcpyHostToDevice, c->stream));
-                UZ_HIP(hipMemcpyAsync(d_rd, v->ref_depth, ns * un * 2, hipMemcpyHostToDevice, c->stream));
-                UZ_HIP(hipMemcpyAsync(d_ad, v->alt_depth, ns * un * 2, hipMemcpyHostToDevice, c->stream));
-                UZ_HIP(hipMemcpyAsync(d_gq, v->gq, ns * un * 2, hipMemcpyHostToDevice, c->stream));
-            }
-            uz_launch_vcf_settle(c, n, m.n_samples, d_site, d_gt, d_rd, d_ad, d_gq, m);
-            if (w) {
-                int64_t *ws = nullptr;
-                int32_t *wr = nullptr, *wa = nullptr;
-                for (int pass = 0; pass < 2; pass++) {
-                    Carver cv(pass ? wide.p : nullptr);
-                    ws = cv.take<int64_t>(w); wr = cv.take<int32_t>(ns * w); wa = cv.take<int32_t>(ns * w);
-                    if (!pass) wide = uz_block_get(c, cv.off + 256);
-                }
-                UZ_HIP(hipMemcpyAsync(ws, wide_site.data(), w * 8, hipMemcpyHostToDevice, c->stream));
-                if (ns) {
-                    UZ_HIP(hipMemcpyAsync(wr, v->wide_ref_depth, ns * w * 4, hipMemcpyHostToDevice, c->stream));
-                    UZ_HIP(hipMemcpyAsync(wa, v->wide_alt_depth, ns * w * 4, hipMemcpyHostToDevice, c->stream));
-                }
-                m.wide_site = ws; m.wide_rd = wr; m.wide_ad = wa;
-            }
-            UZ_HIP(hipStreamSynchronize(c->stream)); // (the host arrays are the caller's)
-        } catch (...) {
-            (void)hipStreamSynchronize(c->stream);
-            uz_block_put(c, tmp); uz_block_put(c, wide);
-            m.wide_site = nullptr; m.wide_rd = m.wide_ad = nullptr;
-            throw;
-        }
-        uz_block_put(c, tmp);
-        m.wide_block = wide;
-        m.n_wide = (int64_t)w;
-        m.need_settle = false;
-    });
-}
-
-int uz_families_from_samples(uz_ctx *c, int samples_id, int32_t n, const int32_t *kid, const int32_t *dad, const int32_t *mom, int *fam_ids) {
-    return guarded(c, [&] {
-        UZ_REQUIRE(n >= 0 && (n == 0 || (kid && dad && mom && fam_ids)), UZ_E_ARG, "bad trio list");
-        SamplesDev &m0 = samples_of(c, samples_id);
-        UZ_REQUIRE(!m0.need_settle, UZ_E_STATE, "the sample table has unsettled sites: uz_samples_settle first");
-        UZ_REQUIRE(m0.sites_id >= 0 && m0.sites_id < (int)c->sites.size() && c->sites[(size_t)m0.sites_id].live, UZ_E_ARG, "the sample table's sites table is gone");
-        std::vector<int32_t> trio((size_t)n * 3);
-        for (int32_t t = 0; t < n; t++) {
-            const int32_t idx[3] = {kid[t], dad[t], mom[t]};
-            for (int q = 0; q < 3; q++) {
-                UZ_REQUIRE(idx[q] >= 0 && idx[q] < m0.n_samples, UZ_E_ARG, "sample index outside the table");
-                trio[(size_t)t * 3 + q] = idx[q];
-            }
-        }
-        if (n == 0) return;
-        SitesDev &s = sites_of(c, m0.sites_id);
-        if (m0.pending) { m0.pending = false; UZ_HIP(hipStreamWaitEvent(c->stream, m0.ready, 0)); }
-        const size_t S = (size_t)s.n, w = (size_t)m0.n_wide;
-        const size_t A = (S + 64 + 255) & ~(size_t)255; // cls and gt of trio t: t * 2A and t * 2A + A; the wide depths behind them
-        const size_t wide_at = (size_t)n * 2 * A;
-        DevBlock blk = uz_block_get(c, wide_at + (size_t)n * 6 * w * sizeof(int32_t) + 512);
-        int made = 0;
-        try {
-            c->trio_idx.ensure(trio.size());
-            UZ_HIP(hipMemcpyAsync(c->trio_idx.p, trio.data(), trio.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-            int32_t *wide_out = reinterpret_cast<int32_t *>(blk.p + wide_at);
-            uz_launch_family_pack(c, m0, s, n, c->trio_idx.p, blk.p + A, 2 * A, wide_out);
-            UZ_HIP(hipStreamSynchronize(c->stream)); // (`trio` is pageable host memory; the families are ready when the call returns)
-            for (int32_t t = 0; t < n; t++) {
-                const int k = new_slot(c->fams); // (may move c->fams: no reference into it is held across)
-                FamilyDev f;
-                f.live = true; f.owned = true; f.sites_id = m0.sites_id; f.samples_id = samples_id;
-                f.cls = blk.p + (size_t)t * 2 * A;
-                f.gt = blk.p + (size_t)t * 2 * A + A;
-                SamplesDev &m = c->samples[(size_t)samples_id];
-                const int32_t *ix = &trio[(size_t)t * 3];
-                for (int q = 0; q < 3; q++) {
-                    f.rd[q] = m.rd + (size_t)ix[q] * m.stride; f.ad[q] = m.ad + (size_t)ix[q] * m.stride; f.gq[q] = m.gq + (size_t)ix[q] * m.stride;
-                }
-                f.n_wide = m.n_wide;
-                f.wide_site = m.wide_site;
-                f.wide_depth = w ? wide_out + (size_t)t * 6 * w : nullptr;
-                c->fams[(size_t)k] = f;
-                m.live_fams++;
-                fam_ids[t] = k;
-                made++;
-            }
-            c->samples[(size_t)samples_id].fam_blocks.push_back(blk);
-        } catch (...) {
-            (void)hipStreamSynchronize(c->stream);
-            for (int t = 0; t < made; t++) free_family(c, c->fams[(size_t)fam_ids[t]]);
-            uz_block_put(c, blk);
-            throw;
-        }
-    });
-}
-
-int uz_family_fetch(uz_ctx *c, int fam_id, uint8_t *gt, uint16_t *cols) {
-    return guarded(c, [&] {
-        FamilyDev &f = fam_of(c, fam_id);
-        refuse_het_only(f, "uz_family_fetch");
-        SitesDev &s = sites_of(c, f.sites_id);
-        const size_t n = (size_t)s.n;
-        if (!n) return;
-        UZ_REQUIRE(gt != nullptr && cols != nullptr, UZ_E_ARG, "null output");
-        uz_family_widen(c, f, s.n);
-        UZ_HIP(hipStreamSynchronize(c->stream));
-        UZ_HIP(hipMemcpy(gt, f.gt, n, hipMemcpyDeviceToHost));
-        for (int q = 0; q < 3; q++) {
-            UZ_HIP(hipMemcpy(cols + (size_t)q * n, f.rd[q], n * 2, hipMemcpyDeviceToHost));
-            UZ_HIP(hipMemcpy(cols + (size_t)(3 + q) * n, f.ad[q], n * 2, hipMemcpyDeviceToHost));
-            UZ_HIP(hipMemcpy(cols + (size_t)(6 + q) * n, f.gq[q], n * 2, hipMemcpyDeviceToHost));
-        }
-    });
-}
-
-int uz_sites_fetch(uz_ctx *c, int sites_id, int32_t *pos, uint8_t *sflags, uint8_t *ref_base, uint8_t *alt_base) {
-    return guarded(c, [&] {
-        SitesDev &s = sites_of(c, sites_id); // (a pending compact table: expanded here, without its family)
-        const size_t n = (size_t)s.n;
-        if (!n) return;
-        UZ_REQUIRE(pos != nullptr && sflags != nullptr && ref_base != nullptr && alt_base != nullptr, UZ_E_ARG, "null output");
-        UZ_HIP(hipStreamSynchronize(c->stream));
-        UZ_HIP(hipMemcpy(pos, s.pos, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-        UZ_HIP(hipMemcpy(sflags, s.sflags, n, hipMemcpyDeviceToHost));
-        UZ_HIP(hipMemcpy(ref_base, s.ref_base, n, hipMemcpyDeviceToHost));
-        UZ_HIP(hipMemcpy(alt_base, s.alt_base, n, hipMemcpyDeviceToHost));
-    });
-}
-
-int uz_samples_free(uz_ctx *c, int samples_id) {
-    return guarded(c, [&] {
-        SamplesDev &m = samples_of(c, samples_id);
-        UZ_REQUIRE(m.live_fams == 0, UZ_E_STATE, "families made from this sample table are alive: uz_sites_free frees them with it");
-        UZ_HIP(hipStreamSynchronize(c->stream));
-        free_samples(c, m);
     });
 }
 
@@ -1383,8 +645,7 @@ int uz_reads_upload_impl(uz_ctx *c, const uz_reads_view *v, ReadsDev &r) {
     uint32_t *cigar = nullptr, *cigar_in = nullptr, *cigar_off_in = nullptr; uint8_t *seq4 = nullptr, *qlow = nullptr, *seq_in = nullptr;
     int32_t *start, *end, *tlen, *mate; uint32_t *qname; uint16_t *flag, *l_seq, *n_cigar; uint8_t *mapq, *aux;
     void *scratch = nullptr;
-    for (int pass = 0; pass < 2; pass++) {
-        Carver cv(pass ? r.block.p : nullptr);
+    r.block = uz_carve(c, [&](Carver &cv) {
         carve_common(cv, r);
         cigar = cv.take<uint32_t>(nc);
         seq4 = cv.take<uint8_t>(nu * UZ_SEQ4_UNIT_BYTES);
@@ -1396,8 +657,7 @@ int uz_reads_upload_impl(uz_ctx *c, const uz_reads_view *v, ReadsDev &r) {
         mapq = cv.take<uint8_t>(n); aux = cv.take<uint8_t>(n);
         cigar_in = cv.take<uint32_t>(nci); cigar_off_in = cv.take<uint32_t>(n); seq_in = cv.take<uint8_t>(nsq);
         scratch = cv.take<uint8_t>(uz_rec_scratch_bytes(r.n));
-        if (!pass) r.block = uz_block_get(c, cv.off + 256);
-    }
+    });
     h2d(st, r.contig_off, v->contig_off, (size_t)v->n_contigs + 1);
     h2d(st, r.max_span, v->max_span, (size_t)v->n_contigs);
     RecColumns col;
@@ -1435,14 +695,12 @@ static int adopt_device(uz_ctx *c, const uz_reads_packed_view *v) {
     const bool a_lists = v->n_low != nullptr || (v->tup && v->tup_n_low);
     r.n_qlow_pos = a_lists ? v->n_qlow_pos : 0;
     r.n_plane_units = a_lists ? v->n_seq_units : v->n_row_units;
-    for (int pass = 0; pass < 2; pass++) {
-        Carver cv(pass ? r.block.p : nullptr);
+    r.block = uz_carve(c, [&](Carver &cv) {
         carve_common(cv, r);
         if (v->seq2) seq4_own = cv.take<uint8_t>((size_t)r.n_seq_units * UZ_SEQ4_UNIT_BYTES);
         if (a_lists) qlow_own = cv.take<uint8_t>((size_t)r.n_seq_units * UZ_QLOW_UNIT_BYTES);
         scratch = cv.take<uint8_t>(uz_rec_scratch_bytes(r.n));
-        if (!pass) r.block = uz_block_get(c, cv.off + 256);
-    }
+    });
     try {
         hipStream_t st = c->stream;
         UZ_HIP(hipMemcpyAsync(r.contig_off, v->contig_off, ((size_t)v->n_contigs + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
@@ -1664,8 +922,7 @@ static int extract_and_adopt(uz_ctx *c, int walk_id, const ExtractJob &j) {
     int32_t *d_span = nullptr, *start = nullptr, *tlen = nullptr, *mate = nullptr, *err = nullptr;
     uint32_t *qname = nullptr, *cigar = nullptr, *plane = nullptr, *name_rec = nullptr;
     uint16_t *flag = nullptr, *l_seq = nullptr, *n_cigar = nullptr;
-    for (int pass = 0; pass < 2; pass++) {
-        Carver cv(pass ? blk.p : nullptr);
+    blk = uz_carve(c, [&](Carver &cv) {
         if (j.from_host) { d_kept = cv.take<uz_kept_rec>(n); d_aux = cv.take<uint8_t>((size_t)j.aux_bytes + 64); }
         d_coff = cv.take<int64_t>(nctg + 1); d_span = cv.take<int32_t>(nctg + 1); err = cv.take<int32_t>(4);
         start = cv.take<int32_t>(n); tlen = cv.take<int32_t>(n); mate = cv.take<int32_t>(n); qname = cv.take<uint32_t>(n);
@@ -1675,8 +932,7 @@ static int extract_and_adopt(uz_ctx *c, int walk_id, const ExtractJob &j) {
         plane = cv.take<uint32_t>((size_t)j.n_row_units);
         if (j.names) d_names = cv.take<uint8_t>((size_t)j.names_bytes);
         if (j.keep_names) { d_kept = cv.take<uz_kept_rec>(n); name_rec = cv.take<uint32_t>((size_t)j.n_qnames); }
-        if (!pass) blk = uz_block_get(c, cv.off + 256);
-    }
+    });
     int id = -1;
     try {
         hipStream_t st = c->stream;
@@ -1882,17 +1138,6 @@ int uz_drop_derived(uz_ctx *c) {
     });
 }
 
-int uz_sites_free(uz_ctx *c, int sites_id) {
-    return guarded(c, [&] {
-        SitesDev &s = sites_of(c, sites_id);
-        UZ_HIP(hipStreamSynchronize(c->stream));
-        for (size_t k = 0; k < c->fams.size(); k++)
-            if (c->fams[k].live && c->fams[k].sites_id == sites_id) { find_forget(c, (int)k); free_family(c, c->fams[k]); }
-        for (auto &m : c->samples)
-            if (m.live && m.sites_id == sites_id) free_samples(c, m);
-        free_sites(c, s);
-    });
-}
 int uz_reads_free(uz_ctx *c, int reads_id) {
     return guarded(c, [&] {
         ReadsDev &r = reads_of(c, reads_id);
@@ -2253,14 +1498,12 @@ static CohortTable cohort_merged_table(uz_ctx *c, const uz_cohort_group *groups,
         m.live = true;
         m.n = tot_n; m.n_contigs = (int32_t)tot_contigs; m.n_qnames = (uint32_t)tot_q; m.n_cigar_total = tot_c; m.n_row_units = tot_u;
         m.n_seq_units = tot_s; m.n_plane_units = tot_p;
-        for (int pass = 0; pass < 2; pass++) {
-            Carver cv(pass ? m.block.p : nullptr);
+        m.block = uz_carve(c, [&](Carver &cv) {
             carve_common(cv, m);
             m.cigar = cv.take<uint32_t>((size_t)tot_c);
             m.seq4 = cv.take<uint8_t>((size_t)tot_s * UZ_SEQ4_UNIT_BYTES);
             m.qlow = cv.take<uint8_t>((size_t)tot_p * UZ_QLOW_UNIT_BYTES);
-            if (!pass) m.block = uz_block_get(c, cv.off + 256);
-        }
+        });
         m.qlow_thr = c->P.min_gt_qual; m.qlow_valid = true;
         try {
             std::vector<int64_t> co((size_t)tot_contigs + 1, 0);

@@ -16,6 +16,7 @@
 #include "io_common.hpp"
 #include "io_index.hpp"
 #include "io_vcf_cell.hpp"
+#include "table_views.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -1323,15 +1324,16 @@ int uz_sites_unpack(const uz_sites_view *v, int32_t *pos, uint8_t *sflags, uint8
     if (!v || !pos || !sflags || !ref_base || !alt_base) { last_error = "null argument"; return UZ_IO_E_ARG; }
     return guarded([&] {
         static const char codes[] = UZ_BASE3_CODES;
-        const int64_t n = v->n_sites, n_spans = (n + UZ_SITE_SPAN - 1) / UZ_SITE_SPAN;
-        if (n && (!v->pos_d16 || !v->bases8 || !v->span_pos || !v->pos_esc_off)) fail(UZ_IO_E_ARG, "not a compact site view");
+        UzSitesForm form;
+        const UzBroken broken = uz_sites_view_form(v, &form); // (the rules the upload holds the view to: every escape lies inside its span, in order)
+        if (broken.code) fail(UZ_IO_E_ARG, "%s", broken.text);
+        const int64_t n = v->n_sites, n_spans = uz_site_spans(n);
+        if (n && form != UZ_SITES_COMPACT) fail(UZ_IO_E_ARG, "not a compact site view");
         for (int64_t s = 0; s < n_spans; s++) {
             const int64_t lo = s * UZ_SITE_SPAN, hi = std::min(n, lo + UZ_SITE_SPAN);
             int64_t e = v->pos_esc_off[s];
             const int64_t e1 = v->pos_esc_off[s + 1];
-            if (e < 0 || e1 < e || e1 > v->n_pos_esc) fail(UZ_IO_E_ARG, "bad escape offsets");
             uint32_t p = (uint32_t)v->span_pos[s];
-            if (e < e1 && v->pos_esc_idx[e] == lo) fail(UZ_IO_E_ARG, "span %lld: an escape at the span's first site (span_pos holds its pos)", (long long)s);
             for (int64_t i = lo; i < hi; i++) {
                 if (e < e1 && v->pos_esc_idx[e] == i) p = (uint32_t)v->pos_esc_val[e++];
                 else if (i > lo) p += v->pos_d16[i];
@@ -1341,7 +1343,6 @@ int uz_sites_unpack(const uz_sites_view *v, int32_t *pos, uint8_t *sflags, uint8
                 alt_base[i] = (uint8_t)codes[std::min(b >> 3 & 7, 5)];
                 sflags[i] = (uint8_t)(b >> 6 & 1);
             }
-            if (e != e1) fail(UZ_IO_E_ARG, "span %lld: an escape outside its span", (long long)s);
         }
     });
 }
@@ -1389,10 +1390,12 @@ int uz_family_pack_het(const uz_family_view *in, int64_t n_sites, uint8_t *out, 
 int uz_family_unpack_het(const uz_family_view *v, int64_t n_sites, uint16_t *cols) {
     if (!v || (n_sites > 0 && !cols)) { last_error = "null argument"; return UZ_IO_E_ARG; }
     return guarded([&] {
-        const int64_t n = n_sites, n_spans = (n + UZ_SITE_SPAN - 1) / UZ_SITE_SPAN;
+        const int64_t n = n_sites, n_spans = uz_site_spans(n);
         if (n < 0) fail(UZ_IO_E_ARG, "bad site count");
-        if (n && (!v->gt || !v->het_span_off || v->n_het < 0 || (v->n_het && !v->het9))) fail(UZ_IO_E_ARG, "not a het-form family view");
-        if (n && (v->het_span_off[0] != 0 || v->het_span_off[n_spans] != v->n_het)) fail(UZ_IO_E_ARG, "het_span_off does not cover het9");
+        UzFamilyForm form;
+        const UzBroken broken = uz_family_view_form(v, n, true, &form); // (the rules the upload holds the view to; what depends on gt is held below)
+        if (broken.code) fail(UZ_IO_E_ARG, "%s", broken.text);
+        if (n && (form != UZ_FAMILY_HET || !v->gt)) fail(UZ_IO_E_ARG, "not a het-form family view");
         for (int64_t s = 0; s < n_spans; s++) {
             const int64_t lo = s * UZ_SITE_SPAN, hi = std::min(n, lo + UZ_SITE_SPAN);
             int64_t e = v->het_span_off[s];

@@ -1,4 +1,4 @@
-// k_bcf.hip -- the per-sample values of a BCF read on the device, straight into the rows of a sample table (uz_samples_from_bcf, abi.hip).
+// k_bcf.hip -- the per-sample values of a BCF read on the device, straight into the rows of a sample table (uz_samples_from_bcf, tables.hip).
 //
 // The host has inflated the blocks, walked the records and proven every FORMAT array to lie inside its record (io_vcf.cpp:
 // uz_vcf_decode_regions_lazy on a .bcf); what is left is GT, AD (or RO / AO) and GQ of every picked sample at every record -- the

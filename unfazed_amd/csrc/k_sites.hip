@@ -1074,7 +1074,7 @@ void uz_sites_expand(uz_ctx *c, SitesDev &s, FamilyDev *f) {
     UZ_HIP(hipGetLastError());
 }
 
-// ---- trios of a sample table (uz_families_from_samples, abi.hip) ---------------------------------------------------------------------
+// ---- trios of a sample table (uz_families_from_samples, tables.hip) ---------------------------------------------------------------------
 // The packed genotype byte of n trios in ONE launch: blockIdx.y picks the trio, a lane takes 16 consecutive sites -- three 16-byte loads (the
 // members' gt rows of the sample table), one of the site flags, one 16-byte store.  The complex bit goes in here, so a family made this way
 // needs no k_fold_complex.  Pure streaming: 4 bytes read and 1 written per site and trio, no LDS; the workgroups walk the site chunks

@@ -1,4 +1,4 @@
-// k_vcf.hip -- the sample cells of a text VCF parsed on the device, straight into the rows of a sample table (uz_samples_from_text, abi.hip).
+// k_vcf.hip -- the sample cells of a text VCF parsed on the device, straight into the rows of a sample table (uz_samples_from_text, tables.hip).
 //
 // The host has inflated the blocks, found the lines and parsed the eight fixed columns and FORMAT (io_vcf.cpp: uz_vcf_decode_regions_lazy); what
 // is left is GT, AD (or RO / AO) and GQ of every picked sample at every record -- more than 99 % of a cohort file's decode time on the host, and

@@ -135,7 +135,7 @@ struct DevBlock {
 struct SitesDev {
     bool live = false, owned = false;
     DevBlock block; // owned tables: every column in one pooled block
-    DevBlock mirror; // asynchronous upload of a slab of host columns: its image (sites + genotype columns; abi.hip: SlabPlan)
+    DevBlock mirror; // asynchronous upload of a slab of host columns: its image (sites + genotype columns; uz_stage.hpp: SlabPlan)
     int64_t n = 0;
     int32_t n_contigs = 0;
     std::vector<int64_t> contig_off_h;
@@ -273,7 +273,7 @@ struct ReadsDev {
     uint32_t n_qnames = 0;
     int64_t n_cigar_total = 0, n_row_units = 0, n_seq_units = 0;
     DevBlock block;            // everything the library owns for this table lives in this one block
-    DevBlock mirror;           // ... except, when the host columns came over the link as one slab, the slab's image (abi.hip: SlabPlan)
+    DevBlock mirror;           // ... except, when the host columns came over the link as one slab, the slab's image (uz_stage.hpp: SlabPlan)
     int64_t *contig_off = nullptr;
     int32_t *max_span = nullptr;
     void *rec_a = nullptr, *rec_b = nullptr; // RecA / RecB headers (phase_body.hpp)
@@ -356,7 +356,7 @@ struct uz_ctx {
     std::vector<DevBlock> block_pool;
     uz_params P;
     std::string err;
-    std::mutex err_mu; // (err is written by whichever thread's call failed: abi.hip set_error)
+    std::mutex err_mu; // (err is written by whichever thread's call failed: uz_stage.hpp set_error)
     std::vector<SitesDev> sites;
     std::vector<FamilyDev> fams;
     std::vector<ReadsDev> reads;

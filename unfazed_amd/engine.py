@@ -1251,7 +1251,7 @@ class PinnedPool:
 
     def new_slab(self, nbytes: int):
         """The allocations that follow come back to back (256-byte aligned) out of ONE page-locked block of `nbytes`: the
-        columns of a table staged this way cross the link as one copy (abi.hip: SlabPlan).  What does not fit any more gets
+        columns of a table staged this way cross the link as one copy (uz_stage.hpp: SlabPlan).  What does not fit any more gets
         a block of its own, as without a slab."""
         nbytes = max(1 << 20, int(nbytes))
         p = C.c_void_p()
