@@ -63,7 +63,9 @@ extern "C" {
 #define UZ_K_BCFOUT_FILL 21 /* k_bcfout_fill */
 #define UZ_K_DEFLATE 22       /* k_bgzf_deflate + k_bgzf_crc32_out + the scan of the blocks' sizes (uz_bgzf_deflate), one launch per chunk of input */
 #define UZ_K_DEFLATE_FRAME 23 /* k_bgzf_frame */
-#define UZ_K_COUNT 24
+#define UZ_K_TBX_KEYS 24      /* k_tbx_mark + the scan of the tiles' line starts + k_tbx_starts + k_tbx_keys (uz_bgzf_deflate_indexed), per chunk of input */
+#define UZ_K_TBX_TABLE 25     /* the passes over all rows behind the last chunk: k_tbx_flags, two scans, k_tbx_emit, k_tbx_nintv, k_tbx_linear, k_tbx_fill */
+#define UZ_K_COUNT 26
 
 typedef struct uz_ctx uz_ctx;
 
@@ -499,6 +501,51 @@ int uz_bgzf_deflate(uz_ctx *ctx, const uint8_t *data /* host */, int64_t n_bytes
 #define UZ_DF_CODE_DYNAMIC 1
 int uz_bgzf_deflate_coded(uz_ctx *ctx, const uint8_t *data /* host */, int64_t n_bytes, int code, int64_t *kinds /* NULL or [3] */, int64_t *n_blocks,
                           const uint8_t **bgzf, int64_t *bgzf_bytes, int repeat, double *kernel_ms);
+
+/* uz_bgzf_deflate_coded, and the tables of a tabix index (.tbi) of the text it compresses, from the same upload (k_tbx.hip; csrc/tbx_key.hpp
+ * states the rules of a line).  The blocks are byte for byte uz_bgzf_deflate_coded's.  preset: UZ_TBX_PRESET_VCF (CHROM, POS, len(REF) and
+ * INFO/END) or UZ_TBX_PRESET_BED (columns 1 / 2 / 3); lines that begin with '#' are meta lines.  A record's virtual offset is
+ * (offset of its block << 16 | offset in the block's 65 280 bytes); the last record ends at (*bgzf_bytes << 16), where the caller's
+ * end-of-file marker goes.
+ * view (page-locked memory of the context, valid until the next uz_bgzf_deflate* call):
+ *   status    0, or why the text has no index (UZ_TBX_S_*): then n_refs = n_runs = n_linear = 0
+ *   refs      per reference, in file order: its name's place in `data`, n_intv, the pseudo-bin's values (first record's start, last record's
+ *             end, the record count)
+ *   runs      maximal runs of consecutive records with one (tid, bin), in file order: a bin's chunks are its runs, in this order (grouping
+ *             them by (tid, bin) is a stable sort of a table the index's own size: the caller's)
+ *   linear    the references' 16 kb windows back to back (n_intv each): the smallest start offset of a record that overlaps the window,
+ *             an empty window filled from the next one
+ *   host_rows the rows the call's host code settled: a chunk's first line (its predecessor is not in the chunk) and a line whose key columns
+ *             the chunk's end cut: at most two per chunk
+ * A contig that comes back after another one is not looked for here: the caller sees it in the references' names.
+ * UZ_E_ARG: any other preset, a NULL view, and what uz_bgzf_deflate_coded refuses. */
+#define UZ_TBX_PRESET_VCF 0
+#define UZ_TBX_PRESET_BED 1
+#define UZ_TBX_S_ORDER 1u  /* a start below the previous record's on the same contig */
+#define UZ_TBX_S_RANGE 2u  /* a begin or end beyond 2^29 */
+#define UZ_TBX_S_META 4u   /* a meta line among the data rows */
+#define UZ_TBX_S_EMPTY 8u  /* an empty line */
+#define UZ_TBX_S_CR 16u    /* a '\r' */
+#define UZ_TBX_S_POS 32u   /* a position that is not 1 to 10 digits */
+#define UZ_TBX_S_CUT 64u   /* (internal) a cut row that nobody settled */
+typedef struct uz_tbx_ref {
+    uint64_t name_off; /* in `data` */
+    uint32_t name_len, n_intv;
+    uint64_t v0, v1, n_rows;
+} uz_tbx_ref;
+typedef struct uz_tbx_run {
+    uint32_t tid, bin;
+    uint64_t v0, v1;
+} uz_tbx_run;
+typedef struct uz_tbx_view {
+    int64_t n_rows, n_refs, n_runs, n_linear, host_rows;
+    uint32_t status, pad_;
+    const uz_tbx_ref *refs;
+    const uz_tbx_run *runs;
+    const uint64_t *linear;
+} uz_tbx_view;
+int uz_bgzf_deflate_indexed(uz_ctx *ctx, const uint8_t *data /* host */, int64_t n_bytes, int code, int64_t *kinds /* NULL or [3] */, int64_t *n_blocks,
+                            const uint8_t **bgzf, int64_t *bgzf_bytes, int repeat, double *kernel_ms, int preset, uz_tbx_view *view);
 
 /* ---- allele-balance (CNV) stage ---------------------------------------- */
 /* K6.  Everything run_cnv_phasing does after its find (sv_phaser.py:357-423: phase_by_snvs :71-85,

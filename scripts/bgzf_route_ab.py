@@ -14,7 +14,11 @@ kernel_ms of their code's kernel over the whole text (repeat=3), the profile slo
 its input plus its output at the 6.3 TB/s a copy reaches on the box; a device-dynamic run records kernel_ms of both kernels, same process,
 alternating (fixed, dynamic, fixed, dynamic), and the split of its blocks.  It decides no default: unset stays unset.
 (profiles/bgzf_route_ab.json is the three-leg measurement from before the fourth leg.)
-    timeout -k 10 1100 python scripts/bgzf_route_ab.py [--shape cohort|trio] [--repeat 3] [--dir D] [--out profiles/bgzf_dynamic_ab.json]"""
+The index leg (--index; UZ_OUT_INDEX=tbi): under the same rules the routes are device / device-index / host / host-index, "files written" includes
+the .tbi, the data file of a route must be the same bytes with and without the index (asserted), and a device-index run records the profile
+slots of the index kernels (UZ_K_TBX_KEYS: mark + scan + starts + keys per chunk; UZ_K_TBX_TABLE: the passes behind the last chunk), the
+rows the host settled and the .tbi's size.  It writes profiles/tbx_route_ab.json.
+    timeout -k 10 1100 python scripts/bgzf_route_ab.py [--shape cohort|trio] [--repeat 3] [--dir D] [--out profiles/bgzf_dynamic_ab.json] [--index]"""
 import argparse
 import gzip
 import hashlib
@@ -32,6 +36,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import vcf_route_ab as shape  # noqa: E402 -- the generator, the records dict, the shapes
 
 ROUTES = ("unset", "host", "device", "device-dynamic")
+INDEX_ROUTES = ("device", "device-index", "host", "host-index")
 COPY_BYTES_PER_S = 6.3e12
 
 
@@ -39,6 +44,9 @@ def child(a):
     """one run of one route in this (fresh) process -> a JSON line on stdout"""
     os.environ.pop("UZ_OUT_BGZF", None)
     os.environ.pop("UZ_OUT_BGZF_CODE", None)
+    os.environ.pop("UZ_OUT_INDEX", None)
+    if a.child.endswith("-index"):
+        os.environ["UZ_OUT_INDEX"] = "tbi"
     if a.child != "unset":
         os.environ["UZ_OUT_BGZF"] = a.child.split("-")[0]
     if a.child == "device-dynamic":
@@ -47,6 +55,8 @@ def child(a):
     n_samples, n_records = shape.SHAPES[a.shape]
     eng = session.get_backend()  # (HIP start-up, the library, the context: before the timer)
     kernels = dict(k_bgzf_deflate=engine.K_DEFLATE, k_bgzf_frame=engine.K_DEFLATE_FRAME)
+    if a.child.endswith("-index"):
+        kernels.update(k_tbx_keys=engine.K_TBX_KEYS, k_tbx_table=engine.K_TBX_TABLE)
     eng.prof_enable(list(kernels.values()))
     records = shape.records_dict(n_samples, n_records)
     src, out = os.path.join(a.dir, "dnms_%s.vcf" % a.shape), os.path.join(a.dir, "out_%s_%s.vcf.gz" % (a.shape, a.child))
@@ -56,8 +66,13 @@ def child(a):
     raw = open(out, "rb").read()
     text = raw if a.child == "unset" else gzip.decompress(raw)
     run = dict(wall_s=wall, host_cpu_s=cpu, file_bytes=len(raw), text_bytes=len(text), text_sha=hashlib.sha256(text).hexdigest()[:16],
-               counters=dict(outfile.OUT_STATS), vcf_counters=dict(unfazed.VCF_STATS))
-    if a.child.startswith("device"):
+               file_sha=hashlib.sha256(raw).hexdigest()[:16], counters=dict(outfile.OUT_STATS), vcf_counters=dict(unfazed.VCF_STATS))
+    if a.child.endswith("-index"):
+        run["tbi_bytes"] = os.path.getsize(out + ".tbi")  # (a text that got no index ends the measurement here)
+        os.remove(out + ".tbi")
+    if a.child == "device-index":
+        run["prof_ms"] = {name: dict(zip(("total_ms", "launches"), eng.prof_get(k))) for name, k in kernels.items()}
+    elif a.child.startswith("device"):
         code = "dynamic" if a.child == "device-dynamic" else "fixed"
         run["prof_ms"] = {name: dict(zip(("total_ms", "launches"), eng.prof_get(k))) for name, k in kernels.items()}
         run["kinds"] = dict(outfile.OUT_KINDS)
@@ -76,11 +91,14 @@ def main():
     ap.add_argument("--shape", default="cohort", choices=sorted(shape.SHAPES))
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--dir", default=None)
-    ap.add_argument("--child", default=None, choices=list(ROUTES))
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bgzf_dynamic_ab.json"))
+    ap.add_argument("--child", default=None, choices=sorted(set(ROUTES + INDEX_ROUTES)))
+    ap.add_argument("--index", action="store_true", help="the index leg: device / device-index / host / host-index -> profiles/tbx_route_ab.json")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.child:
         return child(a)
+    routes = INDEX_ROUTES if a.index else ROUTES
+    a.out = a.out or os.path.join(ROOT, "profiles", "tbx_route_ab.json" if a.index else "bgzf_dynamic_ab.json")
     a.dir = a.dir or tempfile.mkdtemp(prefix="bgzf_route_ab_")
     os.makedirs(a.dir, exist_ok=True)
     n_samples, n_records = shape.SHAPES[a.shape]
@@ -91,9 +109,9 @@ def main():
     with open(src, "rb") as fh:  # the page cache, warm for every route
         while fh.read(1 << 24):
             pass
-    runs = {r: [] for r in ROUTES}
+    runs = {r: [] for r in routes}
     for it in range(a.repeat):
-        for route in ROUTES:
+        for route in routes:
             cmd = [sys.executable, os.path.abspath(__file__), "--child", route, "--shape", a.shape, "--dir", a.dir]
             p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
             if p.returncode != 0:  # (a child that failed ends the measurement: nothing more is started)
@@ -105,10 +123,14 @@ def main():
                   file=sys.stderr, flush=True)
     same = len({r["text_sha"] for rr in runs.values() for r in rr}) == 1
     assert same, "the routes' files hold different text (shape %s)" % a.shape
-    res = dict(what="records dict -> out.vcf.gz, UZ_OUT_BGZF unset (plain text) / host (zlib level 6) / device (uz_bgzf_deflate) / device-dynamic (UZ_OUT_BGZF_CODE=dynamic); a fresh process per run, "
+    if a.index:
+        for base in ("device", "host"):
+            assert len({r["file_sha"] for r in runs[base] + runs[base + "-index"]}) == 1, "the %s route's data file differs with the index" % base
+    res = dict(what="records dict -> out.vcf.gz (+ out.vcf.gz.tbi), UZ_OUT_BGZF device / host, each without and with UZ_OUT_INDEX=tbi; a fresh process per run, routes alternating, "
+                    "page cache warm; wall and host CPU seconds of unfazed.write_vcf_output, HIP start-up excluded" if a.index else "records dict -> out.vcf.gz, UZ_OUT_BGZF unset (plain text) / host (zlib level 6) / device (uz_bgzf_deflate) / device-dynamic (UZ_OUT_BGZF_CODE=dynamic); a fresh process per run, "
                     "routes alternating, page cache warm; wall and host CPU seconds of unfazed.write_vcf_output, HIP start-up excluded",
                shape=a.shape, samples=n_samples, records=n_records, input_bytes=os.path.getsize(src), repeat=a.repeat, runs=runs, same_text_on_every_route=same)
-    for route in ROUTES:
+    for route in routes:
         res[route.replace("-", "_") + "_median_wall_s"] = statistics.median(r["wall_s"] for r in runs[route])
         res[route.replace("-", "_") + "_file_bytes"] = runs[route][0]["file_bytes"]
     os.makedirs(os.path.dirname(a.out), exist_ok=True)

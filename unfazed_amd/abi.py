@@ -625,6 +625,26 @@ class BedView(C.Structure):
     _fields_ = [("n_rows", C.c_int64), ("rows", _p), ("n_strings", C.c_int32), ("str_off", _p), ("str_bytes", _p)]
 
 
+# uz_tbx_ref / uz_tbx_run / uz_tbx_view: the tables of uz_bgzf_deflate_indexed
+TBX_REF = np.dtype([("name_off", np.uint64), ("name_len", np.uint32), ("n_intv", np.uint32), ("v0", np.uint64), ("v1", np.uint64), ("n_rows", np.uint64)])
+TBX_RUN = np.dtype([("tid", np.uint32), ("bin", np.uint32), ("v0", np.uint64), ("v1", np.uint64)])
+TBX_S_ORDER, TBX_S_RANGE, TBX_S_META, TBX_S_EMPTY, TBX_S_CR, TBX_S_POS, TBX_S_CUT = 1, 2, 4, 8, 16, 32, 64  # unfazed_hip.h UZ_TBX_S_*
+
+
+class TbxView(C.Structure):
+    """uz_tbx_view"""
+    _fields_ = [("n_rows", C.c_int64), ("n_refs", C.c_int64), ("n_runs", C.c_int64), ("n_linear", C.c_int64), ("host_rows", C.c_int64),
+                ("status", C.c_uint32), ("pad_", C.c_uint32), ("refs", _p), ("runs", _p), ("linear", _p)]
+
+
+def tbx_arrays(v: TbxView) -> dict:
+    """the view's tables copied out of the context's memory"""
+    def take(ptr, n, dtype):
+        return np.frombuffer(C.string_at(ptr, n * dtype.itemsize), dtype).copy() if n else np.zeros(0, dtype)
+    return dict(status=int(v.status), n_rows=int(v.n_rows), host_rows=int(v.host_rows), refs=take(v.refs, int(v.n_refs), TBX_REF),
+                runs=take(v.runs, int(v.n_runs), TBX_RUN), linear=take(v.linear, int(v.n_linear), np.dtype(np.uint64)))
+
+
 def _ptr(a: np.ndarray) -> int:
     return a.ctypes.data if a.size else 0
 

@@ -8,7 +8,7 @@ import subprocess
 import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = ["abi.hip", "tables.hip", "k_sites.hip", "k_reads.hip", "k_records.hip", "k_inflate.hip", "k_bamwalk.hip", "k_bamjoin.hip", "k_vcf.hip", "k_bcf.hip", "k_bamhead.hip", "k_bed.hip", "k_vcfout.hip", "k_bcfout.hip", "k_deflate.hip"]
+SRC = ["abi.hip", "tables.hip", "k_sites.hip", "k_reads.hip", "k_records.hip", "k_inflate.hip", "k_bamwalk.hip", "k_bamjoin.hip", "k_vcf.hip", "k_bcf.hip", "k_bamhead.hip", "k_bed.hip", "k_vcfout.hip", "k_bcfout.hip", "k_deflate.hip", "k_tbx.hip"]
 DEFAULT_FLAGS = []
 LIB = os.path.join(_HERE, "libunfazed_hip.so")
 

@@ -330,6 +330,7 @@ void uz_destroy(uz_ctx *c) {
     c->find_pin.release(); c->nm_pin.release(); c->bed_pin.release();
     c->bed_in.release(); c->bed_hook.release(); c->bed_out.release(); c->bed_len.release(); c->bed_off.release();
     c->vo.release(); c->bo.release(); c->df.release(); c->df_slots.release(); c->df_tokens.release();
+    c->tbx_rows.release(); c->tbx_chunk.release(); c->tbx_work.release(); c->tbx_tab.release(); c->tbx_pin.release();
     c->nm_ids.release(); c->nm_len.release(); c->nm_off.release(); c->nm_out.release(); c->rf_first.release(); c->rf_mm.release();
     c->ab_lut.release(); c->win_range.release();
     c->dn_fam.release(); c->dn_cutoff.release(); c->fam_cls.release();
@@ -1704,6 +1705,17 @@ int uz_bgzf_deflate(uz_ctx *c, const uint8_t *data, int64_t n_bytes, int64_t *n_
 int uz_bgzf_deflate_coded(uz_ctx *c, const uint8_t *data, int64_t n_bytes, int code, int64_t *kinds, int64_t *n_blocks, const uint8_t **bgzf, int64_t *bgzf_bytes,
                           int repeat, double *kernel_ms) {
     return guarded(c, [&] { (void)uz_bgzf_deflate_impl(c, data, n_bytes, code, kinds, n_blocks, bgzf, bgzf_bytes, repeat, kernel_ms); });
+}
+int uz_bgzf_deflate_indexed(uz_ctx *c, const uint8_t *data, int64_t n_bytes, int code, int64_t *kinds, int64_t *n_blocks, const uint8_t **bgzf, int64_t *bgzf_bytes,
+                            int repeat, double *kernel_ms, int preset, uz_tbx_view *view) {
+    return guarded(c, [&] {
+        UZ_REQUIRE(view && (preset == UZ_TBX_PRESET_VCF || preset == UZ_TBX_PRESET_BED), UZ_E_ARG, "BGZF deflate: bad index arguments (a view; UZ_TBX_PRESET_VCF or UZ_TBX_PRESET_BED)");
+        *view = uz_tbx_view{};
+        TbxCall t;
+        t.preset = preset;
+        t.view = view;
+        (void)uz_bgzf_deflate_impl(c, data, n_bytes, code, kinds, n_blocks, bgzf, bgzf_bytes, repeat, kernel_ms, &t);
+    });
 }
 
 int uz_bed_rows_lists(uz_ctx *c, const uz_bed_view *rows, int verbose, int include_ambiguous, int32_t n_dnms, const int32_t *status, const int64_t *list_off,

@@ -12,6 +12,7 @@
 //   k_bgzf_frame      one workgroup per block: header, stream, CRC-32 and ISIZE, back to back at off; a block whose written bytes differ from its
 //                     scanned size raises the flag
 // No global atomics decide a byte: the only one is the OR of the raised flag.
+// uz_bgzf_deflate_indexed hangs the index kernels of k_tbx.hip into the same loop (TbxCall, uz_ctx.hpp): the blocks do not change.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -150,7 +151,7 @@ struct Timer { // the two events of the measured form
 } // namespace
 
 int uz_bgzf_deflate_impl(uz_ctx *c, const uint8_t *data, int64_t n_bytes, int code, int64_t *kinds, int64_t *n_blocks, const uint8_t **bgzf, int64_t *bgzf_bytes,
-                         int repeat, double *kernel_ms) {
+                         int repeat, double *kernel_ms, TbxCall *tbx) {
     UZ_REQUIRE(n_blocks && bgzf && bgzf_bytes && n_bytes >= 0, UZ_E_ARG, "BGZF deflate: bad arguments");
     UZ_REQUIRE(code == UZ_DF_CODE_FIXED || code == UZ_DF_CODE_DYNAMIC, UZ_E_ARG, "BGZF deflate: bad code argument (UZ_DF_CODE_FIXED or UZ_DF_CODE_DYNAMIC)");
     const bool dyn = code == UZ_DF_CODE_DYNAMIC;
@@ -168,6 +169,7 @@ int uz_bgzf_deflate_impl(uz_ctx *c, const uint8_t *data, int64_t n_bytes, int co
     chunk_bytes = std::max<size_t>(UZ_DF_SLICE, chunk_bytes / UZ_DF_SLICE * UZ_DF_SLICE); // whole slices
     const size_t n_chunks = ((size_t)n_bytes + chunk_bytes - 1) / chunk_bytes;
     const int64_t total_slices = (n_bytes + UZ_DF_SLICE - 1) / UZ_DF_SLICE;
+    if (tbx) { tbx->data = data; tbx->n_bytes = n_bytes; tbx->chunk_bytes = chunk_bytes; tbx->n_chunks = n_chunks; }
     Timer T; // (goes behind the loop, which drains the streams)
     ChunkLoop L(c, c->df, n_chunks);
     auto bytes_of = [&](size_t q) { return std::min<size_t>(chunk_bytes, (size_t)n_bytes - q * chunk_bytes); };
@@ -217,6 +219,7 @@ int uz_bgzf_deflate_impl(uz_ctx *c, const uint8_t *data, int64_t n_bytes, int co
             UZ_HIP(hipGetLastError());
         }
         uz_kcopy(c, c->df.small_pin.p, d_off + ns, 16); // the chunk's bytes, the flag word
+        if (tbx) uz_tbx_mark(c, *tbx, q, d_in, nb);
         if (repeat > 0) { // the measured form: the same launch again, which writes the same bytes into the same slots
             UZ_HIP(hipEventRecord(T.e0, st));
             for (int r = 0; r < repeat; r++) deflate();
@@ -233,6 +236,7 @@ int uz_bgzf_deflate_impl(uz_ctx *c, const uint8_t *data, int64_t n_bytes, int co
         const uint32_t flag = *reinterpret_cast<const uint32_t *>(c->df.small_pin.p + 8);
         UZ_REQUIRE(!(flag & UZ_DF_F_SIZE) && len >= (int64_t)ns * (UZ_BGZF_HEAD + UZ_BGZF_TAIL) && len <= (int64_t)out_cap, UZ_E_STATE,
                    "BGZF deflate: a framed block's written bytes differ from its scanned size");
+        if (tbx) uz_tbx_keys(c, *tbx, q, d_in, nb, d_off, L.total);
         L.result_room(q, (size_t)len, 1.05, (double)n_bytes, (double)nb, 65536);
         L.fetch(c->df.out.p, (size_t)len);
         UZ_HIP(hipStreamSynchronize(st));
@@ -247,6 +251,7 @@ int uz_bgzf_deflate_impl(uz_ctx *c, const uint8_t *data, int64_t n_bytes, int co
             at += ((int64_t)p[at + 16] | ((int64_t)p[at + 17] << 8)) + 1;
         }
     }
+    if (tbx) uz_tbx_tables(c, *tbx, L.total);
     *n_blocks = total_slices;
     *bgzf_bytes = L.total;
     if (kernel_ms) *kernel_ms = ms_sum;

@@ -491,6 +491,10 @@ struct uz_ctx {
     OutBufs vo, bo, df;
     DevBuf<uint8_t> df_slots;
     DevBuf<uint32_t> df_tokens;
+    // uz_bgzf_deflate_indexed (k_tbx.hip): the row table of a call (resident across its chunks), a chunk's tile counts / offsets / line starts,
+    // the work arrays and the tables of the passes behind the last chunk; their page-locked landing place
+    DevBuf<uint8_t> tbx_rows, tbx_chunk, tbx_work, tbx_tab;
+    PinBuf tbx_pin;
 
     // last phase (k_reads.hip)
     bool phase_valid = false;
@@ -690,7 +694,27 @@ void uz_head_rank_impl(uz_ctx *c, int head_id, int32_t readlen, const int64_t *k
 void uz_head_fetch_impl(uz_ctx *c, int head_id, int32_t file, int32_t *out, int64_t cap, int64_t *n);
 void uz_head_free_impl(uz_ctx *c, int head_id);
 // BGZF blocks of a host buffer (k_deflate.hip; deflate_body.hpp is the body)
+// The index side of a deflate call (k_tbx.hip), hung into the chunk loop of uz_bgzf_deflate_impl: uz_tbx_mark before a chunk's host wait (the
+// line starts of its tiles counted and scanned, the count sent down), uz_tbx_keys behind it (the chunk's rows appended to the row table; what the
+// host has to settle noted), uz_tbx_tables behind the last chunk.  tbx == nullptr: uz_bgzf_deflate_coded, launch for launch.
+struct TbxRow { // one line of the text
+    uint64_t v0, name_off;
+    int64_t beg, end;
+    uint32_t name_len, kind; // kind: UZ_TBX_META .. BAD | why << 4 | same_as_prev << 8
+};
+struct TbxCall {
+    int preset = 0;
+    const uint8_t *data = nullptr;
+    int64_t n_bytes = 0;
+    size_t chunk_bytes = 0, n_chunks = 0;
+    int64_t n_rows = 0;                               // of the chunks so far
+    std::vector<std::pair<int64_t, TbxRow>> settled;  // rows the host settled: (row, what it holds)
+    uz_tbx_view *view = nullptr;
+};
+void uz_tbx_mark(uz_ctx *c, TbxCall &t, size_t q, const uint8_t *d_in, size_t nb);
+void uz_tbx_keys(uz_ctx *c, TbxCall &t, size_t q, const uint8_t *d_in, size_t nb, const int64_t *d_off, int64_t base);
+void uz_tbx_tables(uz_ctx *c, TbxCall &t, int64_t eof_at);
 int uz_bgzf_deflate_impl(uz_ctx *c, const uint8_t *data, int64_t n_bytes, int code, int64_t *kinds, int64_t *n_blocks, const uint8_t **bgzf, int64_t *bgzf_bytes,
-                         int repeat, double *kernel_ms);
+                         int repeat, double *kernel_ms, TbxCall *tbx = nullptr);
 // a BCF's records as VCF text lines (k_bcfout.hip; bcf_row.hpp is the body)
 int uz_bcf_rows_impl(uz_ctx *c, const uz_bcf_lines_view *records, int64_t *off, uint64_t *samp_at, const uint8_t **bytes, uint8_t *handed_back);

@@ -23,7 +23,9 @@ K_BED_SIZE, K_BED_FILL = 16, 17  # uz_bed_rows: k_bed_size + the scan of the len
 K_VCFOUT_SIZE, K_VCFOUT_FILL = 18, 19  # uz_vcf_rows: k_vcfout_size + the scan of the lengths, k_vcfout_fill (per chunk)
 K_BCFOUT_SIZE, K_BCFOUT_FILL = 20, 21  # uz_bcf_rows: k_bcfout_size + the scan of the lengths, k_bcfout_fill (per chunk)
 K_DEFLATE, K_DEFLATE_FRAME = 22, 23  # uz_bgzf_deflate: k_bgzf_deflate (or k_bgzf_deflate_dyn) + k_bgzf_crc32_out + the scan of the sizes, k_bgzf_frame (per chunk)
+K_TBX_KEYS, K_TBX_TABLE = 24, 25  # uz_bgzf_deflate_indexed: k_tbx_mark + scan + k_tbx_starts + k_tbx_keys (per chunk), the table passes behind the last chunk
 DEFLATE_CODES = {"fixed": 0, "dynamic": 1}  # unfazed_hip.h UZ_DF_CODE_*
+TBX_PRESETS = {"vcf": 0, "bed": 1}  # unfazed_hip.h UZ_TBX_PRESET_*
 HEAD_NONE, HEAD_DONE, HEAD_END, HEAD_BAD = 0, 1, 2, 3  # unfazed_hip.h UZ_HEAD_*
 HEAD_MAX_BYTES = 8 << 30  # inflated bytes of one uz_head_walk launch unless UZ_HEAD_MAX_BYTES says otherwise: a choice, not a measurement
 HEAD_MAX_ROUNDS = 8       # walks of one file before it is handed back to the host route
@@ -37,7 +39,7 @@ EXPORTS = [
     "uz_sites_free", "uz_reads_free", "uz_drop_derived",
     "uz_site_scan", "uz_site_scan_many", "uz_site_classes", "uz_find", "uz_find_fetch", "uz_find_answer", "uz_find_stats", "uz_find_cohort",
     "uz_phase", "uz_phase_begin", "uz_phase_end", "uz_phase_cohort", "uz_phase_cohort_joined", "uz_phase_votes", "uz_phase_groups", "uz_phase_sizing_fetch", "uz_phase_cnv", "uz_phase_cnv_cohort", "uz_phase_cnv_sites",
-    "uz_bed_rows", "uz_bed_rows_lists", "uz_vcf_rows", "uz_bcf_rows", "uz_bgzf_deflate", "uz_bgzf_deflate_coded",
+    "uz_bed_rows", "uz_bed_rows_lists", "uz_vcf_rows", "uz_bcf_rows", "uz_bgzf_deflate", "uz_bgzf_deflate_coded", "uz_bgzf_deflate_indexed",
     "uz_prof_enable", "uz_prof_reset", "uz_prof_get", "uz_prof_units",
     "uz_head_walk", "uz_head_rank", "uz_head_fetch", "uz_head_free",
 ]
@@ -134,6 +136,7 @@ def load_library(path: Optional[str] = None):
     L.uz_vcf_rows.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.uz_bgzf_deflate.argtypes = [vp, vp, C.c_int64, vp, vp, vp, C.c_int, C.POINTER(C.c_double)]
     L.uz_bgzf_deflate_coded.argtypes = [vp, vp, C.c_int64, C.c_int, vp, vp, vp, vp, C.c_int, C.POINTER(C.c_double)]
+    L.uz_bgzf_deflate_indexed.argtypes = [vp, vp, C.c_int64, C.c_int, vp, vp, vp, vp, C.c_int, C.POINTER(C.c_double), C.c_int, vp]
     L.uz_bcf_rows.argtypes = [vp, vp, vp, vp, vp, vp]
     L.uz_head_walk.argtypes = [vp, C.POINTER(C.c_int), C.c_int32, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.uz_head_rank.argtypes = [vp, C.c_int, C.c_int32, vp, vp, vp]
@@ -518,22 +521,39 @@ class HipEngine:
                                         int(repeat), C.byref(ms)) if nb else 0, "uz_bgzf_inflate")
         return out[: int(out_off[-1])], nb, (ms.value if repeat > 0 else None)
 
-    def bgzf_deflate(self, data, repeat: int = 0, code: str = "fixed", kinds: bool = False):
+    def bgzf_deflate(self, data, repeat: int = 0, code: str = "fixed", kinds: bool = False, index=None):
         """`data` (bytes-like / uint8 array) as BGZF blocks written on the device (uz_bgzf_deflate_coded; csrc/deflate_body.hpp and deflate_dyn.hpp
         state the rules): one block per 65 280 bytes, without the end-of-file marker.  code: "fixed" (one fixed-Huffman block per slice, or a
         stored one) or "dynamic" (per slice the shortest of a dynamic, the fixed and a stored block).  -> (bytes of the blocks, block count, mean
         kernel ms of the code's kernel over `repeat` extra passes or None), and with kinds=True a fourth item: the blocks that came out
-        (stored, fixed, dynamic)"""
+        (stored, fixed, dynamic).
+        index: None, or "vcf" / "bed": the same blocks from uz_bgzf_deflate_indexed (csrc/k_tbx.hip; csrc/tbx_key.hpp states a line's rules),
+        and as the last item the tables of the text's tabix index as numpy arrays (copies): status (0, or abi.TBX_S_* bits: no tables), refs
+        (abi.TBX_REF, file order), runs (abi.TBX_RUN) grouped by (tid, bin) -- a stable sort here, of a table the index's own size: within a bin
+        the runs keep the file's order -- linear, n_rows, host_rows.  unfazed_amd/tabix_index.py turns them into the file."""
         if code not in DEFLATE_CODES:
             raise ValueError("bgzf_deflate: code %r (one of %s)" % (code, ", ".join(sorted(DEFLATE_CODES))))
+        if index is not None and index not in TBX_PRESETS:
+            raise ValueError("bgzf_deflate: index %r (None or one of %s)" % (index, ", ".join(sorted(TBX_PRESETS))))
         buf = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8)
         nb, size, ptr, ms = C.c_int64(0), C.c_int64(0), C.c_void_p(), C.c_double(0.0)
         split = (C.c_int64 * 3)()
-        self._ck(self.L.uz_bgzf_deflate_coded(self.h, buf.ctypes.data if buf.size else None, int(buf.size), DEFLATE_CODES[code], split, C.byref(nb), C.byref(ptr),
-                                              C.byref(size), int(repeat), C.byref(ms)), "uz_bgzf_deflate_coded")
+        args = (self.h, buf.ctypes.data if buf.size else None, int(buf.size), DEFLATE_CODES[code], split, C.byref(nb), C.byref(ptr), C.byref(size), int(repeat),
+                C.byref(ms))
+        tables = None
+        if index is None:
+            self._ck(self.L.uz_bgzf_deflate_coded(*args), "uz_bgzf_deflate_coded")
+        else:
+            view = abi.TbxView()
+            self._ck(self.L.uz_bgzf_deflate_indexed(*args, TBX_PRESETS[index], C.byref(view)), "uz_bgzf_deflate_indexed")
+            tables = abi.tbx_arrays(view)  # (copies: the view is the next call's)
+            runs = tables["runs"]
+            tables["runs"] = runs[np.lexsort((runs["bin"], runs["tid"]))]  # (lexsort is stable: a bin's chunks stay in file order)
         out = C.string_at(ptr.value, size.value) if size.value else b""  # (a copy: the context's block is the next call's)
         res = (out, int(nb.value), (ms.value if repeat > 0 else None))
-        return res + (tuple(int(v) for v in split),) if kinds else res
+        if kinds:
+            res += (tuple(int(v) for v in split),)
+        return res + (tables,) if index is not None else res
 
     def inflate_blocks(self, comp: np.ndarray, comp_bytes: int, in_off: np.ndarray, out_off: np.ndarray, out: np.ndarray):
         """The gathered BGZF blocks of a staged batch (io_native.BamSource.select(inflate=engine.inflate_blocks)) inflated on the device:
